@@ -17,11 +17,22 @@ inside the timed region.
 Defaults: 50 warm-up + 200 timed steps (0.15 s of GPU time): the device needs a few tens of
 launches to reach its steady clock -- 20 steps after 3 warm-ups read 5 % slower than the steady state.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement) with the object
   roofline     -- algorithmic HBM bytes per launch / mean kernel time (HIP events on the launch
                   stream) against the 8 TB/s HBM3E peak
+
+A plain run sets up, warms up, times the K steps and prints that line; nothing else.  Everything
+else the benchmark measures or checks runs only with --full (and its --no-* switches still apply):
+  verified     -- every routing code against the generator's construction truth, counter identities
   cpu_baseline -- the CPU oracle (restated reference loop, 1 thread) timed on this host on a
-                  bounded sample of the same workload (rank 0, N=1 only)
+                  bounded sample of the same workload, and oracle/strong_demux.c (rank 0, N=1 only)
+  extra        -- N=1: streamed rate, the kernel on the other configs, the end-to-end runs;
+                  N>1: the chunk-sharded end-to-end leg of every rank
+
+--dump-outputs DIR writes what the timed path computed in its last step (rank 0's routing codes and
+molecular bytes of a fixed, seeded sample of the pairs, their indices, the counters of the timed
+steps) as DIR/<name>.npy in float32 / float64.  The inputs depend only on the arguments, so two
+builds run with the same arguments can be compared file for file.
 """
 from __future__ import annotations
 
@@ -475,6 +486,34 @@ def e2e_ranks(args, rank, world, local_rank, dist, backend):
             shutil.rmtree(work, ignore_errors=True)
 
 
+DUMP_SEED = 20261016
+DUMP_BUDGET = 48 << 20  # bytes of the sampled arrays (the counters add a few kB): under 64 MB in all
+
+
+def dump_outputs(d, codes, mol, M, counts, n):
+    """--dump-outputs: what a caller of the timed path receives after its last step, as .npy files.  The codes of all n pairs
+    would be 4 bytes each as float32, so the codes and molecular bytes are kept for a fixed, seeded sample of the pairs (all of
+    them when n is small); counts are the counters of the timed steps as the count reduce returned them."""
+    import numpy as np
+    import torch
+    per_pair = 4 + 8 + 4 * M  # codes float32, pair index float64, molecular bytes float32
+    k = min(n, 1 << 20, DUMP_BUDGET // per_pair)
+    if k == n:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=k, dtype=np.int64))
+    it = torch.from_numpy(idx).to(codes.device)
+    out = {"pair_index": idx.astype(np.float64),
+           "codes": (codes.index_select(0, it).to(torch.int32) & 0xFFFF).cpu().numpy().astype(np.float32),
+           "counts": np.asarray(counts, dtype=np.uint64).astype(np.float64)}
+    if M:
+        out["mol"] = mol.index_select(0, it)[:, :M].cpu().numpy().astype(np.float32)
+    os.makedirs(d, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), a)
+    return {"dir": d, "files": sorted(name + ".npy" for name in out), "sampled_pairs": int(idx.size), "pairs": n}
+
+
 def mapped_libraries(word):
     """Distinct shared objects of this process whose file name contains `word` (from /proc/self/maps): with torch's
     `nccl` process group AND the library's own dlopen("librccl.so.1") in one process, two different copies would
@@ -536,7 +575,12 @@ def main():
     ap.add_argument("--e2e-rank-chunks", type=int, default=2, help="N > 1: chunks per rank of the chunk-sharded end-to-end leg (extra.e2e_ranks)")
     ap.add_argument("--config-steps", type=int, default=20, help="timed steps per extra kernel config (extra.kernel_configs)")
     ap.add_argument("--no-verify", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also verify the codes and run the CPU baselines and the extra rates "
+                    "(verified, cpu_baseline, extra); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the outputs of the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Started without a launcher (python bench.py --gpus N): this process has not touched the GPU
@@ -724,10 +768,13 @@ def main():
         comm_world = dist.get_world_size()
         per_rank = [None] * comm_world
         dist.all_gather_object(per_rank, mine)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # the buffers still hold the last timed step's outputs
+        dumped = dump_outputs(args.dump_outputs, codes, mol, M, total_counts, n)
 
-    # ---- verification outside the timed region (every pair, by construction; counts identities)
+    # ---- verification outside the timed region (every pair, by construction; counts identities): --full only
     verified = None
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         got = codes.view(torch.int16).to(torch.int32) & 0xFFFF
         same = bool(torch.equal(got, w.expected))
         S = cfg["S"]
@@ -801,12 +848,15 @@ def main():
         "ranks": per_rank,
         "launched_by": "self-spawn" if os.environ.get("QUADE_BENCH_SPAWNED") else
                        ("external launcher" if "WORLD_SIZE" in os.environ else "single process"),
+        "full": args.full,
     }
+    if dumped:
+        out["dump_outputs"] = dumped
 
     if comm is not None:
         comm.close()
     eng.close()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         ns = min(args.cpu_sample, n)
         rows = {"seq": [t[:ns].cpu().numpy() for t in w.seq], "qual": [t[:ns].cpu().numpy() for t in w.qual]}
         hip_codes = codes[:ns].cpu().numpy().view(np.uint16)
@@ -816,7 +866,7 @@ def main():
             rows = {"seq": [t[:nb].cpu().numpy() for t in w.seq], "qual": [t[:nb].cpu().numpy() for t in w.qual]}
             out["cpu_baseline"]["strong"] = strong_cpu_baseline(rows, w.plan, w.barcode_strings(),
                                                                 codes[:nb].cpu().numpy().view(np.uint16))
-    if world > 1 and not args.no_extras:
+    if args.full and world > 1 and not args.no_extras:
         # the demultiplexing leg of the N > 1 line: every rank takes part (the kernel leg's engine and communicator are closed)
         del codes, mol
         w.seq, w.qual = [], []
@@ -827,7 +877,7 @@ def main():
             er = {"error": repr(e)}
         if rank == 0:
             out["extra"] = {"e2e_ranks": er}
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         # the other two rates of SURVEY.md 8(d); labelled, outside `value`
         extra = {}
         try:

@@ -126,3 +126,13 @@ def kept_records(text):
         if len(seq) == len(qual):
             out.append((starts[4 * r], b"\n".join(lines[4 * r:4 * r + 4]) + b"\n"))
     return out
+
+
+def no_aslr(argv):
+    """argv run with address-space randomisation off for that one process (setarch -R), for ThreadSanitizer builds: libtsan
+    aborts with "unexpected memory mapping" when a kernel with more mmap randomisation bits maps the program outside the
+    ranges of its shadow layout.  argv unchanged where setarch is missing."""
+    import platform
+    import shutil
+    setarch = shutil.which("setarch")
+    return [setarch, platform.machine(), "-R"] + [str(a) for a in argv] if setarch else list(argv)

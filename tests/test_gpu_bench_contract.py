@@ -20,7 +20,7 @@ def _run(args, env=None, launcher=None):
 
 
 def test_single_gpu_line():
-    j = _run(["--steps", "3", "--warmup", "1", "--pairs", "3000000", "--cpu-sample", "20000", "--e2e-pairs", "30000", "--e2e-chunks", "1",
+    j = _run(["--full", "--steps", "3", "--warmup", "1", "--pairs", "3000000", "--cpu-sample", "20000", "--e2e-pairs", "30000", "--e2e-chunks", "1",
               "--strong-sample", "1000000", "--config-steps", "3"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
@@ -81,7 +81,7 @@ def test_two_ranks_self_spawned():
     env = dict(os.environ, QUADE_BENCH_DEVICE="0", QUADE_BENCH_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    j = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--pairs", "2000000"], env=env)
+    j = _run(["--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--pairs", "2000000"], env=env)
     assert j["n_gpus"] == 2 and j["world"] == 2 and j["verified"] is True and j["launched_by"] == "self-spawn"
     assert [r["rank"] for r in j["ranks"]] == [0, 1] and all(r["kernel_ms"] > 0 for r in j["ranks"])
     assert j["count_reduce"]["backend"] == "gloo" and j["count_reduce"]["ms_max_over_ranks"] > 0
@@ -94,7 +94,7 @@ def test_two_rank_rehearsal_line():
     env = dict(os.environ, QUADE_BENCH_DEVICE="0", QUADE_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     launcher = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                 "--master-addr", "127.0.0.1", "--master-port", "29577"]
-    j = _run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--pairs", "2000000", "--e2e-pairs", "40000", "--e2e-rank-chunks", "2"], env=env, launcher=launcher)
+    j = _run(["--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--pairs", "2000000", "--e2e-pairs", "40000", "--e2e-rank-chunks", "2"], env=env, launcher=launcher)
     assert j["n_gpus"] == 2 and j["verified"] is True and "cpu_baseline" not in j
     assert j["launched_by"] == "external launcher" and j["world"] == 2
     assert abs(j["value"] - 2 * 2000000 * 3 / (j["ms_per_step"] * 3e-3)) < 1e-6 * j["value"]
@@ -114,6 +114,36 @@ def test_single_rank_rccl_path():
     env = dict(os.environ, QUADE_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1")
     launcher = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                 "--master-addr", "127.0.0.1", "--master-port", "29578"]
-    j = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--pairs", "2000000", "--no-cpu-baseline"], env=env,
+    j = _run(["--full", "--gpus", "1", "--steps", "3", "--warmup", "1", "--pairs", "2000000", "--no-cpu-baseline"], env=env,
              launcher=launcher)
     assert j["n_gpus"] == 1 and j["verified"] is True
+
+
+def test_plain_line_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full the line carries the headline alone (no verification, CPU baseline or extra rates); --dump-outputs
+    writes the last timed step's outputs, which are the generator's construction truth and the counters of the K steps."""
+    import numpy as np
+    import torch
+    from quade_amd import synth
+    n, steps, d = 3000000, 4, tmp_path / "outputs"
+    j = _run(["--steps", str(steps), "--warmup", "1", "--pairs", str(n), "--dump-outputs", str(d)])
+    assert (j["metric"], j["unit"], j["higher_is_better"], j["dtype"]) == \
+        ("read-pairs/sec demultiplexed (2x150 bp, dual 8 bp index)", "read-pairs/s", True, "u8")
+    assert j["steps"] == steps and j["full"] is False and j["verified"] is None and "cpu_baseline" not in j and "extra" not in j
+    assert abs(j["value"] - n * steps / (j["ms_per_step"] * steps * 1e-3)) < 1e-6 * j["value"]
+    files = sorted(os.listdir(d))
+    assert files == ["codes.npy", "counts.npy", "pair_index.npy"] == j["dump_outputs"]["files"]
+    assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+    a = {f[:-4]: np.load(d / f) for f in files}
+    assert a["codes"].dtype == np.float32 and a["pair_index"].dtype == np.float64 and a["counts"].dtype == np.float64
+    idx = a["pair_index"].astype(np.int64)
+    assert idx.size == a["codes"].size == j["dump_outputs"]["sampled_pairs"] > 0 and (np.diff(idx) > 0).all() and idx[-1] < n
+    w = synth.generate("cfg3", n, seed=20260003, device="cuda", barcode_seed=20260003)  # bench.py's rank-0 workload
+    exp = w.expected.cpu().numpy()
+    assert (a["codes"].astype(np.int64) == exp[idx]).all()
+    S = synth.CONFIGS["cfg3"]["S"]
+    hist = np.bincount(exp[exp != 0xFFFF], minlength=2 * S)
+    c = a["counts"].astype(np.int64)
+    assert c[0] == n * steps == c[1] + c[2] + c[3] and (c[4:] == hist * steps).all()
+    del w
+    torch.cuda.empty_cache()

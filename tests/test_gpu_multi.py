@@ -118,7 +118,7 @@ def test_bench_ranks_reduce_through_the_library_communicator():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "QUADE_BENCH_DEVICE", "QUADE_BENCH_BACKEND"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(N_RANKS), "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(N_RANKS), "--steps", "3", "--warmup", "1",
                         "--pairs", "4000000"], cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

@@ -13,6 +13,7 @@ import pytest
 
 from oracle import quade_oracle as qo
 from quade_amd import hip_backend as hb
+from tests.helpers import no_aslr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -150,7 +151,8 @@ def test_parallel_gunzip_under_sanitizers(tmp_path, sanitizer):
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     rounds = "120" if sanitizer != "thread" else "40"
-    r = subprocess.run([str(exe), str(gz), rounds, "65536"], capture_output=True, text=True,
+    argv = [str(exe), str(gz), rounds, "65536"]
+    r = subprocess.run(no_aslr(argv) if sanitizer == "thread" else argv, capture_output=True, text=True,
                        env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1", ASAN_OPTIONS="detect_leaks=1"))
     assert r.returncode == 0 and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, (r.stdout, r.stderr[-3000:])
     assert "all as zlib" in r.stdout

@@ -13,6 +13,7 @@ import pytest
 from oracle import quade_oracle as qo
 from quade_amd import hip_backend as hb
 from quade_amd.fastq_writer import FastqSink, io_backend
+from tests.helpers import no_aslr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -118,6 +119,7 @@ tags = np.zeros((n, 4), np.uint8); tags[:] = np.frombuffer(b":ACG", np.uint8); t
 s = FastqSink(sys.argv[1], ["A"], 1, quiet=True)
 for _ in range(2):
     s.route(n, codes, buf, off, buf, off, tags, tl)
+s.flush()  # the members are made on the pool's threads: count them once all are in
 st = s.stats(); s.close()
 data = gzip.open(os.path.join(sys.argv[1], "A_pass_R1.fastq.gz")).read()
 ids = [int(l[2:9]) for l in data.split(b"\n")[0::4] if l]
@@ -261,7 +263,7 @@ int main(int argc, char** argv) {
     n_bgzf = 60000
     _gzip_members(b"".join(b"@r%d\nACGTACGTACGTACGTACGTACGTACGTACGT\n+\nIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIII\n" % i for i in range(n_bgzf)),
                   str(tmp_path / "bgzf.fastq.gz"), 1, "bgzf", 2)
-    r = subprocess.run([str(exe), str(tmp_path / "a"), str(tmp_path / "b"), str(tmp_path / "bgzf.fastq.gz"), str(n_bgzf)],
+    r = subprocess.run(no_aslr([str(exe), str(tmp_path / "a"), str(tmp_path / "b"), str(tmp_path / "bgzf.fastq.gz"), str(n_bgzf)]),
                        capture_output=True, text=True,
                        env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1"))
     assert r.returncode == 0 and "ThreadSanitizer" not in r.stderr, (r.stdout, r.stderr[-3000:])

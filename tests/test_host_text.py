@@ -3,6 +3,8 @@ and checked against zlib and the rules they restate."""
 import os
 import subprocess
 
+from tests.helpers import no_aslr
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -38,7 +40,7 @@ def test_io_seams_of_the_pipeline_under_tsan(tmp_path):
     exe = _build_io_seams(tmp_path, "thread")
     d = tmp_path / "w"
     d.mkdir()
-    r = subprocess.run([exe, str(d)], capture_output=True, text=True, timeout=900, env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1"))
+    r = subprocess.run(no_aslr([exe, str(d)]), capture_output=True, text=True, timeout=900, env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1"))
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-2000:], r.stderr[-3000:])
 
 

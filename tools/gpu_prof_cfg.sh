@@ -9,9 +9,9 @@ export TMPDIR=/tmp
 C=${1:-cfg4}; TAG=${2:-r02}
 D=gpurun_out/prof_$C
 rm -rf $D; mkdir -p $D
-BENCH="python3 bench.py --config $C --steps 100 --warmup 50 --no-cpu-baseline --no-extras"
+BENCH="python3 bench.py --full --config $C --steps 100 --warmup 50 --no-cpu-baseline --no-extras"
 echo "[prof $C] bench"
-python bench.py --config $C --no-cpu-baseline --no-extras > $D/bench.json 2> $D/bench.err || { tail -5 $D/bench.err; exit 1; }
+python bench.py --full --config $C --no-cpu-baseline --no-extras > $D/bench.json 2> $D/bench.err || { tail -5 $D/bench.err; exit 1; }
 echo "[prof $C] kernel trace"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$C/trace -- $BENCH > $D/trace.log 2>&1 || tail -5 $D/trace.log
 # fixed names: rocprofv3 prefixes its files with the process id, which repeats from box to box, and merged sessions piled up
