@@ -110,7 +110,8 @@ int qd_device_info(const qd_ctx* ctx, char* name, int32_t name_cap, int32_t* com
 
 /* Replaces Sample.CLASS_INIT(min_qual=...) (src/Sample.py:48-54, called at src/Quade.py:125-129)
  * and the position fields of Quade.__init__ (src/Quade.py:99-116).  The write_* flags are not a
- * device concern: counters move regardless (Sample.py:71-91) and routing is decided by code. */
+ * device concern: counters move regardless (Sample.py:71-91) and routing is decided by code.
+ * Resets the mismatch budgets (qd_set_mismatches) to 0. */
 int qd_set_plan(qd_ctx* ctx, const qd_plan* plan);
 int qd_get_layout(const qd_ctx* ctx, qd_layout* out);
 
@@ -119,7 +120,8 @@ int qd_get_layout(const qd_ctx* ctx, qd_layout* out);
  * `barcodes`, barcode i = barcodes[offsets[i] .. offsets[i+1]).  Lengths may differ from the slice
  * width and from each other (the reference never checks, Sample.py:132-141); such a barcode can
  * only match reads whose clamped slice has exactly that length.  Duplicate -> QD_ERR_BARCODE.
- * Alphabet checks stay on the Python side (message text parity, Sample.py:141). Resets counters. */
+ * Alphabet checks stay on the Python side (message text parity, Sample.py:141). Resets counters and the
+ * mismatch budgets (qd_set_mismatches). */
 int qd_set_barcodes(qd_ctx* ctx, int32_t n_samples, const uint8_t* barcodes, const int32_t* offsets);
 
 /* ---- device-resident hot path ---------------------------------------------------------------------
@@ -165,6 +167,28 @@ int qd_kernel_kind(const qd_ctx* ctx, int has_len);
  *                             before this many pairs have been launched since the last fold (default and
  *                             maximum 2^32 - 1; tests lower it) */
 int qd_set_option(qd_ctx* ctx, const char* name, int64_t value);
+
+/* ---- mismatch-tolerant matching (opt-in; no reference counterpart: Quade 0.3.2 matches exactly) ---------
+ * Budgets m1 (index read 1's part of the fused barcode, bytes [0, w1) with w1 = idx1_end - idx1_start) and m2
+ * (index read 2's part, [w1, K)), each 0..2.  A pair whose exact lookup fails and whose fused slice is K bytes
+ * long is assigned to the barcode of length K with ham(key[0:w1], bc[0:w1]) <= m1 and ham(key[w1:K], bc[w1:K])
+ * <= m2 (bytes compared after the case fold: N is an ordinary symbol).  Exact hits, short slices and barcodes
+ * of another length behave as with budgets 0.  The quality gate, the codes and the counter layout are
+ * unchanged: a rescued pair counts as its sample's pass or fail.  The rescue is a post-pass of every launch
+ * (qd_demux_device, _ragged, qd_submit, qd_submit_ragged) on the launch's stream; with budgets 0 none runs.
+ *
+ * Collision rule: barcodes A and B of length K collide when d1 <= 2*m1 and d2 <= 2*m2 (per-part Hamming
+ * distances), i.e. exactly when some pair is within budget of both.  Host only, never touches the GPU:
+ * returns QD_OK (*first = *second = -1) or QD_ERR_BARCODE with the first colliding ordinal pair (first <
+ * second, lexicographic); QD_ERR_INVALID on bad arguments.  Brute force over all pairs (SWAR, up to 16
+ * threads): DESIGN.md 4.8 gives its time at S = QD_MAX_SAMPLES. */
+int qd_check_mismatch_collisions(int32_t n_samples, const uint8_t* barcodes, const int32_t* offsets, int32_t key_width,
+                                 int32_t w1, int32_t m1, int32_t m2, int32_t* first, int32_t* second);
+/* Sets the budgets of this context.  Needs qd_set_plan and qd_set_barcodes first (QD_ERR_STATE); m1, m2 in
+ * 0..2 and m2 == 0 for a single-index plan (QD_ERR_INVALID); runs the collision check on the registered
+ * barcodes (QD_ERR_BARCODE, qd_last_error names the two ordinals) and builds the device tables.  Waits for
+ * the context's outstanding work.  qd_set_plan and qd_set_barcodes reset both budgets to 0. */
+int qd_set_mismatches(qd_ctx* ctx, int32_t m1, int32_t m2);
 
 /* ---- counters: replace the class counters of src/Sample.py:32,144 and feed Sample.REPORT ---------
  * qd_get_counts waits for outstanding work of this context (only), then writes 2*S+4 values. */

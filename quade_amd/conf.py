@@ -5,7 +5,8 @@ Python 3.  Parsing and validation follow src/Quade.py:92-142 and 258-284 of the 
 sections, option names, 1-based -> 0-based start conversion, assertion messages); the example
 file written by `-i` is the reference's template byte for byte (src/Conf_file.py:18-104; shipped as
 package data, quade_amd/data/Quade_conf_file.txt).  An optional [gpu] section that reference conf
-files simply do not have is read when present (defaults apply otherwise; see GPU_SECTION_HELP).
+files simply do not have is read when present (defaults apply otherwise; see GPU_SECTION_HELP), and so are the optional
+mismatch budgets of the [index] section (MISMATCH_HELP).
 """
 from __future__ import annotations
 
@@ -46,6 +47,15 @@ Optional [gpu] section (not in Quade 0.3.2; a conf file without it runs with the
   device_inflate : True  BGZF (bgzip) input files are inflated on the GPU, one workgroup of 512-1024 lanes per block (every block's
                          CRC-32 is checked against its trailer; a block the device refuses is inflated by the host); ordinary gzip
                          files are inflated by the host's threads whatever this says
+"""
+
+MISMATCH_HELP = """\
+Optional [index] options (not in Quade 0.3.2, whose parser ignores them; absent = 0 = exact matching as the reference):
+  index1_mismatches : 0  substitutions tolerated in index read 1's part of the barcode: 0, 1 or 2
+  index2_mismatches : 0  the same for index read 2's part: 0, 1 or 2 (ignored when index2 is False)
+A read whose barcode slice has no exact match goes to the one sample whose barcode is within both budgets (N counts as an
+ordinary base).  Two samples whose barcodes are within 2 x index1_mismatches and 2 x index2_mismatches of each other collide:
+the configuration is rejected before any read is processed.
 """
 
 
@@ -91,6 +101,14 @@ class QuadeConf(object):
         self.idx2_pos = pos(self.idx2, "index2")
         self.mol1_pos = pos(self.mol1, "molecular1")
         self.mol2_pos = pos(self.mol2, "molecular2")
+        # optional mismatch budgets (extension, MISMATCH_HELP): 0 = exact matching
+        def budget(name, enabled):
+            if not enabled or not cp.has_option("index", name) or cp.get("index", name) in (None, ""):
+                return 0
+            return cp.getint("index", name)
+
+        self.idx1_mismatches = budget("index1_mismatches", True)
+        self.idx2_mismatches = budget("index2_mismatches", self.idx2)
 
         self.seq_R1 = cp.get("fastq", "seq_R1").split()
         self.seq_R2 = cp.get("fastq", "seq_R2").split()
@@ -150,6 +168,8 @@ class QuadeConf(object):
                 "seq_R1, seq_R2 and index_R1 are mandatory and have to contain the same number of files"
             for fp in (self.seq_R1 + self.seq_R2 + self.index_R1):
                 is_readable_file(fp)
+        assert 0 <= self.idx1_mismatches <= 2, "Authorized values for index1_mismatches : 0 to 2"
+        assert 0 <= self.idx2_mismatches <= 2, "Authorized values for index2_mismatches : 0 to 2"
         for pos in [self.idx1_pos, self.idx2_pos, self.mol1_pos, self.mol2_pos]:
             assert pos["start"] >= 0
             assert pos["end"] >= pos["start"]

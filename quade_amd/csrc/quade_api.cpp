@@ -19,6 +19,7 @@
 #include "quade_inflate.h"
 #include "quade_inflate3.h"
 #include "quade_deflate.h"
+#include "quade_mismatch.h"
 
 typedef uint64_t u64;
 
@@ -103,6 +104,19 @@ struct qd_ctx {
     // copies of all submitted slots shared the link, finished together, and the link then idled while the
     // kernels, the downloads and the host's next submits went by (48.7 of the link's 57 GB/s, tools/h2d_probe.py).
     hipStream_t up_stream = nullptr;
+
+    // mismatch-tolerant matching (qd_set_mismatches): budgets, device tables, the parameter block's fixed part, and per
+    // stream the list of a batch's undetermined pairs ([0] = count, the list from [4]; grown on demand)
+    int32_t mm_m1 = 0, mm_m2 = 0;
+    MismatchParams mm{};
+    QdMmBucket* d_mm_htab = nullptr;
+    uint16_t* d_mm_cand = nullptr;
+    struct MmScratch {
+        hipStream_t stream;
+        uint32_t* buf;
+        size_t cap;  // uint32 entries
+    };
+    std::vector<MmScratch> mm_scratch;
 };
 
 namespace {
@@ -226,6 +240,53 @@ void free_table(qd_ctx* c) {
     c->d_partial = nullptr;
     c->d_counts = nullptr;
     c->have_table = false;
+}
+
+// budgets back to 0 and the rescue's tables freed (the caller waited for the context's work)
+void free_mismatch(qd_ctx* c, bool scratch) {
+    if (c->d_mm_htab) (void)hipFree(c->d_mm_htab);
+    if (c->d_mm_cand) (void)hipFree(c->d_mm_cand);
+    c->d_mm_htab = nullptr;
+    c->d_mm_cand = nullptr;
+    c->mm_m1 = c->mm_m2 = 0;
+    if (scratch) {
+        for (auto& m : c->mm_scratch) (void)hipFree(m.buf);
+        c->mm_scratch.clear();
+    }
+}
+
+// the rescue post-pass of a batch on `st` (launch(), budgets set): the stream's list holds n + 4 entries at least
+int launch_mismatch(qd_ctx* c, int64_t n, const qd_rows* rows, uint16_t* codes, hipStream_t st) {
+    qd_ctx::MmScratch* sc = nullptr;
+    for (auto& m : c->mm_scratch)
+        if (m.stream == st) sc = &m;
+    if (!sc) {
+        c->mm_scratch.push_back(qd_ctx::MmScratch{st, nullptr, 0});
+        sc = &c->mm_scratch.back();
+    }
+    if (sc->cap < (size_t)n + 4) {
+        HIPCHK(c, hipStreamSynchronize(st));  // the old list may still be read by this stream's previous batch
+        if (sc->buf) (void)hipFree(sc->buf);
+        sc->buf = nullptr;
+        const size_t cap = std::max<size_t>((size_t)n + 4, sc->cap * 2);
+        HIPCHK(c, hipMalloc(&sc->buf, cap * 4));
+        sc->cap = cap;
+    }
+    MismatchParams p = c->mm;
+    for (int k = 0; k < c->lay.n_streams; ++k) {
+        p.seq[k] = rows->seq[k];
+        p.qual[k] = rows->qual[k];
+    }
+    p.codes = codes;
+    p.adjust = c->d_acc;
+    p.bk32 = c->d_bk32;
+    p.htab = c->d_mm_htab;
+    p.cand = c->d_mm_cand;
+    p.miss = sc->buf;
+    p.n = n;
+    hipError_t e = qd_launch_mismatch(p, sc->buf, c->cu, st);
+    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("mismatch launch: ") + hipGetErrorString(e));
+    return QD_OK;
 }
 
 // (re)build the device table from the host barcodes and the current plan
@@ -492,6 +553,10 @@ int launch(qd_ctx* c, int64_t n, const qd_rows* rows, uint16_t* codes, uint8_t* 
         e = qd_launch_fixup(p, st);
         if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("fixup launch: ") + hipGetErrorString(e));
     }
+    if (c->mm_m1 + c->mm_m2 > 0) {  // opt-in rescue of the undetermined pairs, behind whatever took the batch
+        const int r = launch_mismatch(c, n, rows, codes, st);
+        if (r != QD_OK) return r;
+    }
     c->total_pairs += (uint64_t)n;
     c->pairs_in_rows += (uint64_t)n;
     e = track(c, st);
@@ -568,6 +633,7 @@ int qd_destroy(qd_ctx* c) {
     (void)wait_all(c);
     qd_slots_destroy(c);
     free_table(c);
+    free_mismatch(c, true);
     for (auto& t : c->tracked) (void)hipEventDestroy(t.second);
     c->tracked.clear();
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -590,6 +656,11 @@ int qd_set_plan(qd_ctx* c, const qd_plan* plan) {
     if (r != QD_OK) return fail(c, r, "plan rejected: positions must satisfy 0 <= start <= end <= 255, window <= 64, "
                                        "fused barcode <= 32, 0 <= minimal_qual <= 40");
     if (!c->slots.empty()) return fail(c, QD_ERR_STATE, "destroy the slots before changing the plan");
+    if (c->mm_m1 + c->mm_m2 > 0) {  // a new plan resets the mismatch budgets
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, wait_all(c));
+        free_mismatch(c, false);
+    }
     c->plan = *plan;
     c->lay = L;
     c->have_plan = true;
@@ -623,11 +694,71 @@ int qd_set_barcodes(qd_ctx* c, int32_t S, const uint8_t* barcodes, const int32_t
     if (!c->have_plan) return fail(c, QD_ERR_STATE, "qd_set_plan first");
     for (int i = 0; i < S; ++i)
         if (offsets[i + 1] < offsets[i]) return fail(c, QD_ERR_INVALID, "offsets must be non-decreasing");
+    if (c->mm_m1 + c->mm_m2 > 0) {  // new barcodes reset the mismatch budgets, as they reset the counters
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, wait_all(c));
+        free_mismatch(c, false);
+    }
     c->S = S;
     c->bc.assign(barcodes, barcodes + (S ? offsets[S] : 0));
     c->bc_off.assign(offsets, offsets + (S ? S + 1 : 0));
     if (S == 0) c->bc_off.assign(1, 0);
     return rebuild(c);
+}
+
+int qd_check_mismatch_collisions(int32_t S, const uint8_t* barcodes, const int32_t* offsets, int32_t K, int32_t w1, int32_t m1,
+                                 int32_t m2, int32_t* first, int32_t* second) {
+    if (S < 0 || S > QD_MAX_SAMPLES || (S > 0 && (!barcodes || !offsets)) || !first || !second || K < 1 || K > QD_MAX_KEY ||
+        w1 < 0 || w1 > K || m1 < 0 || m1 > 2 || m2 < 0 || m2 > 2)
+        return QD_ERR_INVALID;
+    for (int i = 0; i < S; ++i)
+        if (offsets[i + 1] < offsets[i]) return QD_ERR_INVALID;
+    *first = *second = -1;
+    return qd_mm_first_collision(S, barcodes, offsets, K, w1, m1, m2, first, second) ? QD_ERR_BARCODE : QD_OK;
+}
+
+int qd_set_mismatches(qd_ctx* c, int32_t m1, int32_t m2) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->have_plan || !c->have_table) return fail(c, QD_ERR_STATE, "qd_set_plan and qd_set_barcodes first");
+    if (m1 < 0 || m1 > 2 || m2 < 0 || m2 > 2) return fail(c, QD_ERR_INVALID, "mismatch budgets must be 0, 1 or 2");
+    if (!c->plan.dual && m2 != 0) return fail(c, QD_ERR_INVALID, "index2_mismatches needs a dual-index plan");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));  // nothing of this context may still read the old tables
+    free_mismatch(c, false);
+    if (m1 + m2 == 0) return QD_OK;
+    const int K = c->lay.key_width, w1 = c->plan.idx1_end - c->plan.idx1_start;
+    int32_t a = -1, b = -1;
+    if (qd_mm_first_collision(c->S, c->bc.data(), c->bc_off.data(), K, w1, m1, m2, &a, &b)) {
+        char m[160];
+        snprintf(m, sizeof m, "barcodes %d and %d collide with index1_mismatches=%d index2_mismatches=%d", a, b, m1, m2);
+        return fail(c, QD_ERR_BARCODE, m);
+    }
+    MismatchParams& p = c->mm;
+    memset(&p, 0, sizeof p);
+    std::vector<QdMmBucket> htab;
+    std::vector<uint16_t> cand;
+    qd_mm_build(c->S, c->bc.data(), c->bc_off.data(), K, w1, m1, m2, p, htab, cand);
+    const qd_layout& L = c->lay;
+    const qd_plan& P = c->plan;
+    const int is[2] = {P.idx1_start, P.idx2_start}, ie[2] = {P.idx1_end, P.idx2_end};
+    p.n_streams = L.n_streams;
+    p.K = K;
+    for (int k = 0; k < L.n_streams; ++k) {
+        p.seq_stride[k] = L.seq_stride[k];
+        p.qual_stride[k] = L.qual_stride[k];
+        p.idx_w[k] = ie[k] - is[k];
+        p.idx_off[k] = p.idx_w[k] ? is[k] - L.seq_off[k] : 0;
+    }
+    p.thr = (uint32_t)(P.min_qual + 33);
+    p.n_samples = (uint32_t)c->S;
+    p.hist_entries = 2 * c->S <= 16000 ? (uint32_t)(2 * c->S) : 0;  // <= 64 KB of LDS, else global 64-bit adds per pair
+    HIPCHK(c, hipMalloc(&c->d_mm_htab, htab.size() * sizeof(QdMmBucket)));
+    HIPCHK(c, hipMalloc(&c->d_mm_cand, cand.size() * sizeof(uint16_t)));
+    HIPCHK(c, hipMemcpy(c->d_mm_htab, htab.data(), htab.size() * sizeof(QdMmBucket), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_mm_cand, cand.data(), cand.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    c->mm_m1 = m1;
+    c->mm_m2 = m2;
+    return QD_OK;
 }
 
 int qd_kernel_kind(const qd_ctx* c, int has_len) {

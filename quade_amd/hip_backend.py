@@ -96,6 +96,9 @@ SYMBOLS = [
     ("qd_demux_device_ragged", C.c_int, [_P, C.c_int64, C.POINTER(qd_rows), _P, _P, C.c_int64, _P, _P]),
     ("qd_kernel_kind", C.c_int, [_P, C.c_int]),
     ("qd_set_option", C.c_int, [_P, C.c_char_p, C.c_int64]),
+    ("qd_check_mismatch_collisions", C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("qd_set_mismatches", C.c_int, [_P, C.c_int32, C.c_int32]),
     ("qd_get_counts", C.c_int, [_P, _P, C.c_int32]),
     ("qd_reset_counts", C.c_int, [_P]),
     ("qd_add_counts", C.c_int, [_P, _P, C.c_int32]),
@@ -347,6 +350,30 @@ def device_count():
     return n.value
 
 
+def _barcode_blob(barcodes):
+    """list of str/bytes -> (blob uint8, offsets int32[S+1]) as qd_set_barcodes takes them"""
+    bs = [b.encode("latin-1") if isinstance(b, str) else bytes(b) for b in barcodes]
+    offs = np.zeros(len(bs) + 1, dtype=np.int32)
+    if bs:
+        np.cumsum([len(b) for b in bs], out=offs[1:])
+    return np.frombuffer(b"".join(bs) + b"\0", dtype=np.uint8), offs, len(bs)
+
+
+def check_mismatch_collisions(barcodes, key_width, w1, m1, m2):
+    """Host only (no GPU): the first colliding ordinal pair (i, j) of the sample sheet under budgets (m1, m2) -- barcodes of
+    length key_width whose per-part Hamming distances are <= 2*m1 on [0, w1) and <= 2*m2 on [w1, key_width) -- or None."""
+    lib = load_library()
+    blob, offs, n = _barcode_blob(barcodes)
+    a, b = C.c_int32(-1), C.c_int32(-1)
+    r = lib.qd_check_mismatch_collisions(n, _ptr(blob), _ptr(offs), int(key_width), int(w1), int(m1), int(m2),
+                                         C.byref(a), C.byref(b))
+    if r == QD_ERR_BARCODE:
+        return a.value, b.value
+    if r != QD_OK:
+        raise QuadeHipError(r, lib.qd_strerror(r).decode())
+    return None
+
+
 # ---- device context -------------------------------------------------------------------------------------
 class Engine(object):
     """One libquade_hip context = one MI355X.  Mirrors what Sample.CLASS_INIT + Sample(name, index)
@@ -410,6 +437,11 @@ class Engine(object):
         blob = np.frombuffer(b"".join(bs) + b"\0", dtype=np.uint8)
         self._chk(self.lib.qd_set_barcodes(self._h, len(bs), _ptr(blob), _ptr(offs)))
         self.n_samples = len(bs)
+
+    def set_mismatches(self, m1, m2=0):
+        """Mismatch budgets of index read 1's and index read 2's part (0..2 each; qd_set_mismatches).  After set_barcodes:
+        set_plan and set_barcodes reset them to 0."""
+        self._chk(self.lib.qd_set_mismatches(self._h, int(m1), int(m2)))
 
     def set_option(self, name, value):
         self._chk(self.lib.qd_set_option(self._h, name.encode(), int(value)))

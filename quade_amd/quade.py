@@ -84,6 +84,7 @@ class Quade(object):
                               gzip_level=self.cf.gzip_level)
             for name, index in self.cf.samples:
                 Sample(name=name, index=index)
+            self._check_mismatch_collisions()
         # same three families of errors, same messages, exit status 1 (src/Quade.py:145-153)
         except (configparser.NoOptionError, configparser.NoSectionError) as E:
             print("Option or section missing. Report to the template configuration file\n" + E.message)
@@ -96,6 +97,20 @@ class Quade(object):
             sys.exit(1)
         self.outdir = outdir
         self.engines = []
+
+    def _check_mismatch_collisions(self):
+        """Optional mismatch budgets ([index] index1_mismatches / index2_mismatches): a sample sheet in which some read would be
+        within budget of two samples is a configuration error, found on the host before any GPU work."""
+        cf = self.cf
+        m1, m2 = cf.idx1_mismatches, cf.idx2_mismatches
+        w1 = cf.idx1_pos["end"] - cf.idx1_pos["start"]
+        K = w1 + (cf.idx2_pos["end"] - cf.idx2_pos["start"])
+        if m1 + m2 == 0 or not 1 <= K <= 32:
+            return
+        hit = hb.check_mismatch_collisions(Sample.BARCODES(), K, w1, m1, m2)
+        if hit is not None:
+            a, b = Sample.SAMPLE_LIST[hit[0]].name, Sample.SAMPLE_LIST[hit[1]].name
+            raise AssertionError("{} and {} : Index collision with index1_mismatches={} index2_mismatches={}".format(a, b, m1, m2))
 
     def __repr__(self):
         return "<Instance of {} from {} >\n".format(self.__class__.__name__, self.__module__)
@@ -148,6 +163,8 @@ class Quade(object):
                 eng = hb.Engine(int(d))  # raises when libquade_hip.so or the GPU is missing: no fallback
                 eng.set_plan(plan)
                 eng.set_barcodes(Sample.BARCODES())
+                if cf.idx1_mismatches + cf.idx2_mismatches > 0:
+                    eng.set_mismatches(cf.idx1_mismatches, cf.idx2_mismatches)
                 if not self.use_pipe:
                     eng.slots_create(cf.slots, cf.batch_pairs)
                 group.append(eng)

@@ -330,3 +330,36 @@ def write_conf(path, paths, bcs, n_chunks=1, minimal_qual=25, gpu=""):
                  "index2_start : 1\nindex2_end : 8\n[output]\nwrite_pass : True\nwrite_fail : True\nwrite_undetermined : True\n" +
                  gpu + "".join("[sample%d]\nname : S%d\nindex1_seq : %s\nindex2_seq : %s\n" % (i + 1, i + 1, a, b)
                                for i, (a, b) in enumerate(bcs)))
+
+
+def make_far_barcodes(S, w1, w2, m1, m2, seed=0, alphabet=b"ACGT"):
+    """S distinct barcodes of w1 + w2 bases (list of str, in draw order) of which no two collide under the mismatch budgets
+    (m1, m2): for every pair, the Hamming distance on the first w1 bases is > 2*m1 or the distance on the last w2 bases is
+    > 2*m2 (qd_check_mismatch_collisions).  Greedy over uniform draws, vectorised (numpy): S = 8192 at 8 + 8 bases and (1, 1)
+    takes a few seconds.  A uniform sheet of cfg5's S = 1536 already collides under (1, 1)."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    alpha = np.frombuffer(alphabet, dtype=np.uint8)
+    K = w1 + w2
+
+    def clash(a, b):  # [n, K] x [m, K] -> [n, m] collision matrix
+        d = a[:, None, :] != b[None, :, :]
+        return (d[:, :, :w1].sum(-1) <= 2 * m1) & (d[:, :, w1:].sum(-1) <= 2 * m2)
+
+    out = np.empty((0, K), dtype=np.uint8)
+    for _ in range(10000):
+        if out.shape[0] >= S:
+            break
+        cand = alpha[rng.integers(0, alpha.size, (min(1024, 2 * (S - out.shape[0]) + 16), K))]
+        ok = np.ones(cand.shape[0], dtype=bool)
+        for a in range(0, out.shape[0], 2048):
+            ok &= ~clash(cand, out[a:a + 2048]).any(1)
+        cand = cand[ok]
+        c = np.triu(clash(cand, cand), k=1)  # also catches duplicates
+        keep = np.ones(cand.shape[0], dtype=bool)
+        for i in range(cand.shape[0]):  # drop the later member of every colliding pair
+            if keep[i]:
+                keep[np.flatnonzero(c[i])] = False
+        out = np.concatenate([out, cand[keep]])[:S]
+    assert out.shape[0] == S, "could not draw %d non-colliding barcodes" % S
+    return [bytes(r).decode() for r in out]
