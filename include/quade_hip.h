@@ -165,7 +165,10 @@ int qd_kernel_kind(const qd_ctx* ctx, int has_len);
  *   "kernel"                  0 = automatic (default), 1 = fast (when the plan is eligible), 2 = generic
  *   "fold_pairs"              the device counts into 32-bit per-workgroup rows that are folded into 64-bit totals
  *                             before this many pairs have been launched since the last fold (default and
- *                             maximum 2^32 - 1; tests lower it) */
+ *                             maximum 2^32 - 1; tests lower it)
+ *   "unknown_tag_bits"        (tests only: the unknown-barcode tally keeps the low b bits of a key's 64-bit tag, 1..64,
+ *                             default 64, so that tag collisions can be produced at will; set it before the first
+ *                             tallied launch or right after qd_reset_counts) */
 int qd_set_option(qd_ctx* ctx, const char* name, int64_t value);
 
 /* ---- mismatch-tolerant matching (opt-in; no reference counterpart: Quade 0.3.2 matches exactly) ---------
@@ -189,6 +192,32 @@ int qd_check_mismatch_collisions(int32_t n_samples, const uint8_t* barcodes, con
  * barcodes (QD_ERR_BARCODE, qd_last_error names the two ordinals) and builds the device tables.  Waits for
  * the context's outstanding work.  qd_set_plan and qd_set_barcodes reset both budgets to 0. */
 int qd_set_mismatches(qd_ctx* ctx, int32_t m1, int32_t m2);
+
+/* ---- top unknown barcodes (opt-in; no reference counterpart: Quade 0.3.2 only writes the Undetermined files) ------
+ * A device-resident table of `slots` entries counts the fused barcode keys of the pairs whose FINAL routing code is
+ * 0xFFFF (after the exact kernels, the ragged fix-up and the mismatch rescue).  The key is the pair's fused slice of
+ * key_width bytes after the case fold, index read 1's part then index read 2's -- the key the lookup uses; N and
+ * any other byte are ordinary symbols.  A pair with a read that ends inside its index window is not tallied by
+ * sequence: it adds 1 to `short`.  A key the table cannot admit (no free entry within the probe limit of 1024, or
+ * another key with the same 64-bit tag holds the entry) adds 1 to `dropped`.  For all work launched since the tally
+ * was enabled or emptied: sum(counts) + short + dropped == qd_get_counts()[3].  Every entry's count is exact; a key
+ * that is not in the table has at most `dropped` occurrences.  The tally is a post-pass of every launch
+ * (qd_demux_device, _ragged, qd_submit, qd_submit_ragged, qd_pipe_run) on the launch's stream; launches on different
+ * streams are ordered among themselves (the tally kernels only).  Disabled, nothing is launched or allocated.
+ *
+ * qd_unknown_enable: slots == 0 turns the tally off and frees the table; otherwise a power of two in 2^10 .. 2^28
+ * (48 bytes each; QD_ERR_INVALID).  Needs qd_set_plan and qd_set_barcodes first (QD_ERR_STATE), waits for the
+ * context's outstanding work.  qd_set_plan and qd_set_barcodes turn the tally off; qd_reset_counts empties it.
+ * qd_unknown_stats: out = {tallied pairs, short, dropped, distinct entries}; waits for the context's work;
+ * QD_ERR_STATE when the tally is off.
+ * qd_unknown_read: the occupied entries are packed on the device and only they are downloaded; entry i is
+ * keys[i*key_width .. (i+1)*key_width) with counts[i], in no particular order (sort on the host).  Returns the number
+ * of entries, or -(entries needed) when cap is too small (cap 0 with NULL arrays asks for the size), or a value
+ * <= QD_UNKNOWN_READ_ERROR on failure: QD_UNKNOWN_READ_ERROR + QD_ERR_* (qd_last_error has the text). */
+#define QD_UNKNOWN_READ_ERROR (-((int64_t)1 << 40))
+int qd_unknown_enable(qd_ctx* ctx, int64_t slots);
+int qd_unknown_stats(qd_ctx* ctx, uint64_t out[4]);
+int64_t qd_unknown_read(qd_ctx* ctx, uint8_t* keys, uint64_t* counts, int64_t cap);
 
 /* ---- counters: replace the class counters of src/Sample.py:32,144 and feed Sample.REPORT ---------
  * qd_get_counts waits for outstanding work of this context (only), then writes 2*S+4 values. */

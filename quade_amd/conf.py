@@ -6,7 +6,7 @@ sections, option names, 1-based -> 0-based start conversion, assertion messages)
 file written by `-i` is the reference's template byte for byte (src/Conf_file.py:18-104; shipped as
 package data, quade_amd/data/Quade_conf_file.txt).  An optional [gpu] section that reference conf
 files simply do not have is read when present (defaults apply otherwise; see GPU_SECTION_HELP), and so are the optional
-mismatch budgets of the [index] section (MISMATCH_HELP).
+mismatch budgets of the [index] section (MISMATCH_HELP) and the unknown-barcode report of the [output] section (UNKNOWN_HELP).
 """
 from __future__ import annotations
 
@@ -56,6 +56,16 @@ Optional [index] options (not in Quade 0.3.2, whose parser ignores them; absent 
 A read whose barcode slice has no exact match goes to the one sample whose barcode is within both budgets (N counts as an
 ordinary base).  Two samples whose barcodes are within 2 x index1_mismatches and 2 x index2_mismatches of each other collide:
 the configuration is rejected before any read is processed.
+"""
+
+UNKNOWN_HELP = """\
+Optional [output] option (not in Quade 0.3.2, whose parser ignores it; absent or empty = 0 = no report):
+  top_unknown_barcodes : 0  0 to 1000: write Quade_unknown_barcodes.csv with the N most frequent barcodes of the Undetermined
+                            pairs (index1_seq, index2_seq, count, percent of Undetermined, the nearest sample and its distance
+                            per index read).  The barcodes are counted on the GPU, in a table of [gpu] unknown_slots entries
+Optional [gpu] option:
+  unknown_slots : 16777216  entries of that table per context: a power of two, 1024 to 268435456 (48 bytes each).  Barcodes that
+                            find no room are counted as "Not tallied" in the report's head
 """
 
 
@@ -118,6 +128,10 @@ class QuadeConf(object):
         self.write_undetermined = cp.getboolean("output", "write_undetermined")
         self.write_pass = cp.getboolean("output", "write_pass")
         self.write_fail = cp.getboolean("output", "write_fail")
+        # optional report of the most frequent unknown barcodes (extension, UNKNOWN_HELP): 0 = none
+        self.top_unknown_barcodes = 0
+        if cp.has_option("output", "top_unknown_barcodes") and cp.get("output", "top_unknown_barcodes") not in (None, ""):
+            self.top_unknown_barcodes = cp.getint("output", "top_unknown_barcodes")
 
         # (name, fused barcode) per [sample*] section, in file order (src/Quade.py:133-139)
         self.samples = []
@@ -140,6 +154,7 @@ class QuadeConf(object):
         self.gzip_level = opt("gzip_level", 1)
         self.chunk_workers = opt("chunk_workers", 1)
         self.io_threads = opt("io_threads", 0)
+        self.unknown_slots = opt("unknown_slots", 1 << 24)
         self.device_inflate = opt("device_inflate", "True", str).strip().lower() in ("true", "1", "yes", "on")
         self.device_deflate = opt("device_deflate", "True", str).strip().lower() in ("true", "1", "yes", "on")
         # the whole chunk loop on the device (qd_pipe_*): text stays in HBM from the inflater to the coder.  Needs the device's
@@ -170,6 +185,9 @@ class QuadeConf(object):
                 is_readable_file(fp)
         assert 0 <= self.idx1_mismatches <= 2, "Authorized values for index1_mismatches : 0 to 2"
         assert 0 <= self.idx2_mismatches <= 2, "Authorized values for index2_mismatches : 0 to 2"
+        assert 0 <= self.top_unknown_barcodes <= 1000, "Authorized values for top_unknown_barcodes : 0 to 1000"
+        assert 1 << 10 <= self.unknown_slots <= 1 << 28 and self.unknown_slots & (self.unknown_slots - 1) == 0, \
+            "[gpu] unknown_slots : a power of two, 1024 to 268435456"
         for pos in [self.idx1_pos, self.idx2_pos, self.mol1_pos, self.mol2_pos]:
             assert pos["start"] >= 0
             assert pos["end"] >= pos["start"]

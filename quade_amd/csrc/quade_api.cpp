@@ -20,6 +20,8 @@
 #include "quade_inflate3.h"
 #include "quade_deflate.h"
 #include "quade_mismatch.h"
+#include "quade_unknown.h"
+#include "quade_pool.h"
 
 typedef uint64_t u64;
 
@@ -117,6 +119,23 @@ struct qd_ctx {
         size_t cap;  // uint32 entries
     };
     std::vector<MmScratch> mm_scratch;
+
+    // tally of the unknown barcodes (qd_unknown_enable): the table (one allocation), per stream the scratch of a batch
+    // ([0] = count and the list of its undetermined pairs from [4], then from [4 + pairs] each listed pair's slot), and the event
+    // behind the last launch's uk_count that a launch on another stream waits for before its uk_claim
+    int64_t uk_slots = 0;  // 0 = off
+    void* d_uk = nullptr;
+    UnknownTable uk{};
+    int uk_tag_bits = 64;  // option "unknown_tag_bits" (tests)
+    hipEvent_t uk_done = nullptr;
+    hipStream_t uk_last = nullptr;
+    bool uk_recorded = false;
+    struct UkScratch {
+        hipStream_t stream;
+        uint32_t* buf;
+        size_t pairs;  // 2 * pairs + 4 uint32 entries
+    };
+    std::vector<UkScratch> uk_scratch;
 };
 
 namespace {
@@ -286,6 +305,81 @@ int launch_mismatch(qd_ctx* c, int64_t n, const qd_rows* rows, uint16_t* codes, 
     p.n = n;
     hipError_t e = qd_launch_mismatch(p, sc->buf, c->cu, st);
     if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("mismatch launch: ") + hipGetErrorString(e));
+    return QD_OK;
+}
+
+// hipMalloc; out of memory: the pool's idle buffers go back to the driver once (it can hold tens of GB) and the call is repeated
+hipError_t uk_malloc(void** p, size_t bytes) {
+    hipError_t e = hipMalloc(p, bytes);
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        (void)qd_pool_trim();
+        e = hipMalloc(p, bytes);
+    }
+    return e;
+}
+
+// the tally off and its memory freed (the caller waited for the context's work)
+void free_unknown(qd_ctx* c) {
+    if (c->d_uk) (void)hipFree(c->d_uk);
+    c->d_uk = nullptr;
+    c->uk_slots = 0;
+    c->uk_recorded = false;
+    for (auto& m : c->uk_scratch) (void)hipFree(m.buf);
+    c->uk_scratch.clear();
+    if (c->uk_done) (void)hipEventDestroy(c->uk_done);
+    c->uk_done = nullptr;
+}
+
+// the tally post-pass of a batch on `st` (launch(), tally enabled), behind the rescue when one ran (`rescued`: its list is reused)
+int launch_unknown(qd_ctx* c, int64_t n, const qd_rows* rows, const uint16_t* codes, hipStream_t st, bool rescued) {
+    qd_ctx::UkScratch* sc = nullptr;
+    for (auto& m : c->uk_scratch)
+        if (m.stream == st) sc = &m;
+    if (!sc) {
+        c->uk_scratch.push_back(qd_ctx::UkScratch{st, nullptr, 0});
+        sc = &c->uk_scratch.back();
+    }
+    if (sc->pairs < (size_t)n) {
+        HIPCHK(c, hipStreamSynchronize(st));  // the old scratch may still be read by this stream's previous batch
+        if (sc->buf) (void)hipFree(sc->buf);
+        sc->buf = nullptr;
+        const size_t pairs = std::max<size_t>((size_t)n, sc->pairs * 2);
+        sc->pairs = 0;
+        HIPCHK(c, uk_malloc(reinterpret_cast<void**>(&sc->buf), (2 * pairs + 4) * 4));
+        sc->pairs = pairs;
+    }
+    uint32_t* list = sc->buf;
+    if (rescued) {
+        for (auto& m : c->mm_scratch)
+            if (m.stream == st) list = m.buf;
+    } else {
+        hipError_t e = qd_launch_compact(codes, n, list, st);
+        if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("unknown tally list: ") + hipGetErrorString(e));
+    }
+    UnknownParams p{};
+    const qd_layout& L = c->lay;
+    const qd_plan& P = c->plan;
+    const int is[2] = {P.idx1_start, P.idx2_start}, ie[2] = {P.idx1_end, P.idx2_end};
+    p.n_streams = L.n_streams;
+    p.K = L.key_width;
+    for (int k = 0; k < L.n_streams; ++k) {
+        p.seq[k] = rows->seq[k];
+        p.seq_stride[k] = L.seq_stride[k];
+        p.idx_w[k] = ie[k] - is[k];
+        p.idx_off[k] = p.idx_w[k] ? is[k] - L.seq_off[k] : 0;
+    }
+    p.codes = codes;
+    p.miss = list;
+    p.where = sc->buf + 4 + sc->pairs;
+    p.t = c->uk;
+    p.t.tag_mask = c->uk_tag_bits >= 64 ? ~0ull : ((1ull << c->uk_tag_bits) - 1);
+    p.n = n;
+    hipError_t e = qd_launch_unknown(p, c->cu, c->uk_recorded && c->uk_last != st ? c->uk_done : nullptr, st);
+    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("unknown tally launch: ") + hipGetErrorString(e));
+    HIPCHK(c, hipEventRecord(c->uk_done, st));
+    c->uk_recorded = true;
+    c->uk_last = st;
     return QD_OK;
 }
 
@@ -557,6 +651,10 @@ int launch(qd_ctx* c, int64_t n, const qd_rows* rows, uint16_t* codes, uint8_t* 
         const int r = launch_mismatch(c, n, rows, codes, st);
         if (r != QD_OK) return r;
     }
+    if (c->uk_slots) {  // opt-in tally of the pairs that stay undetermined, behind the rescue
+        const int r = launch_unknown(c, n, rows, codes, st, c->mm_m1 + c->mm_m2 > 0);
+        if (r != QD_OK) return r;
+    }
     c->total_pairs += (uint64_t)n;
     c->pairs_in_rows += (uint64_t)n;
     e = track(c, st);
@@ -634,6 +732,7 @@ int qd_destroy(qd_ctx* c) {
     qd_slots_destroy(c);
     free_table(c);
     free_mismatch(c, true);
+    free_unknown(c);
     for (auto& t : c->tracked) (void)hipEventDestroy(t.second);
     c->tracked.clear();
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -656,10 +755,11 @@ int qd_set_plan(qd_ctx* c, const qd_plan* plan) {
     if (r != QD_OK) return fail(c, r, "plan rejected: positions must satisfy 0 <= start <= end <= 255, window <= 64, "
                                        "fused barcode <= 32, 0 <= minimal_qual <= 40");
     if (!c->slots.empty()) return fail(c, QD_ERR_STATE, "destroy the slots before changing the plan");
-    if (c->mm_m1 + c->mm_m2 > 0) {  // a new plan resets the mismatch budgets
+    if (c->mm_m1 + c->mm_m2 > 0 || c->uk_slots) {  // a new plan resets the mismatch budgets and turns the unknown tally off
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, wait_all(c));
         free_mismatch(c, false);
+        free_unknown(c);
     }
     c->plan = *plan;
     c->lay = L;
@@ -694,10 +794,11 @@ int qd_set_barcodes(qd_ctx* c, int32_t S, const uint8_t* barcodes, const int32_t
     if (!c->have_plan) return fail(c, QD_ERR_STATE, "qd_set_plan first");
     for (int i = 0; i < S; ++i)
         if (offsets[i + 1] < offsets[i]) return fail(c, QD_ERR_INVALID, "offsets must be non-decreasing");
-    if (c->mm_m1 + c->mm_m2 > 0) {  // new barcodes reset the mismatch budgets, as they reset the counters
+    if (c->mm_m1 + c->mm_m2 > 0 || c->uk_slots) {  // new barcodes reset the mismatch budgets, as they reset the counters, and turn the unknown tally off
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, wait_all(c));
         free_mismatch(c, false);
+        free_unknown(c);
     }
     c->S = S;
     c->bc.assign(barcodes, barcodes + (S ? offsets[S] : 0));
@@ -761,6 +862,73 @@ int qd_set_mismatches(qd_ctx* c, int32_t m1, int32_t m2) {
     return QD_OK;
 }
 
+int qd_unknown_enable(qd_ctx* c, int64_t slots) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->have_plan || !c->have_table) return fail(c, QD_ERR_STATE, "qd_set_plan and qd_set_barcodes first");
+    if (slots != 0 && (slots < ((int64_t)1 << QD_UK_MIN_LG) || slots > ((int64_t)1 << QD_UK_MAX_LG) || (slots & (slots - 1))))
+        return fail(c, QD_ERR_INVALID, "unknown-barcode slots must be 0 (off) or a power of two in 2^10 .. 2^28");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));  // nothing of this context may still use the old table
+    free_unknown(c);
+    if (slots == 0) return QD_OK;
+    hipError_t e = uk_malloc(&c->d_uk, qd_uk_bytes(slots));
+    if (e != hipSuccess) {
+        c->d_uk = nullptr;
+        return fail(c, QD_ERR_HIP, std::string("unknown-barcode table: ") + hipGetErrorString(e));
+    }
+    HIPCHK(c, hipMemsetAsync(c->d_uk, 0, qd_uk_bytes(slots), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipEventCreateWithFlags(&c->uk_done, hipEventDisableTiming));
+    qd_uk_carve(c->d_uk, slots, c->uk);
+    c->uk_slots = slots;
+    return QD_OK;
+}
+
+int qd_unknown_stats(qd_ctx* c, uint64_t out[4]) {
+    if (!c || !out) return QD_ERR_INVALID;
+    if (!c->uk_slots) return fail(c, QD_ERR_STATE, "the unknown-barcode tally is not enabled");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));
+    HIPCHK(c, hipMemcpy(out, c->uk.totals, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return QD_OK;
+}
+
+int64_t qd_unknown_read(qd_ctx* c, uint8_t* keys, uint64_t* counts, int64_t cap) {
+    auto bad = [&](int code, const std::string& msg) { return QD_UNKNOWN_READ_ERROR + (int64_t)fail(c, code, msg); };
+    if (!c || cap < 0 || (cap > 0 && (!keys || !counts))) return bad(QD_ERR_INVALID, "bad arguments");
+    if (!c->uk_slots) return bad(QD_ERR_STATE, "the unknown-barcode tally is not enabled");
+    uint64_t tot[4];
+    hipError_t e = hipSetDevice(c->device);
+    if (e == hipSuccess) e = wait_all(c);
+    if (e == hipSuccess) e = hipMemcpy(tot, c->uk.totals, sizeof tot, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return bad(QD_ERR_HIP, std::string("unknown-barcode read: ") + hipGetErrorString(e));
+    const int64_t D = (int64_t)tot[QD_UK_DISTINCT];
+    if (D > cap) return -D;
+    if (D == 0) return 0;
+    // the occupied entries packed on the device: only they cross the link
+    uint8_t* d_out = nullptr;
+    const size_t kbytes = (size_t)D * QD_KEY_WORDS * 8, cbytes = (size_t)D * 8;
+    if ((e = uk_malloc(reinterpret_cast<void**>(&d_out), kbytes + cbytes + 16)) != hipSuccess)
+        return bad(QD_ERR_HIP, std::string("unknown-barcode read: ") + hipGetErrorString(e));
+    u64* d_keys = reinterpret_cast<u64*>(d_out);
+    u64* d_counts = reinterpret_cast<u64*>(d_out + kbytes);
+    uint32_t* d_n = reinterpret_cast<uint32_t*>(d_out + kbytes + cbytes);
+    std::vector<u64> hk((size_t)D * QD_KEY_WORDS);
+    uint32_t got = 0;
+    e = qd_launch_unknown_gather(c->uk, d_keys, d_counts, d_n, (uint32_t)D, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hk.data(), d_keys, kbytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, cbytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&got, d_n, 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d_out);
+    if (e != hipSuccess) return bad(QD_ERR_HIP, std::string("unknown-barcode read: ") + hipGetErrorString(e));
+    if ((int64_t)got != D) return bad(QD_ERR_HIP, "unknown-barcode read: the table's entry count and its occupied entries differ");
+    const int K = c->lay.key_width;
+    for (int64_t i = 0; i < D; ++i)
+        for (int b = 0; b < K; ++b) keys[i * K + b] = (uint8_t)(hk[(size_t)i * QD_KEY_WORDS + (b >> 3)] >> (8 * (b & 7)));
+    return D;
+}
+
 int qd_kernel_kind(const qd_ctx* c, int has_len) {
     if (!c || !c->have_table) return QD_ERR_STATE;
     return pick_kernel(c, has_len != 0);
@@ -800,6 +968,11 @@ int qd_set_option(qd_ctx* c, const char* name, int64_t value) {
     if (!strcmp(name, "fold_pairs")) {  // test knob: fold the 32-bit counter rows this often (default 2^32 - 1)
         if (value < 1 || value > (int64_t)0xFFFFFFFF) return fail(c, QD_ERR_INVALID, "fold_pairs must be 1..2^32-1");
         c->fold_limit = (uint64_t)value;
+        return QD_OK;
+    }
+    if (!strcmp(name, "unknown_tag_bits")) {  // test knob: the tally keeps this many low bits of a key's tag (default 64), so tag collisions can be made
+        if (value < 1 || value > 64) return fail(c, QD_ERR_INVALID, "unknown_tag_bits must be 1..64");
+        c->uk_tag_bits = (int)value;
         return QD_OK;
     }
     return fail(c, QD_ERR_INVALID, std::string("unknown option ") + name);
@@ -902,6 +1075,7 @@ int qd_reset_counts(qd_ctx* c) {
     HIPCHK(c, join_into_own_stream(c));
     HIPCHK(c, hipMemsetAsync(c->d_partial, 0, (size_t)c->partial_rows * c->cnt_stride * sizeof(qd_row_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_acc, 0, (size_t)c->cnt_stride * 8, c->stream));
+    if (c->uk_slots) HIPCHK(c, hipMemsetAsync(c->d_uk, 0, qd_uk_bytes(c->uk_slots), c->stream));  // sum(counts) + short + dropped == UNDETERMINED stays true
     HIPCHK(c, track(c, c->stream));  // later launches on other streams are not ordered behind this: wait here
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->total_pairs = 0;

@@ -62,5 +62,8 @@ bool qd_mm_first_collision(int32_t S, const uint8_t* barcodes, const int32_t* of
 void qd_mm_build(int32_t S, const uint8_t* barcodes, const int32_t* offsets, int32_t K, int32_t w1, int32_t m1, int32_t m2,
                  MismatchParams& p, std::vector<QdMmBucket>& htab, std::vector<uint16_t>& cand);
 
+// Device: the undetermined pairs of codes[0..n) listed in miss ([0] = count, zeroed first; the list from [4] on, n entries at most).
+hipError_t qd_launch_compact(const uint16_t* codes, int64_t n, uint32_t* miss, hipStream_t st);
+
 // Device: compaction of the undetermined pairs of codes[0..n) into miss (zeroed count first), then the rescue.
 hipError_t qd_launch_mismatch(const MismatchParams& p, uint32_t* miss, int cus, hipStream_t st);

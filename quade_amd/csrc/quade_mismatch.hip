@@ -21,49 +21,13 @@
 
 #include "quade_kernels.h"
 #include "quade_mismatch.h"
+#include "quade_rowkey.h"
 
 namespace {
 
 typedef uint64_t u64;
 constexpr int MM_BLOCK = 256;
 constexpr int MM_ITERS = 16;  // 8-code groups per lane of mm_compact
-
-// nbytes (<= 8 * NW) bytes at p (any alignment) -> little-endian words, zero padded: aligned dword loads, no word read that
-// holds no byte of the slice.  Same scheme as load_bytes in quade_generic.hip (wmax = nbytes: every listed pair covers its window).
-template <int NW>
-__device__ __forceinline__ void mm_load(const uint8_t* p, int nbytes, u64 (&w)[NW]) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-    const uint32_t* q = reinterpret_cast<const uint32_t*>(a & ~(uintptr_t)3);
-    const int sh = (int)(a & 3), need = sh + nbytes;
-    const int ju = nbytes > 0 ? (nbytes + 6) >> 2 : 0;  // dwords that can hold 3 + nbytes bytes (uniform)
-    const int jl = need > 0 ? (need - 1) >> 2 : 0;      // the lane's last needed dword: re-read instead of a per-lane branch
-    uint32_t d[2 * NW + 1];
-#pragma unroll
-    for (int j = 0; j < 2 * NW + 1; ++j) d[j] = (j < ju) ? q[j < jl ? j : jl] : 0u;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) {
-        const u64 lo = (u64)d[2 * i] | ((u64)d[2 * i + 1] << 32), nx = d[2 * i + 2];
-        const u64 v = sh ? (lo >> (8 * sh)) | (nx << (64 - 8 * sh)) : lo;
-        const int left = nbytes - 8 * i;
-        w[i] = left >= 8 ? v : (left <= 0 ? 0 : v & ((1ull << (8 * left)) - 1));
-    }
-}
-
-// w |= v << (8 * off) over the 64 * NW bits
-template <int NW>
-__device__ __forceinline__ void mm_or_shifted(u64 (&w)[NW], const u64 (&v)[NW], int off) {
-    const int ws = off >> 3, bs = (off & 7) * 8;
-#pragma unroll
-    for (int i = 0; i < NW; ++i) {
-        u64 cur = 0, prev = 0;
-#pragma unroll
-        for (int j = 0; j < NW; ++j) {
-            cur = (j == i - ws) ? v[j] : cur;
-            prev = (j == i - ws - 1) ? v[j] : prev;
-        }
-        w[i] |= bs ? (cur << bs) | (prev >> (64 - bs)) : cur;
-    }
-}
 
 // undetermined flags of the 8 codes codes[base .. base + 8) (bit i = codes[base + i]); 16-byte loads where all 8 are in the batch
 __device__ __forceinline__ uint32_t mm_undet_bits(const uint16_t* codes, int64_t n, int64_t base) {
@@ -353,13 +317,19 @@ void qd_mm_build(int32_t S, const uint8_t* barcodes, const int32_t* offsets, int
     if (cand.empty()) cand.push_back(0);  // never read (ncand 0, no bucket), keeps the device array non-empty
 }
 
-hipError_t qd_launch_mismatch(const MismatchParams& p, uint32_t* miss, int cus, hipStream_t st) {
-    if (p.n <= 0) return hipSuccess;
+hipError_t qd_launch_compact(const uint16_t* codes, int64_t n, uint32_t* miss, hipStream_t st) {
+    if (n <= 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(miss, 0, 4, st);
     if (e != hipSuccess) return e;
-    const int64_t groups = (p.n + 7) / 8, per_block = (int64_t)MM_BLOCK * MM_ITERS;
-    hipLaunchKernelGGL(mm_compact, dim3((unsigned)((groups + per_block - 1) / per_block)), dim3(MM_BLOCK), 0, st, p.codes, p.n, miss);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    const int64_t groups = (n + 7) / 8, per_block = (int64_t)MM_BLOCK * MM_ITERS;
+    hipLaunchKernelGGL(mm_compact, dim3((unsigned)((groups + per_block - 1) / per_block)), dim3(MM_BLOCK), 0, st, codes, n, miss);
+    return hipGetLastError();
+}
+
+hipError_t qd_launch_mismatch(const MismatchParams& p, uint32_t* miss, int cus, hipStream_t st) {
+    if (p.n <= 0) return hipSuccess;
+    hipError_t e = qd_launch_compact(p.codes, p.n, miss, st);
+    if (e != hipSuccess) return e;
     const int64_t nb = (p.n + MM_BLOCK - 1) / MM_BLOCK;
     const unsigned grid = (unsigned)std::min<int64_t>(nb, (int64_t)cus * 8);
     const size_t lds = (size_t)p.hist_entries * 4;

@@ -18,6 +18,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libquade_hip.so")
 QD_OK = 0
 QD_ERR_INVALID, QD_ERR_NO_DEVICE, QD_ERR_HIP, QD_ERR_STATE = -1, -2, -3, -4
 QD_ERR_UNSUPPORTED, QD_ERR_BARCODE, QD_ERR_FORMAT = -5, -6, -7
+QD_UNKNOWN_READ_ERROR = -(1 << 40)  # qd_unknown_read: a value <= this is this + QD_ERR_*
 CODE_UNDETERMINED = 0xFFFF
 
 
@@ -99,6 +100,9 @@ SYMBOLS = [
     ("qd_check_mismatch_collisions", C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("qd_set_mismatches", C.c_int, [_P, C.c_int32, C.c_int32]),
+    ("qd_unknown_enable", C.c_int, [_P, C.c_int64]),
+    ("qd_unknown_stats", C.c_int, [_P, _P]),
+    ("qd_unknown_read", C.c_int64, [_P, _P, _P, C.c_int64]),
     ("qd_get_counts", C.c_int, [_P, _P, C.c_int32]),
     ("qd_reset_counts", C.c_int, [_P]),
     ("qd_add_counts", C.c_int, [_P, _P, C.c_int32]),
@@ -374,6 +378,39 @@ def check_mismatch_collisions(barcodes, key_width, w1, m1, m2):
     return None
 
 
+def merge_unknown(tables):
+    """Host: unknown-barcode tables (keys uint8[n, K], counts uint64[n]) of several contexts or ranks -> one table with the counts
+    of equal keys summed, in report order: count descending, then key bytes ascending.  Returns (keys, counts)."""
+    tables = [(np.asarray(k, dtype=np.uint8), np.asarray(c, dtype=np.uint64)) for k, c in tables]
+    tables = [(k.reshape(c.size, -1), c) for k, c in tables if c.size]
+    if not tables:
+        return np.zeros((0, 0), dtype=np.uint8), np.zeros(0, dtype=np.uint64)
+    K = tables[0][0].shape[1]
+    assert all(k.shape[1] == K for k, _ in tables), "tables of different key widths"
+    keys = np.concatenate([k for k, _ in tables])
+    counts = np.concatenate([c for _, c in tables])
+    uniq, inv = np.unique(keys, axis=0, return_inverse=True)  # rows ascending by bytes
+    total = np.zeros(uniq.shape[0], dtype=np.uint64)
+    np.add.at(total, inv.reshape(-1), counts)
+    order = np.argsort(-total.astype(np.int64), kind="stable")
+    return np.ascontiguousarray(uniq[order]), total[order]
+
+
+def pack_unknown(keys, counts, short, dropped):
+    """One context's or rank's tally as bytes (the ranks' exchange through the rendezvous directory); unpack_unknown reverses it."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint8).reshape(len(counts), -1) if len(counts) else np.zeros((0, 0), dtype=np.uint8)
+    head = np.array([len(counts), keys.shape[1] if len(counts) else 0, short, dropped], dtype=np.uint64)
+    return head.tobytes() + keys.tobytes() + np.ascontiguousarray(counts, dtype=np.uint64).tobytes()
+
+
+def unpack_unknown(blob):
+    """-> (keys uint8[n, K], counts uint64[n], short, dropped)"""
+    n, K, short, dropped = (int(x) for x in np.frombuffer(blob, dtype=np.uint64, count=4))
+    keys = np.frombuffer(blob, dtype=np.uint8, count=n * K, offset=32).reshape(n, K)
+    counts = np.frombuffer(blob, dtype=np.uint64, count=n, offset=32 + n * K)
+    return keys, counts, short, dropped
+
+
 # ---- device context -------------------------------------------------------------------------------------
 class Engine(object):
     """One libquade_hip context = one MI355X.  Mirrors what Sample.CLASS_INIT + Sample(name, index)
@@ -442,6 +479,34 @@ class Engine(object):
         """Mismatch budgets of index read 1's and index read 2's part (0..2 each; qd_set_mismatches).  After set_barcodes:
         set_plan and set_barcodes reset them to 0."""
         self._chk(self.lib.qd_set_mismatches(self._h, int(m1), int(m2)))
+
+    def unknown_enable(self, slots):
+        """Tally of the unknown barcodes (qd_unknown_enable): a device table of `slots` entries (a power of two, 2^10 .. 2^28)
+        counts the fused barcode keys of the pairs that stay Undetermined; 0 turns it off.  After set_barcodes (and
+        set_mismatches): set_plan and set_barcodes turn it off, reset_counts empties it."""
+        self._chk(self.lib.qd_unknown_enable(self._h, int(slots)))
+
+    def unknown_stats(self):
+        """numpy uint64[4]: tallied pairs, short slices, dropped (not admitted to the table), distinct entries"""
+        out = np.zeros(4, dtype=np.uint64)
+        self._chk(self.lib.qd_unknown_stats(self._h, _ptr(out)))
+        return out
+
+    def unknown_read(self):
+        """The table's entries in no particular order: (keys uint8[n, key_width], counts uint64[n])."""
+        K = self.layout.key_width if self.layout is not None else 0
+        n = self.lib.qd_unknown_read(self._h, None, None, 0)
+        while True:
+            if n <= QD_UNKNOWN_READ_ERROR:
+                self._chk(int(n - QD_UNKNOWN_READ_ERROR))
+            if n == 0:
+                return np.zeros((0, K), dtype=np.uint8), np.zeros(0, dtype=np.uint64)
+            cap = int(-n)
+            keys = np.zeros((cap, K), dtype=np.uint8)
+            counts = np.zeros(cap, dtype=np.uint64)
+            n = self.lib.qd_unknown_read(self._h, _ptr(keys), _ptr(counts), cap)
+            if n > 0:
+                return keys[:n], counts[:n]
 
     def set_option(self, name, value):
         self._chk(self.lib.qd_set_option(self._h, name.encode(), int(value)))

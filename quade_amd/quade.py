@@ -165,6 +165,8 @@ class Quade(object):
                 eng.set_barcodes(Sample.BARCODES())
                 if cf.idx1_mismatches + cf.idx2_mismatches > 0:
                     eng.set_mismatches(cf.idx1_mismatches, cf.idx2_mismatches)
+                if cf.top_unknown_barcodes > 0:  # the barcodes of the Undetermined pairs are counted on the device
+                    eng.unknown_enable(cf.unknown_slots)
                 if not self.use_pipe:
                     eng.slots_create(cf.slots, cf.batch_pairs)
                 group.append(eng)
@@ -189,6 +191,7 @@ class Quade(object):
         with _timed("drain gzip + close"):
             Sample.FLUSH_ALL()  # every rank's files are complete before its counters join the sum
         counts = self._reduce_counts(devices)
+        unknown = self._collect_unknown() if cf.top_unknown_barcodes > 0 else None
         for eng in self.engines:
             eng.close()
         self.engines = []
@@ -220,6 +223,12 @@ class Quade(object):
             report.write("Program {}\tDate {}\n\n".format(self.VERSION, str(datetime.today())))
             for descr, value in Sample.REPORT():
                 report.write("{}\t{}\n".format(descr, value))
+        if unknown is not None:
+            from .unknown_report import REPORT_NAME, write_report
+            keys, ucounts, short, dropped = unknown
+            w1 = cf.idx1_pos["end"] - cf.idx1_pos["start"]
+            write_report(os.path.join(self.outdir, REPORT_NAME), keys, ucounts, short, dropped, int(counts[3]),
+                         cf.top_unknown_barcodes, w1, bool(cf.idx2), [(s.name, s.index) for s in Sample.SAMPLE_LIST])
         print("Done in {}s".format(round(time() - start_time, 3)))
         if _PROFILE:
             for k, v in sorted(_T.items(), key=lambda kv: -kv[1]):
@@ -267,6 +276,26 @@ class Quade(object):
             counts = dist.sum_counts_through_files(self.outdir, self.token, self.rank, self.world, counts)
             self.count_reduce = {"backend": "files (rehearsal: ranks sharing one GPU)", "seconds": None, "members": self.world}
         return counts
+
+    def _collect_unknown(self):
+        """[output] top_unknown_barcodes: the tables of every context of this process merged (equal keys summed); with several
+        ranks every rank publishes its merged table in the rendezvous directory and merges all of them (rank 0 writes the
+        file).  Returns (keys uint8[n, K], counts uint64[n], short, dropped)."""
+        from . import dist
+        tables, short, dropped = [], 0, 0
+        for eng in self.engines:
+            st = eng.unknown_stats()
+            short += int(st[1])
+            dropped += int(st[2])
+            tables.append(eng.unknown_read())
+        keys, ucounts = hb.merge_unknown(tables)
+        if self.world > 1:
+            got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, "unknown",
+                                       hb.pack_unknown(keys, ucounts, short, dropped))
+            parts = [hb.unpack_unknown(b) for b in got]
+            keys, ucounts = hb.merge_unknown([(k, c) for k, c, _, _ in parts])
+            short, dropped = sum(p[2] for p in parts), sum(p[3] for p in parts)
+        return keys, ucounts, short, dropped
 
     def double_index_parser(self):
         cf = self.cf
