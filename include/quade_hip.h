@@ -581,12 +581,11 @@ int qd_pipe_index(qd_pipe* pipe, const char* path, int32_t world, int32_t rank, 
  * text, less (down to 64 KiB) when thousands of destinations would need more slots than that;
  * "device_gunzip": 1 (default) = ordinary gzip files (one or more members that are not BGZF blocks) are inflated on the device too
  * (gz_probe / inflate3_tokens / gz_resolve / gz_windows / gz_fixup); 0 = by the host's parallel inflater, uploaded as text;
- * "inflate_form": 3 (default) = every DEFLATE symbol decoded once, one lane per block, the blocks of all four streams' uploads in one
- * launch, a workgroup per block resolves the tokens (quade_inflate3.hip); 2 = speculative spans, a launch per stream and eight uploads;
- * "inflate_streams" (form 2): 1 (default) = the BGZF inflate launches go down the compute stream one after the other; 2 = they alternate between
- * two streams of their own, so one launch's last blocks and the next one's first share the device (measured slower: DESIGN.md 4.4);
  * "test_fail_inflate_batch": tests -- the device's BGZF result of that batch is treated as refused;
- * "test_host_code_every": tests -- every k-th member is coded by the host, as one that did not fit its slot on the device would be */
+ * "test_host_code_every": tests -- every k-th member is coded by the host, as one that did not fit its slot on the device would be.
+ * Any other name is QD_ERR_INVALID -- also the names that selected variants which were measured, not kept and have been removed
+ * (another BGZF inflate form, a second inflate stream, the coder on a stream of its own: DESIGN.md 7).  The pipeline inflates BGZF
+ * blocks with quade_inflate3.hip on one stream and codes on the compute stream.  No exported function changed: QD_ABI_VERSION stays 6. */
 int qd_pipe_set_option(qd_pipe* pipe, const char* name, int64_t value);
 int qd_pipe_run(qd_pipe* pipe, const qd_pipe_chunk* chunks, int32_t n_chunks, qd_pipe_stats* stats);
 const char* qd_pipe_last_error(const qd_pipe* pipe);

@@ -1481,6 +1481,47 @@ hipError_t wait_event_napping(hipEvent_t ev) {
         usleep(nap_us);
     }
 }
+// The first n blocks of f->d_blk (states to f->d_st) through the speculative spans (form 2) when that form is allowed and the longest
+// payload leaves its workgroup room in 160 KB of LDS -- beyond ~52 KB, stored blocks, it does not -- else a wave per block (form 1).
+int inflate_spans_or_wave(qd_inflater* f, uint32_t n, uint32_t longest, bool spans_allowed) {
+    if (!spans_allowed || qd_inflate2_lds(longest) > 160 * 1024) {
+        INFCHK(f, qd_launch_inflate(f->d_comp, f->d_blk, n, f->d_out, f->d_st, f->stream));
+        return QD_OK;
+    }
+    if (n > f->cap_matches) {
+        if (f->d_matches) (void)hipFree(f->d_matches);
+        f->d_matches = nullptr;
+        f->cap_matches = 0;
+        const size_t nb = (size_t)n + n / 4 + 16;
+        INFCHK(f, hipMalloc((void**)&f->d_matches, nb * (size_t)QD_INFLATE_MATCHES_PER_BLOCK * 8));
+        f->cap_matches = nb;
+    }
+    static const bool debug_rounds = getenv("QUADE_INFLATE_DEBUG") != nullptr;  // measurement: rounds per block on stderr
+    uint32_t* d_rounds = nullptr;
+    if (debug_rounds) INFCHK(f, hipMalloc((void**)&d_rounds, (size_t)n * 32));
+    INFCHK(f, qd_launch_inflate2(f->d_comp, f->d_blk, n, f->d_out, f->d_st, f->d_matches, QD_INFLATE_MATCHES_PER_BLOCK, longest,
+                                 f->stream, d_rounds));
+    if (debug_rounds) {
+        std::vector<uint32_t> r((size_t)n * 8);
+        INFCHK(f, hipMemcpy(r.data(), d_rounds, (size_t)n * 32, hipMemcpyDeviceToHost));
+        (void)hipFree(d_rounds);
+        uint64_t sum = 0, db = 0, tk[8] = {0};
+        uint32_t mx = 0, over8 = 0;
+        for (size_t q = 0; q < n; ++q) {
+            const uint32_t v = r[8 * q];
+            sum += v & 0xFFFF;
+            db += v >> 16;
+            mx = std::max(mx, v & 0xFFFF);
+            over8 += (v & 0xFFFF) > 8;
+            for (int k = 1; k < 8; ++k) tk[k] += r[8 * q + k];
+        }
+        const double us = 0.01 / (double)n;  // 100 MHz ticks -> microseconds per block
+        fprintf(stderr, "[inflate form 2] %u blocks: %.2f rounds and %.2f deflate blocks per block, most %u, %u blocks over 8 rounds; us per block: stage %.0f "
+                        "header+tables %.0f rounds %.0f scan+write %.0f matches %.0f flush %.0f; %.0f matches per block\n", n, (double)sum / n,
+                (double)db / n, mx, over8, tk[1] * us, tk[2] * us, tk[3] * us, tk[4] * us, tk[5] * us, tk[6] * us, (double)tk[7] / n);
+    }
+    return QD_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1617,41 +1658,9 @@ static int inflater_run(qd_inflater* f, const uint8_t* comp, int64_t comp_len, u
         }
         INFCHK(f, qd_launch_inflate3(f->d_comp, (size_t)comp_len, f->d_blk, (uint32_t)blk.size(), f->d_out, f->d_st, f->d_scratch3, f->stream));
         form3_ran = true;
-    } else if (f->form == 2 && qd_inflate2_lds(longest) <= 160 * 1024) {  // (a run with a payload beyond ~52 KB -- stored blocks -- takes the first form)
-        if (blk.size() > f->cap_matches) {
-            if (f->d_matches) (void)hipFree(f->d_matches);
-            f->d_matches = nullptr;
-            f->cap_matches = 0;
-            const size_t nb = blk.size() + blk.size() / 4 + 16;
-            INFCHK(f, hipMalloc((void**)&f->d_matches, nb * (size_t)QD_INFLATE_MATCHES_PER_BLOCK * 8));
-            f->cap_matches = nb;
-        }
-        static const bool debug_rounds = getenv("QUADE_INFLATE_DEBUG") != nullptr;  // measurement: rounds per block on stderr
-        uint32_t* d_rounds = nullptr;
-        if (debug_rounds) INFCHK(f, hipMalloc((void**)&d_rounds, blk.size() * 32));
-        INFCHK(f, qd_launch_inflate2(f->d_comp, f->d_blk, (uint32_t)blk.size(), f->d_out, f->d_st, f->d_matches, QD_INFLATE_MATCHES_PER_BLOCK, longest,
-                                     f->stream, d_rounds));
-        if (debug_rounds) {
-            std::vector<uint32_t> r(blk.size() * 8);
-            INFCHK(f, hipMemcpy(r.data(), d_rounds, blk.size() * 32, hipMemcpyDeviceToHost));
-            (void)hipFree(d_rounds);
-            uint64_t sum = 0, db = 0, tk[8] = {0};
-            uint32_t mx = 0, over8 = 0;
-            for (size_t q = 0; q < blk.size(); ++q) {
-                const uint32_t v = r[8 * q];
-                sum += v & 0xFFFF;
-                db += v >> 16;
-                mx = std::max(mx, v & 0xFFFF);
-                over8 += (v & 0xFFFF) > 8;
-                for (int k = 1; k < 8; ++k) tk[k] += r[8 * q + k];
-            }
-            const double us = 0.01 / (double)blk.size();  // 100 MHz ticks -> microseconds per block
-            fprintf(stderr, "[inflate form 2] %zu blocks: %.2f rounds and %.2f deflate blocks per block, most %u, %u blocks over 8 rounds; us per block: stage %.0f "
-                            "header+tables %.0f rounds %.0f scan+write %.0f matches %.0f flush %.0f; %.0f matches per block\n", blk.size(), (double)sum / blk.size(),
-                    (double)db / blk.size(), mx, over8, tk[1] * us, tk[2] * us, tk[3] * us, tk[4] * us, tk[5] * us, tk[6] * us, (double)tk[7] / blk.size());
-        }
     } else {
-        INFCHK(f, qd_launch_inflate(f->d_comp, f->d_blk, (uint32_t)blk.size(), f->d_out, f->d_st, f->stream));
+        const int rc = inflate_spans_or_wave(f, (uint32_t)blk.size(), longest, f->form == 2);
+        if (rc != QD_OK) return rc;
     }
     INFCHK(f, hipMemcpyAsync(f->h_st, f->d_st, blk.size() * 4, hipMemcpyDeviceToHost, f->stream));
     if (form3_ran) {
@@ -1669,30 +1678,14 @@ static int inflater_run(qd_inflater* f, const uint8_t* comp, int64_t comp_len, u
                 redo_longest = std::max(redo_longest, blk[i].in_len);
             }
         if (!redo.empty()) {
-            qd_inflate_block* d_redo = nullptr;
-            int32_t* d_rst = nullptr;
-            INFCHK(f, hipMalloc((void**)&d_redo, redo.size() * sizeof(qd_inflate_block)));
-            INFCHK(f, hipMalloc((void**)&d_rst, redo.size() * 4));
-            INFCHK(f, hipMemcpy(d_redo, redo.data(), redo.size() * sizeof(qd_inflate_block), hipMemcpyHostToDevice));
-            hipError_t e2;
-            if (qd_inflate2_lds(redo_longest) <= 160 * 1024) {
-                if (redo.size() > f->cap_matches) {
-                    if (f->d_matches) (void)hipFree(f->d_matches);
-                    f->d_matches = nullptr;
-                    f->cap_matches = 0;
-                    INFCHK(f, hipMalloc((void**)&f->d_matches, (redo.size() + 16) * (size_t)QD_INFLATE_MATCHES_PER_BLOCK * 8));
-                    f->cap_matches = redo.size() + 16;
-                }
-                e2 = qd_launch_inflate2(f->d_comp, d_redo, (uint32_t)redo.size(), f->d_out, d_rst, f->d_matches, QD_INFLATE_MATCHES_PER_BLOCK, redo_longest, f->stream);
-            } else {
-                e2 = qd_launch_inflate(f->d_comp, d_redo, (uint32_t)redo.size(), f->d_out, d_rst, f->stream);
-            }
+            // (the first launch is done with the block table and has handed its states over: the redo's go through the same buffers)
+            memcpy(f->h_blk, redo.data(), redo.size() * sizeof(qd_inflate_block));
+            INFCHK(f, hipMemcpyAsync(f->d_blk, f->h_blk, redo.size() * sizeof(qd_inflate_block), hipMemcpyHostToDevice, f->stream));
+            const int rc = inflate_spans_or_wave(f, (uint32_t)redo.size(), redo_longest, true);
+            if (rc != QD_OK) return rc;
             std::vector<int32_t> rst(redo.size());
-            if (e2 == hipSuccess) e2 = hipMemcpyAsync(rst.data(), d_rst, redo.size() * 4, hipMemcpyDeviceToHost, f->stream);
-            if (e2 == hipSuccess) e2 = hipStreamSynchronize(f->stream);
-            (void)hipFree(d_redo);
-            (void)hipFree(d_rst);
-            INFCHK(f, e2);
+            INFCHK(f, hipMemcpyAsync(rst.data(), f->d_st, redo.size() * 4, hipMemcpyDeviceToHost, f->stream));
+            INFCHK(f, hipStreamSynchronize(f->stream));
             for (size_t k = 0; k < redo.size(); ++k) f->h_st[redo_at[k]] = rst[k];
         }
     }

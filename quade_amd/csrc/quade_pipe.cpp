@@ -4,7 +4,7 @@
 // slice + fuse, Sample.FINDER) and src/FastqWriter.py:61-90 (name tag, record format, gzip append) -- for whole chunks, with
 // the fastq TEXT staying in HBM from the inflater to the coder:
 //
-//   files --read()--> pinned --H2D--> [BGZF blocks]  inflate_bgzf_blocks2 + CRC-32 check          (quade_inflate.hip, quade_text.hip)
+//   files --read()--> pinned --H2D--> [BGZF blocks]  token + resolve kernels, CRC-32 checked       (quade_inflate3.hip)
 //                                     [other input]  text as the host's readers inflate it --H2D-->
 //     -> window of text per stream -> line / record scan (skip-malformed inside the stream)
 //     -> lock step: pair j = kept record j of every stream, the chunk ends with its first exhausted stream (Quade.py:210-224)
@@ -56,12 +56,8 @@ constexpr int RING_SLOTS = 64;           // device ring per stream: how far a fe
 constexpr int PIN_SLOTS = 3;             // page-locked upload buffers per stream
 constexpr uint32_t PIECE_BYTES = 1u << 20;       // text per gzip member at most (piece_bytes_for)
 constexpr size_t WINDOW_MAX = (size_t)1 << 30;   // text per stream and batch (offsets are 32 bit)
-constexpr uint32_t LAUNCH_BLOCKS = 8192;         // BGZF blocks per inflate launch at most (sizes the match scratch)
 constexpr size_t GROUP_SEGMENTS = 8;             // uploads gathered per inflate launch
 constexpr size_t READ_PART = 4u << 20;           // an upload buffer is filled by parallel reads of this much
-#ifndef QD_PIPE_INFLATE_STREAMS
-#define QD_PIPE_INFLATE_STREAMS 1 /* 2: the inflate launches alternate between two streams of their own (measured: slower, see qd_pipe::is) */
-#endif
 
 hipError_t wait_event_napping(hipEvent_t ev) {  // hipEventSynchronize spins on this runtime: poll, then nap
     for (int i = 0; i < 64; ++i) {
@@ -95,7 +91,7 @@ struct DevBuf {  // grow-only device allocation
         size_t got = want;
         hipError_t e = qd_pool_get(want, (void**)&q, &got);  // (quade_pool.h: from what an earlier pipeline of this process released)
         if (e != hipSuccess) return e;
-        // nothing queued anywhere may still use the old allocation (the inflate launches run on streams of their own)
+        // nothing queued anywhere may still use the old allocation (the inflate launches run on a stream of their own)
         if (p) (void)hipDeviceSynchronize();
         if (p && keep) {
             e = hipMemcpyAsync(q, p, keep, hipMemcpyDeviceToDevice, st);
@@ -190,7 +186,6 @@ struct Segment {
     std::vector<qd_inflate_block> blocks;  // in_off inside the slot, out_off inside the segment's text
     std::vector<uint32_t> crcs;
     std::vector<uint32_t> starts;  // where every block starts in the slot (its file offset = file_off + that)
-    uint32_t longest = 0;
     int64_t file_off = 0;   // BGZF: where the blocks start in the file (a run the device refuses is read again by the host)
     std::string err;
 };
@@ -556,7 +551,6 @@ class Feeder {
                 seg.blocks.push_back(qd_inflate_block{(uint32_t)(pos - seg_start + 12 + xlen), in_len, (uint32_t)seg.text_bytes, isize});
                 seg.crcs.push_back(crc);
                 seg.starts.push_back((uint32_t)(pos - seg_start));
-                seg.longest = std::max(seg.longest, in_len);
                 seg.text_bytes += isize;
                 pos += bs;
             }
@@ -638,34 +632,18 @@ struct qd_pipe {
     qd_layout lay{};
     hipStream_t cs = nullptr, ds = nullptr;
     hipEvent_t sync_ev = nullptr;
-    // Option "inflate_streams" = 2: the inflate launches alternate between two streams of their own, so that the next launch
-    // (another stream's window, the short index reads' few hundred blocks) fills the CUs a launch's last blocks leave idle; the
-    // compute stream joins a window's launches when it first reads the window (join_inflate).  Measured: the launches overlap
-    // (their summed time 441 -> 700 ms for the same blocks) and the job gets SLOWER, 0.75 -> 0.82 s per 16 M pairs
-    // (profiles/r04_ab_inflate_streams.txt) -- two 150 KB workgroups do not fit a CU, and blocks of two launches competing for
-    // the CUs run longer than they save at the tails.  So the default is 1: down the compute stream, one after the other.
-    hipStream_t is[2] = {nullptr, nullptr};
-    // Option "coder_stream" (default 0; r05, measured and not kept as the default): the tail of a batch -- the coder's launches, the
-    // pieces' CRC-32s, the members and their packing -- on a stream of its own behind the batch's format kernel, so that the scans,
-    // the row packer, the demultiplexer and the sort of batch k + 1 do not queue behind the coder of batch k.  The tail's tables
-    // (sub-blocks, ranges, CRCs, tokens) exist once: the compute stream waits for the tail of batch k before it uploads those of
-    // batch k + 1.  It overlaps as designed (profiles/r05_e2e_bgzf_timeline_coder_stream.txt: the coder on a queue of its own beside
-    // the whole token launch) and the job is no faster (profiles/r05_coder_stream_ab.txt: 34.5 / 29.8 against 31.2 / 30.8 M pairs/s;
-    // single members 24.5 / 24.8 against 24.4 / 25.3): the token launch stretches from 23 to 30-34 ms beside the coder -- the
-    // device is busy either way, the batch's time is the sum of its kernels' work.
-    hipStream_t es = nullptr;
-    hipEvent_t formatted = nullptr, coded = nullptr;
-    bool coded_pending = false;
-    int coder_stream = 0;
+    // The BGZF inflate launches and the gzip steps go down `is` (option "inflate_overlap", flush_inflate3).  The coder's tail on a
+    // stream of its own made the job no faster (profiles/r05_coder_stream_ab.txt): it runs on the compute stream.
+    hipStream_t is = nullptr;
+    // Nothing is queued on these two.  They stand where the second inflate stream and the coder's stream were created: the runtime
+    // spreads a process's streams over four hardware queues in creation order, the feeders' upload streams come behind these, and
+    // without them the uploads land on other queues -- BGZF jobs 3-7 % slower (profiles/r08_one_inflate_path_ab.txt).  They go
+    // when the streams are placed on purpose.
+    hipStream_t placeholder[2] = {nullptr, nullptr};
     int peek_records = 1;  // option "peek_records": size a run's buffers and first top-up from the heads of its first files (peek_record_bytes)
-    hipEvent_t tables_up = nullptr;  // the launch's block tables are on the device (recorded on cs)
-    int n_is = QD_PIPE_INFLATE_STREAMS, next_is = 0;
-    DevBuf matches_b;                // the second stream's match lists
-    // Option "inflate_form" (default 3): which kernels inflate the BGZF blocks.  3 = quade_inflate3.hip: every symbol decoded once, one
-    // lane per block, the blocks of ALL streams' pending uploads in ONE launch (the token kernel's throughput is the number of
-    // blocks in flight), then a workgroup per block resolves the tokens; 2 = the speculative spans of quade_inflate.hip, a launch per
-    // window and eight uploads.
-    int inflate_form = 3;
+    // The BGZF blocks go through quade_inflate3.hip: every symbol decoded once, one lane per block, the blocks of ALL streams' pending
+    // uploads in ONE launch (the token kernel's throughput is the number of blocks in flight), then a workgroup per block resolves
+    // the tokens.
     struct Queued3 {  // blocks of one window waiting for the next launch
         int stream;
         Feeder* feeder;
@@ -691,7 +669,7 @@ struct qd_pipe {
         bool dirty = true;      // text arrived since the last scan
         double avg = 0;         // bytes per record, learned
         uint32_t carry_kept = 0;
-        DevBuf tile_counts, tile_base, lines, rec_tile, recs, status, crc, blk, expect;
+        DevBuf tile_counts, tile_base, lines, rec_tile, recs;
         uint32_t line_cap = 0;
         std::vector<Segment> pending;                                  // BGZF uploads waiting for their inflate launch
         uint32_t pending_text = 0;
@@ -703,8 +681,8 @@ struct qd_pipe {
         };
         std::vector<Run> runs;
         uint32_t n_blocks = 0;                                         // blocks inflated into this window since the last verification
-        hipEvent_t inflated[2] = {nullptr, nullptr};                   // the window's last launch on each inflate stream
-        bool in_flight[2] = {false, false};
+        hipEvent_t inflated = nullptr;                                 // the window's last launch on the inflate stream
+        bool in_flight = false;
         std::string path;
         qd_scan_result res{};
         // an ordinary gzip file on its way through the device's gzip kernels: the file's bytes [comp_off, comp_off + comp_len) lie in
@@ -734,7 +712,6 @@ struct qd_pipe {
     int n_streams = 4;  // R1, R2, I1 [, I2]
     DevBuf d_res;       // qd_scan_result[4] + pack's short counter
     PinBuf h_res;
-    DevBuf matches;
     // index rows, codes, routing scratch (sized for batch_pairs)
     DevBuf rows_seq[2], rows_qual[2], rows_len[2], codes, mol, short_idx, dest, len1, len2, hist, tmp, perm, sdest, g1, g2, scan_tiles, first, g1_first,
         g2_first;
@@ -992,11 +969,10 @@ using Window = qd_pipe::Window;
 
 // the compute stream goes on behind the window's inflate launches
 int join_inflate(qd_pipe* p, Window& w) {
-    for (int k = 0; k < 2; ++k)
-        if (w.in_flight[k]) {
-            PCHK(p, hipStreamWaitEvent(p->cs, w.inflated[k], 0));
-            w.in_flight[k] = false;
-        }
+    if (w.in_flight) {
+        PCHK(p, hipStreamWaitEvent(p->cs, w.inflated, 0));
+        w.in_flight = false;
+    }
     return QD_OK;
 }
 
@@ -1019,7 +995,7 @@ int flush_inflate3(qd_pipe* p) {
     // latency, a wave per SIMD at most -- shares the device with what batch k still has queued on the compute stream (format, coder); the
     // windows' scans wait for the event (join_inflate).  It reads the upload ring and writes the windows' text behind what the carry
     // copies (compute stream) move to their front: no overlap with anything queued there.
-    const hipStream_t xs = p->inflate_overlap ? p->is[0] : p->cs;
+    const hipStream_t xs = p->inflate_overlap ? p->is : p->cs;
     for (const qd_pipe::Queued3& q : p->q3_parts) {
         Window& w = p->win[q.stream];
         for (uint32_t i = q.first; i < q.first + q.n; ++i) p->q3_jobs[i].out = w.buf[w.cur].p + reinterpret_cast<uintptr_t>(p->q3_jobs[i].out);
@@ -1035,15 +1011,15 @@ int flush_inflate3(qd_pipe* p) {
     }
     for (const qd_pipe::Queued3& q : p->q3_parts) {
         for (int slot : q.slots) PCHK(p, q.feeder->consumed(slot, xs));
-        const uint32_t* st = p->status3.as<uint32_t>() + q.first;  // (a block's CRC-32 is checked by its resolve kernel: the statuses say it all)
-        PCHK(p, qd_text_check_blocks(p->status3.as<int32_t>() + q.first, st, st, q.n, q.block_base, &p->d_res.as<qd_scan_result>()[q.stream].first_bad, xs));
+        // (a block's CRC-32 is checked by its resolve kernel: the statuses say it all)
+        PCHK(p, qd_text_check_blocks(p->status3.as<int32_t>() + q.first, q.n, q.block_base, &p->d_res.as<qd_scan_result>()[q.stream].first_bad, xs));
     }
     if (xs != p->cs) {
         for (const qd_pipe::Queued3& q : p->q3_parts) {
             Window& w = p->win[q.stream];
-            if (!w.inflated[0]) PCHK(p, hipEventCreateWithFlags(&w.inflated[0], hipEventDisableTiming));
-            PCHK(p, hipEventRecord(w.inflated[0], xs));
-            w.in_flight[0] = true;
+            if (!w.inflated) PCHK(p, hipEventCreateWithFlags(&w.inflated, hipEventDisableTiming));
+            PCHK(p, hipEventRecord(w.inflated, xs));
+            w.in_flight = true;
         }
     }
     p->q3_jobs.clear();
@@ -1051,115 +1027,45 @@ int flush_inflate3(qd_pipe* p) {
     return QD_OK;
 }
 
-// the pending BGZF uploads of a window -> inflate launches (+ CRC-32 check of every block), text appended to the window
+// the pending BGZF uploads of a window are queued, their text appended to the window: flush_inflate3 launches every window's blocks together
 int launch_inflate(qd_pipe* p, Feeder& f, Window& w, int stream_index) {
     if (w.pending.empty()) return QD_OK;
-    int rc = window_room(p, w, w.pending_text);
+    const int rc = window_room(p, w, w.pending_text);
     if (rc != QD_OK) return rc;
-    if (p->inflate_form == 3) {  // queued: flush_inflate3 launches every window's blocks together
-        qd_pipe::Queued3 q;
-        q.stream = stream_index;
-        q.feeder = &f;
-        q.first = (uint32_t)p->q3_jobs.size();
-        q.block_base = w.n_blocks;
-        for (Segment& s : w.pending) {
-            const uint8_t* base = f.ring() + (size_t)s.slot * SEG_BYTES;
-            for (size_t i = 0; i < s.blocks.size(); ++i) {
-                const qd_inflate_block& b = s.blocks[i];
-                qd_inflate3_job j;
-                j.payload = base + b.in_off;
-                j.out = reinterpret_cast<uint8_t*>((uintptr_t)w.len + b.out_off);
-                j.in_len = b.in_len;
-                j.out_len = b.out_len;
-                j.expect_crc = s.crcs[i];
-                j.check_crc = 1;
-                p->q3_jobs.push_back(j);
-            }
-            q.slots.push_back(s.slot);
-            w.runs.push_back(Window::Run{s.file_off, s.bytes, (int64_t)w.len, (uint32_t)s.text_bytes});
-            w.len += (uint32_t)s.text_bytes;
-            p->st.text_in_bytes += (int64_t)s.text_bytes;
-        }
-        q.n = (uint32_t)p->q3_jobs.size() - q.first;
-        w.n_blocks += q.n;
-        p->st.bgzf_blocks += (int64_t)q.n;
-        w.pending.clear();
-        w.pending_text = 0;
-        w.dirty = true;
-        p->q3_parts.push_back(std::move(q));
-        size_t queued = 0;
-        for (const qd_pipe::Queued3& x : p->q3_parts)
-            if (x.stream == stream_index) queued += x.slots.size();
-        return queued >= FLUSH_SEGMENTS3 ? flush_inflate3(p) : QD_OK;
-    }
-    std::vector<qd_inflate_block> blk;
-    std::vector<uint32_t> expect;
-    uint32_t longest = 0;
-    const int xi = p->n_is > 1 ? p->next_is : -1;
-    if (xi >= 0) p->next_is ^= 1;
-    const hipStream_t xs = xi >= 0 ? p->is[xi] : p->cs;
+    qd_pipe::Queued3 q;
+    q.stream = stream_index;
+    q.feeder = &f;
+    q.first = (uint32_t)p->q3_jobs.size();
+    q.block_base = w.n_blocks;
     for (Segment& s : w.pending) {
-        PCHK(p, hipStreamWaitEvent(xs, f.ready(s.slot), 0));
+        const uint8_t* base = f.ring() + (size_t)s.slot * SEG_BYTES;
         for (size_t i = 0; i < s.blocks.size(); ++i) {
-            qd_inflate_block b = s.blocks[i];
-            b.in_off += (uint32_t)((size_t)s.slot * SEG_BYTES);
-            b.out_off += w.len;
-            blk.push_back(b);
-            expect.push_back(s.crcs[i]);
+            const qd_inflate_block& b = s.blocks[i];
+            qd_inflate3_job j;
+            j.payload = base + b.in_off;
+            j.out = reinterpret_cast<uint8_t*>((uintptr_t)w.len + b.out_off);
+            j.in_len = b.in_len;
+            j.out_len = b.out_len;
+            j.expect_crc = s.crcs[i];
+            j.check_crc = 1;
+            p->q3_jobs.push_back(j);
         }
-        longest = std::max(longest, s.longest);
+        q.slots.push_back(s.slot);
         w.runs.push_back(Window::Run{s.file_off, s.bytes, (int64_t)w.len, (uint32_t)s.text_bytes});
         w.len += (uint32_t)s.text_bytes;
         p->st.text_in_bytes += (int64_t)s.text_bytes;
     }
-    const size_t nb = blk.size();
-    PCHK(p, w.blk.need((size_t)(w.n_blocks + nb) * sizeof(qd_inflate_block), 0, p->cs));
-    PCHK(p, w.expect.need((size_t)(w.n_blocks + nb) * 4, 0, p->cs));
-    PCHK(p, w.status.need((size_t)(w.n_blocks + nb) * 4, 0, p->cs));
-    PCHK(p, w.crc.need((size_t)(w.n_blocks + nb) * 4, 0, p->cs));
-    // (tables of this launch group go behind those of the batch's earlier groups: a growth above drains the stream first)
-    qd_inflate_block* d_blk = w.blk.as<qd_inflate_block>() + w.n_blocks;
-    uint32_t* d_expect = w.expect.as<uint32_t>() + w.n_blocks;
-    int32_t* d_status = w.status.as<int32_t>() + w.n_blocks;
-    uint32_t* d_crc = w.crc.as<uint32_t>() + w.n_blocks;
-    PCHK(p, p->stage.upload(d_blk, blk.data(), nb * sizeof(qd_inflate_block), p->cs));
-    PCHK(p, p->stage.upload(d_expect, expect.data(), nb * 4, p->cs));
-    uint32_t* first_bad = &p->d_res.as<qd_scan_result>()[stream_index].first_bad;
-    const bool form2 = qd_inflate2_lds(longest) <= 160 * 1024;
-    DevBuf& matches = xi == 1 ? p->matches_b : p->matches;
-    if (form2) PCHK(p, matches.need((size_t)std::min<size_t>(nb, LAUNCH_BLOCKS) * QD_INFLATE_MATCHES_PER_BLOCK * 8, 0, p->cs));
-    if (xi >= 0) {  // behind everything the compute stream has queued so far: the tables above, the last readers of the window's buffer
-        PCHK(p, hipEventRecord(p->tables_up, p->cs));
-        PCHK(p, hipStreamWaitEvent(xs, p->tables_up, 0));
-    }
-    for (size_t at = 0; at < nb; at += LAUNCH_BLOCKS) {
-        const uint32_t n = (uint32_t)std::min<size_t>(LAUNCH_BLOCKS, nb - at);
-        if (form2) {
-            // (every block's CRC-32 against its trailer is checked by the kernel, while the text is in LDS)
-            PCHK(p, qd_launch_inflate2(f.ring(), d_blk + at, n, w.buf[w.cur].p, d_status + at, matches.as<unsigned long long>(), QD_INFLATE_MATCHES_PER_BLOCK,
-                                       longest, xs, nullptr, d_expect + at));
-        } else {
-            PCHK(p, qd_launch_inflate(f.ring(), d_blk + at, n, w.buf[w.cur].p, d_status + at, xs));
-        }
-    }
-    for (Segment& s : w.pending) PCHK(p, f.consumed(s.slot, xs));
-    if (form2) {
-        PCHK(p, qd_text_check_blocks(d_status, d_expect, d_expect, (uint32_t)nb, w.n_blocks, first_bad, xs));  // (the statuses say it all)
-    } else {  // the one-wave form does not check: a CRC-32 pass over the text, one range per block
-        PCHK(p, qd_text_crc32_blocks(w.buf[w.cur].p, d_blk, (uint32_t)nb, d_crc, xs));
-        PCHK(p, qd_text_check_blocks(d_status, d_crc, d_expect, (uint32_t)nb, w.n_blocks, first_bad, xs));
-    }
-    if (xi >= 0) {
-        if (!w.inflated[xi]) PCHK(p, hipEventCreateWithFlags(&w.inflated[xi], hipEventDisableTiming));
-        PCHK(p, hipEventRecord(w.inflated[xi], xs));
-        w.in_flight[xi] = true;
-    }
-    w.n_blocks += (uint32_t)nb;
-    p->st.bgzf_blocks += (int64_t)nb;
+    q.n = (uint32_t)p->q3_jobs.size() - q.first;
+    w.n_blocks += q.n;
+    p->st.bgzf_blocks += (int64_t)q.n;
     w.pending.clear();
     w.pending_text = 0;
     w.dirty = true;
-    return QD_OK;
+    p->q3_parts.push_back(std::move(q));
+    size_t queued = 0;
+    for (const qd_pipe::Queued3& x : p->q3_parts)
+        if (x.stream == stream_index) queued += x.slots.size();
+    return queued >= FLUSH_SEGMENTS3 ? flush_inflate3(p) : QD_OK;
 }
 
 // ---- ordinary gzip files through the device's gzip kernels (qd_gz) --------------------------------------------------------------------
@@ -1227,7 +1133,7 @@ int gz_append(qd_pipe* p, Feeder& f, Window& w, Segment& s) {
         if (rc != QD_OK) return rc;
     }
     if ((uint64_t)s.file_off != g.comp_off + g.comp_len) return pfail(p, QD_ERR_STATE, w.path + ": uploads out of order");
-    const hipStream_t gs = p->inflate_overlap ? p->is[0] : p->cs;  // (the gzip steps' stream: gz_steps)
+    const hipStream_t gs = p->inflate_overlap ? p->is : p->cs;  // (the gzip steps' stream: gz_steps)
     PCHK(p, g.comp[g.ccur].need((size_t)g.comp_len + s.bytes + 8192, (size_t)g.comp_len, gs));
     PCHK(p, hipStreamWaitEvent(gs, f.ready(s.slot), 0));
     PCHK(p, hipMemcpyAsync(g.comp[g.ccur].p + g.comp_len, f.ring() + (size_t)s.slot * SEG_BYTES, s.bytes, hipMemcpyDeviceToDevice, gs));
@@ -1357,9 +1263,9 @@ int gz_steps(qd_pipe* p, std::vector<std::unique_ptr<Feeder>>& feeders, int chun
     // A stream of their own ("inflate_overlap"): a step ends with the host waiting for its results, and on the compute stream that wait
     // would include everything batch k still has queued there (format, coder).  What a step writes -- the windows' text behind what
     // the carry copies move to their front -- nothing queued on the compute stream touches.
-    // (is[0], the BGZF launches' stream too: the runtime spreads streams over four hardware queues, and is[1] landed on the compute
-    //  stream's -- its kernels ran strictly one after the other with the coder's, profiles/r05_e2e_gz_timeline_before.txt)
-    const hipStream_t gs = p->inflate_overlap ? p->is[0] : p->cs;
+    // (the BGZF launches' stream too: the runtime spreads streams over four hardware queues, and a second inflate stream landed on the
+    //  compute stream's -- its kernels ran strictly one after the other with the coder's, profiles/r05_e2e_gz_timeline_before.txt)
+    const hipStream_t gs = p->inflate_overlap ? p->is : p->cs;
     static double t_decode = 0, t_room = 0, t_resolve = 0, t_sync = 0, t_post = 0;  // (QUADE_PIPE_TRACE: where a gzip step's wall time goes)
     static const bool trace = getenv("QUADE_PIPE_TRACE") != nullptr;
     struct Report {
@@ -1587,16 +1493,7 @@ int scan_windows(qd_pipe* p, bool* scanned) {
     }
     *scanned = n > 0;
     if (!n) return QD_OK;
-    static const bool one_by_one = [] {  // (A/B: QUADE_PIPE_SCAN_MANY=0 launches window by window, as before r05)
-        const char* e = getenv("QUADE_PIPE_SCAN_MANY");
-        return e && atoi(e) == 0;
-    }();
-    if (one_by_one) {
-        for (int k = 0; k < n; ++k)
-            PCHK(p, qd_text_scan(jobs[k].text, jobs[k].len, jobs[k].at_eof, jobs[k].want_names, jobs[k].need, jobs[k].s, jobs[k].result, p->cs));
-    } else {
-        PCHK(p, qd_text_scan_many(n, jobs, p->cs));
-    }
+    PCHK(p, qd_text_scan_many(n, jobs, p->cs));
     for (int k = 0; k < n; ++k)
         PCHK(p, hipMemcpyAsync(p->h_res.p + (size_t)which[k] * sizeof(qd_scan_result), p->d_res.p + (size_t)which[k] * sizeof(qd_scan_result), sizeof(qd_scan_result),
                                hipMemcpyDeviceToHost, p->cs));
@@ -1717,11 +1614,6 @@ int reserve_buffers(qd_pipe* p, uint32_t B, uint32_t n_dest) {
         PCHK(p, w.lines.need(lines * 4 + 64, 0, p->cs));
         PCHK(p, w.rec_tile.need((lines / 4 / 1024 + 4) * 4, 0, p->cs));
         PCHK(p, w.recs.need((lines / 4 + 1) * sizeof(qd_rec), 0, p->cs));
-        const size_t blocks = text / 16384 + 1024;  // (bgzip fills its blocks: ~64 KiB of text each)
-        PCHK(p, w.blk.need(blocks * sizeof(qd_inflate_block), 0, p->cs));
-        PCHK(p, w.expect.need(blocks * 4, 0, p->cs));
-        PCHK(p, w.status.need(blocks * 4, 0, p->cs));
-        PCHK(p, w.crc.need(blocks * 4, 0, p->cs));
     }
     {  // ordinary gzip streams: the gzip kernels' buffers for a batch's steps, and the streams' compressed bytes
         uint64_t comp = 0, text = 0;
@@ -1739,7 +1631,7 @@ int reserve_buffers(qd_pipe* p, uint32_t B, uint32_t n_dest) {
             PCHK(p, p->gz->reserve(comp, text));
         }
     }
-    if (p->inflate_form == 3) {  // a batch's blocks of all streams go down together: ~a block per 64 KiB of text
+    {  // a batch's blocks of all streams go down together: ~a block per 64 KiB of text
         size_t blocks3 = 0;
         for (int s = 0; s < p->n_streams; ++s) {
             const double avg = p->win[s].avg > 0 ? p->win[s].avg : (s < 2 ? 400.0 : 64.0);
@@ -1748,9 +1640,6 @@ int reserve_buffers(qd_pipe* p, uint32_t B, uint32_t n_dest) {
         PCHK(p, p->jobs3.need(blocks3 * sizeof(qd_inflate3_job), 0, p->cs));
         PCHK(p, p->status3.need(blocks3 * 4, 0, p->cs));
         PCHK(p, p->scratch3.need(qd_inflate3_scratch_bytes((uint32_t)std::min<size_t>(blocks3, LAUNCH_BLOCKS3)), 0, p->cs));
-    } else {
-        PCHK(p, p->matches.need((size_t)LAUNCH_BLOCKS * QD_INFLATE_MATCHES_PER_BLOCK * 8, 0, p->cs));
-        if (p->n_is > 1) PCHK(p, p->matches_b.need((size_t)LAUNCH_BLOCKS * QD_INFLATE_MATCHES_PER_BLOCK * 8, 0, p->cs));
     }
     const size_t n = B;
     for (int k = 0; k < L.n_streams; ++k) {
@@ -1964,10 +1853,6 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
     PCHK(p, o.member_len.need((size_t)n_pieces * 4, 0, p->cs));
     PCHK(p, o.member_off.need((size_t)(n_pieces + 1) * 8, 0, p->cs));
     PCHK(p, o.packed.need((size_t)n_pieces * (size_t)out_stride, 0, p->cs));
-    // (the tail of the batch before still reads the sub-block tables and the coder's scratch: the uploads below wait for it)
-    const hipStream_t ts = p->coder_stream ? p->es : p->cs;  // the tail's stream
-    if (p->coded_pending && ts != p->cs) PCHK(p, hipStreamWaitEvent(p->cs, p->coded, 0));
-    p->coded_pending = false;
     PCHK(p, p->stage.upload(p->base1.p, base1.data(), (size_t)nd * 8, p->cs));
     PCHK(p, p->stage.upload(p->base2.p, base2.data(), (size_t)nd * 8, p->cs));
     PCHK(p, p->stage.upload(o.pieces.p, bo.pieces.data(), (size_t)n_pieces * sizeof(qd_deflate_piece), p->cs));
@@ -1992,10 +1877,6 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
     fa.out1 = o.text.p;
     fa.out2 = o.text.p;
     PCHK(p, qd_text_format(p->plan, S, si.write_pass, si.write_fail, si.write_undet, n, fa, p->cs));
-    if (ts != p->cs) {  // the tail starts when the text is formatted (and the tables above are up)
-        PCHK(p, hipEventRecord(p->formatted, p->cs));
-        PCHK(p, hipStreamWaitEvent(ts, p->formatted, 0));
-    }
     static_assert(sizeof(qd_deflate_piece) == 16 && offsetof(qd_deflate_piece, crc32) == 12, "the combined CRCs land in the piece table");
     uint32_t* piece_crc = reinterpret_cast<uint32_t*>(o.pieces.p) + 3;
     if (si.level == 1) {
@@ -2006,22 +1887,18 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
         // the sub-blocks' CRC-32s come out of the coder (taken while a sub-block's text is staged), the pieces' are combined from them
         for (uint32_t at = 0; at < n_subs; at += slice)
             PCHK(p, qd_launch_lz_subblocks(o.text.p, p->subs.as<qd_lz_sub>() + at, std::min(slice, n_subs - at), p->tokens.as<uint32_t>(), p->sub_out.p + (size_t)at * sub_stride,
-                                           sub_stride, p->sub_bytes.as<uint32_t>() + at, p->crc.as<uint32_t>() + at, ts));
-        PCHK(p, qd_text_crc32_combine(p->ranges.as<qd_crc_range>(), p->crc.as<uint32_t>(), p->first_sub.as<uint32_t>(), n_pieces, piece_crc, 4, ts));
+                                           sub_stride, p->sub_bytes.as<uint32_t>() + at, p->crc.as<uint32_t>() + at, p->cs));
+        PCHK(p, qd_text_crc32_combine(p->ranges.as<qd_crc_range>(), p->crc.as<uint32_t>(), p->first_sub.as<uint32_t>(), n_pieces, piece_crc, 4, p->cs));
         PCHK(p, qd_launch_lz_members(o.pieces.as<qd_deflate_piece>(), n_pieces, p->subs.as<qd_lz_sub>(), p->first_sub.as<uint32_t>(), n_subs, p->sub_out.p, sub_stride,
-                                     p->sub_bytes.as<uint32_t>(), o.members.p, out_stride, o.member_len.as<uint32_t>(), ts));
+                                     p->sub_bytes.as<uint32_t>(), o.members.p, out_stride, o.member_len.as<uint32_t>(), p->cs));
     } else {
-        PCHK(p, qd_text_crc32(o.text.p, p->ranges.as<qd_crc_range>(), n_subs, p->crc.as<uint32_t>(), ts));
-        PCHK(p, qd_text_crc32_combine(p->ranges.as<qd_crc_range>(), p->crc.as<uint32_t>(), p->first_sub.as<uint32_t>(), n_pieces, piece_crc, 4, ts));
-        PCHK(p, qd_launch_huffman(o.text.p, o.pieces.as<qd_deflate_piece>(), n_pieces, o.members.p, out_stride, o.member_len.as<uint32_t>(), ts));
+        PCHK(p, qd_text_crc32(o.text.p, p->ranges.as<qd_crc_range>(), n_subs, p->crc.as<uint32_t>(), p->cs));
+        PCHK(p, qd_text_crc32_combine(p->ranges.as<qd_crc_range>(), p->crc.as<uint32_t>(), p->first_sub.as<uint32_t>(), n_pieces, piece_crc, 4, p->cs));
+        PCHK(p, qd_launch_huffman(o.text.p, o.pieces.as<qd_deflate_piece>(), n_pieces, o.members.p, out_stride, o.member_len.as<uint32_t>(), p->cs));
     }
-    PCHK(p, qd_text_pack_members(o.members.p, out_stride, o.member_len.as<uint32_t>(), n_pieces, o.member_off.as<uint64_t>(), o.packed.p, ts));
+    PCHK(p, qd_text_pack_members(o.members.p, out_stride, o.member_len.as<uint32_t>(), n_pieces, o.member_off.as<uint64_t>(), o.packed.p, p->cs));
     PCHK(p, hipEventCreateWithFlags(&bo.done, hipEventDisableTiming));
-    PCHK(p, hipEventRecord(bo.done, ts));
-    if (ts != p->cs) {
-        PCHK(p, hipEventRecord(p->coded, ts));
-        p->coded_pending = true;
-    }
+    PCHK(p, hipEventRecord(bo.done, p->cs));
     to_collector(p, std::move(bo));
     return QD_OK;
 }
@@ -2287,7 +2164,7 @@ int run_chunk(qd_pipe* p, std::vector<std::unique_ptr<Feeder>>& feeders, int chu
             if (w.res.n_kept > 0 && (size_t)w.len > WINDOW_MAX / 2) continue;  // a full window: a smaller batch rather than more text
             // (... and a batch that is most of B rather than another round: a top-up is an inflate launch of its own, which takes as
             //  long for a few hundred blocks as for ten thousand -- a lane decodes its block's symbols one after the other)
-            if (p->inflate_form == 3 && (uint64_t)w.res.n_kept * 10 >= (uint64_t)B * 8) continue;
+            if ((uint64_t)w.res.n_kept * 10 >= (uint64_t)B * 8) continue;
             const double per = w.avg > 0 ? w.avg : 256.0;
             const size_t more = (size_t)((double)(B - w.res.n_kept) * per * 1.03) + 4096;
             want[s] = std::min<size_t>(std::max<size_t>((size_t)w.len + more, (size_t)w.len + 1), WINDOW_MAX * 3 / 4);
@@ -2522,17 +2399,14 @@ int qd_pipe_create(qd_ctx* ctx, qd_pipe** out) {
     p->lay = L;
     p->plan = P;
     p->n_streams = 2 + L.n_streams;
-    if (const char* e = getenv("QUADE_PIPE_INFLATE_FORM")) p->inflate_form = atoi(e) == 2 ? 2 : 3;  // (measurement: A/B of the inflaters inside the pipeline)
     if (const char* e = getenv("QUADE_PIPE_DEVICE_GUNZIP")) p->device_gunzip = atoi(e) ? 1 : 0;
     if (const char* e = getenv("QUADE_PIPE_INFLATE_OVERLAP")) p->inflate_overlap = atoi(e) ? 1 : 0;
-    if (const char* e = getenv("QUADE_PIPE_CODER_STREAM")) p->coder_stream = atoi(e) ? 1 : 0;
     if (const char* e = getenv("QUADE_PIPE_PEEK")) p->peek_records = atoi(e) ? 1 : 0;
     if (hipSetDevice(dev) != hipSuccess || hipStreamCreateWithFlags(&p->cs, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&p->ds, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&p->sync_ev, hipEventDisableTiming) != hipSuccess ||
-        hipStreamCreateWithFlags(&p->is[0], hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&p->is[1], hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&p->tables_up, hipEventDisableTiming) != hipSuccess ||
-        hipStreamCreateWithFlags(&p->es, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&p->formatted, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&p->coded, hipEventDisableTiming) != hipSuccess)
+        hipStreamCreateWithFlags(&p->is, hipStreamNonBlocking) != hipSuccess ||
+        hipStreamCreateWithFlags(&p->placeholder[0], hipStreamNonBlocking) != hipSuccess ||
+        hipStreamCreateWithFlags(&p->placeholder[1], hipStreamNonBlocking) != hipSuccess)
         return pfail(nullptr, QD_ERR_HIP, "stream creation failed");
     for (int i = 0; i < 2; ++i)
         if (hipEventCreateWithFlags(&p->out[i].done, hipEventDisableTiming) != hipSuccess) return pfail(nullptr, QD_ERR_HIP, "event creation failed");
@@ -2550,11 +2424,8 @@ int qd_pipe_set_option(qd_pipe* p, const char* name, int64_t value) {
     else if (n == "test_fail_inflate_batch") p->test_fail_inflate_batch = value;
     else if (n == "test_host_code_every" && value >= 0) p->test_host_code_every = value;
     else if (n == "member_slots_bytes" && value >= (1 << 20)) p->member_slots_bytes = value;
-    else if (n == "inflate_streams" && (value == 1 || value == 2)) p->n_is = (int)value;
-    else if (n == "inflate_form" && (value == 2 || value == 3)) p->inflate_form = (int)value;
     else if (n == "device_gunzip" && (value == 0 || value == 1)) p->device_gunzip = (int)value;
     else if (n == "inflate_overlap" && (value == 0 || value == 1)) p->inflate_overlap = (int)value;
-    else if (n == "coder_stream" && (value == 0 || value == 1)) p->coder_stream = (int)value;
     else if (n == "peek_records" && (value == 0 || value == 1)) p->peek_records = (int)value;
     else return pfail(p, QD_ERR_INVALID, "unknown option " + n);
     return QD_OK;
@@ -2631,8 +2502,6 @@ int qd_pipe_run(qd_pipe* p, const qd_pipe_chunk* chunks, int32_t n_chunks, qd_pi
     }
     p->collector.join();
     (void)hipStreamSynchronize(p->cs);
-    if (p->es) (void)hipStreamSynchronize(p->es);
-    p->coded_pending = false;
     for (auto& f : feeders) f->stop();
     {
         std::lock_guard<std::mutex> g(p->cm);
@@ -2672,12 +2541,10 @@ int qd_pipe_destroy(qd_pipe* p) {
     (void)hipSetDevice(p->device);
     if (p->cs) (void)hipStreamSynchronize(p->cs);
     if (p->ds) (void)hipStreamSynchronize(p->ds);
-    for (hipStream_t st : p->is)
-        if (st) (void)hipStreamSynchronize(st);
+    if (p->is) (void)hipStreamSynchronize(p->is);
     for (qd_pipe::Window& w : p->win) {
-        for (hipEvent_t ev : w.inflated)
-            if (ev) (void)hipEventDestroy(ev);
-        for (DevBuf* b : {&w.buf[0], &w.buf[1], &w.tile_counts, &w.tile_base, &w.lines, &w.rec_tile, &w.recs, &w.status, &w.crc, &w.blk, &w.expect}) b->release();
+        if (w.inflated) (void)hipEventDestroy(w.inflated);
+        for (DevBuf* b : {&w.buf[0], &w.buf[1], &w.tile_counts, &w.tile_base, &w.lines, &w.rec_tile, &w.recs}) b->release();
     }
     for (DevBuf* b : {&p->jobs3, &p->status3, &p->scratch3}) b->release();
     for (qd_pipe::Window& w : p->win) {
@@ -2686,7 +2553,7 @@ int qd_pipe_destroy(qd_pipe* p) {
     }
     delete p->gz;
     p->gz = nullptr;
-    for (DevBuf* b : {&p->d_res, &p->matches, &p->matches_b, &p->rows_seq[0], &p->rows_seq[1], &p->rows_qual[0], &p->rows_qual[1], &p->rows_len[0], &p->rows_len[1], &p->codes, &p->mol,
+    for (DevBuf* b : {&p->d_res, &p->rows_seq[0], &p->rows_seq[1], &p->rows_qual[0], &p->rows_qual[1], &p->rows_len[0], &p->rows_len[1], &p->codes, &p->mol,
                       &p->short_idx, &p->dest, &p->len1, &p->len2, &p->hist, &p->tmp, &p->perm, &p->sdest, &p->g1, &p->g2, &p->scan_tiles, &p->first, &p->g1_first,
                       &p->g2_first, &p->subs, &p->first_sub, &p->ranges, &p->crc, &p->tokens, &p->sub_out, &p->sub_bytes, &p->base1, &p->base2})
         b->release();
@@ -2702,11 +2569,8 @@ int qd_pipe_destroy(qd_pipe* p) {
         if (p->slab_ev[k]) (void)hipEventDestroy(p->slab_ev[k]);
     }
     if (p->sync_ev) (void)hipEventDestroy(p->sync_ev);
-    if (p->tables_up) (void)hipEventDestroy(p->tables_up);
-    if (p->formatted) (void)hipEventDestroy(p->formatted);
-    if (p->coded) (void)hipEventDestroy(p->coded);
-    if (p->es) (void)hipStreamDestroy(p->es);
-    for (hipStream_t st : p->is)
+    if (p->is) (void)hipStreamDestroy(p->is);
+    for (hipStream_t st : p->placeholder)
         if (st) (void)hipStreamDestroy(st);
     if (p->cs) (void)hipStreamDestroy(p->cs);
     if (p->ds) (void)hipStreamDestroy(p->ds);

@@ -154,16 +154,12 @@ struct qd_crc_range {
     uint32_t pad;
 };
 hipError_t qd_text_crc32(const uint8_t* text, const qd_crc_range* ranges, uint32_t n, uint32_t* crc, hipStream_t st);
-// the same for the text of inflated BGZF blocks: range i = out[blocks[i].out_off .. + blocks[i].out_len)
-struct qd_inflate_block;
-hipError_t qd_text_crc32_blocks(const uint8_t* out, const qd_inflate_block* blocks, uint32_t n, uint32_t* crc, hipStream_t st);
 // crc of piece i = the CRCs of its ranges first[i] .. first[i + 1] combined, written to piece_crc[i * stride_words] (the
 // pipeline points this at qd_deflate_piece::crc32)
 hipError_t qd_text_crc32_combine(const qd_crc_range* ranges, const uint32_t* crc, const uint32_t* first, uint32_t n_pieces,
                                  uint32_t* piece_crc, uint32_t stride_words, hipStream_t st);
-// BGZF verification: status[i] != 0 or crc[i] != expect[i] -> atomicMin(first_bad, i)
-hipError_t qd_text_check_blocks(const int32_t* status, const uint32_t* crc, const uint32_t* expect, uint32_t n, uint32_t base_index,
-                                uint32_t* first_bad, hipStream_t st);
+// BGZF verification (the inflater's resolve kernel has compared every block's CRC-32): status[i] != 0 -> atomicMin(first_bad, base_index + i)
+hipError_t qd_text_check_blocks(const int32_t* status, uint32_t n, uint32_t base_index, uint32_t* first_bad, hipStream_t st);
 
 // Members made in slots of `stride` bytes -> one packed byte stream: offsets[i] = sum of len[j], j < i (offsets[n] = total),
 // packed[offsets[i] ..] = slots[i * stride .. + len[i]).

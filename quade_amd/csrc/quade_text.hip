@@ -10,7 +10,6 @@
 //   CRC-32 ........... 256 lanes per 64 KiB range, slice-by-4 out of LDS tables, lanes' CRCs combined by x^(8n) mod P
 #include <hip/hip_runtime.h>
 
-#include "quade_inflate.h"
 #include "quade_text.h"
 #include "text_rules.h"
 
@@ -739,12 +738,6 @@ __global__ __launch_bounds__(256) void crc32_ranges(const uint8_t* text, const q
     const uint32_t c = crc32_range(text, rg.off, rg.len);
     if (threadIdx.x == 0) crc[blockIdx.x] = c;
 }
-// the text of inflated BGZF blocks: block i's range is out[out_off .. out_off + out_len) of its table entry
-__global__ __launch_bounds__(256) void crc32_blocks(const uint8_t* out, const qd_inflate_block* blocks, uint32_t* crc) {
-    const qd_inflate_block b = blocks[blockIdx.x];
-    const uint32_t c = crc32_range(out, b.out_off, b.out_len);
-    if (threadIdx.x == 0) crc[blockIdx.x] = c;
-}
 
 __global__ __launch_bounds__(64) void crc32_combine(const qd_crc_range* ranges, const uint32_t* crc, const uint32_t* first, uint32_t n_pieces,
                                                     uint32_t* piece_crc, uint32_t stride_words) {
@@ -758,10 +751,9 @@ __global__ __launch_bounds__(64) void crc32_combine(const qd_crc_range* ranges, 
     piece_crc[(size_t)i * stride_words] = c;
 }
 
-__global__ __launch_bounds__(256) void check_blocks(const int32_t* status, const uint32_t* crc, const uint32_t* expect, uint32_t n,
-                                                    uint32_t base_index, uint32_t* first_bad) {
+__global__ __launch_bounds__(256) void check_blocks(const int32_t* status, uint32_t n, uint32_t base_index, uint32_t* first_bad) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < n && (status[i] != 0 || crc[i] != expect[i])) atomicMin(first_bad, base_index + i);
+    if (i < n && status[i] != 0) atomicMin(first_bad, base_index + i);
 }
 
 // ---- members -> one packed byte stream ------------------------------------------------------------------------------------------
@@ -954,12 +946,6 @@ hipError_t qd_text_crc32(const uint8_t* text, const qd_crc_range* ranges, uint32
     return hipGetLastError();
 }
 
-hipError_t qd_text_crc32_blocks(const uint8_t* out, const qd_inflate_block* blocks, uint32_t n, uint32_t* crc, hipStream_t st) {
-    if (!n) return hipSuccess;
-    hipLaunchKernelGGL(crc32_blocks, dim3(n), dim3(256), 0, st, out, blocks, crc);
-    return hipGetLastError();
-}
-
 hipError_t qd_text_crc32_combine(const qd_crc_range* ranges, const uint32_t* crc, const uint32_t* first, uint32_t n_pieces, uint32_t* piece_crc,
                                  uint32_t stride_words, hipStream_t st) {
     if (!n_pieces) return hipSuccess;
@@ -967,10 +953,9 @@ hipError_t qd_text_crc32_combine(const qd_crc_range* ranges, const uint32_t* crc
     return hipGetLastError();
 }
 
-hipError_t qd_text_check_blocks(const int32_t* status, const uint32_t* crc, const uint32_t* expect, uint32_t n, uint32_t base_index,
-                                uint32_t* first_bad, hipStream_t st) {
+hipError_t qd_text_check_blocks(const int32_t* status, uint32_t n, uint32_t base_index, uint32_t* first_bad, hipStream_t st) {
     if (!n) return hipSuccess;
-    hipLaunchKernelGGL(check_blocks, dim3((n + 255) / 256), dim3(256), 0, st, status, crc, expect, n, base_index, first_bad);
+    hipLaunchKernelGGL(check_blocks, dim3((n + 255) / 256), dim3(256), 0, st, status, n, base_index, first_bad);
     return hipGetLastError();
 }
 
