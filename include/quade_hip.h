@@ -219,6 +219,34 @@ int qd_unknown_enable(qd_ctx* ctx, int64_t slots);
 int qd_unknown_stats(qd_ctx* ctx, uint64_t out[4]);
 int64_t qd_unknown_read(qd_ctx* ctx, uint8_t* keys, uint64_t* counts, int64_t cap);
 
+/* ---- yield and quality per destination (opt-in; no reference counterpart: Quade 0.3.2 reports pair counts only) ------
+ * A device-resident table of exact uint64 counters, [(2*S+1)][2][6], destination-major: destination d = routing code,
+ * 0xFFFF -> 2*S (even = <sample>_pass, odd = <sample>_fail, as the files); read 0 = R1, 1 = R2; counters
+ *   0 records    pairs routed to d
+ *   1 bases      sum of the records' sequence lengths (without a trailing '\r')
+ *   2 qual_sum   sum over the quality bytes b (unsigned, 0..255) of q = max(0, b - 33)
+ *   3 q20_bases  quality bytes with q >= 20        4 q30_bases  ... with q >= 30
+ *   5 n_bases    sequence bytes 'N' or 'n'
+ * The insert reads only reach the device in the device pipeline: qd_pipe_run counts every pair it routes (one launch per
+ * batch on its compute stream, no host sync), whatever the write flags say -- a destination that is not written is still
+ * counted; a chunk part (skip_kept, max_pairs) counts exactly its pairs.  The other launch paths (qd_demux_device,
+ * qd_submit*) never see the insert reads and count nothing.  Disabled, nothing is launched or allocated.
+ *
+ * qd_qstats_enable: on != 0 allocates and zeroes the table (96 * (2*S+1) bytes), 0 frees it.  Needs qd_set_plan and
+ * qd_set_barcodes first (QD_ERR_STATE), waits for the context's outstanding work.  qd_set_plan and qd_set_barcodes turn
+ * the counters off; qd_reset_counts zeroes them.
+ * qd_qstats_read: waits for the context's work, writes n_values = (2*S+1)*12 values (QD_ERR_INVALID on another size,
+ * QD_ERR_STATE when off).
+ * qd_qstats_add: another context's table (qd_qstats_read layout) joins this one's, as qd_add_counts does for the pair
+ * counters of chunk workers.
+ * qd_qstats_kind: how a launch of this context accumulates -- 1 = per-workgroup 32-bit partials in LDS, flushed once per
+ * workgroup (2*S+1 <= 1365 destinations), 2 = 64-bit global atomics, equal destinations merged in the wave (more);
+ * QD_ERR_STATE when off. */
+int qd_qstats_enable(qd_ctx* ctx, int32_t on);
+int qd_qstats_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
+int qd_qstats_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
+int qd_qstats_kind(const qd_ctx* ctx);
+
 /* ---- counters: replace the class counters of src/Sample.py:32,144 and feed Sample.REPORT ---------
  * qd_get_counts waits for outstanding work of this context (only), then writes 2*S+4 values. */
 int qd_get_counts(qd_ctx* ctx, uint64_t* out, int32_t n_values);
@@ -604,6 +632,13 @@ int qd_dev_crc32(int device_id, const uint8_t* data, int64_t n, int64_t range_by
  * (n + 1 values) also the exclusive sums of len in sorted order, i.e. where every pair's output record starts */
 int qd_dev_sort_by_dest(int device_id, const uint16_t* dest, int64_t n, int32_t n_dest, const uint32_t* len, uint32_t* perm_out,
                         uint32_t* offsets_out);
+/* the quality counters' stage (qd_qstats_enable above) over host buffers: pairs [0, n_pairs) of two texts with their record
+ * tables (6 uint32 per record, qd_dev_fastq_scan's layout) and routing codes are uploaded, counted by the kernel qd_pipe_run
+ * launches, and added to the context's table.  Every record's sequence and quality range is checked against len1 / len2 and
+ * every code against 2*S (0xFFFF apart) before anything is launched: QD_ERR_INVALID.  QD_ERR_STATE when the counters are off.
+ * Returns when the launch has finished. */
+int qd_dev_qstats(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+                  const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes);
 /* what a context was made with / holds (the pipeline reads them; bindings may too) */
 int qd_get_plan(const qd_ctx* ctx, qd_plan* out);
 int qd_context_device(const qd_ctx* ctx, int32_t* device_id);

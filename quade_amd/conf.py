@@ -6,7 +6,8 @@ sections, option names, 1-based -> 0-based start conversion, assertion messages)
 file written by `-i` is the reference's template byte for byte (src/Conf_file.py:18-104; shipped as
 package data, quade_amd/data/Quade_conf_file.txt).  An optional [gpu] section that reference conf
 files simply do not have is read when present (defaults apply otherwise; see GPU_SECTION_HELP), and so are the optional
-mismatch budgets of the [index] section (MISMATCH_HELP) and the unknown-barcode report of the [output] section (UNKNOWN_HELP).
+mismatch budgets of the [index] section (MISMATCH_HELP), the unknown-barcode report (UNKNOWN_HELP) and the quality report
+(QUALITY_HELP) of the [output] section.
 """
 from __future__ import annotations
 
@@ -67,6 +68,18 @@ Optional [gpu] option:
   unknown_slots : 16777216  entries of that table per context: a power of two, 1024 to 268435456 (48 bytes each).  Barcodes that
                             find no room are counted as "Not tallied" in the report's head
 """
+
+QUALITY_HELP = """\
+Optional [output] option (not in Quade 0.3.2, whose parser ignores it; absent, empty or False = no report):
+  quality_report : False    True: write Quade_quality_report.csv next to the report -- for every destination (<sample>_pass,
+                            <sample>_fail, Undetermined, Total) and for R1 and R2: reads, bases, mean length, bases at or above
+                            Q20 and Q30 (Phred+33) with their percentages, mean quality, N bases and their percentage.  A
+                            destination whose write flag is off is counted all the same.  The reads are counted on the GPU while
+                            the device pipeline holds their text, so the option needs the device pipeline: [gpu] device_pipeline,
+                            device_inflate and device_deflate True (the defaults) and gzip_level 1 or -1
+"""
+
+QUALITY_NEEDS = "quality_report needs the device pipeline (device_pipeline, device_inflate, device_deflate : True and gzip_level 1 or -1)"
 
 
 def template_bytes():
@@ -132,6 +145,10 @@ class QuadeConf(object):
         self.top_unknown_barcodes = 0
         if cp.has_option("output", "top_unknown_barcodes") and cp.get("output", "top_unknown_barcodes") not in (None, ""):
             self.top_unknown_barcodes = cp.getint("output", "top_unknown_barcodes")
+        # optional yield and quality report per destination (extension, QUALITY_HELP)
+        self.quality_report = False
+        if cp.has_option("output", "quality_report") and cp.get("output", "quality_report") not in (None, ""):
+            self.quality_report = cp.get("output", "quality_report").strip().lower() in ("true", "1", "yes", "on")
 
         # (name, fused barcode) per [sample*] section, in file order (src/Quade.py:133-139)
         self.samples = []
@@ -188,6 +205,8 @@ class QuadeConf(object):
         assert 0 <= self.top_unknown_barcodes <= 1000, "Authorized values for top_unknown_barcodes : 0 to 1000"
         assert 1 << 10 <= self.unknown_slots <= 1 << 28 and self.unknown_slots & (self.unknown_slots - 1) == 0, \
             "[gpu] unknown_slots : a power of two, 1024 to 268435456"
+        assert not self.quality_report or (self.device_pipeline and self.device_inflate and self.device_deflate
+                                           and self.gzip_level in (1, -1)), QUALITY_NEEDS
         for pos in [self.idx1_pos, self.idx2_pos, self.mol1_pos, self.mol2_pos]:
             assert pos["start"] >= 0
             assert pos["end"] >= pos["start"]

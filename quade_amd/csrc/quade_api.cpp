@@ -21,6 +21,7 @@
 #include "quade_deflate.h"
 #include "quade_mismatch.h"
 #include "quade_unknown.h"
+#include "quade_qstats.h"
 #include "quade_pool.h"
 
 typedef uint64_t u64;
@@ -136,6 +137,9 @@ struct qd_ctx {
         size_t pairs;  // 2 * pairs + 4 uint32 entries
     };
     std::vector<UkScratch> uk_scratch;
+
+    // yield and quality counters per destination (qd_qstats_enable): uint64[(2 * S + 1)][2][6], nullptr = off
+    u64* d_qs = nullptr;
 };
 
 namespace {
@@ -381,6 +385,12 @@ int launch_unknown(qd_ctx* c, int64_t n, const qd_rows* rows, const uint16_t* co
     c->uk_recorded = true;
     c->uk_last = st;
     return QD_OK;
+}
+
+// the quality counters off and their table freed (the caller waited for the context's work)
+void free_qstats(qd_ctx* c) {
+    if (c->d_qs) (void)hipFree(c->d_qs);
+    c->d_qs = nullptr;
 }
 
 // (re)build the device table from the host barcodes and the current plan
@@ -733,6 +743,7 @@ int qd_destroy(qd_ctx* c) {
     free_table(c);
     free_mismatch(c, true);
     free_unknown(c);
+    free_qstats(c);
     for (auto& t : c->tracked) (void)hipEventDestroy(t.second);
     c->tracked.clear();
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -755,11 +766,12 @@ int qd_set_plan(qd_ctx* c, const qd_plan* plan) {
     if (r != QD_OK) return fail(c, r, "plan rejected: positions must satisfy 0 <= start <= end <= 255, window <= 64, "
                                        "fused barcode <= 32, 0 <= minimal_qual <= 40");
     if (!c->slots.empty()) return fail(c, QD_ERR_STATE, "destroy the slots before changing the plan");
-    if (c->mm_m1 + c->mm_m2 > 0 || c->uk_slots) {  // a new plan resets the mismatch budgets and turns the unknown tally off
+    if (c->mm_m1 + c->mm_m2 > 0 || c->uk_slots || c->d_qs) {  // a new plan resets the mismatch budgets and turns the unknown tally and the quality counters off
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, wait_all(c));
         free_mismatch(c, false);
         free_unknown(c);
+        free_qstats(c);
     }
     c->plan = *plan;
     c->lay = L;
@@ -794,11 +806,12 @@ int qd_set_barcodes(qd_ctx* c, int32_t S, const uint8_t* barcodes, const int32_t
     if (!c->have_plan) return fail(c, QD_ERR_STATE, "qd_set_plan first");
     for (int i = 0; i < S; ++i)
         if (offsets[i + 1] < offsets[i]) return fail(c, QD_ERR_INVALID, "offsets must be non-decreasing");
-    if (c->mm_m1 + c->mm_m2 > 0 || c->uk_slots) {  // new barcodes reset the mismatch budgets, as they reset the counters, and turn the unknown tally off
+    if (c->mm_m1 + c->mm_m2 > 0 || c->uk_slots || c->d_qs) {  // new barcodes reset the mismatch budgets, as they reset the counters, and turn the unknown tally and the quality counters off
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, wait_all(c));
         free_mismatch(c, false);
         free_unknown(c);
+        free_qstats(c);
     }
     c->S = S;
     c->bc.assign(barcodes, barcodes + (S ? offsets[S] : 0));
@@ -927,6 +940,114 @@ int64_t qd_unknown_read(qd_ctx* c, uint8_t* keys, uint64_t* counts, int64_t cap)
     for (int64_t i = 0; i < D; ++i)
         for (int b = 0; b < K; ++b) keys[i * K + b] = (uint8_t)(hk[(size_t)i * QD_KEY_WORDS + (b >> 3)] >> (8 * (b & 7)));
     return D;
+}
+
+int qd_qstats_enable(qd_ctx* c, int32_t on) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->have_plan || !c->have_table) return fail(c, QD_ERR_STATE, "qd_set_plan and qd_set_barcodes first");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));  // nothing of this context may still add to the old table
+    free_qstats(c);
+    if (!on) return QD_OK;
+    const size_t bytes = qd_qstats_values((uint32_t)c->S) * 8;
+    hipError_t e = uk_malloc(reinterpret_cast<void**>(&c->d_qs), bytes);
+    if (e != hipSuccess) {
+        c->d_qs = nullptr;
+        return fail(c, QD_ERR_HIP, std::string("quality counters: ") + hipGetErrorString(e));
+    }
+    HIPCHK(c, hipMemsetAsync(c->d_qs, 0, bytes, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return QD_OK;
+}
+
+int qd_qstats_kind(const qd_ctx* c) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_qs) return fail(c, QD_ERR_STATE, "the quality counters are not enabled");
+    return qd_qstats_path((uint32_t)c->S);
+}
+
+int qd_qstats_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
+    if (!c || !out) return QD_ERR_INVALID;
+    if (!c->d_qs) return fail(c, QD_ERR_STATE, "the quality counters are not enabled");
+    if (n_values != (int64_t)qd_qstats_values((uint32_t)c->S)) return fail(c, QD_ERR_INVALID, "n_values must be (2*S+1)*12");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));
+    HIPCHK(c, hipMemcpy(out, c->d_qs, (size_t)n_values * 8, hipMemcpyDeviceToHost));
+    return QD_OK;
+}
+
+int qd_qstats_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
+    if (!c || !values) return QD_ERR_INVALID;
+    if (!c->d_qs) return fail(c, QD_ERR_STATE, "the quality counters are not enabled");
+    if (n_values != (int64_t)qd_qstats_values((uint32_t)c->S)) return fail(c, QD_ERR_INVALID, "n_values must be (2*S+1)*12");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));  // the kernels add to the table: nothing of this context may be in flight
+    std::vector<u64> h((size_t)n_values);
+    HIPCHK(c, hipMemcpy(h.data(), c->d_qs, h.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < h.size(); ++i) h[i] += values[i];
+    HIPCHK(c, hipMemcpy(c->d_qs, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+    return QD_OK;
+}
+
+int qd_qstats_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
+                     const uint16_t* codes, void* stream) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_qs || !n) return QD_OK;
+    hipStream_t st = resolve_stream(c, stream);
+    qd_qstats_args a{};
+    a.text[0] = text1;
+    a.text[1] = text2;
+    a.recs[0] = recs1;
+    a.recs[1] = recs2;
+    a.codes = codes;
+    a.table = c->d_qs;
+    hipError_t e = qd_qstats_launch(a, (uint32_t)c->S, n, st);
+    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("quality counters launch: ") + hipGetErrorString(e));
+    HIPCHK(c, track(c, st));
+    return QD_OK;
+}
+
+int qd_dev_qstats(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+                  const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_qs) return fail(c, QD_ERR_STATE, "the quality counters are not enabled");
+    const int64_t len[2] = {len1, len2};
+    const uint8_t* text[2] = {text1, text2};
+    const uint32_t* recs[2] = {recs1, recs2};
+    if (n_pairs < 0 || n_pairs > 0x7FFFFFFF || len1 < 0 || len2 < 0 || len1 > ((int64_t)1 << 30) || len2 > ((int64_t)1 << 30))
+        return fail(c, QD_ERR_INVALID, "bad sizes");
+    if (n_pairs == 0) return QD_OK;
+    if (!recs1 || !recs2 || !codes || (!text1 && len1) || (!text2 && len2)) return fail(c, QD_ERR_INVALID, "null argument");
+    static_assert(sizeof(qd_rec) == 6 * sizeof(uint32_t), "qd_dev_fastq_scan's record layout");
+    // every range and every code is checked here: a bad table cannot become a bad address
+    for (int r = 0; r < 2; ++r)
+        for (int64_t j = 0; j < n_pairs; ++j) {
+            const qd_rec* q = reinterpret_cast<const qd_rec*>(recs[r]) + j;
+            if ((int64_t)q->seq + q->seq_len > len[r] || (int64_t)q->qual + q->seq_len > len[r])
+                return fail(c, QD_ERR_INVALID, "a record's sequence or quality line reaches beyond its text");
+        }
+    for (int64_t j = 0; j < n_pairs; ++j)
+        if (codes[j] != QD_CODE_UNDETERMINED && (int)codes[j] >= 2 * c->S) return fail(c, QD_ERR_INVALID, "a routing code is not below 2*S");
+    HIPCHK(c, hipSetDevice(c->device));
+    struct Dev {
+        void* p = nullptr;
+        ~Dev() {
+            if (p) (void)hipFree(p);
+        }
+    } d_text[2], d_recs[2], d_codes;
+    // the texts start 3 bytes into their buffers: the kernel's aligned words must not depend on an aligned window
+    for (int r = 0; r < 2; ++r) {
+        HIPCHK(c, uk_malloc(&d_text[r].p, (size_t)len[r] + 32));
+        HIPCHK(c, uk_malloc(&d_recs[r].p, (size_t)n_pairs * sizeof(qd_rec)));
+        if (len[r]) HIPCHK(c, hipMemcpyAsync(static_cast<uint8_t*>(d_text[r].p) + 3, text[r], (size_t)len[r], hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_recs[r].p, recs[r], (size_t)n_pairs * sizeof(qd_rec), hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, uk_malloc(&d_codes.p, (size_t)n_pairs * 2));
+    HIPCHK(c, hipMemcpyAsync(d_codes.p, codes, (size_t)n_pairs * 2, hipMemcpyHostToDevice, c->stream));
+    const int rc = qd_qstats_device(c, static_cast<uint8_t*>(d_text[0].p) + 3, static_cast<qd_rec*>(d_recs[0].p), static_cast<uint8_t*>(d_text[1].p) + 3,
+                                    static_cast<qd_rec*>(d_recs[1].p), (uint32_t)n_pairs, static_cast<uint16_t*>(d_codes.p), QD_STREAM_CONTEXT);
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the scratch is freed on return
+    return rc;
 }
 
 int qd_kernel_kind(const qd_ctx* c, int has_len) {
@@ -1076,6 +1197,7 @@ int qd_reset_counts(qd_ctx* c) {
     HIPCHK(c, hipMemsetAsync(c->d_partial, 0, (size_t)c->partial_rows * c->cnt_stride * sizeof(qd_row_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_acc, 0, (size_t)c->cnt_stride * 8, c->stream));
     if (c->uk_slots) HIPCHK(c, hipMemsetAsync(c->d_uk, 0, qd_uk_bytes(c->uk_slots), c->stream));  // sum(counts) + short + dropped == UNDETERMINED stays true
+    if (c->d_qs) HIPCHK(c, hipMemsetAsync(c->d_qs, 0, qd_qstats_values((uint32_t)c->S) * 8, c->stream));  // records stay equal to the pair counters
     HIPCHK(c, track(c, c->stream));  // later launches on other streams are not ordered behind this: wait here
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->total_pairs = 0;

@@ -44,6 +44,7 @@
 #include "quade_inflate3.h"
 #include "quade_io_internal.h"
 #include "quade_pool.h"
+#include "quade_qstats.h"
 #include "quade_text.h"
 
 uint32_t qd_crc32_combine_host(uint32_t crc1, uint32_t crc2, uint64_t len2);  // quade_io.cpp (zlib's)
@@ -1725,6 +1726,11 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
     if (!ragged) {
         const int rc = qd_demux_device(p->ctx, n, &rows, p->codes.as<uint16_t>(), d_mol, p->cs);
         if (rc != QD_OK) return pfail(p, rc, std::string("demux: ") + qd_last_error(p->ctx));
+    }
+    {  // opt-in yield and quality counters of the insert reads (qd_qstats_enable): the codes are final, the windows still hold the pairs
+        const int rc = qd_qstats_device(p->ctx, p->win[0].buf[p->win[0].cur].p, p->win[0].recs.as<qd_rec>(), p->win[1].buf[p->win[1].cur].p,
+                                        p->win[1].recs.as<qd_rec>(), n, p->codes.as<uint16_t>(), p->cs);
+        if (rc != QD_OK) return pfail(p, rc, std::string("quality counters: ") + qd_last_error(p->ctx));
     }
     // 3. destinations, output lengths, stable sort by destination, output offsets
     PCHK(p, p->dest.need((size_t)n * 2 + 64, 0, p->cs));

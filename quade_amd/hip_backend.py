@@ -103,6 +103,10 @@ SYMBOLS = [
     ("qd_unknown_enable", C.c_int, [_P, C.c_int64]),
     ("qd_unknown_stats", C.c_int, [_P, _P]),
     ("qd_unknown_read", C.c_int64, [_P, _P, _P, C.c_int64]),
+    ("qd_qstats_enable", C.c_int, [_P, C.c_int32]),
+    ("qd_qstats_read", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_qstats_add", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_qstats_kind", C.c_int, [_P]),
     ("qd_get_counts", C.c_int, [_P, _P, C.c_int32]),
     ("qd_reset_counts", C.c_int, [_P]),
     ("qd_add_counts", C.c_int, [_P, _P, C.c_int32]),
@@ -181,6 +185,7 @@ SYMBOLS = [
     ("qd_pool_trim", C.c_int, []),
     ("qd_dev_gunzip", C.c_int, [C.c_int, _P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     ("qd_dev_sort_by_dest", C.c_int, [C.c_int, _P, C.c_int64, C.c_int32, _P, _P, _P]),
+    ("qd_dev_qstats", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P]),
     ("qd_get_plan", C.c_int, [_P, C.POINTER(qd_plan)]),
     ("qd_context_device", C.c_int, [_P, C.POINTER(C.c_int32)]),
 ]
@@ -411,6 +416,23 @@ def unpack_unknown(blob):
     return keys, counts, short, dropped
 
 
+QSTATS_COUNTERS = ("records", "bases", "qual_sum", "q20_bases", "q30_bases", "n_bases")  # per destination and read (qd_qstats_*)
+
+
+def pack_qstats(table):
+    """One context's or rank's quality table (uint64[2S+1, 2, 6]) as bytes (the ranks' exchange through the rendezvous
+    directory); unpack_qstats reverses it."""
+    table = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1, 2, len(QSTATS_COUNTERS))
+    return np.array([table.shape[0]], dtype=np.uint64).tobytes() + table.tobytes()
+
+
+def unpack_qstats(blob):
+    """-> uint64[n_dest, 2, 6] (a copy: tables are summed in place)"""
+    n_dest = int(np.frombuffer(blob, dtype=np.uint64, count=1)[0])
+    assert len(blob) == 8 + n_dest * 2 * len(QSTATS_COUNTERS) * 8, "quality table of the wrong size"
+    return np.frombuffer(blob, dtype=np.uint64, offset=8).reshape(n_dest, 2, len(QSTATS_COUNTERS)).copy()
+
+
 # ---- device context -------------------------------------------------------------------------------------
 class Engine(object):
     """One libquade_hip context = one MI355X.  Mirrors what Sample.CLASS_INIT + Sample(name, index)
@@ -507,6 +529,41 @@ class Engine(object):
             n = self.lib.qd_unknown_read(self._h, _ptr(keys), _ptr(counts), cap)
             if n > 0:
                 return keys[:n], counts[:n]
+
+    def qstats_enable(self, on=True):
+        """Yield and quality counters per destination (qd_qstats_enable): every pair the device pipeline routes adds its two
+        insert reads to a device table.  After set_barcodes: set_plan and set_barcodes turn it off, reset_counts zeroes it."""
+        self._chk(self.lib.qd_qstats_enable(self._h, int(bool(on))))
+
+    def qstats_read(self):
+        """numpy uint64[2S+1, 2, 6]: [destination (code; Undetermined last)][R1, R2][QSTATS_COUNTERS]"""
+        out = np.zeros((2 * self.n_samples + 1, 2, len(QSTATS_COUNTERS)), dtype=np.uint64)
+        self._chk(self.lib.qd_qstats_read(self._h, _ptr(out), out.size))
+        return out
+
+    def qstats_add(self, table):
+        """Another context's table (qstats_read's layout) joins this context's (qd_qstats_add)."""
+        table = np.ascontiguousarray(table, dtype=np.uint64)
+        self._chk(self.lib.qd_qstats_add(self._h, _ptr(table), table.size))
+
+    def qstats_kind(self):
+        """How a launch accumulates: "lds" (per-workgroup partials) or "global" (64-bit global atomics)."""
+        kind = self.lib.qd_qstats_kind(self._h)
+        if kind < 0:
+            self._chk(kind)
+        return {1: "lds", 2: "global"}[kind]
+
+    def dev_qstats(self, text1, recs1, text2, recs2, codes):
+        """The counters' stage over host buffers (qd_dev_qstats): texts as bytes or uint8 arrays, recs uint32[n, 6] in
+        dev_fastq_scan's layout, codes uint16[n]; adds to the context's table."""
+        t = [np.frombuffer(bytes(x), dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, dtype=np.uint8)
+             for x in (text1, text2)]
+        r = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, 6) for x in (recs1, recs2)]
+        codes = np.ascontiguousarray(codes, dtype=np.uint16)
+        if not (r[0].shape[0] == r[1].shape[0] == codes.size):
+            raise ValueError("recs1, recs2 and codes must have one entry per pair")
+        self._chk(self.lib.qd_dev_qstats(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]),
+                                         codes.size, _ptr(codes)))
 
     def set_option(self, name, value):
         self._chk(self.lib.qd_set_option(self._h, name.encode(), int(value)))

@@ -167,6 +167,8 @@ class Quade(object):
                     eng.set_mismatches(cf.idx1_mismatches, cf.idx2_mismatches)
                 if cf.top_unknown_barcodes > 0:  # the barcodes of the Undetermined pairs are counted on the device
                     eng.unknown_enable(cf.unknown_slots)
+                if cf.quality_report:  # the insert reads are counted per destination while the pipeline holds their text
+                    eng.qstats_enable(True)
                 if not self.use_pipe:
                     eng.slots_create(cf.slots, cf.batch_pairs)
                 group.append(eng)
@@ -192,6 +194,7 @@ class Quade(object):
             Sample.FLUSH_ALL()  # every rank's files are complete before its counters join the sum
         counts = self._reduce_counts(devices)
         unknown = self._collect_unknown() if cf.top_unknown_barcodes > 0 else None
+        quality = self._collect_quality() if cf.quality_report else None
         for eng in self.engines:
             eng.close()
         self.engines = []
@@ -229,6 +232,10 @@ class Quade(object):
             w1 = cf.idx1_pos["end"] - cf.idx1_pos["start"]
             write_report(os.path.join(self.outdir, REPORT_NAME), keys, ucounts, short, dropped, int(counts[3]),
                          cf.top_unknown_barcodes, w1, bool(cf.idx2), [(s.name, s.index) for s in Sample.SAMPLE_LIST])
+        if quality is not None:
+            from . import quality_report
+            quality_report.write_report(os.path.join(self.outdir, quality_report.REPORT_NAME), quality,
+                                        [s.name for s in Sample.SAMPLE_LIST])
         print("Done in {}s".format(round(time() - start_time, 3)))
         if _PROFILE:
             for k, v in sorted(_T.items(), key=lambda kv: -kv[1]):
@@ -296,6 +303,23 @@ class Quade(object):
             keys, ucounts = hb.merge_unknown([(k, c) for k, c, _, _ in parts])
             short, dropped = sum(p[2] for p in parts), sum(p[3] for p in parts)
         return keys, ucounts, short, dropped
+
+    def _collect_quality(self):
+        """[output] quality_report: the tables of every context of this process summed (chunk workers, devices); with several
+        ranks every rank publishes its sum in the rendezvous directory and adds all of them (rank 0 writes the file).
+        Returns uint64[2S+1, 2, 6]."""
+        from . import dist
+        table = None
+        for eng in self.engines:
+            t = eng.qstats_read()
+            table = t if table is None else table + t
+        if self.world > 1:
+            got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, "quality", hb.pack_qstats(table))
+            tables = [hb.unpack_qstats(b) for b in got]
+            table = tables[0]
+            for t in tables[1:]:
+                table = table + t
+        return table
 
     def double_index_parser(self):
         cf = self.cf
