@@ -1,11 +1,17 @@
 // The third inflater's lane decoder (quade_amd/csrc/inflate3_lane.h) on the host, against zlib: raw deflate streams of every block
 // type, several levels and strategies, texts that stress the tables (many symbols with long codes, one symbol, runs), damaged
 // input, and a stream cut into units at its block boundaries (what the gzip path does).  Build: g++ -O1 -std=c++17 ... -lz
+// With a directory as argv[1]: the forged corpus instead (tests/deflate_forge.py, written there by the Python test as
+// <name>.deflate + <name>.txt | <name>.illegal [+ <name>.tags]) -- streams that are DEFLATE but that zlib never writes.
 #include <zlib.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <filesystem>
+#include <fstream>
+#include <iterator>
 #include <random>
 #include <string>
 #include <vector>
@@ -118,16 +124,24 @@ static Run<C> run_unit(const std::vector<uint8_t>& comp, uint64_t bit_start, uin
     return r;
 }
 
+// forged: a stream of the corpus -- "table space" from ANY configuration is answered by the large one, as the launch does; level is
+// the case's long_codes tag then: beyond 112 no configuration holds the block, and "table space" is the one right answer
 template <class C>
-static void check_stream(const char* what, const std::vector<uint8_t>& text, int level, int strategy, bool allow_space = false) {
-    const std::vector<uint8_t> comp = deflate_raw(text, level, strategy);
+static void check_comp(const char* what, const std::vector<uint8_t>& comp, const std::vector<uint8_t>& text, int level, int strategy, bool allow_space, bool forged) {
     const uint32_t cap = (uint32_t)((text.size() + 16 + 3) & ~3u) + 8;
     Run<C> r = run_unit<C>(comp, 0, ~0ull, cap);
     if (allow_space && r.res.status == QD_INFLATE_TABLE_SPACE) return;
+    if (forged && level > 112) {
+        if (r.res.status != QD_INFLATE_TABLE_SPACE) {
+            printf("FAIL %s: %d long codes, status %u instead of table space\n", what, level, r.res.status);
+            ++g_fail;
+        }
+        return;
+    }
     // a configuration too small for the fixed code (264 symbols behind 7 bits, 112 behind 8) says "table space" at a fixed block: the
     // launch decodes such a unit again with the large configuration (quade_inflate3.hip: launch_tokens) -- so does the test
     constexpr bool fixed_fits = C::LB >= 9 || (C::LB == 8 && C::NLONG >= 112);
-    if (!fixed_fits && r.res.status == QD_INFLATE_TABLE_SPACE) {
+    if ((!fixed_fits || forged) && r.res.status == QD_INFLATE_TABLE_SPACE) {
         ++g_redone;
         Run<qd3::Cfg<8, 7, 112>> again = run_unit<qd3::Cfg<8, 7, 112>>(comp, 0, ~0ull, cap);
         CHECK(again.res.status == 0 && again.res.final_seen && again.res.text_len == text.size());
@@ -176,6 +190,75 @@ static void check_stream(const char* what, const std::vector<uint8_t>& text, int
         Run<C> through = run_unit<C>(comp, r.headers[0], r.headers[1] + 1, cap);
         CHECK(through.res.status == 0 && through.res.final_seen && through.res.text_len == text.size());
     }
+}
+
+template <class C>
+static void check_stream(const char* what, const std::vector<uint8_t>& text, int level, int strategy, bool allow_space = false) {
+    check_comp<C>(what, deflate_raw(text, level, strategy), text, level, strategy, allow_space, false);
+}
+
+// ---- the forged corpus ---------------------------------------------------------------------------------------------------------------
+struct Forged {
+    std::string name;
+    std::vector<uint8_t> comp, text;
+    bool illegal = false;
+    int long_codes = 0;
+};
+static std::vector<uint8_t> slurp(const std::filesystem::path& p) {
+    std::ifstream f(p, std::ios::binary);
+    return std::vector<uint8_t>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+}
+static std::vector<Forged> load_corpus(const char* dir) {
+    namespace fs = std::filesystem;
+    std::vector<Forged> out;
+    for (const fs::directory_entry& e : fs::directory_iterator(dir)) {
+        if (e.path().extension() != ".deflate") continue;
+        Forged c;
+        c.name = e.path().stem().string();
+        c.comp = slurp(e.path());
+        fs::path t = e.path(), bad = e.path(), tags = e.path();
+        t.replace_extension(".txt");
+        bad.replace_extension(".illegal");
+        tags.replace_extension(".tags");
+        c.illegal = fs::exists(bad);
+        if (c.illegal == fs::exists(t)) {
+            printf("FAIL %s: exactly one of .txt and .illegal\n", c.name.c_str());
+            ++g_fail;
+            continue;
+        }
+        if (!c.illegal) c.text = slurp(t);
+        if (fs::exists(tags)) {
+            const std::vector<uint8_t> tg = slurp(tags);
+            const std::string s(tg.begin(), tg.end());
+            const size_t at = s.find("long_codes=");
+            if (at != std::string::npos) c.long_codes = atoi(s.c_str() + at + 11);
+        }
+        out.push_back(std::move(c));
+    }
+    std::sort(out.begin(), out.end(), [](const Forged& a, const Forged& b) { return a.name < b.name; });
+    return out;
+}
+
+template <class C>
+static void forged_suite(const char* name, const std::vector<Forged>& cases) {
+    int refused = 0;
+    for (const Forged& c : cases) {
+        if (!c.illegal) {
+            check_comp<C>(c.name.c_str(), c.comp, c.text, c.long_codes, 0, false, true);
+            continue;
+        }
+        // an illegal stream: a status -- or tokens that do not expand (a distance in front of the stream's start is the resolve stage's to refuse)
+        Run<C> r = run_unit<C>(c.comp, 0, ~0ull, 1u << 20);
+        std::vector<uint8_t> got;
+        const bool ok = r.res.status != 0 || !r.res.final_seen || !expand(r.tok, r.res.n_slots, got);
+        if (!ok) {
+            printf("FAIL %s: an illegal stream decoded to %zu bytes\n", c.name.c_str(), got.size());
+            ++g_fail;
+        }
+        refused += ok;
+    }
+    printf("%s: forged corpus done, %zu cases, %d refused (%d streams decoded again by the large configuration)\n", name, cases.size(), refused, g_redone);
+    g_redone = 0;
 }
 
 static std::vector<uint8_t> fastq(std::mt19937& g, size_t n_bytes, int n_qual) {
@@ -256,7 +339,25 @@ static void suite(const char* name) {
     g_redone = 0;
 }
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc > 1) {
+        const std::vector<Forged> cases = load_corpus(argv[1]);
+        if (cases.empty()) {
+            printf("no corpus in %s\n", argv[1]);
+            return 1;
+        }
+        forged_suite<qd3::Cfg<8, 7, 112>>("LB 8 / DB 7 / 112 long", cases);
+        forged_suite<qd3::Cfg<9, 6, 56>>("LB 9 / DB 6 / 56 long", cases);
+        forged_suite<qd3::Cfg<10, 7, 96>>("LB 10 / DB 7 / 96 long", cases);
+        forged_suite<qd3::Cfg<7, 6, 88, true, 8, 12>>("LB 7 / DB 6 in bytes / 88 long / ring of 8 chunks, 12 turns a round", cases);
+        forged_suite<qd3::Cfg<8, 7, 64, true, 4, 6>>("LB 8 / DB 7 in bytes / 64 long / ring of 4 chunks, 6 turns a round", cases);
+        if (g_fail) {
+            printf("%d checks failed\n", g_fail);
+            return 1;
+        }
+        printf("all checks passed\n");
+        return 0;
+    }
     suite<qd3::Cfg<8, 7, 112>>("LB 8 / DB 7 / 112 long");
     suite<qd3::Cfg<9, 6, 56>>("LB 9 / DB 6 / 56 long");
     suite<qd3::Cfg<10, 7, 96>>("LB 10 / DB 7 / 96 long");

@@ -52,6 +52,13 @@ def test_inflate3_lane_decoder_against_zlib(tmp_path):
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-o", exe, os.path.join(ROOT, "tests", "native", "inflate3_lane_test.cpp"), "-lz"])
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "all checks passed" in r.stdout, r.stdout[-2000:]
+    # ... and against the forged corpus (tests/deflate_forge.py): DEFLATE that zlib never writes, and one stream per refusal
+    from tests.test_host_forge import write_corpus
+    d = tmp_path / "corpus"
+    d.mkdir()
+    write_corpus(d)
+    r = subprocess.run([exe, str(d)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "all checks passed" in r.stdout, r.stdout[-2000:]
 
 
 def test_the_gzip_probes_text_filter_names_exactly_the_bytes_text_does_not_hold():
