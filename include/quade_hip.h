@@ -247,6 +247,48 @@ int qd_qstats_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
 int qd_qstats_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
 int qd_qstats_kind(const qd_ctx* ctx);
 
+/* ---- 3' quality and adapter trimming of the insert reads (opt-in; no reference counterpart: Quade 0.3.2 writes the insert
+ * reads as they came) -----------------------------------------------------------------------------------------------------
+ * For an insert read with sequence s, quality bytes q and length L (index reads, names and the :IDX[:MOL] tag never change):
+ *   1 quality trim, quality_cutoff C > 0 (cutadapt's / BWA's rule): ph[i] = max(0, q[i] - 33), bytes unsigned; walking i from
+ *     L-1 down with a running sum of C - ph[i], stop once it is negative; Lq = the i of its strict maximum above 0, else L
+ *   2 adapter trim, an adapter a of length A set for the read: La = the leftmost p < Lq with ov = min(A, Lq - p) >= min_overlap
+ *     and at most ov * max_mismatch_pct / 100 (rounded down) positions i < ov where upper(s[p+i]) != a[i] (N and every other
+ *     byte mismatch; substitutions only); Lq when there is none
+ *   3 floor: Lout = max(La, min(min_length, L))
+ * and the read's sequence and quality lines become their first Lout bytes.  The reads only reach the device in the device
+ * pipeline: with trimming on, qd_pipe_run trims every pair it routes (one launch per batch on its compute stream, no host sync)
+ * before the quality counters (qd_qstats_enable) and the output stages see them, and adds to a device table uint64[2][8] (R1,
+ * R2), whatever the write flags say:
+ *   0 reads   1 bases_in (sum of L)   2 bases_out (sum of Lout)   3 quality_trimmed_reads (Lq < L)
+ *   4 quality_trimmed_bases (sum of L - Lq)   5 adapter_reads (La < Lq)   6 adapter_bases (sum of Lq - La)
+ *   7 floored_reads (Lout > La)
+ * Off, nothing is allocated or launched.
+ *
+ * qd_trim_set: NULL, or neither an adapter nor a cutoff, turns trimming off and frees the table; otherwise the values are
+ * checked (adapters 0..64 letters of ACGT in either case, quality_cutoff 0..93, min_overlap 1..64 and not above a set adapter's
+ * length, max_mismatch_pct 0..50, min_length 0..65535: QD_ERR_INVALID, the state as before) and a zeroed table allocated.  Waits
+ * for the context's outstanding work.  Independent of plan and barcodes.
+ * qd_trim_get: the parameters in force (adapters upper case; all zero and QD_OK when off).
+ * qd_trim_read: waits for the context's work, writes n_values = 16 values (QD_ERR_INVALID on another size, QD_ERR_STATE when off).
+ * qd_trim_add: another context's table (qd_trim_read's layout) joins this one's, as qd_qstats_add does.  qd_reset_counts
+ * zeroes the table. */
+#define QD_TRIM_ADAPTER_MAX 64
+typedef struct qd_trim_params {
+    uint8_t adapter_r1[QD_TRIM_ADAPTER_MAX]; /* the first adapter_r1_len bytes count */
+    uint8_t adapter_r2[QD_TRIM_ADAPTER_MAX];
+    int32_t adapter_r1_len; /* 0 = none */
+    int32_t adapter_r2_len;
+    int32_t quality_cutoff; /* 0 = off */
+    int32_t min_overlap;
+    int32_t max_mismatch_pct;
+    int32_t min_length;
+} qd_trim_params;
+int qd_trim_set(qd_ctx* ctx, const qd_trim_params* params);
+int qd_trim_get(const qd_ctx* ctx, qd_trim_params* out);
+int qd_trim_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
+int qd_trim_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
+
 /* ---- counters: replace the class counters of src/Sample.py:32,144 and feed Sample.REPORT ---------
  * qd_get_counts waits for outstanding work of this context (only), then writes 2*S+4 values. */
 int qd_get_counts(qd_ctx* ctx, uint64_t* out, int32_t n_values);
@@ -639,6 +681,13 @@ int qd_dev_sort_by_dest(int device_id, const uint16_t* dest, int64_t n, int32_t 
  * Returns when the launch has finished. */
 int qd_dev_qstats(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                   const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes);
+/* the trimming stage (qd_trim_set above; no reference counterpart) over host buffers: reads [0, n_pairs) of two texts with their
+ * record tables (6 uint32 per record, qd_dev_fastq_scan's layout) are uploaded and trimmed by the kernel qd_pipe_run launches;
+ * out_recs1 / out_recs2 receive the tables with every seq_len replaced by the length the read keeps, and the context's counters
+ * grow.  Every record's sequence and quality range is checked against len1 / len2 before anything is launched: QD_ERR_INVALID.
+ * QD_ERR_STATE when trimming is off.  Returns when the launch has finished. */
+int qd_dev_trim(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+                const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2);
 /* what a context was made with / holds (the pipeline reads them; bindings may too) */
 int qd_get_plan(const qd_ctx* ctx, qd_plan* out);
 int qd_context_device(const qd_ctx* ctx, int32_t* device_id);

@@ -7,7 +7,7 @@ file written by `-i` is the reference's template byte for byte (src/Conf_file.py
 package data, quade_amd/data/Quade_conf_file.txt).  An optional [gpu] section that reference conf
 files simply do not have is read when present (defaults apply otherwise; see GPU_SECTION_HELP), and so are the optional
 mismatch budgets of the [index] section (MISMATCH_HELP), the unknown-barcode report (UNKNOWN_HELP) and the quality report
-(QUALITY_HELP) of the [output] section.
+(QUALITY_HELP) of the [output] section, and an optional [trim] section (TRIM_HELP).
 """
 from __future__ import annotations
 
@@ -81,6 +81,28 @@ Optional [output] option (not in Quade 0.3.2, whose parser ignores it; absent, e
 
 QUALITY_NEEDS = "quality_report needs the device pipeline (device_pipeline, device_inflate, device_deflate : True and gzip_level 1 or -1)"
 
+TRIM_HELP = """\
+Optional [trim] section (not in Quade 0.3.2, whose parser ignores it; absent = the insert reads leave as they came): 3' trimming of
+the insert reads on the GPU.  Index reads, names and the :IDX[:MOL] tag are never touched.  In this order:
+  quality_cutoff : 0        1 to 93: cut the low-quality 3' tail (cutadapt's / BWA's rule: walking from the 3' end, the position
+                            where the running sum of cutoff - Phred is largest, stopping once it turns negative); 0 = off
+  adapter_R1 :              1 to 64 letters of ACGT: cut the read at the leftmost position from which it matches the start of the
+  adapter_R2 :              adapter up to the read's end (substitutions only; N and any other byte is a mismatch); empty = none
+  min_overlap : 3           1 to 64 and not above a set adapter's length: shorter overlaps at the 3' end are left alone
+  max_mismatch_pct : 10     0 to 50: an overlap of ov bases may hold ov * max_mismatch_pct // 100 mismatches
+  min_length : 0            0 to 65535: a read is never cut below min(min_length, its length)
+Trimming is on when an adapter is set or quality_cutoff > 0; Quade_trim_report.csv is then written next to the report.  The
+reads are trimmed while the device pipeline holds their text, so the section needs the device pipeline: [gpu] device_pipeline,
+device_inflate and device_deflate True (the defaults) and gzip_level 1 or -1
+"""
+
+TRIM_NEEDS = "[trim] needs the device pipeline (device_pipeline, device_inflate, device_deflate : True and gzip_level 1 or -1)"
+TRIM_ADAPTER = "Authorized values for adapter_R1 and adapter_R2 : 1 to 64 letters of ACGT"
+TRIM_CUTOFF = "Authorized values for quality_cutoff : 0 to 93"
+TRIM_OVERLAP = "Authorized values for min_overlap : 1 to 64, and not above the length of a set adapter"
+TRIM_MISMATCH = "Authorized values for max_mismatch_pct : 0 to 50"
+TRIM_LENGTH = "Authorized values for min_length : 0 to 65535"
+
 
 def template_bytes():
     """The example configuration file, byte for byte the reference's template: the package ships the
@@ -150,6 +172,19 @@ class QuadeConf(object):
         if cp.has_option("output", "quality_report") and cp.get("output", "quality_report") not in (None, ""):
             self.quality_report = cp.get("output", "quality_report").strip().lower() in ("true", "1", "yes", "on")
 
+        # optional [trim] section (extension, TRIM_HELP): 3' quality and adapter trimming of the insert reads
+        def trim(name, default, conv=int):
+            if cp.has_section("trim") and cp.has_option("trim", name) and cp.get("trim", name) not in (None, ""):
+                return conv(cp.get("trim", name))
+            return default
+
+        self.adapter_R1 = trim("adapter_R1", "", str).strip().upper()
+        self.adapter_R2 = trim("adapter_R2", "", str).strip().upper()
+        self.quality_cutoff = trim("quality_cutoff", 0)
+        self.min_overlap = trim("min_overlap", 3)
+        self.max_mismatch_pct = trim("max_mismatch_pct", 10)
+        self.min_length = trim("min_length", 0)
+
         # (name, fused barcode) per [sample*] section, in file order (src/Quade.py:133-139)
         self.samples = []
         for section in [i for i in cp.sections() if i.startswith("sample")]:
@@ -207,12 +242,31 @@ class QuadeConf(object):
             "[gpu] unknown_slots : a power of two, 1024 to 268435456"
         assert not self.quality_report or (self.device_pipeline and self.device_inflate and self.device_deflate
                                            and self.gzip_level in (1, -1)), QUALITY_NEEDS
+        for a in (self.adapter_R1, self.adapter_R2):
+            assert len(a) <= 64 and not a.strip("ACGT"), TRIM_ADAPTER
+        assert 0 <= self.quality_cutoff <= 93, TRIM_CUTOFF
+        assert 1 <= self.min_overlap <= 64 and all(self.min_overlap <= len(a) for a in (self.adapter_R1, self.adapter_R2) if a), \
+            TRIM_OVERLAP
+        assert 0 <= self.max_mismatch_pct <= 50, TRIM_MISMATCH
+        assert 0 <= self.min_length <= 65535, TRIM_LENGTH
+        assert not self.trim or (self.device_pipeline and self.device_inflate and self.device_deflate
+                                 and self.gzip_level in (1, -1)), TRIM_NEEDS
         for pos in [self.idx1_pos, self.idx2_pos, self.mol1_pos, self.mol2_pos]:
             assert pos["start"] >= 0
             assert pos["end"] >= pos["start"]
         assert self.batch_pairs >= 1 and 1 <= self.slots <= 64 and -1 <= self.gzip_level <= 9 and \
             1 <= self.chunk_workers <= 64 and 0 <= self.io_threads <= 1024, \
             "[gpu] batch_pairs >= 1, 1 <= slots <= 64, -1 <= gzip_level <= 9, 1 <= chunk_workers <= 64, 0 <= io_threads <= 1024"
+
+    @property
+    def trim(self):
+        """3' trimming of the insert reads is on (TRIM_HELP)"""
+        return bool(self.adapter_R1 or self.adapter_R2 or self.quality_cutoff > 0)
+
+    def trim_params(self):
+        """what Engine.trim_set takes"""
+        return dict(adapter_r1=self.adapter_R1, adapter_r2=self.adapter_R2, quality_cutoff=self.quality_cutoff,
+                    min_overlap=self.min_overlap, max_mismatch_pct=self.max_mismatch_pct, min_length=self.min_length)
 
     def plan(self):
         """The qd_plan the HIP library takes (include/quade_hip.h)."""

@@ -22,6 +22,7 @@
 #include "quade_mismatch.h"
 #include "quade_unknown.h"
 #include "quade_qstats.h"
+#include "quade_trim.h"
 #include "quade_pool.h"
 
 typedef uint64_t u64;
@@ -140,6 +141,12 @@ struct qd_ctx {
 
     // yield and quality counters per destination (qd_qstats_enable): uint64[(2 * S + 1)][2][6], nullptr = off
     u64* d_qs = nullptr;
+
+    // 3' trimming of the insert reads (qd_trim_set): the parameters as given and as the kernel takes them, and the counters
+    // uint64[2][8]; d_trim == nullptr = off
+    qd_trim_params trim{};
+    qd_trim_dev trim_dev{};
+    u64* d_trim = nullptr;
 };
 
 namespace {
@@ -391,6 +398,14 @@ int launch_unknown(qd_ctx* c, int64_t n, const qd_rows* rows, const uint16_t* co
 void free_qstats(qd_ctx* c) {
     if (c->d_qs) (void)hipFree(c->d_qs);
     c->d_qs = nullptr;
+}
+
+// trimming off and its table freed (the caller waited for the context's work)
+void free_trim(qd_ctx* c) {
+    if (c->d_trim) (void)hipFree(c->d_trim);
+    c->d_trim = nullptr;
+    c->trim = qd_trim_params{};
+    c->trim_dev = qd_trim_dev{};
 }
 
 // (re)build the device table from the host barcodes and the current plan
@@ -744,6 +759,7 @@ int qd_destroy(qd_ctx* c) {
     free_mismatch(c, true);
     free_unknown(c);
     free_qstats(c);
+    free_trim(c);
     for (auto& t : c->tracked) (void)hipEventDestroy(t.second);
     c->tracked.clear();
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1050,6 +1066,150 @@ int qd_dev_qstats(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t*
     return rc;
 }
 
+int qd_trim_set(qd_ctx* c, const qd_trim_params* params) {
+    if (!c) return QD_ERR_INVALID;
+    qd_trim_params P{};
+    qd_trim_dev D{};
+    const bool on = params && (params->adapter_r1_len || params->adapter_r2_len || params->quality_cutoff);
+    if (on) {  // checked as the configuration file's values are, before anything changes
+        P = *params;
+        const int32_t len[2] = {P.adapter_r1_len, P.adapter_r2_len};
+        uint8_t* ad[2] = {P.adapter_r1, P.adapter_r2};
+        for (int r = 0; r < 2; ++r) {
+            if (len[r] < 0 || len[r] > QD_TRIM_ADAPTER_MAX) return fail(c, QD_ERR_INVALID, "an adapter has 1 to 64 letters");
+            for (int i = 0; i < QD_TRIM_ADAPTER_MAX; ++i) {
+                if (i >= len[r]) {
+                    ad[r][i] = 0;
+                    continue;
+                }
+                ad[r][i] &= 0xDF;  // upper case
+                if (ad[r][i] != 'A' && ad[r][i] != 'C' && ad[r][i] != 'G' && ad[r][i] != 'T')
+                    return fail(c, QD_ERR_INVALID, "an adapter holds letters of ACGT only");
+                D.adapter[r][i >> 2] |= (uint32_t)ad[r][i] << (8 * (i & 3));
+            }
+            D.adapter_len[r] = (uint32_t)len[r];
+            if (len[r] && P.min_overlap > len[r]) return fail(c, QD_ERR_INVALID, "min_overlap is above the length of a set adapter");
+        }
+        if (P.quality_cutoff < 0 || P.quality_cutoff > 93) return fail(c, QD_ERR_INVALID, "quality_cutoff: 0 to 93");
+        if (P.min_overlap < 1 || P.min_overlap > QD_TRIM_ADAPTER_MAX) return fail(c, QD_ERR_INVALID, "min_overlap: 1 to 64");
+        if (P.max_mismatch_pct < 0 || P.max_mismatch_pct > 50) return fail(c, QD_ERR_INVALID, "max_mismatch_pct: 0 to 50");
+        if (P.min_length < 0 || P.min_length > 65535) return fail(c, QD_ERR_INVALID, "min_length: 0 to 65535");
+        D.cutoff = (uint32_t)P.quality_cutoff;
+        D.min_overlap = (uint32_t)P.min_overlap;
+        D.mismatch_pct = (uint32_t)P.max_mismatch_pct;
+        D.min_length = (uint32_t)P.min_length;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));  // nothing of this context may still read the old parameters or add to the old table
+    free_trim(c);
+    if (!on) return QD_OK;
+    hipError_t e = uk_malloc(reinterpret_cast<void**>(&c->d_trim), QD_TRIM_VALUES * 8);
+    if (e != hipSuccess) {
+        c->d_trim = nullptr;
+        return fail(c, QD_ERR_HIP, std::string("trim counters: ") + hipGetErrorString(e));
+    }
+    HIPCHK(c, hipMemsetAsync(c->d_trim, 0, QD_TRIM_VALUES * 8, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->trim = P;
+    c->trim_dev = D;
+    return QD_OK;
+}
+
+int qd_trim_get(const qd_ctx* c, qd_trim_params* out) {
+    if (!c || !out) return QD_ERR_INVALID;
+    *out = c->trim;
+    return QD_OK;
+}
+
+int qd_trim_active(const qd_ctx* c) { return c && c->d_trim ? 1 : 0; }
+
+int qd_trim_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
+    if (!c || !out) return QD_ERR_INVALID;
+    if (!c->d_trim) return fail(c, QD_ERR_STATE, "trimming is not on");
+    if (n_values != QD_TRIM_VALUES) return fail(c, QD_ERR_INVALID, "n_values must be 16");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));
+    HIPCHK(c, hipMemcpy(out, c->d_trim, QD_TRIM_VALUES * 8, hipMemcpyDeviceToHost));
+    return QD_OK;
+}
+
+int qd_trim_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
+    if (!c || !values) return QD_ERR_INVALID;
+    if (!c->d_trim) return fail(c, QD_ERR_STATE, "trimming is not on");
+    if (n_values != QD_TRIM_VALUES) return fail(c, QD_ERR_INVALID, "n_values must be 16");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));  // the kernel adds to the table: nothing of this context may be in flight
+    u64 h[QD_TRIM_VALUES];
+    HIPCHK(c, hipMemcpy(h, c->d_trim, sizeof(h), hipMemcpyDeviceToHost));
+    for (int i = 0; i < QD_TRIM_VALUES; ++i) h[i] += values[i];
+    HIPCHK(c, hipMemcpy(c->d_trim, h, sizeof(h), hipMemcpyHostToDevice));
+    return QD_OK;
+}
+
+int qd_trim_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
+                   qd_rec* out1, qd_rec* out2, void* stream) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_trim) return fail(c, QD_ERR_STATE, "trimming is not on");
+    if (!n) return QD_OK;
+    hipStream_t st = resolve_stream(c, stream);
+    qd_trim_args a{};
+    a.text[0] = text1;
+    a.text[1] = text2;
+    a.recs[0] = recs1;
+    a.recs[1] = recs2;
+    a.out[0] = out1;
+    a.out[1] = out2;
+    a.table = c->d_trim;
+    hipError_t e = qd_trim_launch(c->trim_dev, a, n, st);
+    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("trim launch: ") + hipGetErrorString(e));
+    HIPCHK(c, track(c, st));
+    return QD_OK;
+}
+
+int qd_dev_trim(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+                const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_trim) return fail(c, QD_ERR_STATE, "trimming is not on");
+    const int64_t len[2] = {len1, len2};
+    const uint8_t* text[2] = {text1, text2};
+    const uint32_t* recs[2] = {recs1, recs2};
+    uint32_t* out[2] = {out_recs1, out_recs2};
+    if (n_pairs < 0 || n_pairs > 0x7FFFFFFF || len1 < 0 || len2 < 0 || len1 > ((int64_t)1 << 30) || len2 > ((int64_t)1 << 30))
+        return fail(c, QD_ERR_INVALID, "bad sizes");
+    if (n_pairs == 0) return QD_OK;
+    if (!recs1 || !recs2 || !out_recs1 || !out_recs2 || (!text1 && len1) || (!text2 && len2)) return fail(c, QD_ERR_INVALID, "null argument");
+    // every range is checked here: a bad table cannot become a bad address
+    for (int r = 0; r < 2; ++r)
+        for (int64_t j = 0; j < n_pairs; ++j) {
+            const qd_rec* q = reinterpret_cast<const qd_rec*>(recs[r]) + j;
+            if ((int64_t)q->seq + q->seq_len > len[r] || (int64_t)q->qual + q->seq_len > len[r])
+                return fail(c, QD_ERR_INVALID, "a record's sequence or quality line reaches beyond its text");
+        }
+    HIPCHK(c, hipSetDevice(c->device));
+    struct Dev {
+        void* p = nullptr;
+        ~Dev() {
+            if (p) (void)hipFree(p);
+        }
+    } d_text[2], d_recs[2], d_out[2];
+    const size_t rec_bytes = (size_t)n_pairs * sizeof(qd_rec);
+    // the texts start 3 bytes into their buffers: the kernel's aligned words must not depend on an aligned window
+    for (int r = 0; r < 2; ++r) {
+        HIPCHK(c, uk_malloc(&d_text[r].p, (size_t)len[r] + 32));
+        HIPCHK(c, uk_malloc(&d_recs[r].p, rec_bytes));
+        HIPCHK(c, uk_malloc(&d_out[r].p, rec_bytes));
+        if (len[r]) HIPCHK(c, hipMemcpyAsync(static_cast<uint8_t*>(d_text[r].p) + 3, text[r], (size_t)len[r], hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_recs[r].p, recs[r], rec_bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    const int rc = qd_trim_device(c, static_cast<uint8_t*>(d_text[0].p) + 3, static_cast<qd_rec*>(d_recs[0].p), static_cast<uint8_t*>(d_text[1].p) + 3,
+                                  static_cast<qd_rec*>(d_recs[1].p), (uint32_t)n_pairs, static_cast<qd_rec*>(d_out[0].p), static_cast<qd_rec*>(d_out[1].p),
+                                  QD_STREAM_CONTEXT);
+    if (rc == QD_OK)
+        for (int r = 0; r < 2; ++r) HIPCHK(c, hipMemcpyAsync(out[r], d_out[r].p, rec_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the scratch is freed on return
+    return rc;
+}
+
 int qd_kernel_kind(const qd_ctx* c, int has_len) {
     if (!c || !c->have_table) return QD_ERR_STATE;
     return pick_kernel(c, has_len != 0);
@@ -1191,13 +1351,20 @@ int qd_add_counts(qd_ctx* c, const uint64_t* counts, int32_t n_values) {
 
 int qd_reset_counts(qd_ctx* c) {
     if (!c) return QD_ERR_INVALID;
-    if (!c->have_table) return QD_OK;
+    if (!c->have_table) {  // no barcodes, no pair counters; the trim counters do not depend on them
+        if (!c->d_trim) return QD_OK;
+        HIPCHK(c, hipSetDevice(c->device));
+        HIPCHK(c, wait_all(c));
+        HIPCHK(c, hipMemset(c->d_trim, 0, QD_TRIM_VALUES * 8));
+        return QD_OK;
+    }
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, join_into_own_stream(c));
-    HIPCHK(c, hipMemsetAsync(c->d_partial, 0, (size_t)c->partial_rows * c->cnt_stride * sizeof(qd_row_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_partial, 0,(size_t)c->partial_rows * c->cnt_stride * sizeof(qd_row_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_acc, 0, (size_t)c->cnt_stride * 8, c->stream));
     if (c->uk_slots) HIPCHK(c, hipMemsetAsync(c->d_uk, 0, qd_uk_bytes(c->uk_slots), c->stream));  // sum(counts) + short + dropped == UNDETERMINED stays true
     if (c->d_qs) HIPCHK(c, hipMemsetAsync(c->d_qs, 0, qd_qstats_values((uint32_t)c->S) * 8, c->stream));  // records stay equal to the pair counters
+    if (c->d_trim) HIPCHK(c, hipMemsetAsync(c->d_trim, 0, QD_TRIM_VALUES * 8, c->stream));
     HIPCHK(c, track(c, c->stream));  // later launches on other streams are not ordered behind this: wait here
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->total_pairs = 0;

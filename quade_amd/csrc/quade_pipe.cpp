@@ -46,6 +46,7 @@
 #include "quade_pool.h"
 #include "quade_qstats.h"
 #include "quade_text.h"
+#include "quade_trim.h"
 
 uint32_t qd_crc32_combine_host(uint32_t crc1, uint32_t crc2, uint64_t len2);  // quade_io.cpp (zlib's)
 
@@ -716,6 +717,7 @@ struct qd_pipe {
     // index rows, codes, routing scratch (sized for batch_pairs)
     DevBuf rows_seq[2], rows_qual[2], rows_len[2], codes, mol, short_idx, dest, len1, len2, hist, tmp, perm, sdest, g1, g2, scan_tiles, first, g1_first,
         g2_first;
+    DevBuf trimmed[2];  // the insert reads' record tables with trimmed lengths (qd_trim_set; never allocated when trimming is off)
     PinBuf h_first;
     // tables and scratch of the format / CRC / coder launches: read by kernels on the compute stream only, so one set serves every batch
     DevBuf subs, first_sub, ranges, crc, tokens, sub_out, sub_bytes, base1, base2;
@@ -1727,9 +1729,19 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
         const int rc = qd_demux_device(p->ctx, n, &rows, p->codes.as<uint16_t>(), d_mol, p->cs);
         if (rc != QD_OK) return pfail(p, rc, std::string("demux: ") + qd_last_error(p->ctx));
     }
+    // opt-in 3' trimming of the insert reads (qd_trim_set): trimmed copies of their two tables, which everything behind this point
+    // reads sequence and quality through.  The scan's tables stay as they are: the carry and the next batch use them
+    const qd_rec* ins[2] = {p->win[0].recs.as<qd_rec>(), p->win[1].recs.as<qd_rec>()};
+    if (qd_trim_active(p->ctx)) {
+        for (int k = 0; k < 2; ++k) PCHK(p, p->trimmed[k].need((size_t)n * sizeof(qd_rec) + 64, 0, p->cs));
+        const int rc = qd_trim_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p, ins[1], n,
+                                      p->trimmed[0].as<qd_rec>(), p->trimmed[1].as<qd_rec>(), p->cs);
+        if (rc != QD_OK) return pfail(p, rc, std::string("trim: ") + qd_last_error(p->ctx));
+        for (int k = 0; k < 2; ++k) ins[k] = p->trimmed[k].as<qd_rec>();
+    }
     {  // opt-in yield and quality counters of the insert reads (qd_qstats_enable): the codes are final, the windows still hold the pairs
-        const int rc = qd_qstats_device(p->ctx, p->win[0].buf[p->win[0].cur].p, p->win[0].recs.as<qd_rec>(), p->win[1].buf[p->win[1].cur].p,
-                                        p->win[1].recs.as<qd_rec>(), n, p->codes.as<uint16_t>(), p->cs);
+        const int rc = qd_qstats_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p,
+                                        ins[1], n, p->codes.as<uint16_t>(), p->cs);
         if (rc != QD_OK) return pfail(p, rc, std::string("quality counters: ") + qd_last_error(p->ctx));
     }
     // 3. destinations, output lengths, stable sort by destination, output offsets
@@ -1749,8 +1761,8 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
     PCHK(p, p->g2_first.need((size_t)nd * 4, 0, p->cs));
     qd_route_args ra{};
     ra.codes = p->codes.as<uint16_t>();
-    ra.r1 = p->win[0].recs.as<qd_rec>();
-    ra.r2 = p->win[1].recs.as<qd_rec>();
+    ra.r1 = ins[0];
+    ra.r2 = ins[1];
     for (int k = 0; k < ni; ++k) ra.idx[k] = iw[k]->recs.as<qd_rec>();
     ra.dest = p->dest.as<uint16_t>();
     ra.len1 = p->len1.as<uint32_t>();
@@ -2561,7 +2573,7 @@ int qd_pipe_destroy(qd_pipe* p) {
     p->gz = nullptr;
     for (DevBuf* b : {&p->d_res, &p->rows_seq[0], &p->rows_seq[1], &p->rows_qual[0], &p->rows_qual[1], &p->rows_len[0], &p->rows_len[1], &p->codes, &p->mol,
                       &p->short_idx, &p->dest, &p->len1, &p->len2, &p->hist, &p->tmp, &p->perm, &p->sdest, &p->g1, &p->g2, &p->scan_tiles, &p->first, &p->g1_first,
-                      &p->g2_first, &p->subs, &p->first_sub, &p->ranges, &p->crc, &p->tokens, &p->sub_out, &p->sub_bytes, &p->base1, &p->base2})
+                      &p->g2_first, &p->subs, &p->first_sub, &p->ranges, &p->crc, &p->tokens, &p->sub_out, &p->sub_bytes, &p->base1, &p->base2, &p->trimmed[0], &p->trimmed[1]})
         b->release();
     for (OutSet& o : p->out) {
         for (DevBuf* b : {&o.text, &o.pieces, &o.members, &o.member_len, &o.member_off, &o.packed}) b->release();

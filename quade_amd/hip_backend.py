@@ -47,6 +47,11 @@ class qd_rows(C.Structure):
     _fields_ = [("seq", C.c_void_p * 2), ("qual", C.c_void_p * 2), ("len", C.c_void_p * 2)]
 
 
+class qd_trim_params(C.Structure):
+    _fields_ = [("adapter_r1", C.c_uint8 * 64), ("adapter_r2", C.c_uint8 * 64), ("adapter_r1_len", C.c_int32), ("adapter_r2_len", C.c_int32),
+                ("quality_cutoff", C.c_int32), ("min_overlap", C.c_int32), ("max_mismatch_pct", C.c_int32), ("min_length", C.c_int32)]
+
+
 class qd_text_batch(C.Structure):
     _fields_ = [("text", C.c_void_p), ("text_len", C.c_int64), ("rec_off", C.c_void_p), ("n_records", C.c_int64),
                 ("handle", C.c_void_p)]
@@ -107,6 +112,10 @@ SYMBOLS = [
     ("qd_qstats_read", C.c_int, [_P, _P, C.c_int64]),
     ("qd_qstats_add", C.c_int, [_P, _P, C.c_int64]),
     ("qd_qstats_kind", C.c_int, [_P]),
+    ("qd_trim_set", C.c_int, [_P, C.POINTER(qd_trim_params)]),
+    ("qd_trim_get", C.c_int, [_P, C.POINTER(qd_trim_params)]),
+    ("qd_trim_read", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_trim_add", C.c_int, [_P, _P, C.c_int64]),
     ("qd_get_counts", C.c_int, [_P, _P, C.c_int32]),
     ("qd_reset_counts", C.c_int, [_P]),
     ("qd_add_counts", C.c_int, [_P, _P, C.c_int32]),
@@ -186,6 +195,7 @@ SYMBOLS = [
     ("qd_dev_gunzip", C.c_int, [C.c_int, _P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     ("qd_dev_sort_by_dest", C.c_int, [C.c_int, _P, C.c_int64, C.c_int32, _P, _P, _P]),
     ("qd_dev_qstats", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P]),
+    ("qd_dev_trim", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_get_plan", C.c_int, [_P, C.POINTER(qd_plan)]),
     ("qd_context_device", C.c_int, [_P, C.POINTER(C.c_int32)]),
 ]
@@ -433,6 +443,23 @@ def unpack_qstats(blob):
     return np.frombuffer(blob, dtype=np.uint64, offset=8).reshape(n_dest, 2, len(QSTATS_COUNTERS)).copy()
 
 
+TRIM_COUNTERS = ("reads", "bases_in", "bases_out", "quality_trimmed_reads", "quality_trimmed_bases", "adapter_reads", "adapter_bases",
+                 "floored_reads")  # per read R1 / R2 (qd_trim_*)
+
+
+def pack_trim(table):
+    """One context's or rank's trim counters (uint64[2, 8]) as bytes (the ranks' exchange through the rendezvous directory);
+    unpack_trim reverses it."""
+    table = np.ascontiguousarray(table, dtype=np.uint64).reshape(2, len(TRIM_COUNTERS))
+    return table.tobytes()
+
+
+def unpack_trim(blob):
+    """-> uint64[2, 8] (a copy: tables are summed in place)"""
+    assert len(blob) == 2 * len(TRIM_COUNTERS) * 8, "trim counters of the wrong size"
+    return np.frombuffer(blob, dtype=np.uint64).reshape(2, len(TRIM_COUNTERS)).copy()
+
+
 # ---- device context -------------------------------------------------------------------------------------
 class Engine(object):
     """One libquade_hip context = one MI355X.  Mirrors what Sample.CLASS_INIT + Sample(name, index)
@@ -564,6 +591,50 @@ class Engine(object):
             raise ValueError("recs1, recs2 and codes must have one entry per pair")
         self._chk(self.lib.qd_dev_qstats(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]),
                                          codes.size, _ptr(codes)))
+
+    def trim_set(self, adapter_r1="", adapter_r2="", quality_cutoff=0, min_overlap=3, max_mismatch_pct=10, min_length=0):
+        """3' trimming of the insert reads in the device pipeline (qd_trim_set; conf.TRIM_HELP has the rules).  Neither an adapter
+        nor a cutoff turns it off and frees the counters; a value out of range is QD_ERR_INVALID and changes nothing."""
+        P = qd_trim_params()
+        for name, a in (("adapter_r1", adapter_r1), ("adapter_r2", adapter_r2)):
+            a = a.encode() if isinstance(a, str) else bytes(a)
+            if len(a) > 64:
+                raise QuadeHipError(QD_ERR_INVALID, "qd_trim_set: an adapter has 1 to 64 letters")
+            getattr(P, name)[:len(a)] = list(a)
+            setattr(P, name + "_len", len(a))
+        P.quality_cutoff, P.min_overlap, P.max_mismatch_pct, P.min_length = int(quality_cutoff), int(min_overlap), int(max_mismatch_pct), int(min_length)
+        self._chk(self.lib.qd_trim_set(self._h, C.byref(P)))
+
+    def trim_get(self):
+        """The parameters in force, as trim_set's keywords (adapters upper case; trimming off: no adapters, all zero)."""
+        P = qd_trim_params()
+        self._chk(self.lib.qd_trim_get(self._h, C.byref(P)))
+        return dict(adapter_r1=bytes(P.adapter_r1[:P.adapter_r1_len]).decode(), adapter_r2=bytes(P.adapter_r2[:P.adapter_r2_len]).decode(),
+                    quality_cutoff=P.quality_cutoff, min_overlap=P.min_overlap, max_mismatch_pct=P.max_mismatch_pct, min_length=P.min_length)
+
+    def trim_read(self):
+        """numpy uint64[2, 8]: [R1, R2][TRIM_COUNTERS]"""
+        out = np.zeros((2, len(TRIM_COUNTERS)), dtype=np.uint64)
+        self._chk(self.lib.qd_trim_read(self._h, _ptr(out), out.size))
+        return out
+
+    def trim_add(self, table):
+        """Another context's counters (trim_read's layout) join this context's (qd_trim_add)."""
+        table = np.ascontiguousarray(table, dtype=np.uint64)
+        self._chk(self.lib.qd_trim_add(self._h, _ptr(table), table.size))
+
+    def dev_trim(self, text1, recs1, text2, recs2):
+        """The trimming stage over host buffers (qd_dev_trim): texts as bytes or uint8 arrays, recs uint32[n, 6] in
+        dev_fastq_scan's layout; -> the two tables with the lengths the reads keep; adds to the context's counters."""
+        t = [np.frombuffer(bytes(x), dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, dtype=np.uint8)
+             for x in (text1, text2)]
+        r = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, 6) for x in (recs1, recs2)]
+        if r[0].shape[0] != r[1].shape[0]:
+            raise ValueError("recs1 and recs2 must have one entry per pair")
+        out = [np.zeros_like(x) for x in r]
+        self._chk(self.lib.qd_dev_trim(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), r[0].shape[0],
+                                       _ptr(out[0]), _ptr(out[1])))
+        return out[0], out[1]
 
     def set_option(self, name, value):
         self._chk(self.lib.qd_set_option(self._h, name.encode(), int(value)))

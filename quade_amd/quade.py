@@ -169,6 +169,8 @@ class Quade(object):
                     eng.unknown_enable(cf.unknown_slots)
                 if cf.quality_report:  # the insert reads are counted per destination while the pipeline holds their text
                     eng.qstats_enable(True)
+                if cf.trim:  # the insert reads are trimmed at their 3' end while the pipeline holds their text
+                    eng.trim_set(**cf.trim_params())
                 if not self.use_pipe:
                     eng.slots_create(cf.slots, cf.batch_pairs)
                 group.append(eng)
@@ -195,6 +197,7 @@ class Quade(object):
         counts = self._reduce_counts(devices)
         unknown = self._collect_unknown() if cf.top_unknown_barcodes > 0 else None
         quality = self._collect_quality() if cf.quality_report else None
+        trimmed = self._collect_trim() if cf.trim else None
         for eng in self.engines:
             eng.close()
         self.engines = []
@@ -236,6 +239,9 @@ class Quade(object):
             from . import quality_report
             quality_report.write_report(os.path.join(self.outdir, quality_report.REPORT_NAME), quality,
                                         [s.name for s in Sample.SAMPLE_LIST])
+        if trimmed is not None:
+            from . import trim_report
+            trim_report.write_report(os.path.join(self.outdir, trim_report.REPORT_NAME), trimmed, cf.trim_params())
         print("Done in {}s".format(round(time() - start_time, 3)))
         if _PROFILE:
             for k, v in sorted(_T.items(), key=lambda kv: -kv[1]):
@@ -316,6 +322,22 @@ class Quade(object):
         if self.world > 1:
             got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, "quality", hb.pack_qstats(table))
             tables = [hb.unpack_qstats(b) for b in got]
+            table = tables[0]
+            for t in tables[1:]:
+                table = table + t
+        return table
+
+    def _collect_trim(self):
+        """[trim]: the counters of every context of this process summed (chunk workers, devices); with several ranks every rank
+        publishes its sum in the rendezvous directory and adds all of them (rank 0 writes the file).  Returns uint64[2, 8]."""
+        from . import dist
+        table = None
+        for eng in self.engines:
+            t = eng.trim_read()
+            table = t if table is None else table + t
+        if self.world > 1:
+            got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, "trim", hb.pack_trim(table))
+            tables = [hb.unpack_trim(b) for b in got]
             table = tables[0]
             for t in tables[1:]:
                 table = table + t
