@@ -289,6 +289,55 @@ int qd_trim_get(const qd_ctx* ctx, qd_trim_params* out);
 int qd_trim_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
 int qd_trim_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
 
+/* ---- paired-end overlap trimming of the insert reads with insert sizes (opt-in; no reference counterpart: Quade 0.3.2 never
+ * looks at R1 and R2 of a pair together) ------------------------------------------------------------------------------------
+ * When the insert is shorter than the reads, R1 and the reverse complement of R2 overlap over the whole insert and everything
+ * behind it is adapter, whatever its sequence.  Per pair, the two insert reads as the stage receives them -- behind the 3'
+ * trimming above when that is on, as scanned otherwise: sequences s1, s2 of current lengths L1, L2 (only the first L bytes of
+ * each count).
+ *   fold      : u(b) = b & 0xDF; a base is valid only if u(b) is one of A C G T; comp maps A<->T and C<->G
+ *   candidate : an insert length I, 1 <= I <= L1 + L2, pairs position i of R1 with position j = I - 1 - i of R2 for all i with
+ *               0 <= i < L1 and 0 <= j < L2; the number of such positions is ov(I) = min(L1, I) - max(0, I - L2).  A position
+ *               matches iff u(s1[i]) is valid and u(s2[j]) == comp(u(s1[i])); everything else is a mismatch, N in either read
+ *               and N opposite N included.  I is accepted iff ov(I) >= min_overlap and
+ *               mismatches <= min(max_mismatches, ov(I) * max_mismatch_pct / 100) (rounded down)
+ *   insert I* : with M = max(L1, L2): the smallest accepted I >= M if there is one (the reads overlap or the insert spans them;
+ *               nothing is cut, and a tandem repeat that also matches at a shorter I causes no trim); otherwise the largest
+ *               accepted I < M; otherwise there is none
+ *   cut       : I* < M: Lp_r = min(L_r, I*) for each read; otherwise Lp_r = L_r
+ *   floor     : Lout_r = max(Lp_r, min(min_length, L_r)), min_length being the 3' trimming's.  That stage applied the same floor:
+ *               it left L_r >= min(min_length, L0_r) of a read of L0_r bases, so L_r < min_length only where L_r == L0_r and
+ *               min(min_length, L_r) == min(min_length, L0_r) either way -- the stage's input length serves as L_r
+ * and the read's sequence and quality lines become their first Lout_r bytes.  Index reads, names and the :IDX[:MOL] tag never
+ * change and no pair is dropped.  With the stage on, qd_pipe_run runs it over every pair it routes (one launch per batch on its
+ * compute stream, no host sync) directly behind the 3' trimming and before the quality counters (qd_qstats_enable) and the output
+ * stages see the reads, and adds to a device table of 1040 uint64, whatever the write flags say:
+ *   [2][6] per read R1, R2: 0 reads   1 bases_in (sum of L)   2 bases_out (sum of Lout)   3 overlap_trimmed_reads (Lp < L)
+ *                           4 overlap_trimmed_bases (sum of L - Lp)   5 floored_reads (Lout > Lp)
+ *   [12] pairs   [13] overlapped_pairs (an I* exists)   [14] short_insert_pairs (I* < M)
+ *   [15 .. 1039] the insert sizes: bin I* for I* < 1024, the last bin for I* >= 1024
+ * Off, nothing is allocated or launched.
+ *
+ * qd_pairtrim_set: NULL turns the stage off and frees the table; otherwise the values are checked (min_overlap 8..1000,
+ * max_mismatches 0..64, max_mismatch_pct 0..50, min_length 0..65535: QD_ERR_INVALID, the state as before) and a zeroed table
+ * allocated.  Waits for the context's outstanding work.  Independent of plan, barcodes and qd_trim_set.
+ * qd_pairtrim_get: the parameters in force (all zero and QD_OK when off).
+ * qd_pairtrim_read: waits for the context's work, writes n_values = 1040 values (QD_ERR_INVALID on another size, QD_ERR_STATE
+ * when off).
+ * qd_pairtrim_add: another context's table (qd_pairtrim_read's layout) joins this one's, as qd_trim_add does.  qd_reset_counts
+ * zeroes the table. */
+#define QD_PAIRTRIM_VALUES 1040
+typedef struct qd_pairtrim_params {
+    int32_t min_overlap;
+    int32_t max_mismatches;
+    int32_t max_mismatch_pct;
+    int32_t min_length;
+} qd_pairtrim_params;
+int qd_pairtrim_set(qd_ctx* ctx, const qd_pairtrim_params* params);
+int qd_pairtrim_get(const qd_ctx* ctx, qd_pairtrim_params* out);
+int qd_pairtrim_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
+int qd_pairtrim_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
+
 /* ---- counters: replace the class counters of src/Sample.py:32,144 and feed Sample.REPORT ---------
  * qd_get_counts waits for outstanding work of this context (only), then writes 2*S+4 values. */
 int qd_get_counts(qd_ctx* ctx, uint64_t* out, int32_t n_values);
@@ -688,6 +737,13 @@ int qd_dev_qstats(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_
  * QD_ERR_STATE when trimming is off.  Returns when the launch has finished. */
 int qd_dev_trim(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                 const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2);
+/* the overlap trimming stage (qd_pairtrim_set above; no reference counterpart) over host buffers, as qd_dev_trim: pairs
+ * [0, n_pairs) of two texts with their record tables are uploaded and run through the kernel qd_pipe_run launches; out_recs1 /
+ * out_recs2 receive the tables with every seq_len replaced by the length the read keeps, and the context's table grows.  Every
+ * record's sequence and quality range is checked against len1 / len2 before anything is launched: QD_ERR_INVALID.  QD_ERR_STATE
+ * when the stage is off.  Returns when the launch has finished. */
+int qd_dev_pairtrim(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+                    const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2);
 /* what a context was made with / holds (the pipeline reads them; bindings may too) */
 int qd_get_plan(const qd_ctx* ctx, qd_plan* out);
 int qd_context_device(const qd_ctx* ctx, int32_t* device_id);

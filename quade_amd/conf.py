@@ -7,7 +7,7 @@ file written by `-i` is the reference's template byte for byte (src/Conf_file.py
 package data, quade_amd/data/Quade_conf_file.txt).  An optional [gpu] section that reference conf
 files simply do not have is read when present (defaults apply otherwise; see GPU_SECTION_HELP), and so are the optional
 mismatch budgets of the [index] section (MISMATCH_HELP), the unknown-barcode report (UNKNOWN_HELP) and the quality report
-(QUALITY_HELP) of the [output] section, and an optional [trim] section (TRIM_HELP).
+(QUALITY_HELP) of the [output] section, and an optional [trim] section (TRIM_HELP, PAIR_HELP).
 """
 from __future__ import annotations
 
@@ -103,6 +103,26 @@ TRIM_OVERLAP = "Authorized values for min_overlap : 1 to 64, and not above the l
 TRIM_MISMATCH = "Authorized values for max_mismatch_pct : 0 to 50"
 TRIM_LENGTH = "Authorized values for min_length : 0 to 65535"
 
+PAIR_HELP = """\
+Optional [trim] options (not in Quade 0.3.2, whose parser ignores them; absent = as before): paired-end overlap trimming of the
+insert reads on the GPU, which needs no adapter sequence.  When the insert is shorter than the reads, R1 and the reverse complement
+of R2 overlap over the whole insert and everything behind it is adapter.  Runs behind the 3' trimming above when both are on.
+  pair_overlap : False         True: look for the insert length I at which R1 and the reverse complement of R2 agree; an insert
+                               shorter than the longer read cuts both reads to it (an insert at least that long cuts nothing, and
+                               wins over a shorter one); min_length (above) holds for these cuts too
+  pair_min_overlap : 30        8 to 1000: the reads must overlap by at least this many bases at I
+  pair_max_mismatches : 5      0 to 64: an overlap of ov bases may hold min(pair_max_mismatches, ov * pair_max_mismatch_pct // 100)
+  pair_max_mismatch_pct : 20   0 to 50  mismatches (N and any other byte is a mismatch; lower case matches)
+Quade_pair_trim_report.csv is then written next to the report: what was cut and the insert sizes of the library.  The reads are
+trimmed while the device pipeline holds their text, so pair_overlap needs the device pipeline: [gpu] device_pipeline,
+device_inflate and device_deflate True (the defaults) and gzip_level 1 or -1
+"""
+
+PAIR_NEEDS = "pair_overlap needs the device pipeline (device_pipeline, device_inflate, device_deflate : True and gzip_level 1 or -1)"
+PAIR_OVERLAP = "Authorized values for pair_min_overlap : 8 to 1000"
+PAIR_MISMATCHES = "Authorized values for pair_max_mismatches : 0 to 64"
+PAIR_MISMATCH_PCT = "Authorized values for pair_max_mismatch_pct : 0 to 50"
+
 
 def template_bytes():
     """The example configuration file, byte for byte the reference's template: the package ships the
@@ -184,6 +204,11 @@ class QuadeConf(object):
         self.min_overlap = trim("min_overlap", 3)
         self.max_mismatch_pct = trim("max_mismatch_pct", 10)
         self.min_length = trim("min_length", 0)
+        # ... and its paired-end overlap trimming (PAIR_HELP)
+        self.pair_overlap = trim("pair_overlap", False, lambda v: v.strip().lower() in ("true", "1", "yes", "on"))
+        self.pair_min_overlap = trim("pair_min_overlap", 30)
+        self.pair_max_mismatches = trim("pair_max_mismatches", 5)
+        self.pair_max_mismatch_pct = trim("pair_max_mismatch_pct", 20)
 
         # (name, fused barcode) per [sample*] section, in file order (src/Quade.py:133-139)
         self.samples = []
@@ -251,6 +276,11 @@ class QuadeConf(object):
         assert 0 <= self.min_length <= 65535, TRIM_LENGTH
         assert not self.trim or (self.device_pipeline and self.device_inflate and self.device_deflate
                                  and self.gzip_level in (1, -1)), TRIM_NEEDS
+        assert 8 <= self.pair_min_overlap <= 1000, PAIR_OVERLAP
+        assert 0 <= self.pair_max_mismatches <= 64, PAIR_MISMATCHES
+        assert 0 <= self.pair_max_mismatch_pct <= 50, PAIR_MISMATCH_PCT
+        assert not self.pair_trim or (self.device_pipeline and self.device_inflate and self.device_deflate
+                                      and self.gzip_level in (1, -1)), PAIR_NEEDS
         for pos in [self.idx1_pos, self.idx2_pos, self.mol1_pos, self.mol2_pos]:
             assert pos["start"] >= 0
             assert pos["end"] >= pos["start"]
@@ -267,6 +297,16 @@ class QuadeConf(object):
         """what Engine.trim_set takes"""
         return dict(adapter_r1=self.adapter_R1, adapter_r2=self.adapter_R2, quality_cutoff=self.quality_cutoff,
                     min_overlap=self.min_overlap, max_mismatch_pct=self.max_mismatch_pct, min_length=self.min_length)
+
+    @property
+    def pair_trim(self):
+        """paired-end overlap trimming of the insert reads is on (PAIR_HELP)"""
+        return bool(self.pair_overlap)
+
+    def pair_trim_params(self):
+        """what Engine.pairtrim_set takes"""
+        return dict(min_overlap=self.pair_min_overlap, max_mismatches=self.pair_max_mismatches,
+                    max_mismatch_pct=self.pair_max_mismatch_pct, min_length=self.min_length)
 
     def plan(self):
         """The qd_plan the HIP library takes (include/quade_hip.h)."""

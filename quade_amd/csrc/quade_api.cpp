@@ -23,6 +23,7 @@
 #include "quade_unknown.h"
 #include "quade_qstats.h"
 #include "quade_trim.h"
+#include "quade_pairtrim.h"
 #include "quade_pool.h"
 
 typedef uint64_t u64;
@@ -147,6 +148,12 @@ struct qd_ctx {
     qd_trim_params trim{};
     qd_trim_dev trim_dev{};
     u64* d_trim = nullptr;
+
+    // paired-end overlap trimming with insert sizes (qd_pairtrim_set): the parameters as given and as the kernel takes them, and
+    // the table uint64[1040]; d_pairtrim == nullptr = off
+    qd_pairtrim_params pairtrim{};
+    qd_pairtrim_dev pairtrim_dev{};
+    u64* d_pairtrim = nullptr;
 };
 
 namespace {
@@ -406,6 +413,14 @@ void free_trim(qd_ctx* c) {
     c->d_trim = nullptr;
     c->trim = qd_trim_params{};
     c->trim_dev = qd_trim_dev{};
+}
+
+// overlap trimming off and its table freed (the caller waited for the context's work)
+void free_pairtrim(qd_ctx* c) {
+    if (c->d_pairtrim) (void)hipFree(c->d_pairtrim);
+    c->d_pairtrim = nullptr;
+    c->pairtrim = qd_pairtrim_params{};
+    c->pairtrim_dev = qd_pairtrim_dev{};
 }
 
 // (re)build the device table from the host barcodes and the current plan
@@ -760,6 +775,7 @@ int qd_destroy(qd_ctx* c) {
     free_unknown(c);
     free_qstats(c);
     free_trim(c);
+    free_pairtrim(c);
     for (auto& t : c->tracked) (void)hipEventDestroy(t.second);
     c->tracked.clear();
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1210,6 +1226,134 @@ int qd_dev_trim(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* r
     return rc;
 }
 
+static_assert(QD_PAIRTRIM_VALUES == QD_PT_VALUES, "the public table size is the kernel's");
+
+int qd_pairtrim_set(qd_ctx* c, const qd_pairtrim_params* params) {
+    if (!c) return QD_ERR_INVALID;
+    qd_pairtrim_params P{};
+    qd_pairtrim_dev D{};
+    if (params) {  // checked as the configuration file's values are, before anything changes
+        P = *params;
+        if (P.min_overlap < 8 || P.min_overlap > 1000) return fail(c, QD_ERR_INVALID, "pair min_overlap: 8 to 1000");
+        if (P.max_mismatches < 0 || P.max_mismatches > 64) return fail(c, QD_ERR_INVALID, "pair max_mismatches: 0 to 64");
+        if (P.max_mismatch_pct < 0 || P.max_mismatch_pct > 50) return fail(c, QD_ERR_INVALID, "pair max_mismatch_pct: 0 to 50");
+        if (P.min_length < 0 || P.min_length > 65535) return fail(c, QD_ERR_INVALID, "min_length: 0 to 65535");
+        D.min_overlap = (uint32_t)P.min_overlap;
+        D.max_mismatches = (uint32_t)P.max_mismatches;
+        D.mismatch_pct = (uint32_t)P.max_mismatch_pct;
+        D.min_length = (uint32_t)P.min_length;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));  // nothing of this context may still read the old parameters or add to the old table
+    free_pairtrim(c);
+    if (!params) return QD_OK;
+    hipError_t e = uk_malloc(reinterpret_cast<void**>(&c->d_pairtrim), QD_PT_VALUES * 8);
+    if (e != hipSuccess) {
+        c->d_pairtrim = nullptr;
+        return fail(c, QD_ERR_HIP, std::string("overlap trimming table: ") + hipGetErrorString(e));
+    }
+    HIPCHK(c, hipMemsetAsync(c->d_pairtrim, 0, QD_PT_VALUES * 8, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->pairtrim = P;
+    c->pairtrim_dev = D;
+    return QD_OK;
+}
+
+int qd_pairtrim_get(const qd_ctx* c, qd_pairtrim_params* out) {
+    if (!c || !out) return QD_ERR_INVALID;
+    *out = c->pairtrim;
+    return QD_OK;
+}
+
+int qd_pairtrim_active(const qd_ctx* c) { return c && c->d_pairtrim ? 1 : 0; }
+
+int qd_pairtrim_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
+    if (!c || !out) return QD_ERR_INVALID;
+    if (!c->d_pairtrim) return fail(c, QD_ERR_STATE, "overlap trimming is not on");
+    if (n_values != QD_PT_VALUES) return fail(c, QD_ERR_INVALID, "n_values must be 1040");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));
+    HIPCHK(c, hipMemcpy(out, c->d_pairtrim, QD_PT_VALUES * 8, hipMemcpyDeviceToHost));
+    return QD_OK;
+}
+
+int qd_pairtrim_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
+    if (!c || !values) return QD_ERR_INVALID;
+    if (!c->d_pairtrim) return fail(c, QD_ERR_STATE, "overlap trimming is not on");
+    if (n_values != QD_PT_VALUES) return fail(c, QD_ERR_INVALID, "n_values must be 1040");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));  // the kernel adds to the table: nothing of this context may be in flight
+    std::vector<u64> h(QD_PT_VALUES);
+    HIPCHK(c, hipMemcpy(h.data(), c->d_pairtrim, QD_PT_VALUES * 8, hipMemcpyDeviceToHost));
+    for (int i = 0; i < QD_PT_VALUES; ++i) h[i] += values[i];
+    HIPCHK(c, hipMemcpy(c->d_pairtrim, h.data(), QD_PT_VALUES * 8, hipMemcpyHostToDevice));
+    return QD_OK;
+}
+
+int qd_pairtrim_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
+                       qd_rec* out1, qd_rec* out2, void* stream) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_pairtrim) return fail(c, QD_ERR_STATE, "overlap trimming is not on");
+    if (!n) return QD_OK;
+    hipStream_t st = resolve_stream(c, stream);
+    qd_pairtrim_args a{};
+    a.text[0] = text1;
+    a.text[1] = text2;
+    a.recs[0] = recs1;
+    a.recs[1] = recs2;
+    a.out[0] = out1;
+    a.out[1] = out2;
+    a.table = c->d_pairtrim;
+    hipError_t e = qd_pairtrim_launch(c->pairtrim_dev, a, n, st);
+    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("overlap trimming launch: ") + hipGetErrorString(e));
+    HIPCHK(c, track(c, st));
+    return QD_OK;
+}
+
+int qd_dev_pairtrim(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+                    const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_pairtrim) return fail(c, QD_ERR_STATE, "overlap trimming is not on");
+    const int64_t len[2] = {len1, len2};
+    const uint8_t* text[2] = {text1, text2};
+    const uint32_t* recs[2] = {recs1, recs2};
+    uint32_t* out[2] = {out_recs1, out_recs2};
+    if (n_pairs < 0 || n_pairs > 0x7FFFFFFF || len1 < 0 || len2 < 0 || len1 > ((int64_t)1 << 30) || len2 > ((int64_t)1 << 30))
+        return fail(c, QD_ERR_INVALID, "bad sizes");
+    if (n_pairs == 0) return QD_OK;
+    if (!recs1 || !recs2 || !out_recs1 || !out_recs2 || (!text1 && len1) || (!text2 && len2)) return fail(c, QD_ERR_INVALID, "null argument");
+    // every range is checked here: a bad table cannot become a bad address (the stage reads the sequence lines only)
+    for (int r = 0; r < 2; ++r)
+        for (int64_t j = 0; j < n_pairs; ++j) {
+            const qd_rec* q = reinterpret_cast<const qd_rec*>(recs[r]) + j;
+            if ((int64_t)q->seq + q->seq_len > len[r] || (int64_t)q->qual + q->seq_len > len[r])
+                return fail(c, QD_ERR_INVALID, "a record's sequence or quality line reaches beyond its text");
+        }
+    HIPCHK(c, hipSetDevice(c->device));
+    struct Dev {
+        void* p = nullptr;
+        ~Dev() {
+            if (p) (void)hipFree(p);
+        }
+    } d_text[2], d_recs[2], d_out[2];
+    const size_t rec_bytes = (size_t)n_pairs * sizeof(qd_rec);
+    // the texts start 3 bytes into their buffers: the kernel's aligned words must not depend on an aligned window
+    for (int r = 0; r < 2; ++r) {
+        HIPCHK(c, uk_malloc(&d_text[r].p, (size_t)len[r] + 32));
+        HIPCHK(c, uk_malloc(&d_recs[r].p, rec_bytes));
+        HIPCHK(c, uk_malloc(&d_out[r].p, rec_bytes));
+        if (len[r]) HIPCHK(c, hipMemcpyAsync(static_cast<uint8_t*>(d_text[r].p) + 3, text[r], (size_t)len[r], hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_recs[r].p, recs[r], rec_bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    const int rc = qd_pairtrim_device(c, static_cast<uint8_t*>(d_text[0].p) + 3, static_cast<qd_rec*>(d_recs[0].p), static_cast<uint8_t*>(d_text[1].p) + 3,
+                                      static_cast<qd_rec*>(d_recs[1].p), (uint32_t)n_pairs, static_cast<qd_rec*>(d_out[0].p),
+                                      static_cast<qd_rec*>(d_out[1].p), QD_STREAM_CONTEXT);
+    if (rc == QD_OK)
+        for (int r = 0; r < 2; ++r) HIPCHK(c, hipMemcpyAsync(out[r], d_out[r].p, rec_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the scratch is freed on return
+    return rc;
+}
+
 int qd_kernel_kind(const qd_ctx* c, int has_len) {
     if (!c || !c->have_table) return QD_ERR_STATE;
     return pick_kernel(c, has_len != 0);
@@ -1352,10 +1496,11 @@ int qd_add_counts(qd_ctx* c, const uint64_t* counts, int32_t n_values) {
 int qd_reset_counts(qd_ctx* c) {
     if (!c) return QD_ERR_INVALID;
     if (!c->have_table) {  // no barcodes, no pair counters; the trim counters do not depend on them
-        if (!c->d_trim) return QD_OK;
+        if (!c->d_trim && !c->d_pairtrim) return QD_OK;
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, wait_all(c));
-        HIPCHK(c, hipMemset(c->d_trim, 0, QD_TRIM_VALUES * 8));
+        if (c->d_trim) HIPCHK(c, hipMemset(c->d_trim, 0, QD_TRIM_VALUES * 8));
+        if (c->d_pairtrim) HIPCHK(c, hipMemset(c->d_pairtrim, 0, QD_PT_VALUES * 8));
         return QD_OK;
     }
     HIPCHK(c, hipSetDevice(c->device));
@@ -1365,6 +1510,7 @@ int qd_reset_counts(qd_ctx* c) {
     if (c->uk_slots) HIPCHK(c, hipMemsetAsync(c->d_uk, 0, qd_uk_bytes(c->uk_slots), c->stream));  // sum(counts) + short + dropped == UNDETERMINED stays true
     if (c->d_qs) HIPCHK(c, hipMemsetAsync(c->d_qs, 0, qd_qstats_values((uint32_t)c->S) * 8, c->stream));  // records stay equal to the pair counters
     if (c->d_trim) HIPCHK(c, hipMemsetAsync(c->d_trim, 0, QD_TRIM_VALUES * 8, c->stream));
+    if (c->d_pairtrim) HIPCHK(c, hipMemsetAsync(c->d_pairtrim, 0, QD_PT_VALUES * 8, c->stream));
     HIPCHK(c, track(c, c->stream));  // later launches on other streams are not ordered behind this: wait here
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->total_pairs = 0;

@@ -47,6 +47,7 @@
 #include "quade_qstats.h"
 #include "quade_text.h"
 #include "quade_trim.h"
+#include "quade_pairtrim.h"
 
 uint32_t qd_crc32_combine_host(uint32_t crc1, uint32_t crc2, uint64_t len2);  // quade_io.cpp (zlib's)
 
@@ -718,6 +719,7 @@ struct qd_pipe {
     DevBuf rows_seq[2], rows_qual[2], rows_len[2], codes, mol, short_idx, dest, len1, len2, hist, tmp, perm, sdest, g1, g2, scan_tiles, first, g1_first,
         g2_first;
     DevBuf trimmed[2];  // the insert reads' record tables with trimmed lengths (qd_trim_set; never allocated when trimming is off)
+    DevBuf pairtrimmed[2];  // ... with the lengths the overlap trimming leaves (qd_pairtrim_set; never allocated when it is off)
     PinBuf h_first;
     // tables and scratch of the format / CRC / coder launches: read by kernels on the compute stream only, so one set serves every batch
     DevBuf subs, first_sub, ranges, crc, tokens, sub_out, sub_bytes, base1, base2;
@@ -1739,6 +1741,14 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
         if (rc != QD_OK) return pfail(p, rc, std::string("trim: ") + qd_last_error(p->ctx));
         for (int k = 0; k < 2; ++k) ins[k] = p->trimmed[k].as<qd_rec>();
     }
+    // opt-in paired-end overlap trimming (qd_pairtrim_set): R1 and R2 of a pair together, on the lengths the stage above left
+    if (qd_pairtrim_active(p->ctx)) {
+        for (int k = 0; k < 2; ++k) PCHK(p, p->pairtrimmed[k].need((size_t)n * sizeof(qd_rec) + 64, 0, p->cs));
+        const int rc = qd_pairtrim_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p, ins[1], n,
+                                          p->pairtrimmed[0].as<qd_rec>(), p->pairtrimmed[1].as<qd_rec>(), p->cs);
+        if (rc != QD_OK) return pfail(p, rc, std::string("overlap trim: ") + qd_last_error(p->ctx));
+        for (int k = 0; k < 2; ++k) ins[k] = p->pairtrimmed[k].as<qd_rec>();
+    }
     {  // opt-in yield and quality counters of the insert reads (qd_qstats_enable): the codes are final, the windows still hold the pairs
         const int rc = qd_qstats_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p,
                                         ins[1], n, p->codes.as<uint16_t>(), p->cs);
@@ -2573,7 +2583,8 @@ int qd_pipe_destroy(qd_pipe* p) {
     p->gz = nullptr;
     for (DevBuf* b : {&p->d_res, &p->rows_seq[0], &p->rows_seq[1], &p->rows_qual[0], &p->rows_qual[1], &p->rows_len[0], &p->rows_len[1], &p->codes, &p->mol,
                       &p->short_idx, &p->dest, &p->len1, &p->len2, &p->hist, &p->tmp, &p->perm, &p->sdest, &p->g1, &p->g2, &p->scan_tiles, &p->first, &p->g1_first,
-                      &p->g2_first, &p->subs, &p->first_sub, &p->ranges, &p->crc, &p->tokens, &p->sub_out, &p->sub_bytes, &p->base1, &p->base2, &p->trimmed[0], &p->trimmed[1]})
+                      &p->g2_first, &p->subs, &p->first_sub, &p->ranges, &p->crc, &p->tokens, &p->sub_out, &p->sub_bytes, &p->base1, &p->base2, &p->trimmed[0], &p->trimmed[1], &p->pairtrimmed[0],
+                      &p->pairtrimmed[1]})
         b->release();
     for (OutSet& o : p->out) {
         for (DevBuf* b : {&o.text, &o.pieces, &o.members, &o.member_len, &o.member_off, &o.packed}) b->release();

@@ -52,6 +52,10 @@ class qd_trim_params(C.Structure):
                 ("quality_cutoff", C.c_int32), ("min_overlap", C.c_int32), ("max_mismatch_pct", C.c_int32), ("min_length", C.c_int32)]
 
 
+class qd_pairtrim_params(C.Structure):
+    _fields_ = [("min_overlap", C.c_int32), ("max_mismatches", C.c_int32), ("max_mismatch_pct", C.c_int32), ("min_length", C.c_int32)]
+
+
 class qd_text_batch(C.Structure):
     _fields_ = [("text", C.c_void_p), ("text_len", C.c_int64), ("rec_off", C.c_void_p), ("n_records", C.c_int64),
                 ("handle", C.c_void_p)]
@@ -116,6 +120,10 @@ SYMBOLS = [
     ("qd_trim_get", C.c_int, [_P, C.POINTER(qd_trim_params)]),
     ("qd_trim_read", C.c_int, [_P, _P, C.c_int64]),
     ("qd_trim_add", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_pairtrim_set", C.c_int, [_P, C.POINTER(qd_pairtrim_params)]),
+    ("qd_pairtrim_get", C.c_int, [_P, C.POINTER(qd_pairtrim_params)]),
+    ("qd_pairtrim_read", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_pairtrim_add", C.c_int, [_P, _P, C.c_int64]),
     ("qd_get_counts", C.c_int, [_P, _P, C.c_int32]),
     ("qd_reset_counts", C.c_int, [_P]),
     ("qd_add_counts", C.c_int, [_P, _P, C.c_int32]),
@@ -196,6 +204,7 @@ SYMBOLS = [
     ("qd_dev_sort_by_dest", C.c_int, [C.c_int, _P, C.c_int64, C.c_int32, _P, _P, _P]),
     ("qd_dev_qstats", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P]),
     ("qd_dev_trim", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
+    ("qd_dev_pairtrim", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_get_plan", C.c_int, [_P, C.POINTER(qd_plan)]),
     ("qd_context_device", C.c_int, [_P, C.POINTER(C.c_int32)]),
 ]
@@ -460,6 +469,32 @@ def unpack_trim(blob):
     return np.frombuffer(blob, dtype=np.uint64).reshape(2, len(TRIM_COUNTERS)).copy()
 
 
+PAIRTRIM_COUNTERS = ("reads", "bases_in", "bases_out", "overlap_trimmed_reads", "overlap_trimmed_bases", "floored_reads")  # per read
+PAIRTRIM_PAIR_COUNTERS = ("pairs", "overlapped_pairs", "short_insert_pairs")
+PAIRTRIM_BINS = 1025  # insert sizes: bin I for I < 1024, the last bin for I >= 1024
+PAIRTRIM_VALUES = 2 * len(PAIRTRIM_COUNTERS) + len(PAIRTRIM_PAIR_COUNTERS) + PAIRTRIM_BINS  # qd_pairtrim_*'s table: 1040
+
+
+def pack_pairtrim(table):
+    """One context's or rank's overlap trimming table (uint64[1040]) as bytes (the ranks' exchange through the rendezvous
+    directory); unpack_pairtrim reverses it."""
+    table = np.ascontiguousarray(table, dtype=np.uint64).reshape(PAIRTRIM_VALUES)
+    return table.tobytes()
+
+
+def unpack_pairtrim(blob):
+    """-> uint64[1040] (a copy: tables are summed in place)"""
+    assert len(blob) == PAIRTRIM_VALUES * 8, "an overlap trimming table of the wrong size"
+    return np.frombuffer(blob, dtype=np.uint64).copy()
+
+
+def split_pairtrim(table):
+    """a table -> (per read [2][6], the three pair counters, the 1025 insert size bins), Python integers"""
+    t = [int(x) for x in np.asarray(table).reshape(PAIRTRIM_VALUES)]
+    k = len(PAIRTRIM_COUNTERS)
+    return [t[:k], t[k:2 * k]], t[2 * k:2 * k + 3], t[2 * k + 3:]
+
+
 # ---- device context -------------------------------------------------------------------------------------
 class Engine(object):
     """One libquade_hip context = one MI355X.  Mirrors what Sample.CLASS_INIT + Sample(name, index)
@@ -634,6 +669,45 @@ class Engine(object):
         out = [np.zeros_like(x) for x in r]
         self._chk(self.lib.qd_dev_trim(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), r[0].shape[0],
                                        _ptr(out[0]), _ptr(out[1])))
+        return out[0], out[1]
+
+    def pairtrim_set(self, min_overlap=30, max_mismatches=5, max_mismatch_pct=20, min_length=0, on=True):
+        """Paired-end overlap trimming of the insert reads in the device pipeline (qd_pairtrim_set; conf.PAIR_HELP has the
+        rules).  on=False turns it off and frees the table; a value out of range is QD_ERR_INVALID and changes nothing."""
+        if not on:
+            self._chk(self.lib.qd_pairtrim_set(self._h, None))
+            return
+        P = qd_pairtrim_params(int(min_overlap), int(max_mismatches), int(max_mismatch_pct), int(min_length))
+        self._chk(self.lib.qd_pairtrim_set(self._h, C.byref(P)))
+
+    def pairtrim_get(self):
+        """The parameters in force, as pairtrim_set's keywords (the stage off: all zero)."""
+        P = qd_pairtrim_params()
+        self._chk(self.lib.qd_pairtrim_get(self._h, C.byref(P)))
+        return dict(min_overlap=P.min_overlap, max_mismatches=P.max_mismatches, max_mismatch_pct=P.max_mismatch_pct, min_length=P.min_length)
+
+    def pairtrim_read(self):
+        """numpy uint64[1040]: [R1, R2][PAIRTRIM_COUNTERS], PAIRTRIM_PAIR_COUNTERS, the insert size bins (split_pairtrim)"""
+        out = np.zeros(PAIRTRIM_VALUES, dtype=np.uint64)
+        self._chk(self.lib.qd_pairtrim_read(self._h, _ptr(out), out.size))
+        return out
+
+    def pairtrim_add(self, table):
+        """Another context's table (pairtrim_read's layout) joins this context's (qd_pairtrim_add)."""
+        table = np.ascontiguousarray(table, dtype=np.uint64)
+        self._chk(self.lib.qd_pairtrim_add(self._h, _ptr(table), table.size))
+
+    def dev_pairtrim(self, text1, recs1, text2, recs2):
+        """The overlap trimming stage over host buffers (qd_dev_pairtrim): texts as bytes or uint8 arrays, recs uint32[n, 6] in
+        dev_fastq_scan's layout; -> the two tables with the lengths the reads keep; adds to the context's table."""
+        t = [np.frombuffer(bytes(x), dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, dtype=np.uint8)
+             for x in (text1, text2)]
+        r = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, 6) for x in (recs1, recs2)]
+        if r[0].shape[0] != r[1].shape[0]:
+            raise ValueError("recs1 and recs2 must have one entry per pair")
+        out = [np.zeros_like(x) for x in r]
+        self._chk(self.lib.qd_dev_pairtrim(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), r[0].shape[0],
+                                           _ptr(out[0]), _ptr(out[1])))
         return out[0], out[1]
 
     def set_option(self, name, value):

@@ -171,6 +171,8 @@ class Quade(object):
                     eng.qstats_enable(True)
                 if cf.trim:  # the insert reads are trimmed at their 3' end while the pipeline holds their text
                     eng.trim_set(**cf.trim_params())
+                if cf.pair_trim:  # ... and R1 and R2 of a pair together, behind it
+                    eng.pairtrim_set(**cf.pair_trim_params())
                 if not self.use_pipe:
                     eng.slots_create(cf.slots, cf.batch_pairs)
                 group.append(eng)
@@ -198,6 +200,7 @@ class Quade(object):
         unknown = self._collect_unknown() if cf.top_unknown_barcodes > 0 else None
         quality = self._collect_quality() if cf.quality_report else None
         trimmed = self._collect_trim() if cf.trim else None
+        pair_trimmed = self._collect_pair_trim() if cf.pair_trim else None
         for eng in self.engines:
             eng.close()
         self.engines = []
@@ -242,6 +245,9 @@ class Quade(object):
         if trimmed is not None:
             from . import trim_report
             trim_report.write_report(os.path.join(self.outdir, trim_report.REPORT_NAME), trimmed, cf.trim_params())
+        if pair_trimmed is not None:
+            from . import pair_trim_report
+            pair_trim_report.write_report(os.path.join(self.outdir, pair_trim_report.REPORT_NAME), pair_trimmed, cf.pair_trim_params())
         print("Done in {}s".format(round(time() - start_time, 3)))
         if _PROFILE:
             for k, v in sorted(_T.items(), key=lambda kv: -kv[1]):
@@ -338,6 +344,23 @@ class Quade(object):
         if self.world > 1:
             got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, "trim", hb.pack_trim(table))
             tables = [hb.unpack_trim(b) for b in got]
+            table = tables[0]
+            for t in tables[1:]:
+                table = table + t
+        return table
+
+    def _collect_pair_trim(self):
+        """[trim] pair_overlap: the tables of every context of this process summed (chunk workers, devices); with several ranks
+        every rank publishes its sum in the rendezvous directory and adds all of them (rank 0 writes the file).  Returns
+        uint64[1040]."""
+        from . import dist
+        table = None
+        for eng in self.engines:
+            t = eng.pairtrim_read()
+            table = t if table is None else table + t
+        if self.world > 1:
+            got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, "pairtrim", hb.pack_pairtrim(table))
+            tables = [hb.unpack_pairtrim(b) for b in got]
             table = tables[0]
             for t in tables[1:]:
                 table = table + t
