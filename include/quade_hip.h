@@ -338,6 +338,60 @@ int qd_pairtrim_get(const qd_ctx* ctx, qd_pairtrim_params* out);
 int qd_pairtrim_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
 int qd_pairtrim_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
 
+/* ---- read filtering of the insert reads: length, N, quality, complexity (opt-in; no reference counterpart: Quade 0.3.2 writes
+ * every pair it assigns) ----------------------------------------------------------------------------------------------------
+ * The step cutadapt and fastp run directly behind trimming: discard the pairs that are not worth keeping, pair-aware, and say
+ * how many went and why.  The stage sees the two insert reads as the trimming stages above left them (as scanned when those are
+ * off).  For a read of length L with sequence bytes s and quality bytes q (unsigned):
+ *   n_count = the number of bytes 'N' or 'n'
+ *   unq     = the number of q[i] < 33 + qualified_quality
+ *   qsum    = the sum of max(0, q[i] - 33) (QD_QS_QUAL_SUM's definition)
+ *   diff    = the number of i in [0, L - 1) with (s[i] & 0xDF) != (s[i + 1] & 0xDF)
+ * A pair is dropped for the first of these rules that either of its reads fails; a rule whose parameter is -1 is off and
+ * skipped; all comparisons are in 64-bit integers:
+ *   1 too_short         L < min_length                                   (fastp -l, cutadapt -m)
+ *   2 too_many_n        n_count > max_n                                  (fastp -n)
+ *   3 low_quality       unq * 100 > max_unqualified_pct * L              (fastp -u with -q)
+ *   4 low_mean_quality  qsum < min_mean_quality * L                      (fastp -e)
+ *   5 low_complexity    diff * 100 < min_complexity_pct * max(L - 1, 0)  (fastp -y with -Y)
+ * An empty read fails rule 1 only.  The filter applies to every pair, Undetermined included.  A dropped pair appears in no output
+ * file, neither its R1 nor its R2 record, and the quality counters (qd_qstats_enable) do not count it: they count the pairs that
+ * are written.  The pair counters (qd_get_counts), the unknown-barcode tally and the two trimming tables are as without the
+ * stage: they count what their stages saw.  A destination that loses all its pairs is treated exactly as a destination that
+ * received none: the pipeline hands the sink no text for it, and since the sink creates a destination's two files when the first
+ * text for it arrives, it has no files.
+ * With the stage on, qd_pipe_run runs it over every pair it routes (one launch per batch on its compute stream, no host sync)
+ * behind the trimming stages and in front of the quality counters, and adds to a device table uint64[2 * S + 1][8],
+ * destination-major as qd_qstats_read's (destination = routing code, Undetermined last), whatever the write flags say:
+ *   0 pairs   1 .. 5 the pairs dropped by rule 1 .. 5   6 bases_in (L of both reads, every pair)   7 bases_dropped (... of the
+ *   dropped pairs)
+ * Off, nothing is allocated or launched and no path changes.
+ *
+ * qd_filter_set: NULL, or every rule -1, turns the stage off and frees the table; otherwise the values are checked (min_length 1
+ * .. 100000, max_n 0 .. 100000, max_unqualified_pct 0 .. 100, qualified_quality 1 .. 93 with -1 = 15, min_mean_quality 1 .. 93,
+ * min_complexity_pct 1 .. 100: QD_ERR_INVALID, the state as before) and a zeroed table allocated, which needs the plan and the
+ * barcodes (QD_ERR_STATE); a new plan or new barcodes turn the stage off, as they do the quality counters.  Waits for the
+ * context's outstanding work.
+ * qd_filter_get: the parameters in force (every rule -1, qualified_quality 15 and QD_OK when off).
+ * qd_filter_read: waits for the context's work, writes n_values = (2 * S + 1) * 8 values (QD_ERR_INVALID on another size,
+ * QD_ERR_STATE when off).  qd_filter_add: another context's table joins this one's.  qd_reset_counts zeroes the table.
+ * qd_filter_kind: which accumulation the kernel takes for this context's S: 1 = 32-bit partials in LDS (2 * S + 1 <= 2048),
+ * 2 = 64-bit atomics on the table. */
+#define QD_FILTER_VALUES 8
+typedef struct qd_filter_params {
+    int32_t min_length;
+    int32_t max_n;
+    int32_t max_unqualified_pct;
+    int32_t qualified_quality;
+    int32_t min_mean_quality;
+    int32_t min_complexity_pct;
+} qd_filter_params;
+int qd_filter_set(qd_ctx* ctx, const qd_filter_params* params);
+int qd_filter_get(const qd_ctx* ctx, qd_filter_params* out);
+int qd_filter_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
+int qd_filter_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
+int qd_filter_kind(const qd_ctx* ctx);
+
 /* ---- counters: replace the class counters of src/Sample.py:32,144 and feed Sample.REPORT ---------
  * qd_get_counts waits for outstanding work of this context (only), then writes 2*S+4 values. */
 int qd_get_counts(qd_ctx* ctx, uint64_t* out, int32_t n_values);
@@ -744,6 +798,13 @@ int qd_dev_trim(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t*
  * when the stage is off.  Returns when the launch has finished. */
 int qd_dev_pairtrim(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                     const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2);
+/* the read filter (qd_filter_set above; no reference counterpart) over host buffers, as qd_dev_qstats: pairs [0, n_pairs) of two
+ * texts with their record tables and routing codes are uploaded (the texts 3 bytes off alignment) and run through the kernel
+ * qd_pipe_run launches; reasons[j] receives 0 (kept) or the number of the rule that dropped pair j, and the context's table grows.
+ * Every record's sequence and quality range is checked against len1 / len2 and every code against 2 * S before anything is
+ * launched: QD_ERR_INVALID.  QD_ERR_STATE when the stage is off.  Returns when the launch has finished. */
+int qd_dev_filter(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+                  const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes, uint8_t* reasons);
 /* what a context was made with / holds (the pipeline reads them; bindings may too) */
 int qd_get_plan(const qd_ctx* ctx, qd_plan* out);
 int qd_context_device(const qd_ctx* ctx, int32_t* device_id);

@@ -7,7 +7,8 @@ file written by `-i` is the reference's template byte for byte (src/Conf_file.py
 package data, quade_amd/data/Quade_conf_file.txt).  An optional [gpu] section that reference conf
 files simply do not have is read when present (defaults apply otherwise; see GPU_SECTION_HELP), and so are the optional
 mismatch budgets of the [index] section (MISMATCH_HELP), the unknown-barcode report (UNKNOWN_HELP) and the quality report
-(QUALITY_HELP) of the [output] section, and an optional [trim] section (TRIM_HELP, PAIR_HELP).
+(QUALITY_HELP) of the [output] section, an optional [trim] section (TRIM_HELP, PAIR_HELP) and an optional [filter] section
+(FILTER_HELP).
 """
 from __future__ import annotations
 
@@ -123,6 +124,33 @@ PAIR_OVERLAP = "Authorized values for pair_min_overlap : 8 to 1000"
 PAIR_MISMATCHES = "Authorized values for pair_max_mismatches : 0 to 64"
 PAIR_MISMATCH_PCT = "Authorized values for pair_max_mismatch_pct : 0 to 50"
 
+FILTER_HELP = """\
+Optional [filter] section (not in Quade 0.3.2, whose parser ignores it; absent = every pair is written): discard pairs on the GPU,
+behind the [trim] stages and on what they left.  A pair is dropped, its R1 and its R2 record, for the first of these rules that
+either of its reads fails; an absent or empty option turns its rule off.  For a read of L bases:
+  min_length :              1 to 100000: too_short, L < min_length (fastp -l, cutadapt -m)
+  max_n :                   0 to 100000: too_many_n, more than max_n bases N or n (fastp -n)
+  max_unqualified_pct :     0 to 100: low_quality, more than this percentage of the bases below Phred qualified_quality (fastp -u)
+  qualified_quality : 15    1 to 93: the Phred value (Phred+33) a base needs to be qualified (fastp -q)
+  min_mean_quality :        1 to 93: low_mean_quality, mean Phred below it (fastp -e)
+  min_complexity_pct :      1 to 100: low_complexity, less than this percentage of the bases differ from the base behind them
+                            (fastp -y with -Y); a poly-G read has 0
+The filter applies to every pair, Undetermined included.  Quade_report.csv still counts assignments, the trim reports what
+their stages saw, and quality_report the pairs that were written; a destination that loses all its pairs has no files, as one
+that received none.  Quade_filter_report.csv is written next to the report: per destination, pairs in, kept and dropped by
+reason, bases in and kept.  The pairs are filtered while the device pipeline holds their text, so the section needs the device
+pipeline: [gpu] device_pipeline, device_inflate and device_deflate True (the defaults) and gzip_level 1 or -1
+"""
+
+FILTER_NEEDS = "[filter] needs the device pipeline (device_pipeline, device_inflate, device_deflate : True and gzip_level 1 or -1)"
+FILTER_RANGES = {"min_length": (1, 100000), "max_n": (0, 100000), "max_unqualified_pct": (0, 100), "qualified_quality": (1, 93),
+                 "min_mean_quality": (1, 93), "min_complexity_pct": (1, 100)}
+FILTER_RULES = ("min_length", "max_n", "max_unqualified_pct", "min_mean_quality", "min_complexity_pct")  # in the rule's order
+
+
+def filter_range_message(name):
+    return "Authorized values for [filter] %s : %d to %d" % ((name,) + FILTER_RANGES[name])
+
 
 def template_bytes():
     """The example configuration file, byte for byte the reference's template: the package ships the
@@ -210,6 +238,19 @@ class QuadeConf(object):
         self.pair_max_mismatches = trim("pair_max_mismatches", 5)
         self.pair_max_mismatch_pct = trim("pair_max_mismatch_pct", 20)
 
+        # optional [filter] section (extension, FILTER_HELP): None = the rule is off
+        def flt(name, default=None):
+            if cp.has_section("filter") and cp.has_option("filter", name) and cp.get("filter", name) not in (None, ""):
+                return int(cp.get("filter", name))
+            return default
+
+        self.filter_min_length = flt("min_length")
+        self.filter_max_n = flt("max_n")
+        self.filter_max_unqualified_pct = flt("max_unqualified_pct")
+        self.filter_qualified_quality = flt("qualified_quality", 15)
+        self.filter_min_mean_quality = flt("min_mean_quality")
+        self.filter_min_complexity_pct = flt("min_complexity_pct")
+
         # (name, fused barcode) per [sample*] section, in file order (src/Quade.py:133-139)
         self.samples = []
         for section in [i for i in cp.sections() if i.startswith("sample")]:
@@ -281,6 +322,10 @@ class QuadeConf(object):
         assert 0 <= self.pair_max_mismatch_pct <= 50, PAIR_MISMATCH_PCT
         assert not self.pair_trim or (self.device_pipeline and self.device_inflate and self.device_deflate
                                       and self.gzip_level in (1, -1)), PAIR_NEEDS
+        for name, value in self.filter_params().items():
+            assert value is None or FILTER_RANGES[name][0] <= value <= FILTER_RANGES[name][1], filter_range_message(name)
+        assert not self.filter or (self.device_pipeline and self.device_inflate and self.device_deflate
+                                   and self.gzip_level in (1, -1)), FILTER_NEEDS
         for pos in [self.idx1_pos, self.idx2_pos, self.mol1_pos, self.mol2_pos]:
             assert pos["start"] >= 0
             assert pos["end"] >= pos["start"]
@@ -307,6 +352,18 @@ class QuadeConf(object):
         """what Engine.pairtrim_set takes"""
         return dict(min_overlap=self.pair_min_overlap, max_mismatches=self.pair_max_mismatches,
                     max_mismatch_pct=self.pair_max_mismatch_pct, min_length=self.min_length)
+
+    @property
+    def filter(self):
+        """read filtering is on: any rule of the [filter] section is set (FILTER_HELP)"""
+        p = self.filter_params()
+        return any(p[name] is not None for name in FILTER_RULES)
+
+    def filter_params(self):
+        """what Engine.filter_set takes: None = the rule is off"""
+        return dict(min_length=self.filter_min_length, max_n=self.filter_max_n, max_unqualified_pct=self.filter_max_unqualified_pct,
+                    qualified_quality=self.filter_qualified_quality, min_mean_quality=self.filter_min_mean_quality,
+                    min_complexity_pct=self.filter_min_complexity_pct)
 
     def plan(self):
         """The qd_plan the HIP library takes (include/quade_hip.h)."""

@@ -24,6 +24,7 @@
 #include "quade_qstats.h"
 #include "quade_trim.h"
 #include "quade_pairtrim.h"
+#include "quade_filter.h"
 #include "quade_pool.h"
 
 typedef uint64_t u64;
@@ -154,6 +155,12 @@ struct qd_ctx {
     qd_pairtrim_params pairtrim{};
     qd_pairtrim_dev pairtrim_dev{};
     u64* d_pairtrim = nullptr;
+
+    // read filtering (qd_filter_set): the parameters as given and as the kernel takes them, and the table
+    // uint64[(2 * S + 1)][8]; d_filter == nullptr = off
+    qd_filter_params filter{-1, -1, -1, 15, -1, -1};
+    qd_filter_dev filter_dev{-1, -1, -1, 33 + 15, -1, -1};
+    u64* d_filter = nullptr;
 };
 
 namespace {
@@ -421,6 +428,14 @@ void free_pairtrim(qd_ctx* c) {
     c->d_pairtrim = nullptr;
     c->pairtrim = qd_pairtrim_params{};
     c->pairtrim_dev = qd_pairtrim_dev{};
+}
+
+// read filtering off and its table freed (the caller waited for the context's work)
+void free_filter(qd_ctx* c) {
+    if (c->d_filter) (void)hipFree(c->d_filter);
+    c->d_filter = nullptr;
+    c->filter = qd_filter_params{-1, -1, -1, 15, -1, -1};
+    c->filter_dev = qd_filter_dev{-1, -1, -1, 33 + 15, -1, -1};
 }
 
 // (re)build the device table from the host barcodes and the current plan
@@ -776,6 +791,7 @@ int qd_destroy(qd_ctx* c) {
     free_qstats(c);
     free_trim(c);
     free_pairtrim(c);
+    free_filter(c);
     for (auto& t : c->tracked) (void)hipEventDestroy(t.second);
     c->tracked.clear();
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -798,12 +814,13 @@ int qd_set_plan(qd_ctx* c, const qd_plan* plan) {
     if (r != QD_OK) return fail(c, r, "plan rejected: positions must satisfy 0 <= start <= end <= 255, window <= 64, "
                                        "fused barcode <= 32, 0 <= minimal_qual <= 40");
     if (!c->slots.empty()) return fail(c, QD_ERR_STATE, "destroy the slots before changing the plan");
-    if (c->mm_m1 + c->mm_m2 > 0 || c->uk_slots || c->d_qs) {  // a new plan resets the mismatch budgets and turns the unknown tally and the quality counters off
+    if (c->mm_m1 + c->mm_m2 > 0 || c->uk_slots || c->d_qs || c->d_filter) {  // a new plan resets the mismatch budgets and turns the unknown tally, the quality counters and the read filter off
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, wait_all(c));
         free_mismatch(c, false);
         free_unknown(c);
         free_qstats(c);
+        free_filter(c);
     }
     c->plan = *plan;
     c->lay = L;
@@ -838,12 +855,13 @@ int qd_set_barcodes(qd_ctx* c, int32_t S, const uint8_t* barcodes, const int32_t
     if (!c->have_plan) return fail(c, QD_ERR_STATE, "qd_set_plan first");
     for (int i = 0; i < S; ++i)
         if (offsets[i + 1] < offsets[i]) return fail(c, QD_ERR_INVALID, "offsets must be non-decreasing");
-    if (c->mm_m1 + c->mm_m2 > 0 || c->uk_slots || c->d_qs) {  // new barcodes reset the mismatch budgets, as they reset the counters, and turn the unknown tally and the quality counters off
+    if (c->mm_m1 + c->mm_m2 > 0 || c->uk_slots || c->d_qs || c->d_filter) {  // new barcodes reset the mismatch budgets, as they reset the counters, and turn the unknown tally, the quality counters and the read filter off
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, wait_all(c));
         free_mismatch(c, false);
         free_unknown(c);
         free_qstats(c);
+        free_filter(c);
     }
     c->S = S;
     c->bc.assign(barcodes, barcodes + (S ? offsets[S] : 0));
@@ -1022,7 +1040,7 @@ int qd_qstats_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
 }
 
 int qd_qstats_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
-                     const uint16_t* codes, void* stream) {
+                     const uint16_t* codes, const uint8_t* drop, void* stream) {
     if (!c) return QD_ERR_INVALID;
     if (!c->d_qs || !n) return QD_OK;
     hipStream_t st = resolve_stream(c, stream);
@@ -1032,6 +1050,7 @@ int qd_qstats_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const
     a.recs[0] = recs1;
     a.recs[1] = recs2;
     a.codes = codes;
+    a.drop = drop;
     a.table = c->d_qs;
     hipError_t e = qd_qstats_launch(a, (uint32_t)c->S, n, st);
     if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("quality counters launch: ") + hipGetErrorString(e));
@@ -1077,7 +1096,7 @@ int qd_dev_qstats(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t*
     HIPCHK(c, uk_malloc(&d_codes.p, (size_t)n_pairs * 2));
     HIPCHK(c, hipMemcpyAsync(d_codes.p, codes, (size_t)n_pairs * 2, hipMemcpyHostToDevice, c->stream));
     const int rc = qd_qstats_device(c, static_cast<uint8_t*>(d_text[0].p) + 3, static_cast<qd_rec*>(d_recs[0].p), static_cast<uint8_t*>(d_text[1].p) + 3,
-                                    static_cast<qd_rec*>(d_recs[1].p), (uint32_t)n_pairs, static_cast<uint16_t*>(d_codes.p), QD_STREAM_CONTEXT);
+                                    static_cast<qd_rec*>(d_recs[1].p), (uint32_t)n_pairs, static_cast<uint16_t*>(d_codes.p), nullptr, QD_STREAM_CONTEXT);
     HIPCHK(c, hipStreamSynchronize(c->stream));  // the scratch is freed on return
     return rc;
 }
@@ -1354,6 +1373,145 @@ int qd_dev_pairtrim(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_
     return rc;
 }
 
+static_assert(QD_FILTER_VALUES == QD_FL_VALUES, "the public table width is the kernel's");
+
+int qd_filter_set(qd_ctx* c, const qd_filter_params* params) {
+    if (!c) return QD_ERR_INVALID;
+    qd_filter_params P{-1, -1, -1, 15, -1, -1};
+    bool on = false;
+    if (params) {  // checked as the configuration file's values are, before anything changes
+        P = *params;
+        if (P.qualified_quality == -1) P.qualified_quality = 15;
+        if (P.min_length != -1 && (P.min_length < 1 || P.min_length > 100000)) return fail(c, QD_ERR_INVALID, "filter min_length: 1 to 100000 (-1: off)");
+        if (P.max_n != -1 && (P.max_n < 0 || P.max_n > 100000)) return fail(c, QD_ERR_INVALID, "filter max_n: 0 to 100000 (-1: off)");
+        if (P.max_unqualified_pct != -1 && (P.max_unqualified_pct < 0 || P.max_unqualified_pct > 100))
+            return fail(c, QD_ERR_INVALID, "filter max_unqualified_pct: 0 to 100 (-1: off)");
+        if (P.qualified_quality < 1 || P.qualified_quality > 93) return fail(c, QD_ERR_INVALID, "filter qualified_quality: 1 to 93 (-1: 15)");
+        if (P.min_mean_quality != -1 && (P.min_mean_quality < 1 || P.min_mean_quality > 93)) return fail(c, QD_ERR_INVALID, "filter min_mean_quality: 1 to 93 (-1: off)");
+        if (P.min_complexity_pct != -1 && (P.min_complexity_pct < 1 || P.min_complexity_pct > 100))
+            return fail(c, QD_ERR_INVALID, "filter min_complexity_pct: 1 to 100 (-1: off)");
+        on = P.min_length >= 0 || P.max_n >= 0 || P.max_unqualified_pct >= 0 || P.min_mean_quality >= 0 || P.min_complexity_pct >= 0;
+    }
+    if (on && (!c->have_plan || !c->have_table)) return fail(c, QD_ERR_STATE, "qd_set_plan and qd_set_barcodes first");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));  // nothing of this context may still read the old parameters or add to the old table
+    free_filter(c);
+    if (!on) return QD_OK;
+    const size_t bytes = qd_filter_values((uint32_t)c->S) * 8;
+    hipError_t e = uk_malloc(reinterpret_cast<void**>(&c->d_filter), bytes);
+    if (e != hipSuccess) {
+        c->d_filter = nullptr;
+        return fail(c, QD_ERR_HIP, std::string("filter table: ") + hipGetErrorString(e));
+    }
+    HIPCHK(c, hipMemsetAsync(c->d_filter, 0, bytes, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->filter = P;
+    c->filter_dev = qd_filter_dev{P.min_length, P.max_n, P.max_unqualified_pct, 33 + P.qualified_quality, P.min_mean_quality, P.min_complexity_pct};
+    return QD_OK;
+}
+
+int qd_filter_get(const qd_ctx* c, qd_filter_params* out) {
+    if (!c || !out) return QD_ERR_INVALID;
+    *out = c->filter;
+    return QD_OK;
+}
+
+int qd_filter_active(const qd_ctx* c) { return c && c->d_filter ? 1 : 0; }
+
+int qd_filter_kind(const qd_ctx* c) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_filter) return fail(c, QD_ERR_STATE, "the read filter is not on");
+    return qd_filter_path((uint32_t)c->S);
+}
+
+int qd_filter_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
+    if (!c || !out) return QD_ERR_INVALID;
+    if (!c->d_filter) return fail(c, QD_ERR_STATE, "the read filter is not on");
+    if (n_values != (int64_t)qd_filter_values((uint32_t)c->S)) return fail(c, QD_ERR_INVALID, "n_values must be (2*S+1)*8");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));
+    HIPCHK(c, hipMemcpy(out, c->d_filter, (size_t)n_values * 8, hipMemcpyDeviceToHost));
+    return QD_OK;
+}
+
+int qd_filter_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
+    if (!c || !values) return QD_ERR_INVALID;
+    if (!c->d_filter) return fail(c, QD_ERR_STATE, "the read filter is not on");
+    if (n_values != (int64_t)qd_filter_values((uint32_t)c->S)) return fail(c, QD_ERR_INVALID, "n_values must be (2*S+1)*8");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));  // the kernel adds to the table: nothing of this context may be in flight
+    std::vector<u64> h((size_t)n_values);
+    HIPCHK(c, hipMemcpy(h.data(), c->d_filter, h.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < h.size(); ++i) h[i] += values[i];
+    HIPCHK(c, hipMemcpy(c->d_filter, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+    return QD_OK;
+}
+
+int qd_filter_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
+                     const uint16_t* codes, uint8_t* reason, void* stream) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_filter) return fail(c, QD_ERR_STATE, "the read filter is not on");
+    if (!n) return QD_OK;
+    hipStream_t st = resolve_stream(c, stream);
+    qd_filter_args a{};
+    a.text[0] = text1;
+    a.text[1] = text2;
+    a.recs[0] = recs1;
+    a.recs[1] = recs2;
+    a.codes = codes;
+    a.reason = reason;
+    a.table = c->d_filter;
+    hipError_t e = qd_filter_launch(c->filter_dev, a, (uint32_t)c->S, n, st);
+    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("filter launch: ") + hipGetErrorString(e));
+    HIPCHK(c, track(c, st));
+    return QD_OK;
+}
+
+int qd_dev_filter(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+                  const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes, uint8_t* reasons) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_filter) return fail(c, QD_ERR_STATE, "the read filter is not on");
+    const int64_t len[2] = {len1, len2};
+    const uint8_t* text[2] = {text1, text2};
+    const uint32_t* recs[2] = {recs1, recs2};
+    if (n_pairs < 0 || n_pairs > 0x7FFFFFFF || len1 < 0 || len2 < 0 || len1 > ((int64_t)1 << 30) || len2 > ((int64_t)1 << 30))
+        return fail(c, QD_ERR_INVALID, "bad sizes");
+    if (n_pairs == 0) return QD_OK;
+    if (!recs1 || !recs2 || !codes || !reasons || (!text1 && len1) || (!text2 && len2)) return fail(c, QD_ERR_INVALID, "null argument");
+    // every range and every code is checked here: a bad table cannot become a bad address
+    for (int r = 0; r < 2; ++r)
+        for (int64_t j = 0; j < n_pairs; ++j) {
+            const qd_rec* q = reinterpret_cast<const qd_rec*>(recs[r]) + j;
+            if ((int64_t)q->seq + q->seq_len > len[r] || (int64_t)q->qual + q->seq_len > len[r])
+                return fail(c, QD_ERR_INVALID, "a record's sequence or quality line reaches beyond its text");
+        }
+    for (int64_t j = 0; j < n_pairs; ++j)
+        if (codes[j] != QD_CODE_UNDETERMINED && (int)codes[j] >= 2 * c->S) return fail(c, QD_ERR_INVALID, "a routing code is not below 2*S");
+    HIPCHK(c, hipSetDevice(c->device));
+    struct Dev {
+        void* p = nullptr;
+        ~Dev() {
+            if (p) (void)hipFree(p);
+        }
+    } d_text[2], d_recs[2], d_codes, d_reason;
+    // the texts start 3 bytes into their buffers: the kernel's aligned words must not depend on an aligned window
+    for (int r = 0; r < 2; ++r) {
+        HIPCHK(c, uk_malloc(&d_text[r].p, (size_t)len[r] + 32));
+        HIPCHK(c, uk_malloc(&d_recs[r].p, (size_t)n_pairs * sizeof(qd_rec)));
+        if (len[r]) HIPCHK(c, hipMemcpyAsync(static_cast<uint8_t*>(d_text[r].p) + 3, text[r], (size_t)len[r], hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_recs[r].p, recs[r], (size_t)n_pairs * sizeof(qd_rec), hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, uk_malloc(&d_codes.p, (size_t)n_pairs * 2));
+    HIPCHK(c, uk_malloc(&d_reason.p, (size_t)n_pairs));
+    HIPCHK(c, hipMemcpyAsync(d_codes.p, codes, (size_t)n_pairs * 2, hipMemcpyHostToDevice, c->stream));
+    const int rc = qd_filter_device(c, static_cast<uint8_t*>(d_text[0].p) + 3, static_cast<qd_rec*>(d_recs[0].p), static_cast<uint8_t*>(d_text[1].p) + 3,
+                                    static_cast<qd_rec*>(d_recs[1].p), (uint32_t)n_pairs, static_cast<uint16_t*>(d_codes.p),
+                                    static_cast<uint8_t*>(d_reason.p), QD_STREAM_CONTEXT);
+    if (rc == QD_OK) HIPCHK(c, hipMemcpyAsync(reasons, d_reason.p, (size_t)n_pairs, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the scratch is freed on return
+    return rc;
+}
+
 int qd_kernel_kind(const qd_ctx* c, int has_len) {
     if (!c || !c->have_table) return QD_ERR_STATE;
     return pick_kernel(c, has_len != 0);
@@ -1511,6 +1669,7 @@ int qd_reset_counts(qd_ctx* c) {
     if (c->d_qs) HIPCHK(c, hipMemsetAsync(c->d_qs, 0, qd_qstats_values((uint32_t)c->S) * 8, c->stream));  // records stay equal to the pair counters
     if (c->d_trim) HIPCHK(c, hipMemsetAsync(c->d_trim, 0, QD_TRIM_VALUES * 8, c->stream));
     if (c->d_pairtrim) HIPCHK(c, hipMemsetAsync(c->d_pairtrim, 0, QD_PT_VALUES * 8, c->stream));
+    if (c->d_filter) HIPCHK(c, hipMemsetAsync(c->d_filter, 0, qd_filter_values((uint32_t)c->S) * 8, c->stream));
     HIPCHK(c, track(c, c->stream));  // later launches on other streams are not ordered behind this: wait here
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->total_pairs = 0;

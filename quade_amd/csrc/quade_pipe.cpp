@@ -48,6 +48,7 @@
 #include "quade_text.h"
 #include "quade_trim.h"
 #include "quade_pairtrim.h"
+#include "quade_filter.h"
 
 uint32_t qd_crc32_combine_host(uint32_t crc1, uint32_t crc2, uint64_t len2);  // quade_io.cpp (zlib's)
 
@@ -720,6 +721,7 @@ struct qd_pipe {
         g2_first;
     DevBuf trimmed[2];  // the insert reads' record tables with trimmed lengths (qd_trim_set; never allocated when trimming is off)
     DevBuf pairtrimmed[2];  // ... with the lengths the overlap trimming leaves (qd_pairtrim_set; never allocated when it is off)
+    DevBuf drop;  // the read filter's reason byte per pair (qd_filter_set; never allocated when it is off)
     PinBuf h_first;
     // tables and scratch of the format / CRC / coder launches: read by kernels on the compute stream only, so one set serves every batch
     DevBuf subs, first_sub, ranges, crc, tokens, sub_out, sub_bytes, base1, base2;
@@ -1749,9 +1751,19 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
         if (rc != QD_OK) return pfail(p, rc, std::string("overlap trim: ") + qd_last_error(p->ctx));
         for (int k = 0; k < 2; ++k) ins[k] = p->pairtrimmed[k].as<qd_rec>();
     }
+    // opt-in read filtering (qd_filter_set) of what the trimming left: a reason byte per pair; a pair with one is counted by nothing
+    // behind this point, gets output lengths 0 and is not formatted -- the way a destination whose write flag is off leaves no text
+    const uint8_t* drop = nullptr;
+    if (qd_filter_active(p->ctx)) {
+        PCHK(p, p->drop.need((size_t)n + 64, 0, p->cs));
+        const int rc = qd_filter_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p, ins[1], n,
+                                        p->codes.as<uint16_t>(), p->drop.p, p->cs);
+        if (rc != QD_OK) return pfail(p, rc, std::string("filter: ") + qd_last_error(p->ctx));
+        drop = p->drop.p;
+    }
     {  // opt-in yield and quality counters of the insert reads (qd_qstats_enable): the codes are final, the windows still hold the pairs
         const int rc = qd_qstats_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p,
-                                        ins[1], n, p->codes.as<uint16_t>(), p->cs);
+                                        ins[1], n, p->codes.as<uint16_t>(), drop, p->cs);
         if (rc != QD_OK) return pfail(p, rc, std::string("quality counters: ") + qd_last_error(p->ctx));
     }
     // 3. destinations, output lengths, stable sort by destination, output offsets
@@ -1771,6 +1783,7 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
     PCHK(p, p->g2_first.need((size_t)nd * 4, 0, p->cs));
     qd_route_args ra{};
     ra.codes = p->codes.as<uint16_t>();
+    ra.drop = drop;
     ra.r1 = ins[0];
     ra.r2 = ins[1];
     for (int k = 0; k < ni; ++k) ra.idx[k] = iw[k]->recs.as<qd_rec>();
@@ -1861,7 +1874,7 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
     ++p->st.batches;
     p->st.text_out_bytes += (int64_t)h_tot[0] + h_tot[1];
     p->st.pieces += n_pieces;
-    if (!n_pieces) return QD_OK;  // every destination's write flag is off
+    if (!n_pieces) return QD_OK;  // every destination's write flag is off, or the read filter dropped every pair
     // 6. format, CRC-32, code, pack
     const int set = take_out_set(p, (int)(batch_index & 1));
     OutSet& o = p->out[set];
@@ -1889,6 +1902,7 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
     PCHK(p, p->stage.upload(p->ranges.p, ranges.data(), (size_t)n_subs * sizeof(qd_crc_range), p->cs));
     qd_format_args fa{};
     fa.perm = p->perm.as<uint32_t>();
+    fa.drop = drop;
     fa.sdest = p->sdest.as<uint16_t>();
     fa.g1 = p->g1.as<uint32_t>();
     fa.g2 = p->g2.as<uint32_t>();
@@ -2584,7 +2598,7 @@ int qd_pipe_destroy(qd_pipe* p) {
     for (DevBuf* b : {&p->d_res, &p->rows_seq[0], &p->rows_seq[1], &p->rows_qual[0], &p->rows_qual[1], &p->rows_len[0], &p->rows_len[1], &p->codes, &p->mol,
                       &p->short_idx, &p->dest, &p->len1, &p->len2, &p->hist, &p->tmp, &p->perm, &p->sdest, &p->g1, &p->g2, &p->scan_tiles, &p->first, &p->g1_first,
                       &p->g2_first, &p->subs, &p->first_sub, &p->ranges, &p->crc, &p->tokens, &p->sub_out, &p->sub_bytes, &p->base1, &p->base2, &p->trimmed[0], &p->trimmed[1], &p->pairtrimmed[0],
-                      &p->pairtrimmed[1]})
+                      &p->pairtrimmed[1], &p->drop})
         b->release();
     for (OutSet& o : p->out) {
         for (DevBuf* b : {&o.text, &o.pieces, &o.members, &o.member_len, &o.member_off, &o.packed}) b->release();

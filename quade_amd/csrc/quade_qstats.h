@@ -30,11 +30,13 @@ static inline size_t qd_qstats_values(uint32_t n_samples) { return ((size_t)2 * 
 static inline int qd_qstats_path(uint32_t n_samples) { return 2 * n_samples + 1 <= QD_QS_LDS_MAX_DEST ? QD_QS_PATH_LDS : QD_QS_PATH_GLOBAL; }
 
 // Pairs [0, n): pair j is recs[r][j] in text[r] (r = 0: R1, 1: R2), routed by codes[j]; adds to table.  Device pointers,
-// returns after the launch.  n < 2^31.
+// returns after the launch.  n < 2^31.  drop != NULL: pair j is skipped where drop[j] != 0 (the read filter's reason bytes,
+// quade_filter.h: the table counts the pairs that are written).
 struct qd_qstats_args {
     const uint8_t* text[2];
     const qd_rec* recs[2];
     const uint16_t* codes;
+    const uint8_t* drop;  // optional
     uint64_t* table;
 };
 hipError_t qd_qstats_launch(const qd_qstats_args& a, uint32_t n_samples, uint32_t n, hipStream_t st);
@@ -42,4 +44,4 @@ hipError_t qd_qstats_launch(const qd_qstats_args& a, uint32_t n_samples, uint32_
 // The context's table (quade_api.cpp): what qd_pipe_run calls once per batch on its compute stream.  Nothing is launched
 // and QD_OK returned when the table is off.
 extern "C" int qd_qstats_device(qd_ctx* ctx, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
-                     const uint16_t* codes, void* stream);
+                     const uint16_t* codes, const uint8_t* drop, void* stream);

@@ -113,7 +113,7 @@ __global__ __launch_bounds__(QS_BLOCK) void qstats(qd_qstats_args a, uint32_t n_
     const uint32_t first = blockIdx.x * QS_WG_PAIRS, last = min(n, first + QS_WG_PAIRS);
     for (uint32_t j0 = first; j0 < last; j0 += QS_GROUPS) {  // (the same trips for every wave: the DPP sums need whole waves)
         const uint32_t j = j0 + group;
-        const bool valid = j < last;
+        const bool valid = j < last && !(a.drop && a.drop[j]);
         uint32_t d = 0xFFFFFFFFu, len[2] = {0, 0};
         Line line[4];  // R1 sequence, R1 quality, R2 sequence, R2 quality
         uint4 w[4];

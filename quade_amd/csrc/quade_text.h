@@ -99,9 +99,11 @@ struct qd_pack_args {
 hipError_t qd_text_pack_rows(const qd_layout& L, uint32_t n, const qd_pack_args& a, hipStream_t st);
 
 // Destination and output lengths of every pair: dest = routing code (0xFFFF -> 2 * S), len1 / len2 = bytes of the pair's two
-// output records "@name:IDX[:MOL]\nseq\n+\nqual\n" (0 when the destination's write flag is off).
+// output records "@name:IDX[:MOL]\nseq\n+\nqual\n" (0 when the destination's write flag is off, or when drop != NULL and
+// drop[j] != 0: the read filter's reason bytes, quade_filter.h -- such a pair takes no room in any output).
 struct qd_route_args {
     const uint16_t* codes;
+    const uint8_t* drop;  // optional
     const qd_rec* r1;
     const qd_rec* r2;
     const qd_rec* idx[2];
@@ -128,7 +130,9 @@ hipError_t qd_text_dest_bounds(const uint16_t* sdest, const uint32_t* g1, const 
 
 // The records themselves: pair perm[k]'s two records to out1 + base1[sdest[k]] + g1[k] and out2 + base2[sdest[k]] + g2[k]
 // (a destination's base is what the host made of its first position: where its text starts minus g at that position).
+// drop: as qd_route_args', whose lengths left the pair no room -- nothing is written for it.
 struct qd_format_args {
+    const uint8_t* drop;  // optional
     const uint32_t* perm;
     const uint16_t* sdest;
     const uint32_t* g1;

@@ -474,7 +474,7 @@ __global__ __launch_bounds__(256) void dest_lens(PlanParams p, qd_route_args a, 
     const uint32_t d = c == QD_CODE_UNDETERMINED ? 2 * p.n_samples : min(c, 2 * p.n_samples);
     a.dest[j] = (uint16_t)d;
     uint32_t l1 = 0, l2 = 0;
-    if (dest_enabled(p, d)) {
+    if (dest_enabled(p, d) && !(a.drop && a.drop[j])) {
         uint32_t len[2] = {0, 0};
 #pragma unroll
         for (int k = 0; k < 2; ++k)
@@ -621,6 +621,7 @@ __global__ __launch_bounds__(256) void format_records(PlanParams p, qd_format_ar
     const uint32_t d = a.sdest[k];
     if (!dest_enabled(p, d)) return;
     const uint32_t j = a.perm[k];
+    if (a.drop && a.drop[j]) return;  // the read filter dropped the pair: its lengths are 0
     const qd_rec r = read ? a.r2[j] : a.r1[j];
     const uint8_t* text = read ? a.text2 : a.text1;
     uint8_t* o = (read ? a.out2 : a.out1) + ((read ? a.base2[d] : a.base1[d]) + (int64_t)(read ? a.g2[k] : a.g1[k]));

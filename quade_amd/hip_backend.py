@@ -56,6 +56,11 @@ class qd_pairtrim_params(C.Structure):
     _fields_ = [("min_overlap", C.c_int32), ("max_mismatches", C.c_int32), ("max_mismatch_pct", C.c_int32), ("min_length", C.c_int32)]
 
 
+class qd_filter_params(C.Structure):
+    _fields_ = [("min_length", C.c_int32), ("max_n", C.c_int32), ("max_unqualified_pct", C.c_int32), ("qualified_quality", C.c_int32),
+                ("min_mean_quality", C.c_int32), ("min_complexity_pct", C.c_int32)]
+
+
 class qd_text_batch(C.Structure):
     _fields_ = [("text", C.c_void_p), ("text_len", C.c_int64), ("rec_off", C.c_void_p), ("n_records", C.c_int64),
                 ("handle", C.c_void_p)]
@@ -124,6 +129,11 @@ SYMBOLS = [
     ("qd_pairtrim_get", C.c_int, [_P, C.POINTER(qd_pairtrim_params)]),
     ("qd_pairtrim_read", C.c_int, [_P, _P, C.c_int64]),
     ("qd_pairtrim_add", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_filter_set", C.c_int, [_P, C.POINTER(qd_filter_params)]),
+    ("qd_filter_get", C.c_int, [_P, C.POINTER(qd_filter_params)]),
+    ("qd_filter_read", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_filter_add", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_filter_kind", C.c_int, [_P]),
     ("qd_get_counts", C.c_int, [_P, _P, C.c_int32]),
     ("qd_reset_counts", C.c_int, [_P]),
     ("qd_add_counts", C.c_int, [_P, _P, C.c_int32]),
@@ -205,6 +215,7 @@ SYMBOLS = [
     ("qd_dev_qstats", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P]),
     ("qd_dev_trim", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_pairtrim", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
+    ("qd_dev_filter", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_get_plan", C.c_int, [_P, C.POINTER(qd_plan)]),
     ("qd_context_device", C.c_int, [_P, C.POINTER(C.c_int32)]),
 ]
@@ -495,6 +506,27 @@ def split_pairtrim(table):
     return [t[:k], t[k:2 * k]], t[2 * k:2 * k + 3], t[2 * k + 3:]
 
 
+# qd_filter_*: the reasons (the reason byte of a dropped pair is the index + 1), the table's columns and the parameters
+FILTER_REASONS = ("too_short", "too_many_n", "low_quality", "low_mean_quality", "low_complexity")
+FILTER_COUNTERS = ("pairs",) + FILTER_REASONS + ("bases_in", "bases_dropped")  # per destination
+FILTER_KEYS = ("min_length", "max_n", "max_unqualified_pct", "qualified_quality", "min_mean_quality", "min_complexity_pct")
+FILTER_KIND_LDS, FILTER_KIND_GLOBAL = 1, 2
+
+
+def pack_filter(table):
+    """One context's or rank's filter table (uint64[2S+1, 8]) as bytes (the ranks' exchange through the rendezvous directory);
+    unpack_filter reverses it."""
+    table = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1, len(FILTER_COUNTERS))
+    return np.uint64(table.shape[0]).tobytes() + table.tobytes()
+
+
+def unpack_filter(blob):
+    """-> uint64[2S+1, 8] (a copy: tables are summed in place)"""
+    n_dest = int(np.frombuffer(blob[:8], dtype=np.uint64)[0])
+    assert len(blob) == 8 + n_dest * len(FILTER_COUNTERS) * 8, "filter table of the wrong size"
+    return np.frombuffer(blob, dtype=np.uint64, offset=8).reshape(n_dest, len(FILTER_COUNTERS)).copy()
+
+
 # ---- device context -------------------------------------------------------------------------------------
 class Engine(object):
     """One libquade_hip context = one MI355X.  Mirrors what Sample.CLASS_INIT + Sample(name, index)
@@ -709,6 +741,58 @@ class Engine(object):
         self._chk(self.lib.qd_dev_pairtrim(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), r[0].shape[0],
                                            _ptr(out[0]), _ptr(out[1])))
         return out[0], out[1]
+
+    def filter_set(self, min_length=None, max_n=None, max_unqualified_pct=None, qualified_quality=15, min_mean_quality=None,
+                   min_complexity_pct=None, on=True):
+        """Read filtering in the device pipeline (qd_filter_set; conf.FILTER_HELP has the rules).  None = the rule is off;
+        on=False, or every rule None, turns the stage off and frees the table; a value out of range is QD_ERR_INVALID and
+        changes nothing.  Needs the plan and the barcodes."""
+        if not on:
+            self._chk(self.lib.qd_filter_set(self._h, None))
+            return
+        given = (min_length, max_n, max_unqualified_pct, qualified_quality, min_mean_quality, min_complexity_pct)
+        # (a negative number is no way to say "off" here: -2 so that the library refuses it, as it refuses every bad value)
+        P = qd_filter_params(*[-1 if x is None else (int(x) if int(x) >= 0 else -2) for x in given])
+        self._chk(self.lib.qd_filter_set(self._h, C.byref(P)))
+
+    def filter_get(self):
+        """The parameters in force, as filter_set's keywords (a rule that is off: None)."""
+        P = qd_filter_params()
+        self._chk(self.lib.qd_filter_get(self._h, C.byref(P)))
+        return {k: (None if getattr(P, k) < 0 else int(getattr(P, k))) for k in FILTER_KEYS}
+
+    def filter_read(self):
+        """numpy uint64[2S+1, 8]: [destination (code; Undetermined last)][FILTER_COUNTERS]"""
+        out = np.zeros((2 * self.n_samples + 1, len(FILTER_COUNTERS)), dtype=np.uint64)
+        self._chk(self.lib.qd_filter_read(self._h, _ptr(out), out.size))
+        return out
+
+    def filter_add(self, table):
+        """Another context's table (filter_read's layout) joins this context's (qd_filter_add)."""
+        table = np.ascontiguousarray(table, dtype=np.uint64)
+        self._chk(self.lib.qd_filter_add(self._h, _ptr(table), table.size))
+
+    def filter_kind(self):
+        """FILTER_KIND_LDS or FILTER_KIND_GLOBAL: the accumulation the kernel takes for this context's sample count"""
+        kind = self.lib.qd_filter_kind(self._h)
+        if kind < 0:
+            self._chk(kind)
+        return kind
+
+    def dev_filter(self, text1, recs1, text2, recs2, codes):
+        """The filter stage over host buffers (qd_dev_filter): texts as bytes or uint8 arrays, recs uint32[n, 6] in
+        dev_fastq_scan's layout, codes uint16[n]; -> uint8[n], 0 = kept or the rule that dropped the pair; adds to the
+        context's table."""
+        t = [np.frombuffer(bytes(x), dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, dtype=np.uint8)
+             for x in (text1, text2)]
+        r = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, 6) for x in (recs1, recs2)]
+        codes = np.ascontiguousarray(codes, dtype=np.uint16)
+        if r[0].shape[0] != r[1].shape[0] or codes.shape != (r[0].shape[0],):
+            raise ValueError("recs1, recs2 and codes must have one entry per pair")
+        out = np.zeros(codes.size, dtype=np.uint8)
+        self._chk(self.lib.qd_dev_filter(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), codes.size,
+                                         _ptr(codes), _ptr(out)))
+        return out
 
     def set_option(self, name, value):
         self._chk(self.lib.qd_set_option(self._h, name.encode(), int(value)))

@@ -173,6 +173,8 @@ class Quade(object):
                     eng.trim_set(**cf.trim_params())
                 if cf.pair_trim:  # ... and R1 and R2 of a pair together, behind it
                     eng.pairtrim_set(**cf.pair_trim_params())
+                if cf.filter:  # ... and the pairs not worth keeping leave, behind both
+                    eng.filter_set(**cf.filter_params())
                 if not self.use_pipe:
                     eng.slots_create(cf.slots, cf.batch_pairs)
                 group.append(eng)
@@ -201,6 +203,7 @@ class Quade(object):
         quality = self._collect_quality() if cf.quality_report else None
         trimmed = self._collect_trim() if cf.trim else None
         pair_trimmed = self._collect_pair_trim() if cf.pair_trim else None
+        filtered = self._collect_filter() if cf.filter else None
         for eng in self.engines:
             eng.close()
         self.engines = []
@@ -248,6 +251,10 @@ class Quade(object):
         if pair_trimmed is not None:
             from . import pair_trim_report
             pair_trim_report.write_report(os.path.join(self.outdir, pair_trim_report.REPORT_NAME), pair_trimmed, cf.pair_trim_params())
+        if filtered is not None:
+            from . import filter_report
+            filter_report.write_report(os.path.join(self.outdir, filter_report.REPORT_NAME), filtered,
+                                       [s.name for s in Sample.SAMPLE_LIST], cf.filter_params())
         print("Done in {}s".format(round(time() - start_time, 3)))
         if _PROFILE:
             for k, v in sorted(_T.items(), key=lambda kv: -kv[1]):
@@ -361,6 +368,22 @@ class Quade(object):
         if self.world > 1:
             got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, "pairtrim", hb.pack_pairtrim(table))
             tables = [hb.unpack_pairtrim(b) for b in got]
+            table = tables[0]
+            for t in tables[1:]:
+                table = table + t
+        return table
+
+    def _collect_filter(self):
+        """[filter]: the tables of every context of this process summed (chunk workers, devices); with several ranks every rank
+        publishes its sum in the rendezvous directory and adds all of them (rank 0 writes the file).  Returns uint64[2S+1, 8]."""
+        from . import dist
+        table = None
+        for eng in self.engines:
+            t = eng.filter_read()
+            table = t if table is None else table + t
+        if self.world > 1:
+            got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, "filter", hb.pack_filter(table))
+            tables = [hb.unpack_filter(b) for b in got]
             table = tables[0]
             for t in tables[1:]:
                 table = table + t

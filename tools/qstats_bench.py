@@ -63,7 +63,7 @@ def main():
     lib = hb.load_library()
     launch = lib.qd_qstats_device  # the pipeline's internal entry: device pointers and a stream
     launch.restype = C.c_int
-    launch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    launch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
     t1, r1, rec = make_text(n, L, 1)
     t2, r2, _ = make_text(n, L, 2)
     st = torch.cuda.current_stream()
@@ -89,7 +89,7 @@ def main():
         return S, codes.to(torch.int16).contiguous(), engines
 
     def once(eng, codes):
-        rc = launch(eng._h, t1.data_ptr(), r1.data_ptr(), t2.data_ptr(), r2.data_ptr(), n, codes.data_ptr(), st.cuda_stream)
+        rc = launch(eng._h, t1.data_ptr(), r1.data_ptr(), t2.data_ptr(), r2.data_ptr(), n, codes.data_ptr(), None, st.cuda_stream)  # (no drop bytes)
         assert rc == 0, rc
 
     floor_ms = 4.0 * n * L / COPY_RATE * 1e3
