@@ -805,6 +805,42 @@ int qd_dev_pairtrim(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint3
  * launched: QD_ERR_INVALID.  QD_ERR_STATE when the stage is off.  Returns when the launch has finished. */
 int qd_dev_filter(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                   const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes, uint8_t* reasons);
+/* ---- the routing and format stages of qd_pipe_run one at a time (additive: QD_ABI_VERSION stays 6) ----------------------------
+ * These three run the kernels between the record tables and the packed members on host buffers, for tests that compare every stage
+ * with a plain model (tests/route_model.py).  They are stage harnesses: no reference counterpart (what the stages themselves
+ * restate of the reference is said at qd_pipe_run above).  Each uses its own hipMalloc scratch on `device_id` and returns when its
+ * launches have finished.  Record tables are uint32[n][6] in qd_dev_fastq_scan's layout; every range a table names is checked
+ * against its text's length before anything is launched (QD_ERR_INVALID), so a bad table cannot become a bad address.
+ * Bytes that no kernel owns hold QD_DEV_GUARD_BYTE when the entry returns.  qd_dev_pack_rows and qd_dev_route_format take n >= 1
+ * pairs, qd_dev_pack_members n >= 0 members. */
+#define QD_DEV_GUARD_BYTE 0xEE
+/* qd_dev_pack_rows runs qd_text_pack_rows (quade_text.hip: pack_rows; no reference counterpart of its own, it makes the operands
+ * of src/Quade.py:217-218): index rows of pairs [0, n) of `layout`'s one or two index streams, text[k] / recs[k] -> seq_rows[k]
+ * (n x seq_stride[k]), qual_rows[k] (n x qual_stride[k]), len_rows[k] (n).  short_idx holds short_room >= short_cap entries, all
+ * 0xFFFFFFFF before the launch: the kernel stores the pairs with a read shorter than its window (each once, any order) in the first
+ * min(*n_short, short_cap) of them and *n_short says how many there are. */
+int qd_dev_pack_rows(int device_id, const qd_layout* layout, const uint8_t* const text[2], const int64_t text_len[2],
+                     const uint32_t* const recs[2], int64_t n, int64_t short_cap, uint8_t* const seq_rows[2], uint8_t* const qual_rows[2],
+                     uint8_t* const len_rows[2], uint32_t* short_idx, int64_t short_room, uint32_t* n_short);
+/* qd_dev_route_format runs the chain of qd_pipe_run's batches behind the routing codes (no reference counterpart as a stage: its
+ * output is what src/Sample.py:74-91 and src/FastqWriter.py:61-69 write, per destination): qd_text_dest_lens, qd_text_sort_by_dest,
+ * both qd_text_scan_gathered, qd_text_dest_bounds, the host's layout of the output text (qd_text_out_layout, the function the
+ * pipeline calls) and qd_text_format with both reads' records in one buffer.  text / text_len / recs: R1, R2, I1, I2 (I2 is not
+ * read with a single-index plan); byte o of a text lies at device address o + shift (mod 16), shift 0..15.  drop (may be NULL): a
+ * pair with drop[j] != 0 gets no room.  Out: dest, len1, len2, perm, sdest (n each), g1, g2 (n + 1), first, g1_first, g2_first,
+ * base1, base2 (2 * n_samples + 1 each; an entry of g1_first / g2_first whose destination has no pair is 0xFFFFFFFF), and the text
+ * in out[0 .. out_cap), which is QD_DEV_GUARD_BYTE wherever no record lies; *out_used = the bytes the regions take (rounded up to
+ * 16).  QD_ERR_INVALID with *out_used set when out_cap is below that: nothing was formatted. */
+int qd_dev_route_format(int device_id, const qd_plan* plan, int32_t n_samples, int32_t write_pass, int32_t write_fail, int32_t write_undet,
+                        const uint8_t* const text[4], const int64_t text_len[4], const uint32_t* const recs[4], const uint16_t* codes,
+                        const uint8_t* drop, int64_t n, int32_t shift, uint16_t* dest, uint32_t* len1, uint32_t* len2, uint32_t* perm,
+                        uint16_t* sdest, uint32_t* g1, uint32_t* g2, uint32_t* first, uint32_t* g1_first, uint32_t* g2_first, int64_t* base1,
+                        int64_t* base2, uint8_t* out, int64_t out_cap, int64_t* out_used);
+/* qd_dev_pack_members runs qd_text_pack_members (member_offsets + member_copy; no reference counterpart: the reference appends
+ * whole gzip files): members of len[i] <= stride bytes in slots of `stride` bytes -> offsets[n + 1] (exclusive sums of len, the
+ * total last) and packed[0 .. packed_cap) = the members back to back, QD_DEV_GUARD_BYTE behind offsets[n]. */
+int qd_dev_pack_members(int device_id, const uint8_t* slots, int64_t stride, const uint32_t* len, int64_t n, uint64_t* offsets, uint8_t* packed,
+                        int64_t packed_cap);
 /* what a context was made with / holds (the pipeline reads them; bindings may too) */
 int qd_get_plan(const qd_ctx* ctx, qd_plan* out);
 int qd_context_device(const qd_ctx* ctx, int32_t* device_id);

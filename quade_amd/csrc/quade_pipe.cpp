@@ -1822,7 +1822,8 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
     int rc = sync_compute(p);
     if (rc != QD_OK) return rc;
     for (int s = 0; s < p->n_streams; ++s) p->win[s].res.carry_start = reinterpret_cast<qd_scan_result*>(p->h_res.p)[s].carry_start;
-    // 5. layout of the output text: every destination's R1 region, then every R2 region, 16-byte aligned; pieces of 1 MiB
+    // 5. layout of the output text: every destination's R1 region, then every R2 region, 16-byte aligned (qd_text_out_layout,
+    //    quade_text.h); pieces of 1 MiB
     std::vector<int64_t> base1(nd, 0), base2(nd, 0);
     const uint32_t piece_bytes = piece_bytes_for(p, (uint64_t)h_tot[0] + h_tot[1], nd);
     BatchOut bo;
@@ -1831,44 +1832,28 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
     std::vector<qd_lz_sub> subs;
     std::vector<uint32_t> first_sub;
     std::vector<qd_crc_range> ranges;
-    uint64_t at = 0;
-    {
-        // a destination without pairs starts where the next one does
-        std::vector<uint32_t> g1s(nd + 1), g2s(nd + 1);
-        g1s[nd] = h_tot[0];
-        g2s[nd] = h_tot[1];
-        for (int64_t d = (int64_t)nd - 1; d >= 0; --d) {
-            const bool none = h_first[d] == 0xFFFFFFFFu;
-            g1s[d] = none ? g1s[d + 1] : h_g1f[d];
-            g2s[d] = none ? g2s[d + 1] : h_g2f[d];
-        }
-        for (int k = 0; k < 2; ++k)
-            for (uint32_t d = 0; d < nd; ++d) {
-                const std::vector<uint32_t>& gs = k ? g2s : g1s;
-                const uint64_t bytes = gs[d + 1] - gs[d];
-                (k ? base2 : base1)[d] = (int64_t)at - (int64_t)gs[d];
-                if (!bytes) continue;
-                FileRun fr;
-                fr.code = d == 2 * S ? QD_CODE_UNDETERMINED : d;
-                fr.k = k;
-                fr.first = (uint32_t)bo.pieces.size();
-                fr.text_bytes = bytes;
-                for (uint64_t a = 0; a < bytes; a += piece_bytes) {
-                    const uint32_t plen = (uint32_t)std::min<uint64_t>(piece_bytes, bytes - a);
-                    first_sub.push_back((uint32_t)subs.size());
-                    for (uint32_t q = 0; q < plen; q += QD_LZ_SUB) {
-                        const uint32_t slen = std::min<uint32_t>(QD_LZ_SUB, plen - q);
-                        subs.push_back(qd_lz_sub{at + a + q, slen, (uint32_t)bo.pieces.size()});
-                        ranges.push_back(qd_crc_range{at + a + q, slen, 0});
-                    }
-                    bo.pieces.push_back(qd_deflate_piece{at + a, plen, 0});
-                }
-                fr.n = (uint32_t)bo.pieces.size() - fr.first;
-                bo.files.push_back(fr);
-                at = (at + bytes + 15) & ~(uint64_t)15;
+    std::vector<qd_out_region> regions;
+    const uint64_t at = qd_text_out_layout(nd, h_first, h_g1f, h_g2f, h_tot[0], h_tot[1], base1.data(), base2.data(), &regions);
+    for (const qd_out_region& rg : regions) {
+        FileRun fr;
+        fr.code = rg.dest == 2 * S ? QD_CODE_UNDETERMINED : rg.dest;
+        fr.k = rg.k;
+        fr.first = (uint32_t)bo.pieces.size();
+        fr.text_bytes = rg.bytes;
+        for (uint64_t a = 0; a < rg.bytes; a += piece_bytes) {
+            const uint32_t plen = (uint32_t)std::min<uint64_t>(piece_bytes, rg.bytes - a);
+            first_sub.push_back((uint32_t)subs.size());
+            for (uint32_t q = 0; q < plen; q += QD_LZ_SUB) {
+                const uint32_t slen = std::min<uint32_t>(QD_LZ_SUB, plen - q);
+                subs.push_back(qd_lz_sub{rg.at + a + q, slen, (uint32_t)bo.pieces.size()});
+                ranges.push_back(qd_crc_range{rg.at + a + q, slen, 0});
             }
-        first_sub.push_back((uint32_t)subs.size());
+            bo.pieces.push_back(qd_deflate_piece{rg.at + a, plen, 0});
+        }
+        fr.n = (uint32_t)bo.pieces.size() - fr.first;
+        bo.files.push_back(fr);
     }
+    first_sub.push_back((uint32_t)subs.size());
     const uint32_t n_pieces = (uint32_t)bo.pieces.size(), n_subs = (uint32_t)subs.size();
     p->st.pairs += n;
     ++p->st.batches;

@@ -216,6 +216,11 @@ SYMBOLS = [
     ("qd_dev_trim", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_pairtrim", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_filter", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
+    ("qd_dev_pack_rows", C.c_int, [C.c_int, C.POINTER(qd_layout), _P * 2, C.c_int64 * 2, _P * 2, C.c_int64, C.c_int64, _P * 2, _P * 2, _P * 2,
+                                   _P, C.c_int64, C.POINTER(C.c_uint32)]),
+    ("qd_dev_route_format", C.c_int, [C.c_int, C.POINTER(qd_plan), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P * 4, C.c_int64 * 4, _P * 4, _P, _P,
+                                      C.c_int64, C.c_int32] + [_P] * 13 + [C.c_int64, C.POINTER(C.c_int64)]),
+    ("qd_dev_pack_members", C.c_int, [C.c_int, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64]),
     ("qd_get_plan", C.c_int, [_P, C.POINTER(qd_plan)]),
     ("qd_context_device", C.c_int, [_P, C.POINTER(C.c_int32)]),
 ]
@@ -1006,6 +1011,89 @@ def dev_gunzip(gz, out_cap, device_id=0, step_bytes=64 << 20, stretch_bytes=0, u
         e.stats = stats
         raise e
     return out[:n.value].tobytes(), stats
+
+
+DEV_GUARD_BYTE = 0xEE  # QD_DEV_GUARD_BYTE
+
+
+def _text_array(t):
+    return (np.frombuffer(t, dtype=np.uint8) if len(t) else np.zeros(1, np.uint8)) if not isinstance(t, np.ndarray) else t
+
+
+def dev_pack_rows(layout: qd_layout, texts, recs, short_cap, short_room=None, device_id=0):
+    """The index-row stage over host buffers (qd_dev_pack_rows): texts = one or two index texts (bytes or uint8 arrays), recs their
+    uint32[n, 6] tables.  Returns (seq_rows, qual_rows, len_rows: a list per stream; short_idx uint32[short_room], n_short)."""
+    lib = load_library()
+    ns = layout.n_streams
+    t = [_text_array(x) for x in texts[:ns]]
+    r = [np.ascontiguousarray(x, dtype=np.uint32) for x in recs[:ns]]
+    n = r[0].shape[0]
+    assert all(x.shape == (n, 6) for x in r)
+    seq = [np.empty((n, layout.seq_stride[k]), dtype=np.uint8) for k in range(ns)]
+    qual = [np.empty((n, layout.qual_stride[k]), dtype=np.uint8) for k in range(ns)]
+    lens = [np.empty(n, dtype=np.uint8) for k in range(ns)]
+    room = int(short_cap) if short_room is None else int(short_room)
+    short_idx = np.zeros(max(room, 1), dtype=np.uint32)
+    n_short = C.c_uint32(0)
+    two = lambda a: (_P * 2)(*[_ptr(a[k]) if k < ns else None for k in range(2)])  # noqa: E731
+    rc = lib.qd_dev_pack_rows(int(device_id), C.byref(layout), two(t), (C.c_int64 * 2)(*[len(texts[k]) if k < ns else 0 for k in range(2)]), two(r), n,
+                              int(short_cap), two(seq), two(qual), two(lens), _ptr(short_idx), room, C.byref(n_short))
+    if rc != QD_OK:
+        raise QuadeHipError(rc, "qd_dev_pack_rows: " + lib.qd_strerror(rc).decode())
+    return seq, qual, lens, short_idx[:room], int(n_short.value)
+
+
+ROUTE_TABLES = ("dest", "len1", "len2", "perm", "sdest", "g1", "g2", "first", "g1_first", "g2_first", "base1", "base2")
+
+
+def dev_route_format(plan: qd_plan, n_samples, flags, texts, recs, codes, drop=None, shift=0, out_cap=0, device_id=0):
+    """The routing and format chain of a batch over host buffers (qd_dev_route_format): flags = (write_pass, write_fail,
+    write_undetermined); texts / recs = R1, R2, I1[, I2] (bytes or uint8 arrays; uint32[n, 6] tables).  Returns a dict of
+    ROUTE_TABLES plus "out" (uint8[out_cap], DEV_GUARD_BYTE where no record lies) and "used".  QuadeHipError(QD_ERR_INVALID) with
+    .used set when out_cap is too small."""
+    lib = load_library()
+    ns = 4 if plan.dual else 3
+    t = [_text_array(x) for x in texts[:ns]]
+    r = [np.ascontiguousarray(x, dtype=np.uint32) for x in recs[:ns]]
+    codes = np.ascontiguousarray(codes, dtype=np.uint16)
+    n, nd = codes.size, 2 * int(n_samples) + 1
+    assert all(x.shape == (n, 6) for x in r)
+    if drop is not None:
+        drop = np.ascontiguousarray(drop, dtype=np.uint8)
+        assert drop.shape == (n,)
+    four = lambda a: (_P * 4)(*[_ptr(a[k]) if k < ns else None for k in range(4)])  # noqa: E731
+    res = {"dest": np.zeros(n, np.uint16), "len1": np.zeros(n, np.uint32), "len2": np.zeros(n, np.uint32), "perm": np.zeros(n, np.uint32),
+           "sdest": np.zeros(n, np.uint16), "g1": np.zeros(n + 1, np.uint32), "g2": np.zeros(n + 1, np.uint32), "first": np.zeros(nd, np.uint32),
+           "g1_first": np.zeros(nd, np.uint32), "g2_first": np.zeros(nd, np.uint32), "base1": np.zeros(nd, np.int64), "base2": np.zeros(nd, np.int64)}
+    out = np.zeros(max(int(out_cap), 1), dtype=np.uint8)
+    used = C.c_int64(-1)
+    rc = lib.qd_dev_route_format(int(device_id), C.byref(plan), int(n_samples), int(flags[0]), int(flags[1]), int(flags[2]), four(t),
+                                 (C.c_int64 * 4)(*[len(texts[k]) if k < ns else 0 for k in range(4)]), four(r), _ptr(codes), _ptr(drop), n, int(shift),
+                                 *([_ptr(res[k]) for k in ROUTE_TABLES] + [_ptr(out), int(out_cap), C.byref(used)]))
+    if rc != QD_OK:
+        e = QuadeHipError(rc, "qd_dev_route_format: " + lib.qd_strerror(rc).decode())
+        e.used = used.value
+        raise e
+    res["out"] = out[:int(out_cap)]
+    res["used"] = used.value
+    return res
+
+
+def dev_pack_members(slots, stride, lens, packed_cap, device_id=0):
+    """Members in slots of `stride` bytes -> (offsets uint64[n + 1], packed uint8[packed_cap]) by qd_dev_pack_members; the bytes
+    behind offsets[n] are DEV_GUARD_BYTE."""
+    lib = load_library()
+    lens = np.ascontiguousarray(lens, dtype=np.uint32)
+    slots = np.ascontiguousarray(slots, dtype=np.uint8)
+    n = lens.size
+    assert slots.size >= n * int(stride)
+    offsets = np.zeros(n + 1, dtype=np.uint64)
+    packed = np.zeros(max(int(packed_cap), 1), dtype=np.uint8)
+    rc = lib.qd_dev_pack_members(int(device_id), _ptr(slots) if n else None, int(stride), _ptr(lens) if n else None, n, _ptr(offsets), _ptr(packed),
+                                 int(packed_cap))
+    if rc != QD_OK:
+        raise QuadeHipError(rc, "qd_dev_pack_members: " + lib.qd_strerror(rc).decode())
+    return offsets, packed[:int(packed_cap)]
 
 
 class Pipe(object):
