@@ -392,6 +392,61 @@ int qd_filter_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
 int qd_filter_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
 int qd_filter_kind(const qd_ctx* ctx);
 
+/* ---- per-cycle quality and base content, per-read distributions (opt-in; no reference counterpart) -----------------------------
+ * What the first plots of a read QC tool show: quality and base composition by cycle, and the distributions of read length,
+ * per-read mean quality and GC content.  A device-resident table of exact uint64 counters over the insert reads as the output
+ * stages see them -- behind the trimming stages, without the pairs the read filter dropped, whatever the write flags say: exactly
+ * the reads the quality counters (qd_qstats_enable) count.
+ *
+ * Groups.  g comes from the routing code: an even code is pass (0), an odd code is fail (1), and 0xFFFF is Undetermined (2).
+ * Reads.  r = 0 / 1 for R1 / R2.
+ * Bytes.  Sequence bytes are s.  Quality bytes q are unsigned, with ph = max(0, q - 33), as in qd_qstats.
+ * Per cycle, for c < QD_CS_CYCLES = 1024, every read with L > c adds to cycle[g][r][c][8]:
+ *   0 A  1 C  2 G  3 T  4 N    (s[c] & 0xDF) == the letter
+ *   5 qual_sum  += ph[c]       6 q20  ph[c] >= 20       7 q30  ph[c] >= 30
+ * Cycles from 1024 on are not counted per cycle.
+ * Per read:
+ *   len[g][r][1025]    bin min(L, 1024)
+ *   meanq[g][r][94]    for L > 0: bin min(93, sum(ph) / L), integer division over the whole read
+ *   gc[g][r][101]      for L > 0: bin 100 * (G and C count, either case) / L, over the whole read
+ * Derived values.  reads(c) is not stored: it is the sum of len minus the sum of len[0..c].  other(c) = reads(c) - A - C - G - T - N.
+ * Table.  uint64, group-major, then read.  For each (g, r) the order is cycle, len, meanq, gc, which is 1024*8 + 1025 + 94 + 101
+ * = QD_CS_GR_VALUES = 9412 values.  The whole table is QD_CS_VALUES = 56 472 values, independent of S.
+ * Cross-checks.  For reads of at most 1024 bases, summed over cycles and groups, N, qual_sum, q20 and q30 equal the qd_qstats
+ * table's columns, and the sum of L * len[L] equals its bases.
+ *
+ * With the table on, qd_pipe_run adds every pair it routes (one launch per batch on its compute stream, no host sync), directly
+ * behind the quality counters; a chunk part (skip_kept, max_pairs) counts exactly its pairs.  Off, nothing is allocated or
+ * launched.
+ * qd_cstats_enable: on != 0 allocates and zeroes the table, 0 frees it.  Waits for the context's outstanding work.  Independent of
+ * plan and barcodes (the table does not depend on S): neither turns it off.  qd_reset_counts zeroes the table.
+ * qd_cstats_read: waits for the context's work, writes n_values = QD_CS_VALUES values (QD_ERR_INVALID on another size,
+ * QD_ERR_STATE when off).  qd_cstats_add: another context's table joins this one's (the same errors).
+ * qd_cstats_lds_cycles: the cycles below which a workgroup of the kernel counts in LDS partials; later cycles go to the 64-bit
+ * table directly (a constant of the build: tests straddle it). */
+enum {
+    QD_CS_A = 0,
+    QD_CS_C = 1,
+    QD_CS_G = 2,
+    QD_CS_T = 3,
+    QD_CS_N = 4,
+    QD_CS_QUAL_SUM = 5,
+    QD_CS_Q20 = 6,
+    QD_CS_Q30 = 7,
+    QD_CS_COUNTERS = 8,
+    QD_CS_GROUPS = 3,
+    QD_CS_CYCLES = 1024,
+    QD_CS_LEN_BINS = 1025,
+    QD_CS_MEANQ_BINS = 94,
+    QD_CS_GC_BINS = 101,
+    QD_CS_GR_VALUES = 9412,
+    QD_CS_VALUES = 56472
+};
+int qd_cstats_enable(qd_ctx* ctx, int32_t on);
+int qd_cstats_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
+int qd_cstats_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
+int qd_cstats_lds_cycles(void);
+
 /* ---- counters: replace the class counters of src/Sample.py:32,144 and feed Sample.REPORT ---------
  * qd_get_counts waits for outstanding work of this context (only), then writes 2*S+4 values. */
 int qd_get_counts(qd_ctx* ctx, uint64_t* out, int32_t n_values);
@@ -805,6 +860,14 @@ int qd_dev_pairtrim(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint3
  * launched: QD_ERR_INVALID.  QD_ERR_STATE when the stage is off.  Returns when the launch has finished. */
 int qd_dev_filter(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                   const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes, uint8_t* reasons);
+/* the per-cycle counters' stage (qd_cstats_enable above; no reference counterpart) over host buffers, as qd_dev_qstats: pairs
+ * [0, n_pairs) of two texts with their record tables and routing codes are uploaded (the texts 3 bytes off alignment), counted by
+ * the kernel qd_pipe_run launches, and added to the context's table.  drop may be NULL; otherwise pair j is skipped where
+ * drop[j] != 0 (the read filter's reason bytes).  Every record's sequence and quality range is checked against len1 / len2 and
+ * every code against 2 * S (0xFFFF apart) before anything is launched: QD_ERR_INVALID.  QD_ERR_STATE when the table is off.
+ * Returns when the launch has finished. */
+int qd_dev_cstats(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+                  const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes, const uint8_t* drop);
 /* ---- the routing and format stages of qd_pipe_run one at a time (additive: QD_ABI_VERSION stays 6) ----------------------------
  * These three run the kernels between the record tables and the packed members on host buffers, for tests that compare every stage
  * with a plain model (tests/route_model.py).  They are stage harnesses: no reference counterpart (what the stages themselves

@@ -7,7 +7,7 @@ file written by `-i` is the reference's template byte for byte (src/Conf_file.py
 package data, quade_amd/data/Quade_conf_file.txt).  An optional [gpu] section that reference conf
 files simply do not have is read when present (defaults apply otherwise; see GPU_SECTION_HELP), and so are the optional
 mismatch budgets of the [index] section (MISMATCH_HELP), the unknown-barcode report (UNKNOWN_HELP) and the quality report
-(QUALITY_HELP) of the [output] section, an optional [trim] section (TRIM_HELP, PAIR_HELP) and an optional [filter] section
+(QUALITY_HELP) and the per-cycle report (CYCLE_HELP) of the [output] section, an optional [trim] section (TRIM_HELP, PAIR_HELP) and an optional [filter] section
 (FILTER_HELP).
 """
 from __future__ import annotations
@@ -81,6 +81,20 @@ Optional [output] option (not in Quade 0.3.2, whose parser ignores it; absent, e
 """
 
 QUALITY_NEEDS = "quality_report needs the device pipeline (device_pipeline, device_inflate, device_deflate : True and gzip_level 1 or -1)"
+
+CYCLE_HELP = """\
+Optional [output] option (not in Quade 0.3.2, whose parser ignores it; absent, empty or False = no report):
+  cycle_report : False      True: write Quade_cycle_report.csv next to the report -- for the groups pass, fail, Undetermined and
+                            Total and for R1 and R2: per cycle (up to 1024) the reads, A, C, G, T, N and other bases, GC percent,
+                            mean quality and the bases at or above Q20 and Q30 (Phred+33) with their percentages; then the
+                            distributions of read length, per-read mean quality and per-read GC percent.  The reads are those
+                            the output stages see (behind [trim], pair_overlap and [filter]), whatever the write flags say:
+                            the reads quality_report counts.  They are counted on the GPU while the device pipeline holds their
+                            text, so the option needs the device pipeline: [gpu] device_pipeline, device_inflate and
+                            device_deflate True (the defaults) and gzip_level 1 or -1
+"""
+
+CYCLE_NEEDS = "cycle_report needs the device pipeline (device_pipeline, device_inflate, device_deflate : True and gzip_level 1 or -1)"
 
 TRIM_HELP = """\
 Optional [trim] section (not in Quade 0.3.2, whose parser ignores it; absent = the insert reads leave as they came): 3' trimming of
@@ -238,6 +252,10 @@ class QuadeConf(object):
         self.pair_max_mismatches = trim("pair_max_mismatches", 5)
         self.pair_max_mismatch_pct = trim("pair_max_mismatch_pct", 20)
 
+        # optional per-cycle quality and base-content report (extension, CYCLE_HELP)
+        self.cycle_report = False
+        if cp.has_option("output", "cycle_report") and cp.get("output", "cycle_report") not in (None, ""):
+            self.cycle_report = cp.get("output", "cycle_report").strip().lower() in ("true", "1", "yes", "on")
         # optional [filter] section (extension, FILTER_HELP): None = the rule is off
         def flt(name, default=None):
             if cp.has_section("filter") and cp.has_option("filter", name) and cp.get("filter", name) not in (None, ""):
@@ -308,6 +326,8 @@ class QuadeConf(object):
             "[gpu] unknown_slots : a power of two, 1024 to 268435456"
         assert not self.quality_report or (self.device_pipeline and self.device_inflate and self.device_deflate
                                            and self.gzip_level in (1, -1)), QUALITY_NEEDS
+        assert not self.cycle_report or (self.device_pipeline and self.device_inflate and self.device_deflate
+                                         and self.gzip_level in (1, -1)), CYCLE_NEEDS
         for a in (self.adapter_R1, self.adapter_R2):
             assert len(a) <= 64 and not a.strip("ACGT"), TRIM_ADAPTER
         assert 0 <= self.quality_cutoff <= 93, TRIM_CUTOFF

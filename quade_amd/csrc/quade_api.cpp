@@ -22,6 +22,7 @@
 #include "quade_mismatch.h"
 #include "quade_unknown.h"
 #include "quade_qstats.h"
+#include "quade_cstats.h"
 #include "quade_trim.h"
 #include "quade_pairtrim.h"
 #include "quade_filter.h"
@@ -143,6 +144,8 @@ struct qd_ctx {
 
     // yield and quality counters per destination (qd_qstats_enable): uint64[(2 * S + 1)][2][6], nullptr = off
     u64* d_qs = nullptr;
+    // per-cycle counters and per-read distributions (qd_cstats_enable): uint64[QD_CS_VALUES], nullptr = off
+    u64* d_cs = nullptr;
 
     // 3' trimming of the insert reads (qd_trim_set): the parameters as given and as the kernel takes them, and the counters
     // uint64[2][8]; d_trim == nullptr = off
@@ -412,6 +415,12 @@ int launch_unknown(qd_ctx* c, int64_t n, const qd_rows* rows, const uint16_t* co
 void free_qstats(qd_ctx* c) {
     if (c->d_qs) (void)hipFree(c->d_qs);
     c->d_qs = nullptr;
+}
+
+// the per-cycle counters off and their table freed (the caller waited for the context's work)
+void free_cstats(qd_ctx* c) {
+    if (c->d_cs) (void)hipFree(c->d_cs);
+    c->d_cs = nullptr;
 }
 
 // trimming off and its table freed (the caller waited for the context's work)
@@ -789,6 +798,7 @@ int qd_destroy(qd_ctx* c) {
     free_mismatch(c, true);
     free_unknown(c);
     free_qstats(c);
+    free_cstats(c);
     free_trim(c);
     free_pairtrim(c);
     free_filter(c);
@@ -1097,6 +1107,114 @@ int qd_dev_qstats(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t*
     HIPCHK(c, hipMemcpyAsync(d_codes.p, codes, (size_t)n_pairs * 2, hipMemcpyHostToDevice, c->stream));
     const int rc = qd_qstats_device(c, static_cast<uint8_t*>(d_text[0].p) + 3, static_cast<qd_rec*>(d_recs[0].p), static_cast<uint8_t*>(d_text[1].p) + 3,
                                     static_cast<qd_rec*>(d_recs[1].p), (uint32_t)n_pairs, static_cast<uint16_t*>(d_codes.p), nullptr, QD_STREAM_CONTEXT);
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the scratch is freed on return
+    return rc;
+}
+
+int qd_cstats_enable(qd_ctx* c, int32_t on) {
+    if (!c) return QD_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));  // nothing of this context may still add to the old table
+    free_cstats(c);
+    if (!on) return QD_OK;
+    const size_t bytes = (size_t)QD_CS_VALUES * 8;
+    hipError_t e = uk_malloc(reinterpret_cast<void**>(&c->d_cs), bytes);
+    if (e != hipSuccess) {
+        c->d_cs = nullptr;
+        return fail(c, QD_ERR_HIP, std::string("cycle counters: ") + hipGetErrorString(e));
+    }
+    HIPCHK(c, hipMemsetAsync(c->d_cs, 0, bytes, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return QD_OK;
+}
+
+int qd_cstats_lds_cycles(void) { return (int)QD_CS_LDS_CYCLES; }
+
+int qd_cstats_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
+    if (!c || !out) return QD_ERR_INVALID;
+    if (!c->d_cs) return fail(c, QD_ERR_STATE, "the cycle counters are not enabled");
+    if (n_values != (int64_t)QD_CS_VALUES) return fail(c, QD_ERR_INVALID, "n_values must be QD_CS_VALUES");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));
+    HIPCHK(c, hipMemcpy(out, c->d_cs, (size_t)n_values * 8, hipMemcpyDeviceToHost));
+    return QD_OK;
+}
+
+int qd_cstats_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
+    if (!c || !values) return QD_ERR_INVALID;
+    if (!c->d_cs) return fail(c, QD_ERR_STATE, "the cycle counters are not enabled");
+    if (n_values != (int64_t)QD_CS_VALUES) return fail(c, QD_ERR_INVALID, "n_values must be QD_CS_VALUES");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));  // the kernel adds to the table: nothing of this context may be in flight
+    std::vector<u64> h((size_t)n_values);
+    HIPCHK(c, hipMemcpy(h.data(), c->d_cs, h.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < h.size(); ++i) h[i] += values[i];
+    HIPCHK(c, hipMemcpy(c->d_cs, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+    return QD_OK;
+}
+
+int qd_cstats_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
+                     const uint16_t* codes, const uint8_t* drop, void* stream) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_cs || !n) return QD_OK;
+    hipStream_t st = resolve_stream(c, stream);
+    qd_cstats_args a{};
+    a.text[0] = text1;
+    a.text[1] = text2;
+    a.recs[0] = recs1;
+    a.recs[1] = recs2;
+    a.codes = codes;
+    a.drop = drop;
+    a.table = c->d_cs;
+    hipError_t e = qd_cstats_launch(a, n, st);
+    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("cycle counters launch: ") + hipGetErrorString(e));
+    HIPCHK(c, track(c, st));
+    return QD_OK;
+}
+
+int qd_dev_cstats(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+                  const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes, const uint8_t* drop) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_cs) return fail(c, QD_ERR_STATE, "the cycle counters are not enabled");
+    const int64_t len[2] = {len1, len2};
+    const uint8_t* text[2] = {text1, text2};
+    const uint32_t* recs[2] = {recs1, recs2};
+    if (n_pairs < 0 || n_pairs > 0x7FFFFFFF || len1 < 0 || len2 < 0 || len1 > ((int64_t)1 << 30) || len2 > ((int64_t)1 << 30))
+        return fail(c, QD_ERR_INVALID, "bad sizes");
+    if (n_pairs == 0) return QD_OK;
+    if (!recs1 || !recs2 || !codes || (!text1 && len1) || (!text2 && len2)) return fail(c, QD_ERR_INVALID, "null argument");
+    // every range and every code is checked here: a bad table cannot become a bad address
+    for (int r = 0; r < 2; ++r)
+        for (int64_t j = 0; j < n_pairs; ++j) {
+            const qd_rec* q = reinterpret_cast<const qd_rec*>(recs[r]) + j;
+            if ((int64_t)q->seq + q->seq_len > len[r] || (int64_t)q->qual + q->seq_len > len[r])
+                return fail(c, QD_ERR_INVALID, "a record's sequence or quality line reaches beyond its text");
+        }
+    for (int64_t j = 0; j < n_pairs; ++j)
+        if (codes[j] != QD_CODE_UNDETERMINED && (int)codes[j] >= 2 * c->S) return fail(c, QD_ERR_INVALID, "a routing code is not below 2*S");
+    HIPCHK(c, hipSetDevice(c->device));
+    struct Dev {
+        void* p = nullptr;
+        ~Dev() {
+            if (p) (void)hipFree(p);
+        }
+    } d_text[2], d_recs[2], d_codes, d_drop;
+    // the texts start 3 bytes into their buffers: the kernel's aligned words must not depend on an aligned window
+    for (int r = 0; r < 2; ++r) {
+        HIPCHK(c, uk_malloc(&d_text[r].p, (size_t)len[r] + 32));
+        HIPCHK(c, uk_malloc(&d_recs[r].p, (size_t)n_pairs * sizeof(qd_rec)));
+        if (len[r]) HIPCHK(c, hipMemcpyAsync(static_cast<uint8_t*>(d_text[r].p) + 3, text[r], (size_t)len[r], hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_recs[r].p, recs[r], (size_t)n_pairs * sizeof(qd_rec), hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, uk_malloc(&d_codes.p, (size_t)n_pairs * 2));
+    HIPCHK(c, hipMemcpyAsync(d_codes.p, codes, (size_t)n_pairs * 2, hipMemcpyHostToDevice, c->stream));
+    if (drop) {
+        HIPCHK(c, uk_malloc(&d_drop.p, (size_t)n_pairs));
+        HIPCHK(c, hipMemcpyAsync(d_drop.p, drop, (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
+    }
+    const int rc = qd_cstats_device(c, static_cast<uint8_t*>(d_text[0].p) + 3, static_cast<qd_rec*>(d_recs[0].p), static_cast<uint8_t*>(d_text[1].p) + 3,
+                                    static_cast<qd_rec*>(d_recs[1].p), (uint32_t)n_pairs, static_cast<uint16_t*>(d_codes.p),
+                                    static_cast<uint8_t*>(d_drop.p), QD_STREAM_CONTEXT);
     HIPCHK(c, hipStreamSynchronize(c->stream));  // the scratch is freed on return
     return rc;
 }
@@ -1667,6 +1785,7 @@ int qd_reset_counts(qd_ctx* c) {
     HIPCHK(c, hipMemsetAsync(c->d_acc, 0, (size_t)c->cnt_stride * 8, c->stream));
     if (c->uk_slots) HIPCHK(c, hipMemsetAsync(c->d_uk, 0, qd_uk_bytes(c->uk_slots), c->stream));  // sum(counts) + short + dropped == UNDETERMINED stays true
     if (c->d_qs) HIPCHK(c, hipMemsetAsync(c->d_qs, 0, qd_qstats_values((uint32_t)c->S) * 8, c->stream));  // records stay equal to the pair counters
+    if (c->d_cs) HIPCHK(c, hipMemsetAsync(c->d_cs, 0, (size_t)QD_CS_VALUES * 8, c->stream));
     if (c->d_trim) HIPCHK(c, hipMemsetAsync(c->d_trim, 0, QD_TRIM_VALUES * 8, c->stream));
     if (c->d_pairtrim) HIPCHK(c, hipMemsetAsync(c->d_pairtrim, 0, QD_PT_VALUES * 8, c->stream));
     if (c->d_filter) HIPCHK(c, hipMemsetAsync(c->d_filter, 0, qd_filter_values((uint32_t)c->S) * 8, c->stream));

@@ -45,6 +45,7 @@
 #include "quade_io_internal.h"
 #include "quade_pool.h"
 #include "quade_qstats.h"
+#include "quade_cstats.h"
 #include "quade_text.h"
 #include "quade_trim.h"
 #include "quade_pairtrim.h"
@@ -1765,6 +1766,11 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
         const int rc = qd_qstats_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p,
                                         ins[1], n, p->codes.as<uint16_t>(), drop, p->cs);
         if (rc != QD_OK) return pfail(p, rc, std::string("quality counters: ") + qd_last_error(p->ctx));
+    }
+    {  // opt-in per-cycle counters and per-read distributions (qd_cstats_enable): the same reads, by pass / fail / Undetermined
+        const int rc = qd_cstats_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p,
+                                        ins[1], n, p->codes.as<uint16_t>(), drop, p->cs);
+        if (rc != QD_OK) return pfail(p, rc, std::string("cycle counters: ") + qd_last_error(p->ctx));
     }
     // 3. destinations, output lengths, stable sort by destination, output offsets
     PCHK(p, p->dest.need((size_t)n * 2 + 64, 0, p->cs));

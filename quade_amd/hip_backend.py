@@ -134,6 +134,10 @@ SYMBOLS = [
     ("qd_filter_read", C.c_int, [_P, _P, C.c_int64]),
     ("qd_filter_add", C.c_int, [_P, _P, C.c_int64]),
     ("qd_filter_kind", C.c_int, [_P]),
+    ("qd_cstats_enable", C.c_int, [_P, C.c_int32]),
+    ("qd_cstats_read", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_cstats_add", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_cstats_lds_cycles", C.c_int, []),
     ("qd_get_counts", C.c_int, [_P, _P, C.c_int32]),
     ("qd_reset_counts", C.c_int, [_P]),
     ("qd_add_counts", C.c_int, [_P, _P, C.c_int32]),
@@ -216,6 +220,7 @@ SYMBOLS = [
     ("qd_dev_trim", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_pairtrim", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_filter", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
+    ("qd_dev_cstats", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_pack_rows", C.c_int, [C.c_int, C.POINTER(qd_layout), _P * 2, C.c_int64 * 2, _P * 2, C.c_int64, C.c_int64, _P * 2, _P * 2, _P * 2,
                                    _P, C.c_int64, C.POINTER(C.c_uint32)]),
     ("qd_dev_route_format", C.c_int, [C.c_int, C.POINTER(qd_plan), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P * 4, C.c_int64 * 4, _P * 4, _P, _P,
@@ -532,6 +537,56 @@ def unpack_filter(blob):
     return np.frombuffer(blob, dtype=np.uint64, offset=8).reshape(n_dest, len(FILTER_COUNTERS)).copy()
 
 
+# the per-cycle table (qd_cstats_*): uint64, group-major (pass, fail, Undetermined), then read; per (group, read) the sections
+CSTATS_GROUPS = ("pass", "fail", "Undetermined")
+CSTATS_COUNTERS = ("A", "C", "G", "T", "N", "qual_sum", "q20", "q30")  # per cycle
+CSTATS_CYCLES, CSTATS_LEN_BINS, CSTATS_MEANQ_BINS, CSTATS_GC_BINS = 1024, 1025, 94, 101
+CSTATS_SECTIONS = (("cycle", (CSTATS_CYCLES, len(CSTATS_COUNTERS))), ("len", (CSTATS_LEN_BINS,)), ("meanq", (CSTATS_MEANQ_BINS,)),
+                   ("gc", (CSTATS_GC_BINS,)))
+CSTATS_GR_VALUES = CSTATS_CYCLES * len(CSTATS_COUNTERS) + CSTATS_LEN_BINS + CSTATS_MEANQ_BINS + CSTATS_GC_BINS  # 9412
+CSTATS_VALUES = len(CSTATS_GROUPS) * 2 * CSTATS_GR_VALUES  # 56472
+
+
+def cstats_views(flat):
+    """The flat table (uint64[CSTATS_VALUES]) as a dict of views into it: cycle[3, 2, 1024, 8], len[3, 2, 1025],
+    meanq[3, 2, 94], gc[3, 2, 101] -- [group][R1, R2][...]"""
+    flat = np.asarray(flat)
+    assert flat.shape == (CSTATS_VALUES,) and flat.dtype == np.uint64, "cycle table of the wrong size"
+    per = flat.reshape(len(CSTATS_GROUPS), 2, CSTATS_GR_VALUES)
+    out, at = {}, 0
+    for name, shape in CSTATS_SECTIONS:
+        size = int(np.prod(shape))
+        out[name] = per[:, :, at:at + size].reshape((len(CSTATS_GROUPS), 2) + shape)
+        at += size
+    return out
+
+
+def cstats_flat(table):
+    """cstats_views' dict (or a flat table) -> the flat uint64[CSTATS_VALUES] layout of qd_cstats_read"""
+    if not isinstance(table, dict):
+        flat = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1)
+        assert flat.size == CSTATS_VALUES, "cycle table of the wrong size"
+        return flat
+    per = np.concatenate([np.asarray(table[name], dtype=np.uint64).reshape(len(CSTATS_GROUPS), 2, -1) for name, _ in CSTATS_SECTIONS],
+                         axis=2)
+    assert per.shape == (len(CSTATS_GROUPS), 2, CSTATS_GR_VALUES), "cycle table of the wrong size"
+    return np.ascontiguousarray(per).reshape(-1)
+
+
+def pack_cstats(table):
+    """One context's or rank's cycle table (cstats_views' dict or flat) as bytes (the ranks' exchange through the rendezvous
+    directory); unpack_cstats reverses it."""
+    flat = cstats_flat(table)
+    return np.array([flat.size], dtype=np.uint64).tobytes() + flat.tobytes()
+
+
+def unpack_cstats(blob):
+    """-> cstats_views' dict over a writable copy (tables are summed in place)"""
+    n = int(np.frombuffer(blob, dtype=np.uint64, count=1)[0])
+    assert n == CSTATS_VALUES and len(blob) == 8 + n * 8, "cycle table of the wrong size"
+    return cstats_views(np.frombuffer(blob, dtype=np.uint64, offset=8).copy())
+
+
 # ---- device context -------------------------------------------------------------------------------------
 class Engine(object):
     """One libquade_hip context = one MI355X.  Mirrors what Sample.CLASS_INIT + Sample(name, index)
@@ -798,6 +853,40 @@ class Engine(object):
         self._chk(self.lib.qd_dev_filter(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), codes.size,
                                          _ptr(codes), _ptr(out)))
         return out
+
+    def cstats_enable(self, on=True):
+        """Per-cycle quality and base content and the per-read distributions (qd_cstats_enable): every pair the device pipeline
+        routes adds its two insert reads to a device table.  Independent of plan and barcodes; reset_counts zeroes it."""
+        self._chk(self.lib.qd_cstats_enable(self._h, int(bool(on))))
+
+    def cstats_read(self):
+        """dict of uint64 views into one flat table: cycle[3, 2, 1024, 8], len[3, 2, 1025], meanq[3, 2, 94], gc[3, 2, 101] --
+        [CSTATS_GROUPS][R1, R2][...] (cstats_flat gives the flat table back)"""
+        out = np.zeros(CSTATS_VALUES, dtype=np.uint64)
+        self._chk(self.lib.qd_cstats_read(self._h, _ptr(out), out.size))
+        return cstats_views(out)
+
+    def cstats_add(self, table):
+        """Another context's table (cstats_read's dict or flat) joins this context's (qd_cstats_add)."""
+        flat = cstats_flat(table) if isinstance(table, dict) else np.ascontiguousarray(table, dtype=np.uint64).reshape(-1)
+        self._chk(self.lib.qd_cstats_add(self._h, _ptr(flat), flat.size))
+
+    def dev_cstats(self, text1, recs1, text2, recs2, codes, drop=None):
+        """The per-cycle stage over host buffers (qd_dev_cstats): texts as bytes or uint8 arrays, recs uint32[n, 6] in
+        dev_fastq_scan's layout, codes uint16[n], drop None or uint8[n] (non-zero = the pair is skipped); adds to the context's
+        table."""
+        t = [np.frombuffer(bytes(x), dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, dtype=np.uint8)
+             for x in (text1, text2)]
+        r = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, 6) for x in (recs1, recs2)]
+        codes = np.ascontiguousarray(codes, dtype=np.uint16)
+        if r[0].shape[0] != r[1].shape[0] or codes.shape != (r[0].shape[0],):
+            raise ValueError("recs1, recs2 and codes must have one entry per pair")
+        if drop is not None:
+            drop = np.ascontiguousarray(drop, dtype=np.uint8)
+            if drop.shape != codes.shape:
+                raise ValueError("drop must have one byte per pair")
+        self._chk(self.lib.qd_dev_cstats(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), codes.size,
+                                         _ptr(codes), _ptr(drop) if drop is not None else None))
 
     def set_option(self, name, value):
         self._chk(self.lib.qd_set_option(self._h, name.encode(), int(value)))

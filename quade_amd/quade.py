@@ -169,6 +169,8 @@ class Quade(object):
                     eng.unknown_enable(cf.unknown_slots)
                 if cf.quality_report:  # the insert reads are counted per destination while the pipeline holds their text
                     eng.qstats_enable(True)
+                if cf.cycle_report:  # ... and per cycle, by pass / fail / Undetermined
+                    eng.cstats_enable(True)
                 if cf.trim:  # the insert reads are trimmed at their 3' end while the pipeline holds their text
                     eng.trim_set(**cf.trim_params())
                 if cf.pair_trim:  # ... and R1 and R2 of a pair together, behind it
@@ -201,6 +203,7 @@ class Quade(object):
         counts = self._reduce_counts(devices)
         unknown = self._collect_unknown() if cf.top_unknown_barcodes > 0 else None
         quality = self._collect_quality() if cf.quality_report else None
+        cycles = self._collect_cycles() if cf.cycle_report else None
         trimmed = self._collect_trim() if cf.trim else None
         pair_trimmed = self._collect_pair_trim() if cf.pair_trim else None
         filtered = self._collect_filter() if cf.filter else None
@@ -245,6 +248,9 @@ class Quade(object):
             from . import quality_report
             quality_report.write_report(os.path.join(self.outdir, quality_report.REPORT_NAME), quality,
                                         [s.name for s in Sample.SAMPLE_LIST])
+        if cycles is not None:
+            from . import cycle_report
+            cycle_report.write_report(os.path.join(self.outdir, cycle_report.REPORT_NAME), cycles)
         if trimmed is not None:
             from . import trim_report
             trim_report.write_report(os.path.join(self.outdir, trim_report.REPORT_NAME), trimmed, cf.trim_params())
@@ -388,6 +394,22 @@ class Quade(object):
             for t in tables[1:]:
                 table = table + t
         return table
+
+    def _collect_cycles(self):
+        """[output] cycle_report: the tables of every context of this process summed (chunk workers, devices); with several
+        ranks every rank publishes its sum in the rendezvous directory and adds all of them (rank 0 writes the file).
+        Returns hip_backend.cstats_views' dict."""
+        from . import dist
+        flat = None
+        for eng in self.engines:
+            t = hb.cstats_flat(eng.cstats_read())
+            flat = t if flat is None else flat + t
+        if self.world > 1:
+            got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, "cycle", hb.pack_cstats(flat))
+            flat = hb.cstats_flat(hb.unpack_cstats(got[0]))
+            for b in got[1:]:
+                flat = flat + hb.cstats_flat(hb.unpack_cstats(b))
+        return hb.cstats_views(flat)
 
     def double_index_parser(self):
         cf = self.cf
