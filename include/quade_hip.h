@@ -247,6 +247,53 @@ int qd_qstats_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
 int qd_qstats_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
 int qd_qstats_kind(const qd_ctx* ctx);
 
+/* ---- end clipping, sliding-window quality trimming and poly-G tail trimming of the insert reads (opt-in; no reference
+ * counterpart: Quade 0.3.2 writes the insert reads as they came) ----------------------------------------------------------------
+ * One stage in front of the 3' trimming below, in fastp's order: fixed trimming, cut_right, poly-G, then adapters.  For an insert
+ * read r (R1 or R2) with sequence bytes s, quality bytes q (unsigned) and length L, with u(b) = b & 0xDF and
+ * ph[i] = max(0, q[i] - 33); F_r = front_clip[r], T_r = tail_clip[r], W = window_size, Q = window_quality, P = poly_g_min_length.
+ * Steps 1 to 3 are each skipped when not configured; their output length is then their input length.
+ *   1 fixed clip: f = min(F_r, L) and Lc = max(0, L - f - T_r).  From here on position i means byte f + i of the line.
+ *   2 window, W > 0 (Trimmomatic SLIDINGWINDOW, fastp cut_right): Lw = the smallest p in [0, Lc - W] with
+ *     ph[p] + .. + ph[p+W-1] < Q * W; Lc when there is none, which includes every read with Lc < W
+ *   3 poly-G, P > 0 (fastp's trimPolyG, folded to upper case): for t = 1 .. Lw let b_t = u(s[Lw - t]) and mm(t) the number of
+ *     k <= t with b_k != 'G'; stop(t) is true when mm(t) > 5, or when t >= P and 8 * mm(t) > t; T = the smallest t with stop(t),
+ *     Lw + 1 when there is none.  If T - 1 >= P then Lg = Lw - g, g being the largest t <= T - 1 with b_t == 'G' (one exists
+ *     because P >= 6); otherwise Lg = Lw.  One mismatch per 8 bases, at most 5, a run of at least P, cut at the leftmost G reached
+ *   4 floor: Lout = max(Lg, min(min_length, L - f)), min_length being the 3' trimming's.  A front clip is never given back;
+ *     everything cut from the 3' end can be
+ * and the read's record becomes seq + f, qual + f, seq_len = Lout; its other three fields stay.  Index reads, names and the
+ * :IDX[:MOL] tag never change and no pair is dropped.  With the stage on, qd_pipe_run runs it over every pair it routes (one launch
+ * per batch on its compute stream, no host sync) directly in front of the 3' trimming, so that the trimming stages, the read
+ * filter, the quality and cycle counters and the output stages all see the clipped reads, and adds to a device table
+ * uint64[2][12] (R1, R2), whatever the write flags say:
+ *   0 reads   1 bases_in (sum of L)   2 bases_out (sum of Lout)   3 front_clipped_reads (f > 0)   4 front_clipped_bases
+ *   5 tail_clipped_reads (Lc < L - f)   6 tail_clipped_bases   7 window_reads (Lw < Lc)   8 window_bases
+ *   9 polyg_reads (Lg < Lw)   10 polyg_bases   11 floored_reads (Lout > Lg)
+ * Off, nothing is allocated or launched.
+ *
+ * qd_clip_set: NULL, or every rule off (all clips 0, no window, no poly-G), turns the stage off and frees the table; otherwise
+ * the values are checked (front_clip and tail_clip 0..1000, window_size 0 = off or 1..100, window_quality 1..93 and set together
+ * with window_size or not at all, poly_g_min_length 0 = off or 6..100, min_length 0..65535: QD_ERR_INVALID, the state as before)
+ * and a zeroed table allocated.  Waits for the context's outstanding work.  Independent of plan, barcodes and qd_trim_set.
+ * qd_clip_get: the parameters in force (all zero and QD_OK when off).
+ * qd_clip_read: waits for the context's work, writes n_values = 24 values (QD_ERR_INVALID on another size, QD_ERR_STATE when off).
+ * qd_clip_add: another context's table (qd_clip_read's layout) joins this one's, as qd_trim_add does.  qd_reset_counts zeroes
+ * the table. */
+#define QD_CLIP_VALUES 24
+typedef struct qd_clip_params {
+    int32_t front_clip[2]; /* R1, R2 */
+    int32_t tail_clip[2];
+    int32_t window_size;    /* 0 = off */
+    int32_t window_quality; /* 0 with window_size 0 */
+    int32_t poly_g_min_length; /* 0 = off */
+    int32_t min_length;
+} qd_clip_params;
+int qd_clip_set(qd_ctx* ctx, const qd_clip_params* params);
+int qd_clip_get(const qd_ctx* ctx, qd_clip_params* out);
+int qd_clip_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
+int qd_clip_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
+
 /* ---- 3' quality and adapter trimming of the insert reads (opt-in; no reference counterpart: Quade 0.3.2 writes the insert
  * reads as they came) -----------------------------------------------------------------------------------------------------
  * For an insert read with sequence s, quality bytes q and length L (index reads, names and the :IDX[:MOL] tag never change):
@@ -839,6 +886,13 @@ int qd_dev_sort_by_dest(int device_id, const uint16_t* dest, int64_t n, int32_t 
  * Returns when the launch has finished. */
 int qd_dev_qstats(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                   const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes);
+/* the clip stage (qd_clip_set above; no reference counterpart) over host buffers, as qd_dev_trim: reads [0, n_pairs) of two texts
+ * with their record tables are uploaded (the texts 3 bytes off alignment) and run through the kernel qd_pipe_run launches;
+ * out_recs1 / out_recs2 receive the whole tables, seq and qual moved by the front clip and seq_len the length the read keeps, and
+ * the context's table grows.  Every record's sequence and quality range is checked against len1 / len2 before anything is
+ * launched: QD_ERR_INVALID.  QD_ERR_STATE when the stage is off.  Returns when the launch has finished. */
+int qd_dev_clip(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+                const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2);
 /* the trimming stage (qd_trim_set above; no reference counterpart) over host buffers: reads [0, n_pairs) of two texts with their
  * record tables (6 uint32 per record, qd_dev_fastq_scan's layout) are uploaded and trimmed by the kernel qd_pipe_run launches;
  * out_recs1 / out_recs2 receive the tables with every seq_len replaced by the length the read keeps, and the context's counters

@@ -7,7 +7,7 @@ file written by `-i` is the reference's template byte for byte (src/Conf_file.py
 package data, quade_amd/data/Quade_conf_file.txt).  An optional [gpu] section that reference conf
 files simply do not have is read when present (defaults apply otherwise; see GPU_SECTION_HELP), and so are the optional
 mismatch budgets of the [index] section (MISMATCH_HELP), the unknown-barcode report (UNKNOWN_HELP) and the quality report
-(QUALITY_HELP) and the per-cycle report (CYCLE_HELP) of the [output] section, an optional [trim] section (TRIM_HELP, PAIR_HELP) and an optional [filter] section
+(QUALITY_HELP) and the per-cycle report (CYCLE_HELP) of the [output] section, an optional [trim] section (CLIP_HELP, TRIM_HELP, PAIR_HELP) and an optional [filter] section
 (FILTER_HELP).
 """
 from __future__ import annotations
@@ -117,6 +117,37 @@ TRIM_CUTOFF = "Authorized values for quality_cutoff : 0 to 93"
 TRIM_OVERLAP = "Authorized values for min_overlap : 1 to 64, and not above the length of a set adapter"
 TRIM_MISMATCH = "Authorized values for max_mismatch_pct : 0 to 50"
 TRIM_LENGTH = "Authorized values for min_length : 0 to 65535"
+
+CLIP_HELP = """\
+Optional [trim] options (not in Quade 0.3.2, whose parser ignores them; absent = as before): end clipping, sliding-window quality
+trimming and poly-G tail trimming of the insert reads on the GPU, in front of the 3' trimming above (fastp's order: fixed
+trimming, cut_right, poly-G, then adapters).  Index reads, names and the :IDX[:MOL] tag are never touched.  In this order:
+  front_clip_R1 : 0         0 to 1000: bases cut from the 5' end of every R1 / R2 read (a spacer, a random primer); the read's
+  front_clip_R2 : 0         sequence and quality lines then start that many bytes later
+  tail_clip_R1 : 0          0 to 1000: bases cut from the 3' end of every R1 / R2 read (the last cycle of a 151-cycle run)
+  tail_clip_R2 : 0
+  window_size :             1 to 100, with window_quality 1 to 93 (both or neither): cut the read at the start of the first window
+  window_quality :          of window_size bases whose mean Phred is below window_quality (Trimmomatic SLIDINGWINDOW, fastp
+                            cut_right); a read shorter than the window is left alone
+  poly_g : False            True: cut a poly-G tail (two-colour instruments read a dark cluster as high-quality G) of at least
+  poly_g_min_length : 10    poly_g_min_length bases, 6 to 100: walking from the 3' end, one base other than G per 8 is forgiven,
+                            at most 5; the cut is at the leftmost G reached (fastp's rule; g counts as G, N does not)
+min_length (above) holds for these cuts too, except that a front clip is never given back.  The stage is on when a clip is > 0, a
+window is set or poly_g is True; Quade_clip_report.csv is then written next to the report.  These options do not turn the 3'
+trimming on.  Quade_trim_report.csv's bases_in, pair_overlap, [filter], quality_report and cycle_report see the reads as this
+stage left them: with pair_overlap a front clip of F1 + F2 bases shortens the reported insert sizes by that much, and the
+reverse complement of R2's clipped 5' bases is cut from R1's 3' end when the insert is short (as fastp's trim_front in front of
+its overlap analysis).  The reads are clipped while the device pipeline holds their text, so the options need the device pipeline:
+[gpu] device_pipeline, device_inflate and device_deflate True (the defaults) and gzip_level 1 or -1
+"""
+
+CLIP_NEEDS = ("[trim] clipping (front_clip, tail_clip, window_size, poly_g) needs the device pipeline (device_pipeline, device_inflate, "
+              "device_deflate : True and gzip_level 1 or -1)")
+CLIP_FIXED = "Authorized values for front_clip_R1, front_clip_R2, tail_clip_R1 and tail_clip_R2 : 0 to 1000"
+CLIP_WINDOW_SIZE = "Authorized values for window_size : 1 to 100"
+CLIP_WINDOW_QUALITY = "Authorized values for window_quality : 1 to 93"
+CLIP_WINDOW_BOTH = "window_size and window_quality are set together or not at all"
+CLIP_POLY_G = "Authorized values for poly_g_min_length : 6 to 100"
 
 PAIR_HELP = """\
 Optional [trim] options (not in Quade 0.3.2, whose parser ignores them; absent = as before): paired-end overlap trimming of the
@@ -246,6 +277,13 @@ class QuadeConf(object):
         self.min_overlap = trim("min_overlap", 3)
         self.max_mismatch_pct = trim("max_mismatch_pct", 10)
         self.min_length = trim("min_length", 0)
+        # ... its end clipping, window and poly-G trimming in front of that (CLIP_HELP): None = no window
+        self.front_clip = (trim("front_clip_R1", 0), trim("front_clip_R2", 0))
+        self.tail_clip = (trim("tail_clip_R1", 0), trim("tail_clip_R2", 0))
+        self.window_size = trim("window_size", None)
+        self.window_quality = trim("window_quality", None)
+        self.poly_g = trim("poly_g", False, lambda v: v.strip().lower() in ("true", "1", "yes", "on"))
+        self.poly_g_min_length = trim("poly_g_min_length", 10)
         # ... and its paired-end overlap trimming (PAIR_HELP)
         self.pair_overlap = trim("pair_overlap", False, lambda v: v.strip().lower() in ("true", "1", "yes", "on"))
         self.pair_min_overlap = trim("pair_min_overlap", 30)
@@ -337,6 +375,13 @@ class QuadeConf(object):
         assert 0 <= self.min_length <= 65535, TRIM_LENGTH
         assert not self.trim or (self.device_pipeline and self.device_inflate and self.device_deflate
                                  and self.gzip_level in (1, -1)), TRIM_NEEDS
+        assert all(0 <= v <= 1000 for v in self.front_clip + self.tail_clip), CLIP_FIXED
+        assert (self.window_size is None) == (self.window_quality is None), CLIP_WINDOW_BOTH
+        assert self.window_size is None or 1 <= self.window_size <= 100, CLIP_WINDOW_SIZE
+        assert self.window_quality is None or 1 <= self.window_quality <= 93, CLIP_WINDOW_QUALITY
+        assert 6 <= self.poly_g_min_length <= 100, CLIP_POLY_G
+        assert not self.clip or (self.device_pipeline and self.device_inflate and self.device_deflate
+                                 and self.gzip_level in (1, -1)), CLIP_NEEDS
         assert 8 <= self.pair_min_overlap <= 1000, PAIR_OVERLAP
         assert 0 <= self.pair_max_mismatches <= 64, PAIR_MISMATCHES
         assert 0 <= self.pair_max_mismatch_pct <= 50, PAIR_MISMATCH_PCT
@@ -362,6 +407,17 @@ class QuadeConf(object):
         """what Engine.trim_set takes"""
         return dict(adapter_r1=self.adapter_R1, adapter_r2=self.adapter_R2, quality_cutoff=self.quality_cutoff,
                     min_overlap=self.min_overlap, max_mismatch_pct=self.max_mismatch_pct, min_length=self.min_length)
+
+    @property
+    def clip(self):
+        """end clipping, window or poly-G trimming of the insert reads is on (CLIP_HELP)"""
+        return bool(any(self.front_clip) or any(self.tail_clip) or self.window_size is not None or self.poly_g)
+
+    def clip_params(self):
+        """what Engine.clip_set takes"""
+        return dict(front_clip_r1=self.front_clip[0], front_clip_r2=self.front_clip[1], tail_clip_r1=self.tail_clip[0],
+                    tail_clip_r2=self.tail_clip[1], window_size=self.window_size or 0, window_quality=self.window_quality or 0,
+                    poly_g_min_length=self.poly_g_min_length if self.poly_g else 0, min_length=self.min_length)
 
     @property
     def pair_trim(self):

@@ -23,6 +23,7 @@
 #include "quade_unknown.h"
 #include "quade_qstats.h"
 #include "quade_cstats.h"
+#include "quade_clip.h"
 #include "quade_trim.h"
 #include "quade_pairtrim.h"
 #include "quade_filter.h"
@@ -147,6 +148,11 @@ struct qd_ctx {
     // per-cycle counters and per-read distributions (qd_cstats_enable): uint64[QD_CS_VALUES], nullptr = off
     u64* d_cs = nullptr;
 
+    // end clipping, window and poly-G trimming of the insert reads (qd_clip_set): the parameters as given and as the kernel takes
+    // them, and the counters uint64[2][12]; d_clip == nullptr = off
+    qd_clip_params clip{};
+    qd_clip_dev clip_dev{};
+    u64* d_clip = nullptr;
     // 3' trimming of the insert reads (qd_trim_set): the parameters as given and as the kernel takes them, and the counters
     // uint64[2][8]; d_trim == nullptr = off
     qd_trim_params trim{};
@@ -421,6 +427,14 @@ void free_qstats(qd_ctx* c) {
 void free_cstats(qd_ctx* c) {
     if (c->d_cs) (void)hipFree(c->d_cs);
     c->d_cs = nullptr;
+}
+
+// clipping off and its table freed (the caller waited for the context's work)
+void free_clip(qd_ctx* c) {
+    if (c->d_clip) (void)hipFree(c->d_clip);
+    c->d_clip = nullptr;
+    c->clip = qd_clip_params{};
+    c->clip_dev = qd_clip_dev{};
 }
 
 // trimming off and its table freed (the caller waited for the context's work)
@@ -799,6 +813,7 @@ int qd_destroy(qd_ctx* c) {
     free_unknown(c);
     free_qstats(c);
     free_cstats(c);
+    free_clip(c);
     free_trim(c);
     free_pairtrim(c);
     free_filter(c);
@@ -1215,6 +1230,144 @@ int qd_dev_cstats(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t*
     const int rc = qd_cstats_device(c, static_cast<uint8_t*>(d_text[0].p) + 3, static_cast<qd_rec*>(d_recs[0].p), static_cast<uint8_t*>(d_text[1].p) + 3,
                                     static_cast<qd_rec*>(d_recs[1].p), (uint32_t)n_pairs, static_cast<uint16_t*>(d_codes.p),
                                     static_cast<uint8_t*>(d_drop.p), QD_STREAM_CONTEXT);
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // the scratch is freed on return
+    return rc;
+}
+
+static_assert(QD_CLIP_VALUES == QD_CLIP_TABLE, "the public table size is the kernel's");
+
+int qd_clip_set(qd_ctx* c, const qd_clip_params* params) {
+    if (!c) return QD_ERR_INVALID;
+    qd_clip_params P{};
+    qd_clip_dev D{};
+    const bool on = params && (params->front_clip[0] || params->front_clip[1] || params->tail_clip[0] || params->tail_clip[1] ||
+                               params->window_size || params->window_quality || params->poly_g_min_length);
+    if (on) {  // checked as the configuration file's values are, before anything changes
+        P = *params;
+        for (int r = 0; r < 2; ++r) {
+            if (P.front_clip[r] < 0 || P.front_clip[r] > 1000) return fail(c, QD_ERR_INVALID, "front_clip: 0 to 1000");
+            if (P.tail_clip[r] < 0 || P.tail_clip[r] > 1000) return fail(c, QD_ERR_INVALID, "tail_clip: 0 to 1000");
+            D.front[r] = (uint32_t)P.front_clip[r];
+            D.tail[r] = (uint32_t)P.tail_clip[r];
+        }
+        if (P.window_size < 0 || P.window_size > QD_CLIP_MAX_WINDOW) return fail(c, QD_ERR_INVALID, "window_size: 0 (off) or 1 to 100");
+        if (P.window_size ? (P.window_quality < 1 || P.window_quality > 93) : P.window_quality != 0)
+            return fail(c, QD_ERR_INVALID, "window_quality: 1 to 93, set together with window_size");
+        if (P.poly_g_min_length && (P.poly_g_min_length < 6 || P.poly_g_min_length > QD_CLIP_MAX_POLYG))
+            return fail(c, QD_ERR_INVALID, "poly_g_min_length: 0 (off) or 6 to 100");
+        if (P.min_length < 0 || P.min_length > 65535) return fail(c, QD_ERR_INVALID, "min_length: 0 to 65535");
+        D.window = (uint32_t)P.window_size;
+        D.window_sum = (uint32_t)(P.window_size * P.window_quality);
+        D.poly_g = (uint32_t)P.poly_g_min_length;
+        D.min_length = (uint32_t)P.min_length;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));  // nothing of this context may still read the old parameters or add to the old table
+    free_clip(c);
+    if (!on) return QD_OK;
+    hipError_t e = uk_malloc(reinterpret_cast<void**>(&c->d_clip), QD_CLIP_TABLE * 8);
+    if (e != hipSuccess) {
+        c->d_clip = nullptr;
+        return fail(c, QD_ERR_HIP, std::string("clip counters: ") + hipGetErrorString(e));
+    }
+    HIPCHK(c, hipMemsetAsync(c->d_clip, 0, QD_CLIP_TABLE * 8, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->clip = P;
+    c->clip_dev = D;
+    return QD_OK;
+}
+
+int qd_clip_get(const qd_ctx* c, qd_clip_params* out) {
+    if (!c || !out) return QD_ERR_INVALID;
+    *out = c->clip;
+    return QD_OK;
+}
+
+int qd_clip_active(const qd_ctx* c) { return c && c->d_clip ? 1 : 0; }
+
+int qd_clip_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
+    if (!c || !out) return QD_ERR_INVALID;
+    if (!c->d_clip) return fail(c, QD_ERR_STATE, "clipping is not on");
+    if (n_values != QD_CLIP_TABLE) return fail(c, QD_ERR_INVALID, "n_values must be 24");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));
+    HIPCHK(c, hipMemcpy(out, c->d_clip, QD_CLIP_TABLE * 8, hipMemcpyDeviceToHost));
+    return QD_OK;
+}
+
+int qd_clip_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
+    if (!c || !values) return QD_ERR_INVALID;
+    if (!c->d_clip) return fail(c, QD_ERR_STATE, "clipping is not on");
+    if (n_values != QD_CLIP_TABLE) return fail(c, QD_ERR_INVALID, "n_values must be 24");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));  // the kernel adds to the table: nothing of this context may be in flight
+    u64 h[QD_CLIP_TABLE];
+    HIPCHK(c, hipMemcpy(h, c->d_clip, sizeof(h), hipMemcpyDeviceToHost));
+    for (int i = 0; i < QD_CLIP_TABLE; ++i) h[i] += values[i];
+    HIPCHK(c, hipMemcpy(c->d_clip, h, sizeof(h), hipMemcpyHostToDevice));
+    return QD_OK;
+}
+
+int qd_clip_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
+                   qd_rec* out1, qd_rec* out2, void* stream) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_clip) return fail(c, QD_ERR_STATE, "clipping is not on");
+    if (!n) return QD_OK;
+    hipStream_t st = resolve_stream(c, stream);
+    qd_clip_args a{};
+    a.text[0] = text1;
+    a.text[1] = text2;
+    a.recs[0] = recs1;
+    a.recs[1] = recs2;
+    a.out[0] = out1;
+    a.out[1] = out2;
+    a.table = c->d_clip;
+    hipError_t e = qd_clip_launch(c->clip_dev, a, n, st);
+    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("clip launch: ") + hipGetErrorString(e));
+    HIPCHK(c, track(c, st));
+    return QD_OK;
+}
+
+int qd_dev_clip(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+                const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_clip) return fail(c, QD_ERR_STATE, "clipping is not on");
+    const int64_t len[2] = {len1, len2};
+    const uint8_t* text[2] = {text1, text2};
+    const uint32_t* recs[2] = {recs1, recs2};
+    uint32_t* out[2] = {out_recs1, out_recs2};
+    if (n_pairs < 0 || n_pairs > 0x7FFFFFFF || len1 < 0 || len2 < 0 || len1 > ((int64_t)1 << 30) || len2 > ((int64_t)1 << 30))
+        return fail(c, QD_ERR_INVALID, "bad sizes");
+    if (n_pairs == 0) return QD_OK;
+    if (!recs1 || !recs2 || !out_recs1 || !out_recs2 || (!text1 && len1) || (!text2 && len2)) return fail(c, QD_ERR_INVALID, "null argument");
+    // every range is checked here: a bad table cannot become a bad address
+    for (int r = 0; r < 2; ++r)
+        for (int64_t j = 0; j < n_pairs; ++j) {
+            const qd_rec* q = reinterpret_cast<const qd_rec*>(recs[r]) + j;
+            if ((int64_t)q->seq + q->seq_len > len[r] || (int64_t)q->qual + q->seq_len > len[r])
+                return fail(c, QD_ERR_INVALID, "a record's sequence or quality line reaches beyond its text");
+        }
+    HIPCHK(c, hipSetDevice(c->device));
+    struct Dev {
+        void* p = nullptr;
+        ~Dev() {
+            if (p) (void)hipFree(p);
+        }
+    } d_text[2], d_recs[2], d_out[2];
+    const size_t rec_bytes = (size_t)n_pairs * sizeof(qd_rec);
+    // the texts start 3 bytes into their buffers: the kernel's aligned words must not depend on an aligned window
+    for (int r = 0; r < 2; ++r) {
+        HIPCHK(c, uk_malloc(&d_text[r].p, (size_t)len[r] + 32));
+        HIPCHK(c, uk_malloc(&d_recs[r].p, rec_bytes));
+        HIPCHK(c, uk_malloc(&d_out[r].p, rec_bytes));
+        if (len[r]) HIPCHK(c, hipMemcpyAsync(static_cast<uint8_t*>(d_text[r].p) + 3, text[r], (size_t)len[r], hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_recs[r].p, recs[r], rec_bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    const int rc = qd_clip_device(c, static_cast<uint8_t*>(d_text[0].p) + 3, static_cast<qd_rec*>(d_recs[0].p), static_cast<uint8_t*>(d_text[1].p) + 3,
+                                  static_cast<qd_rec*>(d_recs[1].p), (uint32_t)n_pairs, static_cast<qd_rec*>(d_out[0].p), static_cast<qd_rec*>(d_out[1].p),
+                                  QD_STREAM_CONTEXT);
+    if (rc == QD_OK)
+        for (int r = 0; r < 2; ++r) HIPCHK(c, hipMemcpyAsync(out[r], d_out[r].p, rec_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // the scratch is freed on return
     return rc;
 }
@@ -1772,9 +1925,10 @@ int qd_add_counts(qd_ctx* c, const uint64_t* counts, int32_t n_values) {
 int qd_reset_counts(qd_ctx* c) {
     if (!c) return QD_ERR_INVALID;
     if (!c->have_table) {  // no barcodes, no pair counters; the trim counters do not depend on them
-        if (!c->d_trim && !c->d_pairtrim) return QD_OK;
+        if (!c->d_clip && !c->d_trim && !c->d_pairtrim) return QD_OK;
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, wait_all(c));
+        if (c->d_clip) HIPCHK(c, hipMemset(c->d_clip, 0, QD_CLIP_TABLE * 8));
         if (c->d_trim) HIPCHK(c, hipMemset(c->d_trim, 0, QD_TRIM_VALUES * 8));
         if (c->d_pairtrim) HIPCHK(c, hipMemset(c->d_pairtrim, 0, QD_PT_VALUES * 8));
         return QD_OK;
@@ -1786,6 +1940,7 @@ int qd_reset_counts(qd_ctx* c) {
     if (c->uk_slots) HIPCHK(c, hipMemsetAsync(c->d_uk, 0, qd_uk_bytes(c->uk_slots), c->stream));  // sum(counts) + short + dropped == UNDETERMINED stays true
     if (c->d_qs) HIPCHK(c, hipMemsetAsync(c->d_qs, 0, qd_qstats_values((uint32_t)c->S) * 8, c->stream));  // records stay equal to the pair counters
     if (c->d_cs) HIPCHK(c, hipMemsetAsync(c->d_cs, 0, (size_t)QD_CS_VALUES * 8, c->stream));
+    if (c->d_clip) HIPCHK(c, hipMemsetAsync(c->d_clip, 0, QD_CLIP_TABLE * 8, c->stream));
     if (c->d_trim) HIPCHK(c, hipMemsetAsync(c->d_trim, 0, QD_TRIM_VALUES * 8, c->stream));
     if (c->d_pairtrim) HIPCHK(c, hipMemsetAsync(c->d_pairtrim, 0, QD_PT_VALUES * 8, c->stream));
     if (c->d_filter) HIPCHK(c, hipMemsetAsync(c->d_filter, 0, qd_filter_values((uint32_t)c->S) * 8, c->stream));

@@ -47,6 +47,7 @@
 #include "quade_qstats.h"
 #include "quade_cstats.h"
 #include "quade_text.h"
+#include "quade_clip.h"
 #include "quade_trim.h"
 #include "quade_pairtrim.h"
 #include "quade_filter.h"
@@ -720,6 +721,7 @@ struct qd_pipe {
     // index rows, codes, routing scratch (sized for batch_pairs)
     DevBuf rows_seq[2], rows_qual[2], rows_len[2], codes, mol, short_idx, dest, len1, len2, hist, tmp, perm, sdest, g1, g2, scan_tiles, first, g1_first,
         g2_first;
+    DevBuf clipped[2];  // the insert reads' record tables as the clip stage leaves them (qd_clip_set; never allocated when it is off)
     DevBuf trimmed[2];  // the insert reads' record tables with trimmed lengths (qd_trim_set; never allocated when trimming is off)
     DevBuf pairtrimmed[2];  // ... with the lengths the overlap trimming leaves (qd_pairtrim_set; never allocated when it is off)
     DevBuf drop;  // the read filter's reason byte per pair (qd_filter_set; never allocated when it is off)
@@ -1734,9 +1736,19 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
         const int rc = qd_demux_device(p->ctx, n, &rows, p->codes.as<uint16_t>(), d_mol, p->cs);
         if (rc != QD_OK) return pfail(p, rc, std::string("demux: ") + qd_last_error(p->ctx));
     }
-    // opt-in 3' trimming of the insert reads (qd_trim_set): trimmed copies of their two tables, which everything behind this point
-    // reads sequence and quality through.  The scan's tables stay as they are: the carry and the next batch use them
+    // The insert reads' tables: the opt-in stages below write copies of their own, which everything behind them reads sequence and
+    // quality through.  The scan's tables stay as they are: the carry and the next batch use them
     const qd_rec* ins[2] = {p->win[0].recs.as<qd_rec>(), p->win[1].recs.as<qd_rec>()};
+    // opt-in end clipping, window and poly-G trimming (qd_clip_set), in front of the 3' trimming: copies with seq, qual and seq_len
+    // of their own, so that a 5' clip reaches every stage behind it through the tables alone
+    if (qd_clip_active(p->ctx)) {
+        for (int k = 0; k < 2; ++k) PCHK(p, p->clipped[k].need((size_t)n * sizeof(qd_rec) + 64, 0, p->cs));
+        const int rc = qd_clip_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p, ins[1], n,
+                                      p->clipped[0].as<qd_rec>(), p->clipped[1].as<qd_rec>(), p->cs);
+        if (rc != QD_OK) return pfail(p, rc, std::string("clip: ") + qd_last_error(p->ctx));
+        for (int k = 0; k < 2; ++k) ins[k] = p->clipped[k].as<qd_rec>();
+    }
+    // opt-in 3' trimming of the insert reads (qd_trim_set): trimmed copies of the two tables
     if (qd_trim_active(p->ctx)) {
         for (int k = 0; k < 2; ++k) PCHK(p, p->trimmed[k].need((size_t)n * sizeof(qd_rec) + 64, 0, p->cs));
         const int rc = qd_trim_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p, ins[1], n,
@@ -2588,7 +2600,7 @@ int qd_pipe_destroy(qd_pipe* p) {
     p->gz = nullptr;
     for (DevBuf* b : {&p->d_res, &p->rows_seq[0], &p->rows_seq[1], &p->rows_qual[0], &p->rows_qual[1], &p->rows_len[0], &p->rows_len[1], &p->codes, &p->mol,
                       &p->short_idx, &p->dest, &p->len1, &p->len2, &p->hist, &p->tmp, &p->perm, &p->sdest, &p->g1, &p->g2, &p->scan_tiles, &p->first, &p->g1_first,
-                      &p->g2_first, &p->subs, &p->first_sub, &p->ranges, &p->crc, &p->tokens, &p->sub_out, &p->sub_bytes, &p->base1, &p->base2, &p->trimmed[0], &p->trimmed[1], &p->pairtrimmed[0],
+                      &p->g2_first, &p->subs, &p->first_sub, &p->ranges, &p->crc, &p->tokens, &p->sub_out, &p->sub_bytes, &p->base1, &p->base2, &p->clipped[0], &p->clipped[1], &p->trimmed[0], &p->trimmed[1], &p->pairtrimmed[0],
                       &p->pairtrimmed[1], &p->drop})
         b->release();
     for (OutSet& o : p->out) {

@@ -47,6 +47,11 @@ class qd_rows(C.Structure):
     _fields_ = [("seq", C.c_void_p * 2), ("qual", C.c_void_p * 2), ("len", C.c_void_p * 2)]
 
 
+class qd_clip_params(C.Structure):
+    _fields_ = [("front_clip", C.c_int32 * 2), ("tail_clip", C.c_int32 * 2), ("window_size", C.c_int32), ("window_quality", C.c_int32),
+                ("poly_g_min_length", C.c_int32), ("min_length", C.c_int32)]
+
+
 class qd_trim_params(C.Structure):
     _fields_ = [("adapter_r1", C.c_uint8 * 64), ("adapter_r2", C.c_uint8 * 64), ("adapter_r1_len", C.c_int32), ("adapter_r2_len", C.c_int32),
                 ("quality_cutoff", C.c_int32), ("min_overlap", C.c_int32), ("max_mismatch_pct", C.c_int32), ("min_length", C.c_int32)]
@@ -121,6 +126,10 @@ SYMBOLS = [
     ("qd_qstats_read", C.c_int, [_P, _P, C.c_int64]),
     ("qd_qstats_add", C.c_int, [_P, _P, C.c_int64]),
     ("qd_qstats_kind", C.c_int, [_P]),
+    ("qd_clip_set", C.c_int, [_P, C.POINTER(qd_clip_params)]),
+    ("qd_clip_get", C.c_int, [_P, C.POINTER(qd_clip_params)]),
+    ("qd_clip_read", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_clip_add", C.c_int, [_P, _P, C.c_int64]),
     ("qd_trim_set", C.c_int, [_P, C.POINTER(qd_trim_params)]),
     ("qd_trim_get", C.c_int, [_P, C.POINTER(qd_trim_params)]),
     ("qd_trim_read", C.c_int, [_P, _P, C.c_int64]),
@@ -217,6 +226,7 @@ SYMBOLS = [
     ("qd_dev_gunzip", C.c_int, [C.c_int, _P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
     ("qd_dev_sort_by_dest", C.c_int, [C.c_int, _P, C.c_int64, C.c_int32, _P, _P, _P]),
     ("qd_dev_qstats", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P]),
+    ("qd_dev_clip", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_trim", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_pairtrim", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_filter", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
@@ -473,6 +483,23 @@ def unpack_qstats(blob):
     return np.frombuffer(blob, dtype=np.uint64, offset=8).reshape(n_dest, 2, len(QSTATS_COUNTERS)).copy()
 
 
+CLIP_COUNTERS = ("reads", "bases_in", "bases_out", "front_clipped_reads", "front_clipped_bases", "tail_clipped_reads", "tail_clipped_bases",
+                 "window_reads", "window_bases", "polyg_reads", "polyg_bases", "floored_reads")  # per read R1 / R2 (qd_clip_*)
+
+
+def pack_clip(table):
+    """One context's or rank's clip counters (uint64[2, 12]) as bytes (the ranks' exchange through the rendezvous directory);
+    unpack_clip reverses it."""
+    table = np.ascontiguousarray(table, dtype=np.uint64).reshape(2, len(CLIP_COUNTERS))
+    return table.tobytes()
+
+
+def unpack_clip(blob):
+    """-> uint64[2, 12] (a copy: tables are summed in place)"""
+    assert len(blob) == 2 * len(CLIP_COUNTERS) * 8, "clip counters of the wrong size"
+    return np.frombuffer(blob, dtype=np.uint64).reshape(2, len(CLIP_COUNTERS)).copy()
+
+
 TRIM_COUNTERS = ("reads", "bases_in", "bases_out", "quality_trimmed_reads", "quality_trimmed_bases", "adapter_reads", "adapter_bases",
                  "floored_reads")  # per read R1 / R2 (qd_trim_*)
 
@@ -718,6 +745,53 @@ class Engine(object):
             raise ValueError("recs1, recs2 and codes must have one entry per pair")
         self._chk(self.lib.qd_dev_qstats(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]),
                                          codes.size, _ptr(codes)))
+
+    def clip_set(self, front_clip_r1=0, front_clip_r2=0, tail_clip_r1=0, tail_clip_r2=0, window_size=0, window_quality=0,
+                 poly_g_min_length=0, min_length=0):
+        """End clipping, window and poly-G trimming of the insert reads in the device pipeline, in front of trim_set's stage
+        (qd_clip_set; conf.CLIP_HELP has the rules).  Every rule off (the defaults) turns the stage off and frees the counters; a
+        value out of range is QD_ERR_INVALID and changes nothing."""
+        P = qd_clip_params()
+        P.front_clip[0], P.front_clip[1], P.tail_clip[0], P.tail_clip[1] = int(front_clip_r1), int(front_clip_r2), int(tail_clip_r1), int(tail_clip_r2)
+        P.window_size, P.window_quality, P.poly_g_min_length, P.min_length = int(window_size), int(window_quality), int(poly_g_min_length), int(min_length)
+        self._chk(self.lib.qd_clip_set(self._h, C.byref(P)))
+
+    def clip_get(self):
+        """The parameters in force, as clip_set's keywords (the stage off: all zero)."""
+        P = qd_clip_params()
+        self._chk(self.lib.qd_clip_get(self._h, C.byref(P)))
+        return dict(front_clip_r1=P.front_clip[0], front_clip_r2=P.front_clip[1], tail_clip_r1=P.tail_clip[0], tail_clip_r2=P.tail_clip[1],
+                    window_size=P.window_size, window_quality=P.window_quality, poly_g_min_length=P.poly_g_min_length, min_length=P.min_length)
+
+    def clip_active(self):
+        """whether the stage is on: what the pipeline asks before every batch (qd_clip_active, an internal entry of the library)"""
+        f = self.lib.qd_clip_active
+        f.restype, f.argtypes = C.c_int, [_P]
+        return bool(f(self._h))
+
+    def clip_read(self):
+        """numpy uint64[2, 12]: [R1, R2][CLIP_COUNTERS]"""
+        out = np.zeros((2, len(CLIP_COUNTERS)), dtype=np.uint64)
+        self._chk(self.lib.qd_clip_read(self._h, _ptr(out), out.size))
+        return out
+
+    def clip_add(self, table):
+        """Another context's counters (clip_read's layout) join this context's (qd_clip_add)."""
+        table = np.ascontiguousarray(table, dtype=np.uint64)
+        self._chk(self.lib.qd_clip_add(self._h, _ptr(table), table.size))
+
+    def dev_clip(self, text1, recs1, text2, recs2):
+        """The clip stage over host buffers (qd_dev_clip): texts as bytes or uint8 arrays, recs uint32[n, 6] in dev_fastq_scan's
+        layout; -> the two tables as the stage leaves them (seq, qual and seq_len change); adds to the context's counters."""
+        t = [np.frombuffer(bytes(x), dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, dtype=np.uint8)
+             for x in (text1, text2)]
+        r = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, 6) for x in (recs1, recs2)]
+        if r[0].shape[0] != r[1].shape[0]:
+            raise ValueError("recs1 and recs2 must have one entry per pair")
+        out = [np.zeros_like(x) for x in r]
+        self._chk(self.lib.qd_dev_clip(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), r[0].shape[0],
+                                       _ptr(out[0]), _ptr(out[1])))
+        return out[0], out[1]
 
     def trim_set(self, adapter_r1="", adapter_r2="", quality_cutoff=0, min_overlap=3, max_mismatch_pct=10, min_length=0):
         """3' trimming of the insert reads in the device pipeline (qd_trim_set; conf.TRIM_HELP has the rules).  Neither an adapter

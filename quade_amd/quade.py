@@ -171,7 +171,9 @@ class Quade(object):
                     eng.qstats_enable(True)
                 if cf.cycle_report:  # ... and per cycle, by pass / fail / Undetermined
                     eng.cstats_enable(True)
-                if cf.trim:  # the insert reads are trimmed at their 3' end while the pipeline holds their text
+                if cf.clip:  # the insert reads are clipped (ends, window, poly-G) while the pipeline holds their text
+                    eng.clip_set(**cf.clip_params())
+                if cf.trim:  # ... trimmed at their 3' end while the pipeline holds their text
                     eng.trim_set(**cf.trim_params())
                 if cf.pair_trim:  # ... and R1 and R2 of a pair together, behind it
                     eng.pairtrim_set(**cf.pair_trim_params())
@@ -204,6 +206,7 @@ class Quade(object):
         unknown = self._collect_unknown() if cf.top_unknown_barcodes > 0 else None
         quality = self._collect_quality() if cf.quality_report else None
         cycles = self._collect_cycles() if cf.cycle_report else None
+        clipped = self._collect_clip() if cf.clip else None
         trimmed = self._collect_trim() if cf.trim else None
         pair_trimmed = self._collect_pair_trim() if cf.pair_trim else None
         filtered = self._collect_filter() if cf.filter else None
@@ -251,6 +254,9 @@ class Quade(object):
         if cycles is not None:
             from . import cycle_report
             cycle_report.write_report(os.path.join(self.outdir, cycle_report.REPORT_NAME), cycles)
+        if clipped is not None:
+            from . import clip_report
+            clip_report.write_report(os.path.join(self.outdir, clip_report.REPORT_NAME), clipped, cf.clip_params())
         if trimmed is not None:
             from . import trim_report
             trim_report.write_report(os.path.join(self.outdir, trim_report.REPORT_NAME), trimmed, cf.trim_params())
@@ -341,6 +347,22 @@ class Quade(object):
         if self.world > 1:
             got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, "quality", hb.pack_qstats(table))
             tables = [hb.unpack_qstats(b) for b in got]
+            table = tables[0]
+            for t in tables[1:]:
+                table = table + t
+        return table
+
+    def _collect_clip(self):
+        """[trim] clipping: the counters of every context of this process summed (chunk workers, devices); with several ranks every
+        rank publishes its sum in the rendezvous directory and adds all of them (rank 0 writes the file).  Returns uint64[2, 12]."""
+        from . import dist
+        table = None
+        for eng in self.engines:
+            t = eng.clip_read()
+            table = t if table is None else table + t
+        if self.world > 1:
+            got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, "clip", hb.pack_clip(table))
+            tables = [hb.unpack_clip(b) for b in got]
             table = tables[0]
             for t in tables[1:]:
                 table = table + t
