@@ -353,6 +353,154 @@ hipError_t uk_malloc(void** p, size_t bytes) {
     return e;
 }
 
+// ---- the read stages (qstats, cstats, clip, trim, pairtrim, filter): their tables and the harness of their qd_dev_* entries ----
+
+// a stage's table: n_values 64-bit counters on the device, zero
+int table_alloc(qd_ctx* c, u64*& t, size_t n_values, const char* what) {
+    hipError_t e = uk_malloc(reinterpret_cast<void**>(&t), n_values * 8);
+    if (e != hipSuccess) {
+        t = nullptr;
+        return fail(c, QD_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    }
+    HIPCHK(c, hipMemsetAsync(t, 0, n_values * 8, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return QD_OK;
+}
+
+// (the caller waited for the context's work)
+void table_free(u64*& t) {
+    if (t) (void)hipFree(t);
+    t = nullptr;
+}
+
+// qd_*_read: off_text when the stage is off (t == nullptr), size_text when n_values is not the table's n_expected
+int table_read(qd_ctx* c, const u64* t, size_t n_expected, uint64_t* out, int64_t n_values, const char* off_text, const char* size_text) {
+    if (!out) return QD_ERR_INVALID;
+    if (!t) return fail(c, QD_ERR_STATE, off_text);
+    if (n_values != (int64_t)n_expected) return fail(c, QD_ERR_INVALID, size_text);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));
+    HIPCHK(c, hipMemcpy(out, t, n_expected * 8, hipMemcpyDeviceToHost));
+    return QD_OK;
+}
+
+// qd_*_add: another context's table joins this one
+int table_add(qd_ctx* c, u64* t, size_t n_expected, const uint64_t* values, int64_t n_values, const char* off_text, const char* size_text) {
+    if (!values) return QD_ERR_INVALID;
+    if (!t) return fail(c, QD_ERR_STATE, off_text);
+    if (n_values != (int64_t)n_expected) return fail(c, QD_ERR_INVALID, size_text);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));  // the kernels add to the table: nothing of this context may be in flight
+    std::vector<u64> h(n_expected);
+    HIPCHK(c, hipMemcpy(h.data(), t, h.size() * 8, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < h.size(); ++i) h[i] += values[i];
+    HIPCHK(c, hipMemcpy(t, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+    return QD_OK;
+}
+
+// the four pointers every qd_*_args begins with
+template <typename ARGS>
+void fill_pair_args(ARGS& a, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2) {
+    a.text[0] = text1;
+    a.text[1] = text2;
+    a.recs[0] = recs1;
+    a.recs[1] = recs2;
+}
+
+// What every qd_dev_* does around its stage: a batch in host memory is checked, copied to scratch on the device, and after the
+// stage what it wrote comes back; the scratch is freed with the object.
+//     PairUpload up(c);
+//     rc = up.open(...);  if (rc != QD_OK || up.empty()) return rc;
+//     return up.close(qd_<stage>_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), ..., QD_STREAM_CONTEXT));
+class PairUpload {
+public:
+    enum { CODES = 1, OUT_RECS = 2, REASONS = 4 };  // what the stage needs besides the texts and record tables
+
+    explicit PairUpload(qd_ctx* ctx) : c(ctx) {}
+
+    // Every size, range and code is checked here, before anything is allocated: a bad table cannot become a bad address.  want:
+    // which of codes, out_recs1 / out_recs2 and reasons must be given; drop is uploaded when it is.
+    int open(const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2, const uint32_t* recs2,
+             int64_t n_pairs, int want, const uint16_t* codes, const uint8_t* drop, uint32_t* out_recs1, uint32_t* out_recs2, uint8_t* reasons) {
+        const int64_t len[2] = {len1, len2};
+        const uint8_t* text[2] = {text1, text2};
+        const uint32_t* recs[2] = {recs1, recs2};
+        if (n_pairs < 0 || n_pairs > 0x7FFFFFFF || len1 < 0 || len2 < 0 || len1 > ((int64_t)1 << 30) || len2 > ((int64_t)1 << 30))
+            return fail(c, QD_ERR_INVALID, "bad sizes");
+        if (n_pairs == 0) return QD_OK;
+        if (!recs1 || !recs2 || ((want & CODES) && !codes) || ((want & OUT_RECS) && (!out_recs1 || !out_recs2)) || ((want & REASONS) && !reasons) ||
+            (!text1 && len1) || (!text2 && len2))
+            return fail(c, QD_ERR_INVALID, "null argument");
+        static_assert(sizeof(qd_rec) == 6 * sizeof(uint32_t), "qd_dev_fastq_scan's record layout");
+        for (int r = 0; r < 2; ++r)
+            for (int64_t j = 0; j < n_pairs; ++j) {
+                const qd_rec* q = reinterpret_cast<const qd_rec*>(recs[r]) + j;
+                if ((int64_t)q->seq + q->seq_len > len[r] || (int64_t)q->qual + q->seq_len > len[r])
+                    return fail(c, QD_ERR_INVALID, "a record's sequence or quality line reaches beyond its text");
+            }
+        for (int64_t j = 0; (want & CODES) && j < n_pairs; ++j)
+            if (codes[j] != QD_CODE_UNDETERMINED && (int)codes[j] >= 2 * c->S) return fail(c, QD_ERR_INVALID, "a routing code is not below 2*S");
+        HIPCHK(c, hipSetDevice(c->device));
+        const size_t rec_bytes = (size_t)n_pairs * sizeof(qd_rec);
+        // the texts start 3 bytes into their buffers: the kernels' aligned words must not depend on an aligned window (and reach up to
+        // 15 bytes beyond a line: 32 bytes of slack)
+        for (int r = 0; r < 2; ++r) {
+            HIPCHK(c, uk_malloc(&d_text[r].p, (size_t)len[r] + 32));
+            HIPCHK(c, uk_malloc(&d_recs[r].p, rec_bytes));
+            if (want & OUT_RECS) HIPCHK(c, uk_malloc(&d_out[r].p, rec_bytes));
+            if (len[r]) HIPCHK(c, hipMemcpyAsync(static_cast<uint8_t*>(d_text[r].p) + 3, text[r], (size_t)len[r], hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(d_recs[r].p, recs[r], rec_bytes, hipMemcpyHostToDevice, c->stream));
+        }
+        if (want & CODES) {
+            HIPCHK(c, uk_malloc(&d_codes.p, (size_t)n_pairs * 2));
+            HIPCHK(c, hipMemcpyAsync(d_codes.p, codes, (size_t)n_pairs * 2, hipMemcpyHostToDevice, c->stream));
+        }
+        if (drop) {
+            HIPCHK(c, uk_malloc(&d_drop.p, (size_t)n_pairs));
+            HIPCHK(c, hipMemcpyAsync(d_drop.p, drop, (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
+        }
+        if (want & REASONS) HIPCHK(c, uk_malloc(&d_reason.p, (size_t)n_pairs));
+        pairs = n_pairs;
+        h_out[0] = out_recs1;
+        h_out[1] = out_recs2;
+        h_reason = reasons;
+        return QD_OK;
+    }
+    bool empty() const { return pairs == 0; }  // open() found no pairs: nothing was uploaded, there is nothing to launch
+
+    uint32_t n() const { return (uint32_t)pairs; }
+    const uint8_t* text(int r) const { return static_cast<const uint8_t*>(d_text[r].p) + 3; }
+    const qd_rec* recs(int r) const { return static_cast<const qd_rec*>(d_recs[r].p); }
+    const uint16_t* codes() const { return static_cast<const uint16_t*>(d_codes.p); }
+    const uint8_t* drop() const { return static_cast<const uint8_t*>(d_drop.p); }  // nullptr when none was given
+    qd_rec* out(int r) const { return static_cast<qd_rec*>(d_out[r].p); }
+    uint8_t* reason() const { return static_cast<uint8_t*>(d_reason.p); }
+
+    // behind the stage, which returned rc: what it wrote goes to the host when it succeeded, and the stream is waited for
+    int close(int rc) {
+        if (rc == QD_OK) {
+            for (int r = 0; r < 2; ++r)
+                if (d_out[r].p) HIPCHK(c, hipMemcpyAsync(h_out[r], d_out[r].p, (size_t)pairs * sizeof(qd_rec), hipMemcpyDeviceToHost, c->stream));
+            if (d_reason.p) HIPCHK(c, hipMemcpyAsync(h_reason, d_reason.p, (size_t)pairs, hipMemcpyDeviceToHost, c->stream));
+        }
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // the scratch is freed on return
+        return rc;
+    }
+
+private:
+    struct Dev {
+        void* p = nullptr;
+        ~Dev() {
+            if (p) (void)hipFree(p);
+        }
+    };
+    qd_ctx* c;
+    int64_t pairs = 0;
+    Dev d_text[2], d_recs[2], d_codes, d_drop, d_out[2], d_reason;
+    uint32_t* h_out[2] = {nullptr, nullptr};
+    uint8_t* h_reason = nullptr;
+};
+
 // the tally off and its memory freed (the caller waited for the context's work)
 void free_unknown(qd_ctx* c) {
     if (c->d_uk) (void)hipFree(c->d_uk);
@@ -419,44 +567,38 @@ int launch_unknown(qd_ctx* c, int64_t n, const qd_rows* rows, const uint16_t* co
 
 // the quality counters off and their table freed (the caller waited for the context's work)
 void free_qstats(qd_ctx* c) {
-    if (c->d_qs) (void)hipFree(c->d_qs);
-    c->d_qs = nullptr;
+    table_free(c->d_qs);
 }
 
 // the per-cycle counters off and their table freed (the caller waited for the context's work)
 void free_cstats(qd_ctx* c) {
-    if (c->d_cs) (void)hipFree(c->d_cs);
-    c->d_cs = nullptr;
+    table_free(c->d_cs);
 }
 
 // clipping off and its table freed (the caller waited for the context's work)
 void free_clip(qd_ctx* c) {
-    if (c->d_clip) (void)hipFree(c->d_clip);
-    c->d_clip = nullptr;
+    table_free(c->d_clip);
     c->clip = qd_clip_params{};
     c->clip_dev = qd_clip_dev{};
 }
 
 // trimming off and its table freed (the caller waited for the context's work)
 void free_trim(qd_ctx* c) {
-    if (c->d_trim) (void)hipFree(c->d_trim);
-    c->d_trim = nullptr;
+    table_free(c->d_trim);
     c->trim = qd_trim_params{};
     c->trim_dev = qd_trim_dev{};
 }
 
 // overlap trimming off and its table freed (the caller waited for the context's work)
 void free_pairtrim(qd_ctx* c) {
-    if (c->d_pairtrim) (void)hipFree(c->d_pairtrim);
-    c->d_pairtrim = nullptr;
+    table_free(c->d_pairtrim);
     c->pairtrim = qd_pairtrim_params{};
     c->pairtrim_dev = qd_pairtrim_dev{};
 }
 
 // read filtering off and its table freed (the caller waited for the context's work)
 void free_filter(qd_ctx* c) {
-    if (c->d_filter) (void)hipFree(c->d_filter);
-    c->d_filter = nullptr;
+    table_free(c->d_filter);
     c->filter = qd_filter_params{-1, -1, -1, 15, -1, -1};
     c->filter_dev = qd_filter_dev{-1, -1, -1, 33 + 15, -1, -1};
 }
@@ -1024,15 +1166,7 @@ int qd_qstats_enable(qd_ctx* c, int32_t on) {
     HIPCHK(c, wait_all(c));  // nothing of this context may still add to the old table
     free_qstats(c);
     if (!on) return QD_OK;
-    const size_t bytes = qd_qstats_values((uint32_t)c->S) * 8;
-    hipError_t e = uk_malloc(reinterpret_cast<void**>(&c->d_qs), bytes);
-    if (e != hipSuccess) {
-        c->d_qs = nullptr;
-        return fail(c, QD_ERR_HIP, std::string("quality counters: ") + hipGetErrorString(e));
-    }
-    HIPCHK(c, hipMemsetAsync(c->d_qs, 0, bytes, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return QD_OK;
+    return table_alloc(c, c->d_qs, qd_qstats_values((uint32_t)c->S), "quality counters");
 }
 
 int qd_qstats_kind(const qd_ctx* c) {
@@ -1042,26 +1176,13 @@ int qd_qstats_kind(const qd_ctx* c) {
 }
 
 int qd_qstats_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
-    if (!c || !out) return QD_ERR_INVALID;
-    if (!c->d_qs) return fail(c, QD_ERR_STATE, "the quality counters are not enabled");
-    if (n_values != (int64_t)qd_qstats_values((uint32_t)c->S)) return fail(c, QD_ERR_INVALID, "n_values must be (2*S+1)*12");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));
-    HIPCHK(c, hipMemcpy(out, c->d_qs, (size_t)n_values * 8, hipMemcpyDeviceToHost));
-    return QD_OK;
+    if (!c) return QD_ERR_INVALID;
+    return table_read(c, c->d_qs, qd_qstats_values((uint32_t)c->S), out, n_values, "the quality counters are not enabled", "n_values must be (2*S+1)*12");
 }
 
 int qd_qstats_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
-    if (!c || !values) return QD_ERR_INVALID;
-    if (!c->d_qs) return fail(c, QD_ERR_STATE, "the quality counters are not enabled");
-    if (n_values != (int64_t)qd_qstats_values((uint32_t)c->S)) return fail(c, QD_ERR_INVALID, "n_values must be (2*S+1)*12");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));  // the kernels add to the table: nothing of this context may be in flight
-    std::vector<u64> h((size_t)n_values);
-    HIPCHK(c, hipMemcpy(h.data(), c->d_qs, h.size() * 8, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < h.size(); ++i) h[i] += values[i];
-    HIPCHK(c, hipMemcpy(c->d_qs, h.data(), h.size() * 8, hipMemcpyHostToDevice));
-    return QD_OK;
+    if (!c) return QD_ERR_INVALID;
+    return table_add(c, c->d_qs, qd_qstats_values((uint32_t)c->S), values, n_values, "the quality counters are not enabled", "n_values must be (2*S+1)*12");
 }
 
 int qd_qstats_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
@@ -1070,10 +1191,7 @@ int qd_qstats_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const
     if (!c->d_qs || !n) return QD_OK;
     hipStream_t st = resolve_stream(c, stream);
     qd_qstats_args a{};
-    a.text[0] = text1;
-    a.text[1] = text2;
-    a.recs[0] = recs1;
-    a.recs[1] = recs2;
+    fill_pair_args(a, text1, recs1, text2, recs2);
     a.codes = codes;
     a.drop = drop;
     a.table = c->d_qs;
@@ -1087,43 +1205,10 @@ int qd_dev_qstats(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t*
                   const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes) {
     if (!c) return QD_ERR_INVALID;
     if (!c->d_qs) return fail(c, QD_ERR_STATE, "the quality counters are not enabled");
-    const int64_t len[2] = {len1, len2};
-    const uint8_t* text[2] = {text1, text2};
-    const uint32_t* recs[2] = {recs1, recs2};
-    if (n_pairs < 0 || n_pairs > 0x7FFFFFFF || len1 < 0 || len2 < 0 || len1 > ((int64_t)1 << 30) || len2 > ((int64_t)1 << 30))
-        return fail(c, QD_ERR_INVALID, "bad sizes");
-    if (n_pairs == 0) return QD_OK;
-    if (!recs1 || !recs2 || !codes || (!text1 && len1) || (!text2 && len2)) return fail(c, QD_ERR_INVALID, "null argument");
-    static_assert(sizeof(qd_rec) == 6 * sizeof(uint32_t), "qd_dev_fastq_scan's record layout");
-    // every range and every code is checked here: a bad table cannot become a bad address
-    for (int r = 0; r < 2; ++r)
-        for (int64_t j = 0; j < n_pairs; ++j) {
-            const qd_rec* q = reinterpret_cast<const qd_rec*>(recs[r]) + j;
-            if ((int64_t)q->seq + q->seq_len > len[r] || (int64_t)q->qual + q->seq_len > len[r])
-                return fail(c, QD_ERR_INVALID, "a record's sequence or quality line reaches beyond its text");
-        }
-    for (int64_t j = 0; j < n_pairs; ++j)
-        if (codes[j] != QD_CODE_UNDETERMINED && (int)codes[j] >= 2 * c->S) return fail(c, QD_ERR_INVALID, "a routing code is not below 2*S");
-    HIPCHK(c, hipSetDevice(c->device));
-    struct Dev {
-        void* p = nullptr;
-        ~Dev() {
-            if (p) (void)hipFree(p);
-        }
-    } d_text[2], d_recs[2], d_codes;
-    // the texts start 3 bytes into their buffers: the kernel's aligned words must not depend on an aligned window
-    for (int r = 0; r < 2; ++r) {
-        HIPCHK(c, uk_malloc(&d_text[r].p, (size_t)len[r] + 32));
-        HIPCHK(c, uk_malloc(&d_recs[r].p, (size_t)n_pairs * sizeof(qd_rec)));
-        if (len[r]) HIPCHK(c, hipMemcpyAsync(static_cast<uint8_t*>(d_text[r].p) + 3, text[r], (size_t)len[r], hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_recs[r].p, recs[r], (size_t)n_pairs * sizeof(qd_rec), hipMemcpyHostToDevice, c->stream));
-    }
-    HIPCHK(c, uk_malloc(&d_codes.p, (size_t)n_pairs * 2));
-    HIPCHK(c, hipMemcpyAsync(d_codes.p, codes, (size_t)n_pairs * 2, hipMemcpyHostToDevice, c->stream));
-    const int rc = qd_qstats_device(c, static_cast<uint8_t*>(d_text[0].p) + 3, static_cast<qd_rec*>(d_recs[0].p), static_cast<uint8_t*>(d_text[1].p) + 3,
-                                    static_cast<qd_rec*>(d_recs[1].p), (uint32_t)n_pairs, static_cast<uint16_t*>(d_codes.p), nullptr, QD_STREAM_CONTEXT);
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // the scratch is freed on return
-    return rc;
+    PairUpload up(c);
+    const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::CODES, codes, nullptr, nullptr, nullptr, nullptr);
+    if (rc != QD_OK || up.empty()) return rc;
+    return up.close(qd_qstats_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), up.codes(), nullptr, QD_STREAM_CONTEXT));
 }
 
 int qd_cstats_enable(qd_ctx* c, int32_t on) {
@@ -1132,40 +1217,19 @@ int qd_cstats_enable(qd_ctx* c, int32_t on) {
     HIPCHK(c, wait_all(c));  // nothing of this context may still add to the old table
     free_cstats(c);
     if (!on) return QD_OK;
-    const size_t bytes = (size_t)QD_CS_VALUES * 8;
-    hipError_t e = uk_malloc(reinterpret_cast<void**>(&c->d_cs), bytes);
-    if (e != hipSuccess) {
-        c->d_cs = nullptr;
-        return fail(c, QD_ERR_HIP, std::string("cycle counters: ") + hipGetErrorString(e));
-    }
-    HIPCHK(c, hipMemsetAsync(c->d_cs, 0, bytes, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return QD_OK;
+    return table_alloc(c, c->d_cs, QD_CS_VALUES, "cycle counters");
 }
 
 int qd_cstats_lds_cycles(void) { return (int)QD_CS_LDS_CYCLES; }
 
 int qd_cstats_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
-    if (!c || !out) return QD_ERR_INVALID;
-    if (!c->d_cs) return fail(c, QD_ERR_STATE, "the cycle counters are not enabled");
-    if (n_values != (int64_t)QD_CS_VALUES) return fail(c, QD_ERR_INVALID, "n_values must be QD_CS_VALUES");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));
-    HIPCHK(c, hipMemcpy(out, c->d_cs, (size_t)n_values * 8, hipMemcpyDeviceToHost));
-    return QD_OK;
+    if (!c) return QD_ERR_INVALID;
+    return table_read(c, c->d_cs, QD_CS_VALUES, out, n_values, "the cycle counters are not enabled", "n_values must be QD_CS_VALUES");
 }
 
 int qd_cstats_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
-    if (!c || !values) return QD_ERR_INVALID;
-    if (!c->d_cs) return fail(c, QD_ERR_STATE, "the cycle counters are not enabled");
-    if (n_values != (int64_t)QD_CS_VALUES) return fail(c, QD_ERR_INVALID, "n_values must be QD_CS_VALUES");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));  // the kernel adds to the table: nothing of this context may be in flight
-    std::vector<u64> h((size_t)n_values);
-    HIPCHK(c, hipMemcpy(h.data(), c->d_cs, h.size() * 8, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < h.size(); ++i) h[i] += values[i];
-    HIPCHK(c, hipMemcpy(c->d_cs, h.data(), h.size() * 8, hipMemcpyHostToDevice));
-    return QD_OK;
+    if (!c) return QD_ERR_INVALID;
+    return table_add(c, c->d_cs, QD_CS_VALUES, values, n_values, "the cycle counters are not enabled", "n_values must be QD_CS_VALUES");
 }
 
 int qd_cstats_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
@@ -1174,10 +1238,7 @@ int qd_cstats_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const
     if (!c->d_cs || !n) return QD_OK;
     hipStream_t st = resolve_stream(c, stream);
     qd_cstats_args a{};
-    a.text[0] = text1;
-    a.text[1] = text2;
-    a.recs[0] = recs1;
-    a.recs[1] = recs2;
+    fill_pair_args(a, text1, recs1, text2, recs2);
     a.codes = codes;
     a.drop = drop;
     a.table = c->d_cs;
@@ -1191,47 +1252,10 @@ int qd_dev_cstats(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t*
                   const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes, const uint8_t* drop) {
     if (!c) return QD_ERR_INVALID;
     if (!c->d_cs) return fail(c, QD_ERR_STATE, "the cycle counters are not enabled");
-    const int64_t len[2] = {len1, len2};
-    const uint8_t* text[2] = {text1, text2};
-    const uint32_t* recs[2] = {recs1, recs2};
-    if (n_pairs < 0 || n_pairs > 0x7FFFFFFF || len1 < 0 || len2 < 0 || len1 > ((int64_t)1 << 30) || len2 > ((int64_t)1 << 30))
-        return fail(c, QD_ERR_INVALID, "bad sizes");
-    if (n_pairs == 0) return QD_OK;
-    if (!recs1 || !recs2 || !codes || (!text1 && len1) || (!text2 && len2)) return fail(c, QD_ERR_INVALID, "null argument");
-    // every range and every code is checked here: a bad table cannot become a bad address
-    for (int r = 0; r < 2; ++r)
-        for (int64_t j = 0; j < n_pairs; ++j) {
-            const qd_rec* q = reinterpret_cast<const qd_rec*>(recs[r]) + j;
-            if ((int64_t)q->seq + q->seq_len > len[r] || (int64_t)q->qual + q->seq_len > len[r])
-                return fail(c, QD_ERR_INVALID, "a record's sequence or quality line reaches beyond its text");
-        }
-    for (int64_t j = 0; j < n_pairs; ++j)
-        if (codes[j] != QD_CODE_UNDETERMINED && (int)codes[j] >= 2 * c->S) return fail(c, QD_ERR_INVALID, "a routing code is not below 2*S");
-    HIPCHK(c, hipSetDevice(c->device));
-    struct Dev {
-        void* p = nullptr;
-        ~Dev() {
-            if (p) (void)hipFree(p);
-        }
-    } d_text[2], d_recs[2], d_codes, d_drop;
-    // the texts start 3 bytes into their buffers: the kernel's aligned words must not depend on an aligned window
-    for (int r = 0; r < 2; ++r) {
-        HIPCHK(c, uk_malloc(&d_text[r].p, (size_t)len[r] + 32));
-        HIPCHK(c, uk_malloc(&d_recs[r].p, (size_t)n_pairs * sizeof(qd_rec)));
-        if (len[r]) HIPCHK(c, hipMemcpyAsync(static_cast<uint8_t*>(d_text[r].p) + 3, text[r], (size_t)len[r], hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_recs[r].p, recs[r], (size_t)n_pairs * sizeof(qd_rec), hipMemcpyHostToDevice, c->stream));
-    }
-    HIPCHK(c, uk_malloc(&d_codes.p, (size_t)n_pairs * 2));
-    HIPCHK(c, hipMemcpyAsync(d_codes.p, codes, (size_t)n_pairs * 2, hipMemcpyHostToDevice, c->stream));
-    if (drop) {
-        HIPCHK(c, uk_malloc(&d_drop.p, (size_t)n_pairs));
-        HIPCHK(c, hipMemcpyAsync(d_drop.p, drop, (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
-    }
-    const int rc = qd_cstats_device(c, static_cast<uint8_t*>(d_text[0].p) + 3, static_cast<qd_rec*>(d_recs[0].p), static_cast<uint8_t*>(d_text[1].p) + 3,
-                                    static_cast<qd_rec*>(d_recs[1].p), (uint32_t)n_pairs, static_cast<uint16_t*>(d_codes.p),
-                                    static_cast<uint8_t*>(d_drop.p), QD_STREAM_CONTEXT);
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // the scratch is freed on return
-    return rc;
+    PairUpload up(c);
+    const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::CODES, codes, drop, nullptr, nullptr, nullptr);
+    if (rc != QD_OK || up.empty()) return rc;
+    return up.close(qd_cstats_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), up.codes(), up.drop(), QD_STREAM_CONTEXT));
 }
 
 static_assert(QD_CLIP_VALUES == QD_CLIP_TABLE, "the public table size is the kernel's");
@@ -1265,13 +1289,8 @@ int qd_clip_set(qd_ctx* c, const qd_clip_params* params) {
     HIPCHK(c, wait_all(c));  // nothing of this context may still read the old parameters or add to the old table
     free_clip(c);
     if (!on) return QD_OK;
-    hipError_t e = uk_malloc(reinterpret_cast<void**>(&c->d_clip), QD_CLIP_TABLE * 8);
-    if (e != hipSuccess) {
-        c->d_clip = nullptr;
-        return fail(c, QD_ERR_HIP, std::string("clip counters: ") + hipGetErrorString(e));
-    }
-    HIPCHK(c, hipMemsetAsync(c->d_clip, 0, QD_CLIP_TABLE * 8, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int rc = table_alloc(c, c->d_clip, QD_CLIP_TABLE, "clip counters");
+    if (rc != QD_OK) return rc;
     c->clip = P;
     c->clip_dev = D;
     return QD_OK;
@@ -1286,26 +1305,13 @@ int qd_clip_get(const qd_ctx* c, qd_clip_params* out) {
 int qd_clip_active(const qd_ctx* c) { return c && c->d_clip ? 1 : 0; }
 
 int qd_clip_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
-    if (!c || !out) return QD_ERR_INVALID;
-    if (!c->d_clip) return fail(c, QD_ERR_STATE, "clipping is not on");
-    if (n_values != QD_CLIP_TABLE) return fail(c, QD_ERR_INVALID, "n_values must be 24");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));
-    HIPCHK(c, hipMemcpy(out, c->d_clip, QD_CLIP_TABLE * 8, hipMemcpyDeviceToHost));
-    return QD_OK;
+    if (!c) return QD_ERR_INVALID;
+    return table_read(c, c->d_clip, QD_CLIP_TABLE, out, n_values, "clipping is not on", "n_values must be 24");
 }
 
 int qd_clip_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
-    if (!c || !values) return QD_ERR_INVALID;
-    if (!c->d_clip) return fail(c, QD_ERR_STATE, "clipping is not on");
-    if (n_values != QD_CLIP_TABLE) return fail(c, QD_ERR_INVALID, "n_values must be 24");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));  // the kernel adds to the table: nothing of this context may be in flight
-    u64 h[QD_CLIP_TABLE];
-    HIPCHK(c, hipMemcpy(h, c->d_clip, sizeof(h), hipMemcpyDeviceToHost));
-    for (int i = 0; i < QD_CLIP_TABLE; ++i) h[i] += values[i];
-    HIPCHK(c, hipMemcpy(c->d_clip, h, sizeof(h), hipMemcpyHostToDevice));
-    return QD_OK;
+    if (!c) return QD_ERR_INVALID;
+    return table_add(c, c->d_clip, QD_CLIP_TABLE, values, n_values, "clipping is not on", "n_values must be 24");
 }
 
 int qd_clip_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
@@ -1315,10 +1321,7 @@ int qd_clip_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const u
     if (!n) return QD_OK;
     hipStream_t st = resolve_stream(c, stream);
     qd_clip_args a{};
-    a.text[0] = text1;
-    a.text[1] = text2;
-    a.recs[0] = recs1;
-    a.recs[1] = recs2;
+    fill_pair_args(a, text1, recs1, text2, recs2);
     a.out[0] = out1;
     a.out[1] = out2;
     a.table = c->d_clip;
@@ -1332,44 +1335,11 @@ int qd_dev_clip(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* r
                 const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2) {
     if (!c) return QD_ERR_INVALID;
     if (!c->d_clip) return fail(c, QD_ERR_STATE, "clipping is not on");
-    const int64_t len[2] = {len1, len2};
-    const uint8_t* text[2] = {text1, text2};
-    const uint32_t* recs[2] = {recs1, recs2};
-    uint32_t* out[2] = {out_recs1, out_recs2};
-    if (n_pairs < 0 || n_pairs > 0x7FFFFFFF || len1 < 0 || len2 < 0 || len1 > ((int64_t)1 << 30) || len2 > ((int64_t)1 << 30))
-        return fail(c, QD_ERR_INVALID, "bad sizes");
-    if (n_pairs == 0) return QD_OK;
-    if (!recs1 || !recs2 || !out_recs1 || !out_recs2 || (!text1 && len1) || (!text2 && len2)) return fail(c, QD_ERR_INVALID, "null argument");
-    // every range is checked here: a bad table cannot become a bad address
-    for (int r = 0; r < 2; ++r)
-        for (int64_t j = 0; j < n_pairs; ++j) {
-            const qd_rec* q = reinterpret_cast<const qd_rec*>(recs[r]) + j;
-            if ((int64_t)q->seq + q->seq_len > len[r] || (int64_t)q->qual + q->seq_len > len[r])
-                return fail(c, QD_ERR_INVALID, "a record's sequence or quality line reaches beyond its text");
-        }
-    HIPCHK(c, hipSetDevice(c->device));
-    struct Dev {
-        void* p = nullptr;
-        ~Dev() {
-            if (p) (void)hipFree(p);
-        }
-    } d_text[2], d_recs[2], d_out[2];
-    const size_t rec_bytes = (size_t)n_pairs * sizeof(qd_rec);
-    // the texts start 3 bytes into their buffers: the kernel's aligned words must not depend on an aligned window
-    for (int r = 0; r < 2; ++r) {
-        HIPCHK(c, uk_malloc(&d_text[r].p, (size_t)len[r] + 32));
-        HIPCHK(c, uk_malloc(&d_recs[r].p, rec_bytes));
-        HIPCHK(c, uk_malloc(&d_out[r].p, rec_bytes));
-        if (len[r]) HIPCHK(c, hipMemcpyAsync(static_cast<uint8_t*>(d_text[r].p) + 3, text[r], (size_t)len[r], hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_recs[r].p, recs[r], rec_bytes, hipMemcpyHostToDevice, c->stream));
-    }
-    const int rc = qd_clip_device(c, static_cast<uint8_t*>(d_text[0].p) + 3, static_cast<qd_rec*>(d_recs[0].p), static_cast<uint8_t*>(d_text[1].p) + 3,
-                                  static_cast<qd_rec*>(d_recs[1].p), (uint32_t)n_pairs, static_cast<qd_rec*>(d_out[0].p), static_cast<qd_rec*>(d_out[1].p),
-                                  QD_STREAM_CONTEXT);
-    if (rc == QD_OK)
-        for (int r = 0; r < 2; ++r) HIPCHK(c, hipMemcpyAsync(out[r], d_out[r].p, rec_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // the scratch is freed on return
-    return rc;
+    PairUpload up(c);
+    const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::OUT_RECS, nullptr, nullptr, out_recs1, out_recs2,
+                           nullptr);
+    if (rc != QD_OK || up.empty()) return rc;
+    return up.close(qd_clip_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), up.out(0), up.out(1), QD_STREAM_CONTEXT));
 }
 
 int qd_trim_set(qd_ctx* c, const qd_trim_params* params) {
@@ -1409,13 +1379,8 @@ int qd_trim_set(qd_ctx* c, const qd_trim_params* params) {
     HIPCHK(c, wait_all(c));  // nothing of this context may still read the old parameters or add to the old table
     free_trim(c);
     if (!on) return QD_OK;
-    hipError_t e = uk_malloc(reinterpret_cast<void**>(&c->d_trim), QD_TRIM_VALUES * 8);
-    if (e != hipSuccess) {
-        c->d_trim = nullptr;
-        return fail(c, QD_ERR_HIP, std::string("trim counters: ") + hipGetErrorString(e));
-    }
-    HIPCHK(c, hipMemsetAsync(c->d_trim, 0, QD_TRIM_VALUES * 8, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int rc = table_alloc(c, c->d_trim, QD_TRIM_VALUES, "trim counters");
+    if (rc != QD_OK) return rc;
     c->trim = P;
     c->trim_dev = D;
     return QD_OK;
@@ -1430,26 +1395,13 @@ int qd_trim_get(const qd_ctx* c, qd_trim_params* out) {
 int qd_trim_active(const qd_ctx* c) { return c && c->d_trim ? 1 : 0; }
 
 int qd_trim_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
-    if (!c || !out) return QD_ERR_INVALID;
-    if (!c->d_trim) return fail(c, QD_ERR_STATE, "trimming is not on");
-    if (n_values != QD_TRIM_VALUES) return fail(c, QD_ERR_INVALID, "n_values must be 16");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));
-    HIPCHK(c, hipMemcpy(out, c->d_trim, QD_TRIM_VALUES * 8, hipMemcpyDeviceToHost));
-    return QD_OK;
+    if (!c) return QD_ERR_INVALID;
+    return table_read(c, c->d_trim, QD_TRIM_VALUES, out, n_values, "trimming is not on", "n_values must be 16");
 }
 
 int qd_trim_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
-    if (!c || !values) return QD_ERR_INVALID;
-    if (!c->d_trim) return fail(c, QD_ERR_STATE, "trimming is not on");
-    if (n_values != QD_TRIM_VALUES) return fail(c, QD_ERR_INVALID, "n_values must be 16");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));  // the kernel adds to the table: nothing of this context may be in flight
-    u64 h[QD_TRIM_VALUES];
-    HIPCHK(c, hipMemcpy(h, c->d_trim, sizeof(h), hipMemcpyDeviceToHost));
-    for (int i = 0; i < QD_TRIM_VALUES; ++i) h[i] += values[i];
-    HIPCHK(c, hipMemcpy(c->d_trim, h, sizeof(h), hipMemcpyHostToDevice));
-    return QD_OK;
+    if (!c) return QD_ERR_INVALID;
+    return table_add(c, c->d_trim, QD_TRIM_VALUES, values, n_values, "trimming is not on", "n_values must be 16");
 }
 
 int qd_trim_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
@@ -1459,10 +1411,7 @@ int qd_trim_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const u
     if (!n) return QD_OK;
     hipStream_t st = resolve_stream(c, stream);
     qd_trim_args a{};
-    a.text[0] = text1;
-    a.text[1] = text2;
-    a.recs[0] = recs1;
-    a.recs[1] = recs2;
+    fill_pair_args(a, text1, recs1, text2, recs2);
     a.out[0] = out1;
     a.out[1] = out2;
     a.table = c->d_trim;
@@ -1476,44 +1425,11 @@ int qd_dev_trim(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* r
                 const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2) {
     if (!c) return QD_ERR_INVALID;
     if (!c->d_trim) return fail(c, QD_ERR_STATE, "trimming is not on");
-    const int64_t len[2] = {len1, len2};
-    const uint8_t* text[2] = {text1, text2};
-    const uint32_t* recs[2] = {recs1, recs2};
-    uint32_t* out[2] = {out_recs1, out_recs2};
-    if (n_pairs < 0 || n_pairs > 0x7FFFFFFF || len1 < 0 || len2 < 0 || len1 > ((int64_t)1 << 30) || len2 > ((int64_t)1 << 30))
-        return fail(c, QD_ERR_INVALID, "bad sizes");
-    if (n_pairs == 0) return QD_OK;
-    if (!recs1 || !recs2 || !out_recs1 || !out_recs2 || (!text1 && len1) || (!text2 && len2)) return fail(c, QD_ERR_INVALID, "null argument");
-    // every range is checked here: a bad table cannot become a bad address
-    for (int r = 0; r < 2; ++r)
-        for (int64_t j = 0; j < n_pairs; ++j) {
-            const qd_rec* q = reinterpret_cast<const qd_rec*>(recs[r]) + j;
-            if ((int64_t)q->seq + q->seq_len > len[r] || (int64_t)q->qual + q->seq_len > len[r])
-                return fail(c, QD_ERR_INVALID, "a record's sequence or quality line reaches beyond its text");
-        }
-    HIPCHK(c, hipSetDevice(c->device));
-    struct Dev {
-        void* p = nullptr;
-        ~Dev() {
-            if (p) (void)hipFree(p);
-        }
-    } d_text[2], d_recs[2], d_out[2];
-    const size_t rec_bytes = (size_t)n_pairs * sizeof(qd_rec);
-    // the texts start 3 bytes into their buffers: the kernel's aligned words must not depend on an aligned window
-    for (int r = 0; r < 2; ++r) {
-        HIPCHK(c, uk_malloc(&d_text[r].p, (size_t)len[r] + 32));
-        HIPCHK(c, uk_malloc(&d_recs[r].p, rec_bytes));
-        HIPCHK(c, uk_malloc(&d_out[r].p, rec_bytes));
-        if (len[r]) HIPCHK(c, hipMemcpyAsync(static_cast<uint8_t*>(d_text[r].p) + 3, text[r], (size_t)len[r], hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_recs[r].p, recs[r], rec_bytes, hipMemcpyHostToDevice, c->stream));
-    }
-    const int rc = qd_trim_device(c, static_cast<uint8_t*>(d_text[0].p) + 3, static_cast<qd_rec*>(d_recs[0].p), static_cast<uint8_t*>(d_text[1].p) + 3,
-                                  static_cast<qd_rec*>(d_recs[1].p), (uint32_t)n_pairs, static_cast<qd_rec*>(d_out[0].p), static_cast<qd_rec*>(d_out[1].p),
-                                  QD_STREAM_CONTEXT);
-    if (rc == QD_OK)
-        for (int r = 0; r < 2; ++r) HIPCHK(c, hipMemcpyAsync(out[r], d_out[r].p, rec_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // the scratch is freed on return
-    return rc;
+    PairUpload up(c);
+    const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::OUT_RECS, nullptr, nullptr, out_recs1, out_recs2,
+                           nullptr);
+    if (rc != QD_OK || up.empty()) return rc;
+    return up.close(qd_trim_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), up.out(0), up.out(1), QD_STREAM_CONTEXT));
 }
 
 static_assert(QD_PAIRTRIM_VALUES == QD_PT_VALUES, "the public table size is the kernel's");
@@ -1537,13 +1453,8 @@ int qd_pairtrim_set(qd_ctx* c, const qd_pairtrim_params* params) {
     HIPCHK(c, wait_all(c));  // nothing of this context may still read the old parameters or add to the old table
     free_pairtrim(c);
     if (!params) return QD_OK;
-    hipError_t e = uk_malloc(reinterpret_cast<void**>(&c->d_pairtrim), QD_PT_VALUES * 8);
-    if (e != hipSuccess) {
-        c->d_pairtrim = nullptr;
-        return fail(c, QD_ERR_HIP, std::string("overlap trimming table: ") + hipGetErrorString(e));
-    }
-    HIPCHK(c, hipMemsetAsync(c->d_pairtrim, 0, QD_PT_VALUES * 8, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int rc = table_alloc(c, c->d_pairtrim, QD_PT_VALUES, "overlap trimming table");
+    if (rc != QD_OK) return rc;
     c->pairtrim = P;
     c->pairtrim_dev = D;
     return QD_OK;
@@ -1558,26 +1469,13 @@ int qd_pairtrim_get(const qd_ctx* c, qd_pairtrim_params* out) {
 int qd_pairtrim_active(const qd_ctx* c) { return c && c->d_pairtrim ? 1 : 0; }
 
 int qd_pairtrim_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
-    if (!c || !out) return QD_ERR_INVALID;
-    if (!c->d_pairtrim) return fail(c, QD_ERR_STATE, "overlap trimming is not on");
-    if (n_values != QD_PT_VALUES) return fail(c, QD_ERR_INVALID, "n_values must be 1040");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));
-    HIPCHK(c, hipMemcpy(out, c->d_pairtrim, QD_PT_VALUES * 8, hipMemcpyDeviceToHost));
-    return QD_OK;
+    if (!c) return QD_ERR_INVALID;
+    return table_read(c, c->d_pairtrim, QD_PT_VALUES, out, n_values, "overlap trimming is not on", "n_values must be 1040");
 }
 
 int qd_pairtrim_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
-    if (!c || !values) return QD_ERR_INVALID;
-    if (!c->d_pairtrim) return fail(c, QD_ERR_STATE, "overlap trimming is not on");
-    if (n_values != QD_PT_VALUES) return fail(c, QD_ERR_INVALID, "n_values must be 1040");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));  // the kernel adds to the table: nothing of this context may be in flight
-    std::vector<u64> h(QD_PT_VALUES);
-    HIPCHK(c, hipMemcpy(h.data(), c->d_pairtrim, QD_PT_VALUES * 8, hipMemcpyDeviceToHost));
-    for (int i = 0; i < QD_PT_VALUES; ++i) h[i] += values[i];
-    HIPCHK(c, hipMemcpy(c->d_pairtrim, h.data(), QD_PT_VALUES * 8, hipMemcpyHostToDevice));
-    return QD_OK;
+    if (!c) return QD_ERR_INVALID;
+    return table_add(c, c->d_pairtrim, QD_PT_VALUES, values, n_values, "overlap trimming is not on", "n_values must be 1040");
 }
 
 int qd_pairtrim_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
@@ -1587,10 +1485,7 @@ int qd_pairtrim_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, con
     if (!n) return QD_OK;
     hipStream_t st = resolve_stream(c, stream);
     qd_pairtrim_args a{};
-    a.text[0] = text1;
-    a.text[1] = text2;
-    a.recs[0] = recs1;
-    a.recs[1] = recs2;
+    fill_pair_args(a, text1, recs1, text2, recs2);
     a.out[0] = out1;
     a.out[1] = out2;
     a.table = c->d_pairtrim;
@@ -1604,44 +1499,11 @@ int qd_dev_pairtrim(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_
                     const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2) {
     if (!c) return QD_ERR_INVALID;
     if (!c->d_pairtrim) return fail(c, QD_ERR_STATE, "overlap trimming is not on");
-    const int64_t len[2] = {len1, len2};
-    const uint8_t* text[2] = {text1, text2};
-    const uint32_t* recs[2] = {recs1, recs2};
-    uint32_t* out[2] = {out_recs1, out_recs2};
-    if (n_pairs < 0 || n_pairs > 0x7FFFFFFF || len1 < 0 || len2 < 0 || len1 > ((int64_t)1 << 30) || len2 > ((int64_t)1 << 30))
-        return fail(c, QD_ERR_INVALID, "bad sizes");
-    if (n_pairs == 0) return QD_OK;
-    if (!recs1 || !recs2 || !out_recs1 || !out_recs2 || (!text1 && len1) || (!text2 && len2)) return fail(c, QD_ERR_INVALID, "null argument");
-    // every range is checked here: a bad table cannot become a bad address (the stage reads the sequence lines only)
-    for (int r = 0; r < 2; ++r)
-        for (int64_t j = 0; j < n_pairs; ++j) {
-            const qd_rec* q = reinterpret_cast<const qd_rec*>(recs[r]) + j;
-            if ((int64_t)q->seq + q->seq_len > len[r] || (int64_t)q->qual + q->seq_len > len[r])
-                return fail(c, QD_ERR_INVALID, "a record's sequence or quality line reaches beyond its text");
-        }
-    HIPCHK(c, hipSetDevice(c->device));
-    struct Dev {
-        void* p = nullptr;
-        ~Dev() {
-            if (p) (void)hipFree(p);
-        }
-    } d_text[2], d_recs[2], d_out[2];
-    const size_t rec_bytes = (size_t)n_pairs * sizeof(qd_rec);
-    // the texts start 3 bytes into their buffers: the kernel's aligned words must not depend on an aligned window
-    for (int r = 0; r < 2; ++r) {
-        HIPCHK(c, uk_malloc(&d_text[r].p, (size_t)len[r] + 32));
-        HIPCHK(c, uk_malloc(&d_recs[r].p, rec_bytes));
-        HIPCHK(c, uk_malloc(&d_out[r].p, rec_bytes));
-        if (len[r]) HIPCHK(c, hipMemcpyAsync(static_cast<uint8_t*>(d_text[r].p) + 3, text[r], (size_t)len[r], hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_recs[r].p, recs[r], rec_bytes, hipMemcpyHostToDevice, c->stream));
-    }
-    const int rc = qd_pairtrim_device(c, static_cast<uint8_t*>(d_text[0].p) + 3, static_cast<qd_rec*>(d_recs[0].p), static_cast<uint8_t*>(d_text[1].p) + 3,
-                                      static_cast<qd_rec*>(d_recs[1].p), (uint32_t)n_pairs, static_cast<qd_rec*>(d_out[0].p),
-                                      static_cast<qd_rec*>(d_out[1].p), QD_STREAM_CONTEXT);
-    if (rc == QD_OK)
-        for (int r = 0; r < 2; ++r) HIPCHK(c, hipMemcpyAsync(out[r], d_out[r].p, rec_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // the scratch is freed on return
-    return rc;
+    PairUpload up(c);
+    const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::OUT_RECS, nullptr, nullptr, out_recs1, out_recs2,
+                           nullptr);
+    if (rc != QD_OK || up.empty()) return rc;
+    return up.close(qd_pairtrim_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), up.out(0), up.out(1), QD_STREAM_CONTEXT));
 }
 
 static_assert(QD_FILTER_VALUES == QD_FL_VALUES, "the public table width is the kernel's");
@@ -1668,14 +1530,8 @@ int qd_filter_set(qd_ctx* c, const qd_filter_params* params) {
     HIPCHK(c, wait_all(c));  // nothing of this context may still read the old parameters or add to the old table
     free_filter(c);
     if (!on) return QD_OK;
-    const size_t bytes = qd_filter_values((uint32_t)c->S) * 8;
-    hipError_t e = uk_malloc(reinterpret_cast<void**>(&c->d_filter), bytes);
-    if (e != hipSuccess) {
-        c->d_filter = nullptr;
-        return fail(c, QD_ERR_HIP, std::string("filter table: ") + hipGetErrorString(e));
-    }
-    HIPCHK(c, hipMemsetAsync(c->d_filter, 0, bytes, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int rc = table_alloc(c, c->d_filter, qd_filter_values((uint32_t)c->S), "filter table");
+    if (rc != QD_OK) return rc;
     c->filter = P;
     c->filter_dev = qd_filter_dev{P.min_length, P.max_n, P.max_unqualified_pct, 33 + P.qualified_quality, P.min_mean_quality, P.min_complexity_pct};
     return QD_OK;
@@ -1696,26 +1552,13 @@ int qd_filter_kind(const qd_ctx* c) {
 }
 
 int qd_filter_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
-    if (!c || !out) return QD_ERR_INVALID;
-    if (!c->d_filter) return fail(c, QD_ERR_STATE, "the read filter is not on");
-    if (n_values != (int64_t)qd_filter_values((uint32_t)c->S)) return fail(c, QD_ERR_INVALID, "n_values must be (2*S+1)*8");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));
-    HIPCHK(c, hipMemcpy(out, c->d_filter, (size_t)n_values * 8, hipMemcpyDeviceToHost));
-    return QD_OK;
+    if (!c) return QD_ERR_INVALID;
+    return table_read(c, c->d_filter, qd_filter_values((uint32_t)c->S), out, n_values, "the read filter is not on", "n_values must be (2*S+1)*8");
 }
 
 int qd_filter_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
-    if (!c || !values) return QD_ERR_INVALID;
-    if (!c->d_filter) return fail(c, QD_ERR_STATE, "the read filter is not on");
-    if (n_values != (int64_t)qd_filter_values((uint32_t)c->S)) return fail(c, QD_ERR_INVALID, "n_values must be (2*S+1)*8");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));  // the kernel adds to the table: nothing of this context may be in flight
-    std::vector<u64> h((size_t)n_values);
-    HIPCHK(c, hipMemcpy(h.data(), c->d_filter, h.size() * 8, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < h.size(); ++i) h[i] += values[i];
-    HIPCHK(c, hipMemcpy(c->d_filter, h.data(), h.size() * 8, hipMemcpyHostToDevice));
-    return QD_OK;
+    if (!c) return QD_ERR_INVALID;
+    return table_add(c, c->d_filter, qd_filter_values((uint32_t)c->S), values, n_values, "the read filter is not on", "n_values must be (2*S+1)*8");
 }
 
 int qd_filter_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
@@ -1725,10 +1568,7 @@ int qd_filter_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const
     if (!n) return QD_OK;
     hipStream_t st = resolve_stream(c, stream);
     qd_filter_args a{};
-    a.text[0] = text1;
-    a.text[1] = text2;
-    a.recs[0] = recs1;
-    a.recs[1] = recs2;
+    fill_pair_args(a, text1, recs1, text2, recs2);
     a.codes = codes;
     a.reason = reason;
     a.table = c->d_filter;
@@ -1742,45 +1582,11 @@ int qd_dev_filter(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t*
                   const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes, uint8_t* reasons) {
     if (!c) return QD_ERR_INVALID;
     if (!c->d_filter) return fail(c, QD_ERR_STATE, "the read filter is not on");
-    const int64_t len[2] = {len1, len2};
-    const uint8_t* text[2] = {text1, text2};
-    const uint32_t* recs[2] = {recs1, recs2};
-    if (n_pairs < 0 || n_pairs > 0x7FFFFFFF || len1 < 0 || len2 < 0 || len1 > ((int64_t)1 << 30) || len2 > ((int64_t)1 << 30))
-        return fail(c, QD_ERR_INVALID, "bad sizes");
-    if (n_pairs == 0) return QD_OK;
-    if (!recs1 || !recs2 || !codes || !reasons || (!text1 && len1) || (!text2 && len2)) return fail(c, QD_ERR_INVALID, "null argument");
-    // every range and every code is checked here: a bad table cannot become a bad address
-    for (int r = 0; r < 2; ++r)
-        for (int64_t j = 0; j < n_pairs; ++j) {
-            const qd_rec* q = reinterpret_cast<const qd_rec*>(recs[r]) + j;
-            if ((int64_t)q->seq + q->seq_len > len[r] || (int64_t)q->qual + q->seq_len > len[r])
-                return fail(c, QD_ERR_INVALID, "a record's sequence or quality line reaches beyond its text");
-        }
-    for (int64_t j = 0; j < n_pairs; ++j)
-        if (codes[j] != QD_CODE_UNDETERMINED && (int)codes[j] >= 2 * c->S) return fail(c, QD_ERR_INVALID, "a routing code is not below 2*S");
-    HIPCHK(c, hipSetDevice(c->device));
-    struct Dev {
-        void* p = nullptr;
-        ~Dev() {
-            if (p) (void)hipFree(p);
-        }
-    } d_text[2], d_recs[2], d_codes, d_reason;
-    // the texts start 3 bytes into their buffers: the kernel's aligned words must not depend on an aligned window
-    for (int r = 0; r < 2; ++r) {
-        HIPCHK(c, uk_malloc(&d_text[r].p, (size_t)len[r] + 32));
-        HIPCHK(c, uk_malloc(&d_recs[r].p, (size_t)n_pairs * sizeof(qd_rec)));
-        if (len[r]) HIPCHK(c, hipMemcpyAsync(static_cast<uint8_t*>(d_text[r].p) + 3, text[r], (size_t)len[r], hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_recs[r].p, recs[r], (size_t)n_pairs * sizeof(qd_rec), hipMemcpyHostToDevice, c->stream));
-    }
-    HIPCHK(c, uk_malloc(&d_codes.p, (size_t)n_pairs * 2));
-    HIPCHK(c, uk_malloc(&d_reason.p, (size_t)n_pairs));
-    HIPCHK(c, hipMemcpyAsync(d_codes.p, codes, (size_t)n_pairs * 2, hipMemcpyHostToDevice, c->stream));
-    const int rc = qd_filter_device(c, static_cast<uint8_t*>(d_text[0].p) + 3, static_cast<qd_rec*>(d_recs[0].p), static_cast<uint8_t*>(d_text[1].p) + 3,
-                                    static_cast<qd_rec*>(d_recs[1].p), (uint32_t)n_pairs, static_cast<uint16_t*>(d_codes.p),
-                                    static_cast<uint8_t*>(d_reason.p), QD_STREAM_CONTEXT);
-    if (rc == QD_OK) HIPCHK(c, hipMemcpyAsync(reasons, d_reason.p, (size_t)n_pairs, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // the scratch is freed on return
-    return rc;
+    PairUpload up(c);
+    const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::CODES | PairUpload::REASONS, codes, nullptr,
+                           nullptr, nullptr, reasons);
+    if (rc != QD_OK || up.empty()) return rc;
+    return up.close(qd_filter_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), up.codes(), up.reason(), QD_STREAM_CONTEXT));
 }
 
 int qd_kernel_kind(const qd_ctx* c, int has_len) {

@@ -2,9 +2,8 @@
 // (qd_clip_set) while their text sits in HBM.  A clip is a new seq, qual and seq_len: the kernel writes copies of the scan's
 // record tables and counts what it cut.  include/quade_hip.h states the rule.
 //
-// Shape (quade_trim.hip's): 16 lanes (one DPP row) share a read; blockIdx.y says R1 or R2.  What the fixed clip leaves of the
-// quality and the sequence line is read as 16-byte aligned words, one or two per lane, into a slab of LDS that belongs to the row
-// (the sequence with its case folded), so that every lane reaches any offset of the line.
+// Shape (quade_row.h's searching stage): 16 lanes (one DPP row) share a read; blockIdx.y says R1 or R2.  What the fixed clip
+// leaves of the quality and the sequence line is staged in the row's slab of LDS, the sequence with its case folded.
 //   window : lane i takes the starts in the i-th stretch of T = ceil(Lc / 16) bytes, slides the window over them and notes the first
 //            that fails; the row minimum is the cut.  The window's sum at the lane's first start: for W <= 2 T its W bytes are
 //            added up; for a longer window the stretch sums are scanned over the row (DPP row_shr), which gives every lane the
@@ -15,88 +14,19 @@
 //            first t at which the walk stops and the last G in front of it.  The lowest lane that stopped ends the walk; the
 //            largest G position of the lanes up to it is the cut.  A read without a G tail stops in the first round.
 // A line of more than 21 words does not fit its slab: the same two walks then read bytes from global memory, the window's sums in
-// 64 bits.  Lanes 0 .. 11 of every row keep one counter each in a register; a workgroup adds them in LDS and flushes twelve
-// 64-bit atomics.
+// 64 bits.  Lanes 0 .. 11 of every row keep one counter each in a register (quade_row.h's flush_row_counters).
 #include <hip/hip_runtime.h>
 
+#include "quade_row.h"
 #include "quade_clip.h"
 
 namespace {
 
 constexpr uint32_t CL_BLOCK = 256;
-constexpr uint32_t CL_GROUP = 16;                   // lanes per read: one DPP row
-constexpr uint32_t CL_GROUPS = CL_BLOCK / CL_GROUP; // reads per step of a workgroup
+constexpr uint32_t CL_GROUPS = CL_BLOCK / ROW;      // reads per step of a workgroup
 constexpr uint32_t CL_WG_READS = 1024;              // reads per workgroup
-constexpr uint32_t CL_FAST_WORDS = 21;              // 16-byte words of a staged line: 321 bases at any alignment, 336 at the best
 constexpr uint32_t CL_G_STEP = 4;                   // bases per lane and round of the poly-G walk
-static_assert(CL_WG_READS % CL_GROUPS == 0 && QD_CLIP_COUNTERS <= CL_GROUP, "one lane per counter");
-static_assert(CL_FAST_WORDS <= 2 * CL_GROUP, "two words per lane stage a line");
-// the prefix sums of a staged line stay in 32 bits
-static_assert((uint64_t)CL_FAST_WORDS * 16 * 255 < 0x7FFFFFFFull, "a staged line's quality sum can overflow");
-
-// the value of another lane of the row (DPP), 32 or 64 bits wide
-template <int CTRL, bool BOUND>
-__device__ __forceinline__ int32_t dpp(int32_t v) {
-    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, BOUND);
-}
-template <int CTRL, bool BOUND>
-__device__ __forceinline__ uint32_t dpp(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, BOUND);
-}
-template <int CTRL, bool BOUND>
-__device__ __forceinline__ int64_t dpp(int64_t v) {
-    const uint32_t lo = dpp<CTRL, BOUND>((uint32_t)v), hi = dpp<CTRL, BOUND>((uint32_t)((uint64_t)v >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-// over the 16 lanes of a row, the result in every lane: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror
-template <typename T, typename F>
-__device__ __forceinline__ T row_all(T v, F f) {
-    v = f(v, dpp<0xB1, false>(v));
-    v = f(v, dpp<0x4E, false>(v));
-    v = f(v, dpp<0x141, false>(v));
-    v = f(v, dpp<0x140, false>(v));
-    return v;
-}
-template <typename T>
-__device__ __forceinline__ T row_min(T v) {
-    return row_all(v, [](T a, T b) { return a < b ? a : b; });
-}
-template <typename T>
-__device__ __forceinline__ T row_max(T v) {
-    return row_all(v, [](T a, T b) { return a > b ? a : b; });
-}
-// sum of the lanes below this one in the row (row_shr 1, 2, 4, 8; lanes shifted in from outside the row are zero)
-template <typename T>
-__device__ __forceinline__ T row_sum_below(T v) {
-    T s = v;
-    s += dpp<0x111, true>(s);
-    s += dpp<0x112, true>(s);
-    s += dpp<0x114, true>(s);
-    s += dpp<0x118, true>(s);
-    return s - v;
-}
-// the value lane `lane` (0 .. 15) of this row holds (ds_bpermute)
-__device__ __forceinline__ int32_t row_get(int32_t v, uint32_t lane) { return __shfl(v, (int)lane, (int)CL_GROUP); }
-__device__ __forceinline__ int64_t row_get(int64_t v, uint32_t lane) {
-    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, (int)lane, (int)CL_GROUP);
-    const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)((uint64_t)v >> 32), (int)lane, (int)CL_GROUP);
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
-// one line of a record as aligned 16-byte words: bytes [s, s + len) of the words from w0 on
-struct Line {
-    const uint4* w0;
-    uint32_t s;
-    uint32_t n_words;
-};
-__device__ __forceinline__ Line make_line(const uint8_t* text, uint32_t start, uint32_t len) {
-    const uint8_t* p = text + start;
-    Line L;
-    L.s = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u);
-    L.w0 = reinterpret_cast<const uint4*>(p - L.s);
-    L.n_words = len ? (uint32_t)(((uint64_t)L.s + len + 15) >> 4) : 0;  // every word holds at least one byte of the line
-    return L;
-}
+static_assert(CL_WG_READS % CL_GROUPS == 0, "whole steps");
 
 // Window rule over q[0 .. Lc) (the caller's row holds one read): the smallest p in [0, Lc - W] whose W Phred values sum to less
 // than QW = Q * W, Lc when there is none; in every lane.  SUM: wide enough for Lc * 222.
@@ -104,7 +34,7 @@ template <typename SUM, typename PTR>
 __device__ __forceinline__ uint32_t window_trim(PTR q, uint32_t Lc, uint32_t W, uint32_t QW, uint32_t sub) {
     if (Lc < W) return Lc;
     const uint32_t n_p = Lc - W + 1;                     // starts
-    const uint32_t T = (Lc + CL_GROUP - 1) / CL_GROUP;   // lane i: bytes [i T, (i + 1) T)
+    const uint32_t T = (Lc + ROW - 1) / ROW;   // lane i: bytes [i T, (i + 1) T)
     const uint32_t lo = min(sub * T, Lc), hi = lo + min(T, Lc - lo);
     auto ph = [&](uint32_t i) {
         const uint32_t b = q[i];
@@ -130,7 +60,7 @@ __device__ __forceinline__ uint32_t window_trim(PTR q, uint32_t Lc, uint32_t W, 
         for (uint32_t i = lo; i < hi; ++i) sum += ph(i);
         const SUM below = row_sum_below(sum);  // the prefix sum at lo
         // ... and at lo + W: from the lane whose stretch holds that byte (a lane without starts asks for Lc: every lane takes part)
-        const uint32_t e = lo + min(W, Lc - lo), j = min(e / T, CL_GROUP - 1);
+        const uint32_t e = lo + min(W, Lc - lo), j = min(e / T, ROW - 1);
         SUM B = row_get(below, j);
         for (uint32_t i = j * T; i < e; ++i) B += ph(i);
         SUM A = below;
@@ -150,7 +80,7 @@ __device__ __forceinline__ uint32_t window_trim(PTR q, uint32_t Lc, uint32_t W, 
 // Poly-G rule over s[0 .. Lw) with minimum run P >= 6 (the bytes are folded here: a staged line is folded already): Lg in every lane
 template <typename PTR>
 __device__ __forceinline__ uint32_t polyg_trim(PTR s, uint32_t Lw, uint32_t P, uint32_t sub) {
-    constexpr uint32_t ROUND = CL_GROUP * CL_G_STEP;
+    constexpr uint32_t ROUND = ROW * CL_G_STEP;
     uint32_t mm0 = 0, g = 0;  // mismatches and the largest G position of the rounds done
     for (uint32_t t0 = 0; t0 < Lw;) {
         const uint32_t n = min(Lw - t0, ROUND);
@@ -170,9 +100,9 @@ __device__ __forceinline__ uint32_t polyg_trim(PTR s, uint32_t Lw, uint32_t P, u
             if (is_g) last = t;
         }
         // stretches ascend with the lane: the lowest lane that stopped holds the first stop; the lanes above it saw nothing real
-        const uint32_t w = row_min(stop != 0xFFFFFFFFu ? sub : CL_GROUP);
+        const uint32_t w = row_min(stop != 0xFFFFFFFFu ? sub : ROW);
         g = max(g, row_max(sub <= w ? last : 0u));
-        if (w < CL_GROUP) {
+        if (w < ROW) {
             const uint32_t T = row_min(stop);
             return T - 1 >= P ? Lw - g : Lw;
         }
@@ -183,11 +113,11 @@ __device__ __forceinline__ uint32_t polyg_trim(PTR s, uint32_t Lw, uint32_t P, u
 }
 
 __global__ __launch_bounds__(CL_BLOCK) void clip_reads(qd_clip_dev P, qd_clip_args a, uint32_t n) {
-    __shared__ uint4 slab[CL_GROUPS][2][CL_FAST_WORDS];  // per row: the quality line, the folded sequence line
+    __shared__ uint4 slab[CL_GROUPS][2][FAST_WORDS];  // per row: the quality line, the folded sequence line (read by bytes: no dword ahead)
     __shared__ unsigned long long part[QD_CLIP_COUNTERS];
     const uint32_t r = blockIdx.y;
     if (threadIdx.x < QD_CLIP_COUNTERS) part[threadIdx.x] = 0;
-    const uint32_t sub = threadIdx.x & (CL_GROUP - 1), group = threadIdx.x / CL_GROUP;
+    const uint32_t sub = threadIdx.x & (ROW - 1), group = threadIdx.x / ROW;
     const uint8_t* text = a.text[r];
     const qd_rec* recs = a.recs[r];
     qd_rec* out = a.out[r];
@@ -205,18 +135,11 @@ __global__ __launch_bounds__(CL_BLOCK) void clip_reads(qd_clip_dev P, qd_clip_ar
         const uint32_t f = min(F, L), Lc = L - f > Tl ? L - f - Tl : 0;
         const uint32_t seq = rec.seq + f, qual = rec.qual + f;
         const Line ql = make_line(text, qual, Lc), sl = make_line(text, seq, Lc);
-        const bool staged = ql.n_words <= CL_FAST_WORDS && sl.n_words <= CL_FAST_WORDS;
+        const bool staged = ql.n_words <= FAST_WORDS && sl.n_words <= FAST_WORDS;
         __syncthreads();  // the row's earlier read is done with the slab
         if (staged) {
-            for (uint32_t k = sub; k < ql.n_words && W; k += CL_GROUP) sq[k] = ql.w0[k];
-            for (uint32_t k = sub; k < sl.n_words && G; k += CL_GROUP) {
-                uint4 v = sl.w0[k];
-                v.x &= 0xDFDFDFDFu;  // upper case for the letters; no other byte becomes G
-                v.y &= 0xDFDFDFDFu;
-                v.z &= 0xDFDFDFDFu;
-                v.w &= 0xDFDFDFDFu;
-                ss[k] = v;
-            }
+            if (W) stage_line<false>(sq, ql, sub);
+            if (G) stage_line<true>(ss, sl, sub);
         }
         __syncthreads();
         uint32_t Lw = Lc, Lg;
@@ -241,11 +164,7 @@ __global__ __launch_bounds__(CL_BLOCK) void clip_reads(qd_clip_dev P, qd_clip_ar
                 if (sub == i) acc += v[i];
         }
     }
-    __syncthreads();
-    if (sub < QD_CLIP_COUNTERS && acc) atomicAdd(&part[sub], (unsigned long long)acc);
-    __syncthreads();
-    if (threadIdx.x < QD_CLIP_COUNTERS && part[threadIdx.x])
-        atomicAdd(reinterpret_cast<unsigned long long*>(a.table) + r * QD_CLIP_COUNTERS + threadIdx.x, part[threadIdx.x]);
+    flush_row_counters<QD_CLIP_COUNTERS>(acc, sub, part, reinterpret_cast<unsigned long long*>(a.table) + r * QD_CLIP_COUNTERS);
 }
 
 }  // namespace

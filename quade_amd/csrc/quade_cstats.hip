@@ -2,12 +2,12 @@
 // over the sequence and quality lines of a batch's insert reads while their text sits in HBM.  The definition of every
 // counter: quade_cstats.h.
 //
-// Shape (quade_qstats.hip's, which reads the same four lines): 16 lanes (one DPP row) share a pair.  Each of the pair's
-// four lines is read as 16-byte aligned words, one word per lane, head and tail masked (a masked byte is zero: no letter,
+// Shape (quade_row.h's counting stage; quade_qstats.hip reads the same four lines): 16 lanes (one DPP row) share a pair.  Each of
+// the pair's four lines is read one aligned word per lane, head and tail masked (a masked byte is zero: no letter,
 // ph = 0, so it adds nothing); the first word of all four lines is in flight together.  A lane walks the 16 bytes of its
 // word: byte i of word k of a line that starts s bytes into its first word is cycle c = 16 k + i - s.
 //
-// Accumulation: a workgroup keeps 32-bit partials in LDS and flushes the non-zero words once, with 64-bit global atomics:
+// Accumulation (this stage's own, see quade_row.h): a workgroup keeps 32-bit partials in LDS and flushes the non-zero words once, with 64-bit global atomics:
 //   cycles c < QD_CS_LDS_CYCLES   [g][r][counter][c & 15][c >> 4]   (see below)
 //   every per-read histogram bin  [g][r][len 1025 | meanq 94 | gc 101]
 // so a read within the LDS range costs no global atomic at all, and the one length of a run is an LDS word.  Cycles from
@@ -23,13 +23,13 @@
 // CU: 16 waves per CU, 4 per SIMD.
 #include <hip/hip_runtime.h>
 
+#include "quade_row.h"
 #include "quade_cstats.h"
 
 namespace {
 
 constexpr uint32_t CS_BLOCK = 1024;
-constexpr uint32_t CS_GROUP = 16;                    // lanes per pair: one DPP row
-constexpr uint32_t CS_GROUPS = CS_BLOCK / CS_GROUP;  // pairs per step of a workgroup
+constexpr uint32_t CS_GROUPS = CS_BLOCK / ROW;       // pairs per step of a workgroup
 constexpr uint32_t CS_WG_PAIRS = 4096;               // pairs per workgroup
 constexpr uint32_t CS_MAX_Q = 255 - 33;
 constexpr uint32_t CS_COLS = QD_CS_LDS_CYCLES / 16;  // words per (c & 15) column
@@ -41,49 +41,6 @@ constexpr uint32_t CS_LDS_WORDS = CS_CYC_WORDS + QD_CS_GROUPS * 2 * CS_HIST;
 static_assert((uint64_t)CS_WG_PAIRS * CS_MAX_Q <= 0xFFFFFFFFull, "a workgroup's LDS partials can overflow");
 static_assert(CS_LDS_WORDS * 4 <= 160 * 1024, "the LDS partials exceed a CU's LDS");
 static_assert(CS_WG_PAIRS % CS_GROUPS == 0 && QD_CS_LDS_CYCLES % 32 == 0, "whole steps; counter arrays start at bank 0");
-
-// sum over the 16 lanes of a row, in every lane (all lanes of the wave active)
-__device__ __forceinline__ uint32_t row_sum(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false);  // row_half_mirror
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false);  // row_mirror
-    return v;
-}
-
-// one line of a record as aligned 16-byte words: bytes [s, e) of the words from w0 on
-struct Line {
-    const uint4* w0;
-    uint32_t s;
-    uint32_t n_words;
-    uint64_t e;
-};
-__device__ __forceinline__ Line make_line(const uint8_t* text, uint32_t start, uint32_t len) {
-    const uint8_t* p = text + start;
-    Line L;
-    L.s = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u);
-    L.w0 = reinterpret_cast<const uint4*>(p - L.s);
-    L.e = (uint64_t)L.s + len;
-    L.n_words = len ? (uint32_t)((L.e + 15) >> 4) : 0;  // every word holds at least one byte of the line
-    return L;
-}
-// the bytes of [s, e) among the four at o .. o + 3
-__device__ __forceinline__ uint32_t byte_mask(int64_t s, int64_t e, int64_t o) {
-    const int64_t lo = s > o ? s - o : 0, hi = e - o < 4 ? e - o : 4;
-    if (hi <= lo) return 0;
-    const uint32_t upto = hi >= 4 ? 0xFFFFFFFFu : (1u << (8 * (uint32_t)hi)) - 1u;
-    return upto & ~((1u << (8 * (uint32_t)lo)) - 1u);
-}
-__device__ __forceinline__ uint4 mask_word(const Line& L, uint32_t k, uint4 v) {
-    if (k == 0 || k + 1 == L.n_words) {
-        const int64_t o = (int64_t)k * 16;
-        v.x &= byte_mask(L.s, (int64_t)L.e, o);
-        v.y &= byte_mask(L.s, (int64_t)L.e, o + 4);
-        v.z &= byte_mask(L.s, (int64_t)L.e, o + 8);
-        v.w &= byte_mask(L.s, (int64_t)L.e, o + 12);
-    }
-    return v;
-}
 
 // where the counters of one (g, r) live
 struct Sink {
@@ -134,7 +91,7 @@ __global__ __launch_bounds__(CS_BLOCK) void cstats(qd_cstats_args a, uint32_t n)
     extern __shared__ uint32_t part[];  // cycles [g][r][counter][column][row], then histograms [g][r][len | meanq | gc]
     for (uint32_t i = threadIdx.x; i < CS_LDS_WORDS; i += CS_BLOCK) part[i] = 0;
     __syncthreads();
-    const uint32_t sub = threadIdx.x & (CS_GROUP - 1), group = threadIdx.x / CS_GROUP;
+    const uint32_t sub = threadIdx.x & (ROW - 1), group = threadIdx.x / ROW;
     const uint32_t first = blockIdx.x * CS_WG_PAIRS, last = min(n, first + CS_WG_PAIRS);
     for (uint32_t j0 = first; j0 < last; j0 += CS_GROUPS) {  // (the same trips for every wave: the DPP sums need whole waves)
         const uint32_t j = j0 + group;
@@ -172,9 +129,9 @@ __global__ __launch_bounds__(CS_BLOCK) void cstats(qd_cstats_args a, uint32_t n)
             uint64_t qsum = 0;
             if (sub < ls.n_words) add_seq(mask_word(ls, sub, w[2 * r]), 16 * sub - ls.s, k, gc);
             if (sub < lq.n_words) add_qual(mask_word(lq, sub, w[2 * r + 1]), 16 * sub - lq.s, k, qsum);
-            for (uint32_t i = sub + CS_GROUP; i < ls.n_words; i += CS_GROUP)  // reads longer than 241 .. 256 bases
+            for (uint32_t i = sub + ROW; i < ls.n_words; i += ROW)  // reads longer than 241 .. 256 bases
                 add_seq(mask_word(ls, i, ls.w0[i]), 16 * i - ls.s, k, gc);
-            for (uint32_t i = sub + CS_GROUP; i < lq.n_words; i += CS_GROUP)
+            for (uint32_t i = sub + ROW; i < lq.n_words; i += ROW)
                 add_qual(mask_word(lq, i, lq.w0[i]), 16 * i - lq.s, k, qsum);
             // the read's own values, in every lane of the row
             gc = row_sum(gc);

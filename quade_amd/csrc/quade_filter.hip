@@ -1,90 +1,30 @@
 // gfx950 (CDNA4 / MI355X): read filtering of the insert reads (qd_filter_set), one pass over the sequence and quality lines of a
 // batch's insert reads while their text sits in HBM: a reason byte per pair and eight counters per destination.
 //
-// Shape (quade_qstats.hip's, which reads the same four lines): 16 lanes (one DPP row) share a pair.  Each of the pair's four lines
-// is read as 16-byte aligned words, one word per lane, head and tail masked: 256 bytes per step, so a 2 x 150 bp pair costs four
-// loads per lane, all in flight together.  The bytes are counted four at a time in 32-bit words (SWAR compares, popcount,
-// v_sad_u8 for the byte sum).  New here is the neighbour compare: every folded word against itself shifted by one byte
+// Shape (quade_row.h's counting stage; quade_qstats.hip reads the same four lines): 16 lanes (one DPP row) share a pair.  Each of
+// the pair's four lines is read one aligned word per lane, head and tail masked: 256 bytes per step, so a 2 x 150 bp pair costs
+// four loads per lane, all in flight together.  The bytes are counted four at a time in 32-bit words (SWAR compares, popcount,
+// v_sad_u8 for the byte sum).  Particular to this stage is the neighbour compare: every folded word against itself shifted by one byte
 // (v_alignbyte); the byte beyond a lane's 16 comes from the next lane (DPP row_shl:1), the byte beyond a 256-byte step from the
 // next step's first word, and the positions are masked to [0, L - 1), so that neither the newline behind the line nor the byte in
 // front of it ever counts.  The sums go over the row with DPP, every lane of the row then applies the rule, lane 0 stores the
-// reason and lanes 0 .. 7 hold the pair's 8 values, one each:
-//   S small  : one LDS add per value into the workgroup's 32-bit partials, flushed (non-zero entries, 64-bit global atomics) once
-//              per workgroup.
-//   S large  : the partials no longer fit; the wave's four pairs are merged where their destinations are equal, then 64-bit
-//              global atomics per distinct destination.
+// reason and lanes 0 .. 7 hold the pair's 8 values, one each, for quade_row.h's DestTable: LDS partials for a small S, merged
+// global atomics for a large one.
 #include <hip/hip_runtime.h>
 
+#include "quade_row.h"
 #include "quade_filter.h"
 
 namespace {
 
 constexpr uint32_t FL_BLOCK = 256;
-constexpr uint32_t FL_GROUP = 16;                    // lanes per pair: one DPP row
-constexpr uint32_t FL_GROUPS = FL_BLOCK / FL_GROUP;  // pairs per step of a workgroup
+constexpr uint32_t FL_GROUPS = FL_BLOCK / ROW;       // pairs per step of a workgroup
 constexpr uint32_t FL_WG_PAIRS = 2048;               // pairs per workgroup
 constexpr uint32_t FL_LDS_MAX_LEN = 2047;            // longer reads bypass the 32-bit partials
 // the largest 32-bit partial is a destination's bases_in when it receives every pair of the workgroup
 static_assert((uint64_t)FL_WG_PAIRS * 2 * FL_LDS_MAX_LEN <= 0xFFFFFFFFull, "a workgroup's LDS partials can overflow");
 static_assert(QD_FL_LDS_MAX_DEST * QD_FL_VALUES * 4 <= 65536, "the LDS partials exceed 64 KiB");
-static_assert(FL_WG_PAIRS % FL_GROUPS == 0 && QD_FL_VALUES <= FL_GROUP, "one lane per value");
-
-// sum over the 16 lanes of a row, in every lane (all lanes of the row active)
-__device__ __forceinline__ uint32_t row_sum(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false);  // row_half_mirror
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false);  // row_mirror
-    return v;
-}
-// the next lane's value (row_shl:1); lane 15 of the row gets 0
-__device__ __forceinline__ uint32_t from_next_lane(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x101, 0xF, 0xF, true);
-}
-
-// 0x80 in every byte of w that is >= t (bytes unsigned, 1 <= t <= 128)
-__device__ __forceinline__ uint32_t bytes_ge(uint32_t w, uint32_t t) {
-    return (((w & 0x7F7F7F7Fu) + (0x80u - t) * 0x01010101u) | w) & 0x80808080u;
-}
-// 0x80 in every byte of w that is not zero
-__device__ __forceinline__ uint32_t bytes_nz(uint32_t w) {
-    return (((w & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | w) & 0x80808080u;
-}
-
-// one line of a record as aligned 16-byte words: bytes [s, e) of the words from w0 on
-struct Line {
-    const uint4* w0;
-    uint32_t s;
-    uint32_t n_words;
-    uint64_t e;
-};
-__device__ __forceinline__ Line make_line(const uint8_t* text, uint32_t start, uint32_t len) {
-    const uint8_t* p = text + start;
-    Line L;
-    L.s = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u);
-    L.w0 = reinterpret_cast<const uint4*>(p - L.s);
-    L.e = (uint64_t)L.s + len;
-    L.n_words = len ? (uint32_t)((L.e + 15) >> 4) : 0;  // every word holds at least one byte of the line
-    return L;
-}
-// the bytes of [s, e) among the four at o .. o + 3
-__device__ __forceinline__ uint32_t byte_mask(int64_t s, int64_t e, int64_t o) {
-    const int64_t lo = s > o ? s - o : 0, hi = e - o < 4 ? e - o : 4;
-    if (hi <= lo) return 0;
-    const uint32_t upto = hi >= 4 ? 0xFFFFFFFFu : (1u << (8 * (uint32_t)hi)) - 1u;
-    return upto & ~((1u << (8 * (uint32_t)lo)) - 1u);
-}
-__device__ __forceinline__ bool edge_word(const Line& L, uint32_t k) { return k == 0 || k + 1 >= L.n_words; }
-__device__ __forceinline__ uint4 mask_word(const Line& L, uint32_t k, uint4 v) {
-    if (edge_word(L, k)) {
-        const int64_t o = (int64_t)k * 16;
-        v.x &= byte_mask(L.s, (int64_t)L.e, o);
-        v.y &= byte_mask(L.s, (int64_t)L.e, o + 4);
-        v.z &= byte_mask(L.s, (int64_t)L.e, o + 8);
-        v.w &= byte_mask(L.s, (int64_t)L.e, o + 12);
-    }
-    return v;
-}
+static_assert(FL_WG_PAIRS % FL_GROUPS == 0, "whole steps");
 
 struct ReadSums {  // one lane's share of a read
     uint32_t ge, nn, diff;
@@ -102,7 +42,8 @@ __device__ __forceinline__ void add_seq(uint4 v, ReadSums& a) {
 // word k of a sequence line as loaded (not masked) and the dword behind it: the positions of [s, e - 1) whose byte and the byte
 // behind it differ once bit 5 is folded away.  (Word n_words - 2 lies inside [s, e - 1) whole: only the edge words need the mask.)
 __device__ __forceinline__ void add_diff(const Line& L, uint32_t k, uint4 v, uint32_t next, ReadSums& a) {
-    const uint32_t f[5] = {v.x & 0xDFDFDFDFu, v.y & 0xDFDFDFDFu, v.z & 0xDFDFDFDFu, v.w & 0xDFDFDFDFu, next & 0xDFDFDFDFu};
+    v = fold_case(v);
+    const uint32_t f[5] = {v.x, v.y, v.z, v.w, next & 0xDFDFDFDFu};
     const bool edge = edge_word(L, k);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -127,7 +68,7 @@ __device__ __forceinline__ void add_qual(uint4 v, uint32_t t, ReadSums& a) {
 __device__ __forceinline__ void seq_step(const Line& L, uint32_t k0, uint32_t sub, uint4 v, ReadSums& a) {
     const uint32_t k = k0 + sub;
     uint32_t next = from_next_lane(v.x);
-    if (sub == FL_GROUP - 1 && k + 1 < L.n_words) next = L.w0[k + 1].x;  // the next step's first word
+    if (sub == ROW - 1 && k + 1 < L.n_words) next = L.w0[k + 1].x;  // the next step's first word
     add_seq(mask_word(L, k, v), a);
     add_diff(L, k, v, next, a);
 }
@@ -157,12 +98,10 @@ __device__ __forceinline__ uint32_t reason_of(const qd_filter_dev& P, const uint
 template <bool LDS>
 __global__ __launch_bounds__(FL_BLOCK) void filter_pairs(qd_filter_dev P, qd_filter_args a, uint32_t n_samples, uint32_t n) {
     extern __shared__ uint32_t part[];  // LDS path: [n_dest][QD_FL_VALUES]
-    const uint32_t n_dest = 2 * n_samples + 1, n_values = n_dest * QD_FL_VALUES;
-    if (LDS) {
-        for (uint32_t i = threadIdx.x; i < n_values; i += FL_BLOCK) part[i] = 0;
-        __syncthreads();
-    }
-    const uint32_t sub = threadIdx.x & (FL_GROUP - 1), group = threadIdx.x / FL_GROUP;
+    const uint32_t n_dest = 2 * n_samples + 1;
+    const DestTable<LDS, QD_FL_VALUES, FL_BLOCK> table{part, reinterpret_cast<unsigned long long*>(a.table), n_dest * QD_FL_VALUES};
+    table.init();
+    const uint32_t sub = threadIdx.x & (ROW - 1), group = threadIdx.x / ROW;
     const uint32_t first = blockIdx.x * FL_WG_PAIRS, last = min(n, first + FL_WG_PAIRS);
     const uint32_t qual_byte = (uint32_t)P.qual_byte;
     for (uint32_t j0 = first; j0 < last; j0 += FL_GROUPS) {  // (the same trips for every wave: the DPP sums need whole rows)
@@ -198,11 +137,11 @@ __global__ __launch_bounds__(FL_BLOCK) void filter_pairs(qd_filter_dev P, qd_fil
             seq_step(sl, 0, sub, w[2 * r], s[r]);  // (a lane beyond the line holds zeros)
             add_qual(mask_word(ql, sub, w[2 * r + 1]), qual_byte, s[r]);
             // reads longer than 241 .. 256 bases: the trip count is the row's, so that row_shl finds every lane of the row
-            for (uint32_t k0 = FL_GROUP; k0 < sl.n_words; k0 += FL_GROUP) {
+            for (uint32_t k0 = ROW; k0 < sl.n_words; k0 += ROW) {
                 const uint32_t k = k0 + sub;
                 seq_step(sl, k0, sub, k < sl.n_words ? sl.w0[k] : make_uint4(0, 0, 0, 0), s[r]);
             }
-            for (uint32_t k = sub + FL_GROUP; k < ql.n_words; k += FL_GROUP) add_qual(mask_word(ql, k, ql.w0[k]), qual_byte, s[r]);
+            for (uint32_t k = sub + ROW; k < ql.n_words; k += ROW) add_qual(mask_word(ql, k, ql.w0[k]), qual_byte, s[r]);
         }
         uint32_t nn[2], unq[2], diff[2];
         uint64_t qsum[2];
@@ -225,34 +164,9 @@ __global__ __launch_bounds__(FL_BLOCK) void filter_pairs(qd_filter_dev P, qd_fil
         else if (sub == QD_FL_BASES_DROPPED) v = why ? bases : 0;
         const bool mine = valid && sub < QD_FL_VALUES;
         if (!mine) v = 0;
-        if (LDS) {
-            if (mine && v) {
-                if (len[0] <= FL_LDS_MAX_LEN && len[1] <= FL_LDS_MAX_LEN) atomicAdd(&part[d * QD_FL_VALUES + sub], (uint32_t)v);
-                else atomicAdd(reinterpret_cast<unsigned long long*>(a.table) + (size_t)d * QD_FL_VALUES + sub, (unsigned long long)v);
-            }
-        } else {
-            // the wave's four pairs: the first of each destination adds for the later ones
-            bool leader = true;
-            uint64_t total = v;
-#pragma unroll
-            for (uint32_t h = 0; h < 64 / FL_GROUP; ++h) {
-                const uint32_t dh = __shfl(d, (int)(h * FL_GROUP), 64);
-                const unsigned long long vh = __shfl((unsigned long long)v, (int)(h * FL_GROUP + sub), 64);
-                const uint32_t me = (threadIdx.x & 63u) / FL_GROUP;
-                if (dh == d && h < me) leader = false;
-                if (dh == d && h > me) total += vh;
-            }
-            if (mine && leader && total)
-                atomicAdd(reinterpret_cast<unsigned long long*>(a.table) + (size_t)d * QD_FL_VALUES + sub, (unsigned long long)total);
-        }
+        table.add(d, sub, v, mine, len[0] <= FL_LDS_MAX_LEN && len[1] <= FL_LDS_MAX_LEN);
     }
-    if (LDS) {
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < n_values; i += FL_BLOCK) {
-            const uint32_t c = part[i];
-            if (c) atomicAdd(reinterpret_cast<unsigned long long*>(a.table) + i, (unsigned long long)c);
-        }
-    }
+    table.flush();
 }
 
 }  // namespace

@@ -1,8 +1,8 @@
 // gfx950 (CDNA4 / MI355X): paired-end overlap trimming of a batch's insert reads with insert sizes (qd_pairtrim_set) while their
 // text sits in HBM.  quade_pairtrim.h states the definition; a cut is a new seq_len, written into copies of the record tables.
 //
-// Shape: 16 lanes (one DPP row) share a pair.  Both sequence lines are read as 16-byte aligned words, one or two per lane, into a
-// slab of LDS that belongs to the row:
+// Shape (quade_row.h's searching stage): 16 lanes (one DPP row) share a pair.  Both sequence lines are staged in the row's slab of
+// LDS:
 //   R1  : case folded (b & 0xDF), so a byte that is no letter of ACGT equals none of them and has bit 5 clear;
 //   R2  : reverse-complemented -- source word k becomes word n_words - 1 - k with its bytes reversed, which puts RC2[x] at byte
 //         t + x of the slab, t = 16 * n_words - (s + L2) -- and every byte that is no letter of ACGT becomes one with bit 5 set,
@@ -12,73 +12,21 @@
 // its budget is spent.  Lane i of a round tries the i-th candidate of 16: first I >= M ascending, ending with the first round that
 // accepts one (row minimum), then I < M descending (row maximum).
 // A line of more than 21 words does not fit its slab: the pair then takes the same search over bytes in global memory.
-// Lanes 0 .. 14 of every row keep one counter each in a register; a workgroup adds them and the insert sizes in LDS and flushes
-// 64-bit atomics for what is not zero.
+// Lanes 0 .. 14 of every row keep one counter each in a register (quade_row.h's flush_row_counters); the insert sizes are a
+// histogram in LDS of the workgroup's own, flushed behind them with 64-bit atomics for what is not zero.
 #include <hip/hip_runtime.h>
 
+#include "quade_row.h"
 #include "quade_pairtrim.h"
 
 namespace {
 
 constexpr uint32_t PT_BLOCK = 256;
-constexpr uint32_t PT_GROUP = 16;                   // lanes per pair: one DPP row
-constexpr uint32_t PT_GROUPS = PT_BLOCK / PT_GROUP; // pairs per step of a workgroup
+constexpr uint32_t PT_GROUPS = PT_BLOCK / ROW;      // pairs per step of a workgroup
 constexpr uint32_t PT_WG_PAIRS = 1024;              // pairs per workgroup: a 32-bit partial cannot overflow
-constexpr uint32_t PT_FAST_WORDS = 21;              // 16-byte words of a staged line: 321 bases at any alignment, 336 at the best
-constexpr uint32_t PT_SLAB_WORDS = PT_FAST_WORDS + 1;  // the compare looks one dword ahead
 constexpr uint32_t PT_SCALARS = QD_PT_HIST;         // the 15 counters in front of the histogram
-static_assert(PT_WG_PAIRS % PT_GROUPS == 0 && PT_SCALARS <= PT_GROUP, "one lane per counter");
-static_assert(PT_FAST_WORDS <= 2 * PT_GROUP, "two words per lane stage a line");
+static_assert(PT_WG_PAIRS % PT_GROUPS == 0, "whole steps");
 
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp(uint32_t v) {
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
-}
-template <int CTRL>
-__device__ __forceinline__ uint64_t dpp(uint64_t v) {
-    return ((uint64_t)dpp<CTRL>((uint32_t)(v >> 32)) << 32) | dpp<CTRL>((uint32_t)v);
-}
-// over the 16 lanes of a row, the result in every lane: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror
-template <typename T, typename F>
-__device__ __forceinline__ T row_all(T v, F f) {
-    v = f(v, dpp<0xB1>(v));
-    v = f(v, dpp<0x4E>(v));
-    v = f(v, dpp<0x141>(v));
-    v = f(v, dpp<0x140>(v));
-    return v;
-}
-template <typename T>
-__device__ __forceinline__ T row_min(T v) {
-    return row_all(v, [](T a, T b) { return a < b ? a : b; });
-}
-template <typename T>
-__device__ __forceinline__ T row_max(T v) {
-    return row_all(v, [](T a, T b) { return a > b ? a : b; });
-}
-
-// one line of a record as aligned 16-byte words: bytes [s, s + len) of the words from w0 on
-struct Line {
-    const uint4* w0;
-    uint32_t s;
-    uint32_t n_words;
-};
-__device__ __forceinline__ Line make_line(const uint8_t* text, uint32_t start, uint32_t len) {
-    const uint8_t* p = text + start;
-    Line L;
-    L.s = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u);
-    L.w0 = reinterpret_cast<const uint4*>(p - L.s);
-    L.n_words = len ? (uint32_t)(((uint64_t)L.s + len + 15) >> 4) : 0;  // every word holds at least one byte of the line
-    return L;
-}
-
-__device__ __forceinline__ uint32_t differing_bytes(uint32_t x) {
-    return (uint32_t)__popc((((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u);
-}
-// 0xFF in every byte of w that equals c
-__device__ __forceinline__ uint32_t bytes_eq(uint32_t w, uint32_t c) {
-    const uint32_t z = w ^ (c * 0x01010101u);
-    return ((~(((z & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | z) & 0x80808080u) >> 7) * 0xFFu;
-}
 // four bytes of R2, in place: the complement of a letter of ACGT (either case) in upper case, a byte with bit 5 set for any other
 __device__ __forceinline__ uint32_t complement4(uint32_t w) {
     w &= 0xDFDFDFDFu;
@@ -158,7 +106,7 @@ template <typename T, typename ACCEPT>
 __device__ __forceinline__ T find_insert(const ACCEPT& accept, T L1, T L2, T min_overlap, uint32_t sub) {
     if (min(L1, L2) < min_overlap) return 0;  // ov(I) <= min(L1, L2)
     const T M = max(L1, L2), hi = L1 + L2 - min_overlap;  // I >= M: ov = L1 + L2 - I, so I <= hi; hi >= M here
-    for (T I0 = M; I0 <= hi; I0 += PT_GROUP) {
+    for (T I0 = M; I0 <= hi; I0 += ROW) {
         const T I = I0 + sub;
         T hit = ~(T)0;
         if (I <= hi && accept(I)) hit = I;
@@ -166,7 +114,7 @@ __device__ __forceinline__ T find_insert(const ACCEPT& accept, T L1, T L2, T min
         if (hit != ~(T)0) return hit;
     }
     // I < M: ov <= I, so I >= min_overlap (>= 1)
-    for (T top = M; top > min_overlap; top = top > PT_GROUP ? top - PT_GROUP : 0) {  // this round: I = top - 1 - sub
+    for (T top = M; top > min_overlap; top = top > ROW ? top - ROW : 0) {  // this round: I = top - 1 - sub
         T hit = 0;
         if (top > sub && top - 1 - sub >= min_overlap && accept(top - 1 - sub)) hit = top - 1 - sub;
         hit = row_max(hit);
@@ -176,12 +124,12 @@ __device__ __forceinline__ T find_insert(const ACCEPT& accept, T L1, T L2, T min
 }
 
 __global__ __launch_bounds__(PT_BLOCK) void pairtrim(qd_pairtrim_dev P, qd_pairtrim_args a, uint32_t n) {
-    __shared__ uint4 slab[PT_GROUPS][2][PT_SLAB_WORDS];  // per row: R1 folded, R2 reverse-complemented
+    __shared__ uint4 slab[PT_GROUPS][2][SLAB_WORDS];  // per row: R1 folded, R2 reverse-complemented
     __shared__ uint32_t hist[QD_PT_BINS];
     __shared__ unsigned long long part[PT_SCALARS];
     for (uint32_t i = threadIdx.x; i < QD_PT_BINS; i += PT_BLOCK) hist[i] = 0;
     if (threadIdx.x < PT_SCALARS) part[threadIdx.x] = 0;
-    const uint32_t sub = threadIdx.x & (PT_GROUP - 1), group = threadIdx.x / PT_GROUP;
+    const uint32_t sub = threadIdx.x & (ROW - 1), group = threadIdx.x / ROW;
     uint4* sa = slab[group][0];
     uint4* sb = slab[group][1];
     const Budget B{P.min_overlap, P.max_mismatches, P.mismatch_pct};
@@ -197,19 +145,12 @@ __global__ __launch_bounds__(PT_BLOCK) void pairtrim(qd_pairtrim_dev P, qd_pairt
         }
         const uint32_t L[2] = {rec[0].seq_len, rec[1].seq_len};
         const Line l1 = make_line(a.text[0], rec[0].seq, L[0]), l2 = make_line(a.text[1], rec[1].seq, L[1]);
-        const bool staged = l1.n_words <= PT_FAST_WORDS && l2.n_words <= PT_FAST_WORDS;
+        const bool staged = l1.n_words <= FAST_WORDS && l2.n_words <= FAST_WORDS;
         const bool search = min(L[0], L[1]) >= P.min_overlap;  // otherwise no candidate has overlap enough: nothing is read
         __syncthreads();  // the row's earlier pair is done with the slab (and, the first time, the partials are zero)
         if (staged && search) {
-            for (uint32_t k = sub; k < l1.n_words; k += PT_GROUP) {
-                uint4 v = l1.w0[k];
-                v.x &= 0xDFDFDFDFu;
-                v.y &= 0xDFDFDFDFu;
-                v.z &= 0xDFDFDFDFu;
-                v.w &= 0xDFDFDFDFu;
-                sa[k] = v;
-            }
-            for (uint32_t k = sub; k < l2.n_words; k += PT_GROUP) {
+            stage_line<true>(sa, l1, sub);
+            for (uint32_t k = sub; k < l2.n_words; k += ROW) {
                 const uint4 v = l2.w0[k];
                 uint4 o;
                 o.x = __builtin_bswap32(complement4(v.w));
@@ -265,11 +206,8 @@ __global__ __launch_bounds__(PT_BLOCK) void pairtrim(qd_pairtrim_dev P, qd_pairt
             acc += add;
         }
     }
-    __syncthreads();
-    if (sub < PT_SCALARS && acc) atomicAdd(&part[sub], (unsigned long long)acc);
-    __syncthreads();
     unsigned long long* table = reinterpret_cast<unsigned long long*>(a.table);
-    if (threadIdx.x < PT_SCALARS && part[threadIdx.x]) atomicAdd(table + threadIdx.x, part[threadIdx.x]);
+    flush_row_counters<PT_SCALARS>(acc, sub, part, table);
     for (uint32_t i = threadIdx.x; i < QD_PT_BINS; i += PT_BLOCK)
         if (hist[i]) atomicAdd(table + QD_PT_HIST + i, (unsigned long long)hist[i]);
 }

@@ -1,78 +1,27 @@
 // gfx950 (CDNA4 / MI355X): yield and quality counters per destination (qd_qstats_enable), one pass over the sequence and
 // quality lines of a batch's insert reads while their text sits in HBM.
 //
-// Shape: 16 lanes (one DPP row) share a pair.  Each of the pair's four lines (R1 / R2 sequence and quality) is read as
-// 16-byte aligned words, one word per lane, head and tail masked: 256 bytes per step, so a 2 x 150 bp pair costs four
+// Shape (quade_row.h's counting stage): 16 lanes (one DPP row) share a pair.  Each of the pair's four lines (R1 / R2 sequence
+// and quality) is read one aligned word per lane, head and tail masked: 256 bytes per step, so a 2 x 150 bp pair costs four
 // loads per lane, all in flight together.  The bytes are counted four at a time in 32-bit words (SWAR compares, popcount,
-// v_sad_u8 for the byte sum), summed over the row with DPP, and lanes 0 .. 11 then hold the pair's 12 values, one each:
-//   S small  : one LDS add per pair into the workgroup's 32-bit partials, flushed (non-zero entries, 64-bit global
-//              atomics) once per workgroup.  A few destinations receive most pairs: the hot words stay in LDS.
-//   S large  : the partials no longer fit; contention is low.  The wave's four pairs are merged where their destinations
-//              are equal, then 12 contiguous 64-bit global atomics per distinct destination.
+// v_sad_u8 for the byte sum), summed over the row with DPP, and lanes 0 .. 11 then hold the pair's 12 values, one each, for
+// quade_row.h's DestTable: LDS partials for a small S, merged global atomics for a large one.
 #include <hip/hip_runtime.h>
 
+#include "quade_row.h"
 #include "quade_qstats.h"
 
 namespace {
 
 constexpr uint32_t QS_BLOCK = 256;
-constexpr uint32_t QS_GROUP = 16;                   // lanes per pair: one DPP row
-constexpr uint32_t QS_GROUPS = QS_BLOCK / QS_GROUP; // pairs per step of a workgroup
+constexpr uint32_t QS_GROUPS = QS_BLOCK / ROW;      // pairs per step of a workgroup
 constexpr uint32_t QS_WG_PAIRS = 2048;              // pairs per workgroup
 constexpr uint32_t QS_LDS_MAX_LEN = 2047;           // longer reads bypass the 32-bit partials
 constexpr uint32_t QS_MAX_Q = 255 - 33;
 // the largest 32-bit partial is a destination's qual_sum when it receives every pair of the workgroup
 static_assert((uint64_t)QS_WG_PAIRS * QS_MAX_Q * QS_LDS_MAX_LEN <= 0xFFFFFFFFull, "a workgroup's LDS partials can overflow");
 static_assert(QD_QS_LDS_MAX_DEST * QD_QS_VALUES * 4 <= 65536, "the LDS partials exceed 64 KiB");
-static_assert(QS_WG_PAIRS % QS_GROUPS == 0 && QD_QS_VALUES <= QS_GROUP, "one lane per value");
-
-// sum over the 16 lanes of a row, in every lane (all lanes of the wave active)
-__device__ __forceinline__ uint32_t row_sum(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false);  // row_half_mirror
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false);  // row_mirror
-    return v;
-}
-
-// 0x80 in every byte of w that is >= t (bytes unsigned, 1 <= t <= 128)
-__device__ __forceinline__ uint32_t bytes_ge(uint32_t w, uint32_t t) {
-    return (((w & 0x7F7F7F7Fu) + (0x80u - t) * 0x01010101u) | w) & 0x80808080u;
-}
-
-// one line of a record as aligned 16-byte words: bytes [s, e) of the words from w0 on
-struct Line {
-    const uint4* w0;
-    uint32_t s;
-    uint32_t n_words;
-    uint64_t e;
-};
-__device__ __forceinline__ Line make_line(const uint8_t* text, uint32_t start, uint32_t len) {
-    const uint8_t* p = text + start;
-    Line L;
-    L.s = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u);
-    L.w0 = reinterpret_cast<const uint4*>(p - L.s);
-    L.e = (uint64_t)L.s + len;
-    L.n_words = len ? (uint32_t)((L.e + 15) >> 4) : 0;  // every word holds at least one byte of the line
-    return L;
-}
-// the bytes of [s, e) among the four at o .. o + 3
-__device__ __forceinline__ uint32_t byte_mask(int64_t s, int64_t e, int64_t o) {
-    const int64_t lo = s > o ? s - o : 0, hi = e - o < 4 ? e - o : 4;
-    if (hi <= lo) return 0;
-    const uint32_t upto = hi >= 4 ? 0xFFFFFFFFu : (1u << (8 * (uint32_t)hi)) - 1u;
-    return upto & ~((1u << (8 * (uint32_t)lo)) - 1u);
-}
-__device__ __forceinline__ uint4 mask_word(const Line& L, uint32_t k, uint4 v) {
-    if (k == 0 || k + 1 == L.n_words) {
-        const int64_t o = (int64_t)k * 16;
-        v.x &= byte_mask(L.s, (int64_t)L.e, o);
-        v.y &= byte_mask(L.s, (int64_t)L.e, o + 4);
-        v.z &= byte_mask(L.s, (int64_t)L.e, o + 8);
-        v.w &= byte_mask(L.s, (int64_t)L.e, o + 12);
-    }
-    return v;
-}
+static_assert(QS_WG_PAIRS % QS_GROUPS == 0, "whole steps");
 
 struct ReadSums {  // one lane's share of a read
     uint32_t q20, q30, nn;
@@ -84,7 +33,7 @@ __device__ __forceinline__ void add_seq(uint4 v, ReadSums& a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const uint32_t y = (w[i] | 0x20202020u) ^ 0x6E6E6E6Eu;  // zero bytes: 'N' and 'n' only
-        a.nn += __popc(~(((y & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | y) & 0x80808080u);
+        a.nn += __popc(~bytes_nz(y) & 0x80808080u);
     }
 }
 __device__ __forceinline__ void add_qual(uint4 v, ReadSums& a) {
@@ -104,12 +53,10 @@ __device__ __forceinline__ void add_qual(uint4 v, ReadSums& a) {
 template <bool LDS>
 __global__ __launch_bounds__(QS_BLOCK) void qstats(qd_qstats_args a, uint32_t n_samples, uint32_t n) {
     extern __shared__ uint32_t part[];  // LDS path: [n_dest][QD_QS_VALUES]
-    const uint32_t n_dest = 2 * n_samples + 1, n_values = n_dest * QD_QS_VALUES;
-    if (LDS) {
-        for (uint32_t i = threadIdx.x; i < n_values; i += QS_BLOCK) part[i] = 0;
-        __syncthreads();
-    }
-    const uint32_t sub = threadIdx.x & (QS_GROUP - 1), group = threadIdx.x / QS_GROUP;
+    const uint32_t n_dest = 2 * n_samples + 1;
+    const DestTable<LDS, QD_QS_VALUES, QS_BLOCK> table{part, reinterpret_cast<unsigned long long*>(a.table), n_dest * QD_QS_VALUES};
+    table.init();
+    const uint32_t sub = threadIdx.x & (ROW - 1), group = threadIdx.x / ROW;
     const uint32_t first = blockIdx.x * QS_WG_PAIRS, last = min(n, first + QS_WG_PAIRS);
     for (uint32_t j0 = first; j0 < last; j0 += QS_GROUPS) {  // (the same trips for every wave: the DPP sums need whole waves)
         const uint32_t j = j0 + group;
@@ -141,9 +88,9 @@ __global__ __launch_bounds__(QS_BLOCK) void qstats(qd_qstats_args a, uint32_t n_
             s[r] = ReadSums{0, 0, 0, 0};
             add_seq(mask_word(line[2 * r], sub, w[2 * r]), s[r]);  // (a lane beyond the line holds zeros)
             add_qual(mask_word(line[2 * r + 1], sub, w[2 * r + 1]), s[r]);
-            for (uint32_t k = sub + QS_GROUP; k < line[2 * r].n_words; k += QS_GROUP)  // reads longer than 241 .. 256 bases
+            for (uint32_t k = sub + ROW; k < line[2 * r].n_words; k += ROW)  // reads longer than 241 .. 256 bases
                 add_seq(mask_word(line[2 * r], k, line[2 * r].w0[k]), s[r]);
-            for (uint32_t k = sub + QS_GROUP; k < line[2 * r + 1].n_words; k += QS_GROUP)
+            for (uint32_t k = sub + ROW; k < line[2 * r + 1].n_words; k += ROW)
                 add_qual(mask_word(line[2 * r + 1], k, line[2 * r + 1].w0[k]), s[r]);
         }
         // the pair's 12 values, value i in lane i of the row
@@ -161,35 +108,9 @@ __global__ __launch_bounds__(QS_BLOCK) void qstats(qd_qstats_args a, uint32_t n_
             if (i == QD_QS_Q30) v = q30;
             if (i == QD_QS_N) v = nn;
         }
-        const bool mine = valid && sub < QD_QS_VALUES;
-        if (LDS) {
-            if (mine && v) {
-                if (len[0] <= QS_LDS_MAX_LEN && len[1] <= QS_LDS_MAX_LEN) atomicAdd(&part[d * QD_QS_VALUES + sub], (uint32_t)v);
-                else atomicAdd(reinterpret_cast<unsigned long long*>(a.table) + (size_t)d * QD_QS_VALUES + sub, (unsigned long long)v);
-            }
-        } else {
-            // the wave's four pairs: the first of each destination adds for the later ones
-            bool leader = true;
-            uint64_t total = v;
-#pragma unroll
-            for (uint32_t h = 0; h < 64 / QS_GROUP; ++h) {
-                const uint32_t dh = __shfl(d, (int)(h * QS_GROUP), 64);
-                const unsigned long long vh = __shfl((unsigned long long)v, (int)(h * QS_GROUP + sub), 64);
-                const uint32_t me = (threadIdx.x & 63u) / QS_GROUP;
-                if (dh == d && h < me) leader = false;
-                if (dh == d && h > me) total += vh;
-            }
-            if (mine && leader && total)
-                atomicAdd(reinterpret_cast<unsigned long long*>(a.table) + (size_t)d * QD_QS_VALUES + sub, (unsigned long long)total);
-        }
+        table.add(d, sub, v, valid && sub < QD_QS_VALUES, len[0] <= QS_LDS_MAX_LEN && len[1] <= QS_LDS_MAX_LEN);
     }
-    if (LDS) {
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < n_values; i += QS_BLOCK) {
-            const uint32_t c = part[i];
-            if (c) atomicAdd(reinterpret_cast<unsigned long long*>(a.table) + i, (unsigned long long)c);
-        }
-    }
+    table.flush();
 }
 
 }  // namespace

@@ -711,6 +711,39 @@ class Engine(object):
             if n > 0:
                 return keys[:n], counts[:n]
 
+    # -- the read stages: what their dev_* and *_add methods share
+    @staticmethod
+    def _pair_inputs(text1, recs1, text2, recs2, codes=None, drop=None):
+        """A batch as the qd_dev_* entries take it: texts as bytes or uint8 arrays, recs uint32[n, 6] in dev_fastq_scan's layout,
+        codes None or uint16[n], drop None or uint8[n] -> (the two texts, the two record tables, codes, drop, n), contiguous."""
+        t = [np.frombuffer(bytes(x), dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, dtype=np.uint8)
+             for x in (text1, text2)]
+        r = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, 6) for x in (recs1, recs2)]
+        n = r[0].shape[0]
+        if codes is None:
+            if r[1].shape[0] != n:
+                raise ValueError("recs1 and recs2 must have one entry per pair")
+        else:
+            codes = np.ascontiguousarray(codes, dtype=np.uint16).reshape(-1)
+            if not (r[1].shape[0] == n == codes.size):
+                raise ValueError("recs1, recs2 and codes must have one entry per pair")
+        if drop is not None:
+            drop = np.ascontiguousarray(drop, dtype=np.uint8)
+            if drop.shape != (n,):
+                raise ValueError("drop must have one byte per pair")
+        return t, r, codes, drop, n
+
+    def _dev_recs(self, fn, text1, recs1, text2, recs2):
+        """a stage that writes new record tables (qd_dev_clip, qd_dev_trim, qd_dev_pairtrim) -> the two tables"""
+        t, r, _, _, n = self._pair_inputs(text1, recs1, text2, recs2)
+        out = [np.zeros_like(x) for x in r]
+        self._chk(fn(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), n, _ptr(out[0]), _ptr(out[1])))
+        return out[0], out[1]
+
+    def _table_add(self, fn, table):
+        table = np.ascontiguousarray(table, dtype=np.uint64)
+        self._chk(fn(self._h, _ptr(table), table.size))
+
     def qstats_enable(self, on=True):
         """Yield and quality counters per destination (qd_qstats_enable): every pair the device pipeline routes adds its two
         insert reads to a device table.  After set_barcodes: set_plan and set_barcodes turn it off, reset_counts zeroes it."""
@@ -724,8 +757,7 @@ class Engine(object):
 
     def qstats_add(self, table):
         """Another context's table (qstats_read's layout) joins this context's (qd_qstats_add)."""
-        table = np.ascontiguousarray(table, dtype=np.uint64)
-        self._chk(self.lib.qd_qstats_add(self._h, _ptr(table), table.size))
+        self._table_add(self.lib.qd_qstats_add, table)
 
     def qstats_kind(self):
         """How a launch accumulates: "lds" (per-workgroup partials) or "global" (64-bit global atomics)."""
@@ -737,14 +769,8 @@ class Engine(object):
     def dev_qstats(self, text1, recs1, text2, recs2, codes):
         """The counters' stage over host buffers (qd_dev_qstats): texts as bytes or uint8 arrays, recs uint32[n, 6] in
         dev_fastq_scan's layout, codes uint16[n]; adds to the context's table."""
-        t = [np.frombuffer(bytes(x), dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, dtype=np.uint8)
-             for x in (text1, text2)]
-        r = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, 6) for x in (recs1, recs2)]
-        codes = np.ascontiguousarray(codes, dtype=np.uint16)
-        if not (r[0].shape[0] == r[1].shape[0] == codes.size):
-            raise ValueError("recs1, recs2 and codes must have one entry per pair")
-        self._chk(self.lib.qd_dev_qstats(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]),
-                                         codes.size, _ptr(codes)))
+        t, r, codes, _, n = self._pair_inputs(text1, recs1, text2, recs2, codes)
+        self._chk(self.lib.qd_dev_qstats(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), n, _ptr(codes)))
 
     def clip_set(self, front_clip_r1=0, front_clip_r2=0, tail_clip_r1=0, tail_clip_r2=0, window_size=0, window_quality=0,
                  poly_g_min_length=0, min_length=0):
@@ -777,21 +803,12 @@ class Engine(object):
 
     def clip_add(self, table):
         """Another context's counters (clip_read's layout) join this context's (qd_clip_add)."""
-        table = np.ascontiguousarray(table, dtype=np.uint64)
-        self._chk(self.lib.qd_clip_add(self._h, _ptr(table), table.size))
+        self._table_add(self.lib.qd_clip_add, table)
 
     def dev_clip(self, text1, recs1, text2, recs2):
         """The clip stage over host buffers (qd_dev_clip): texts as bytes or uint8 arrays, recs uint32[n, 6] in dev_fastq_scan's
         layout; -> the two tables as the stage leaves them (seq, qual and seq_len change); adds to the context's counters."""
-        t = [np.frombuffer(bytes(x), dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, dtype=np.uint8)
-             for x in (text1, text2)]
-        r = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, 6) for x in (recs1, recs2)]
-        if r[0].shape[0] != r[1].shape[0]:
-            raise ValueError("recs1 and recs2 must have one entry per pair")
-        out = [np.zeros_like(x) for x in r]
-        self._chk(self.lib.qd_dev_clip(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), r[0].shape[0],
-                                       _ptr(out[0]), _ptr(out[1])))
-        return out[0], out[1]
+        return self._dev_recs(self.lib.qd_dev_clip, text1, recs1, text2, recs2)
 
     def trim_set(self, adapter_r1="", adapter_r2="", quality_cutoff=0, min_overlap=3, max_mismatch_pct=10, min_length=0):
         """3' trimming of the insert reads in the device pipeline (qd_trim_set; conf.TRIM_HELP has the rules).  Neither an adapter
@@ -821,21 +838,12 @@ class Engine(object):
 
     def trim_add(self, table):
         """Another context's counters (trim_read's layout) join this context's (qd_trim_add)."""
-        table = np.ascontiguousarray(table, dtype=np.uint64)
-        self._chk(self.lib.qd_trim_add(self._h, _ptr(table), table.size))
+        self._table_add(self.lib.qd_trim_add, table)
 
     def dev_trim(self, text1, recs1, text2, recs2):
         """The trimming stage over host buffers (qd_dev_trim): texts as bytes or uint8 arrays, recs uint32[n, 6] in
         dev_fastq_scan's layout; -> the two tables with the lengths the reads keep; adds to the context's counters."""
-        t = [np.frombuffer(bytes(x), dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, dtype=np.uint8)
-             for x in (text1, text2)]
-        r = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, 6) for x in (recs1, recs2)]
-        if r[0].shape[0] != r[1].shape[0]:
-            raise ValueError("recs1 and recs2 must have one entry per pair")
-        out = [np.zeros_like(x) for x in r]
-        self._chk(self.lib.qd_dev_trim(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), r[0].shape[0],
-                                       _ptr(out[0]), _ptr(out[1])))
-        return out[0], out[1]
+        return self._dev_recs(self.lib.qd_dev_trim, text1, recs1, text2, recs2)
 
     def pairtrim_set(self, min_overlap=30, max_mismatches=5, max_mismatch_pct=20, min_length=0, on=True):
         """Paired-end overlap trimming of the insert reads in the device pipeline (qd_pairtrim_set; conf.PAIR_HELP has the
@@ -860,21 +868,12 @@ class Engine(object):
 
     def pairtrim_add(self, table):
         """Another context's table (pairtrim_read's layout) joins this context's (qd_pairtrim_add)."""
-        table = np.ascontiguousarray(table, dtype=np.uint64)
-        self._chk(self.lib.qd_pairtrim_add(self._h, _ptr(table), table.size))
+        self._table_add(self.lib.qd_pairtrim_add, table)
 
     def dev_pairtrim(self, text1, recs1, text2, recs2):
         """The overlap trimming stage over host buffers (qd_dev_pairtrim): texts as bytes or uint8 arrays, recs uint32[n, 6] in
         dev_fastq_scan's layout; -> the two tables with the lengths the reads keep; adds to the context's table."""
-        t = [np.frombuffer(bytes(x), dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, dtype=np.uint8)
-             for x in (text1, text2)]
-        r = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, 6) for x in (recs1, recs2)]
-        if r[0].shape[0] != r[1].shape[0]:
-            raise ValueError("recs1 and recs2 must have one entry per pair")
-        out = [np.zeros_like(x) for x in r]
-        self._chk(self.lib.qd_dev_pairtrim(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), r[0].shape[0],
-                                           _ptr(out[0]), _ptr(out[1])))
-        return out[0], out[1]
+        return self._dev_recs(self.lib.qd_dev_pairtrim, text1, recs1, text2, recs2)
 
     def filter_set(self, min_length=None, max_n=None, max_unqualified_pct=None, qualified_quality=15, min_mean_quality=None,
                    min_complexity_pct=None, on=True):
@@ -903,8 +902,7 @@ class Engine(object):
 
     def filter_add(self, table):
         """Another context's table (filter_read's layout) joins this context's (qd_filter_add)."""
-        table = np.ascontiguousarray(table, dtype=np.uint64)
-        self._chk(self.lib.qd_filter_add(self._h, _ptr(table), table.size))
+        self._table_add(self.lib.qd_filter_add, table)
 
     def filter_kind(self):
         """FILTER_KIND_LDS or FILTER_KIND_GLOBAL: the accumulation the kernel takes for this context's sample count"""
@@ -917,15 +915,9 @@ class Engine(object):
         """The filter stage over host buffers (qd_dev_filter): texts as bytes or uint8 arrays, recs uint32[n, 6] in
         dev_fastq_scan's layout, codes uint16[n]; -> uint8[n], 0 = kept or the rule that dropped the pair; adds to the
         context's table."""
-        t = [np.frombuffer(bytes(x), dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, dtype=np.uint8)
-             for x in (text1, text2)]
-        r = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, 6) for x in (recs1, recs2)]
-        codes = np.ascontiguousarray(codes, dtype=np.uint16)
-        if r[0].shape[0] != r[1].shape[0] or codes.shape != (r[0].shape[0],):
-            raise ValueError("recs1, recs2 and codes must have one entry per pair")
-        out = np.zeros(codes.size, dtype=np.uint8)
-        self._chk(self.lib.qd_dev_filter(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), codes.size,
-                                         _ptr(codes), _ptr(out)))
+        t, r, codes, _, n = self._pair_inputs(text1, recs1, text2, recs2, codes)
+        out = np.zeros(n, dtype=np.uint8)
+        self._chk(self.lib.qd_dev_filter(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), n, _ptr(codes), _ptr(out)))
         return out
 
     def cstats_enable(self, on=True):
@@ -942,25 +934,15 @@ class Engine(object):
 
     def cstats_add(self, table):
         """Another context's table (cstats_read's dict or flat) joins this context's (qd_cstats_add)."""
-        flat = cstats_flat(table) if isinstance(table, dict) else np.ascontiguousarray(table, dtype=np.uint64).reshape(-1)
-        self._chk(self.lib.qd_cstats_add(self._h, _ptr(flat), flat.size))
+        self._table_add(self.lib.qd_cstats_add, cstats_flat(table) if isinstance(table, dict) else np.reshape(table, -1))
 
     def dev_cstats(self, text1, recs1, text2, recs2, codes, drop=None):
         """The per-cycle stage over host buffers (qd_dev_cstats): texts as bytes or uint8 arrays, recs uint32[n, 6] in
         dev_fastq_scan's layout, codes uint16[n], drop None or uint8[n] (non-zero = the pair is skipped); adds to the context's
         table."""
-        t = [np.frombuffer(bytes(x), dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x, dtype=np.uint8)
-             for x in (text1, text2)]
-        r = [np.ascontiguousarray(x, dtype=np.uint32).reshape(-1, 6) for x in (recs1, recs2)]
-        codes = np.ascontiguousarray(codes, dtype=np.uint16)
-        if r[0].shape[0] != r[1].shape[0] or codes.shape != (r[0].shape[0],):
-            raise ValueError("recs1, recs2 and codes must have one entry per pair")
-        if drop is not None:
-            drop = np.ascontiguousarray(drop, dtype=np.uint8)
-            if drop.shape != codes.shape:
-                raise ValueError("drop must have one byte per pair")
-        self._chk(self.lib.qd_dev_cstats(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), codes.size,
-                                         _ptr(codes), _ptr(drop) if drop is not None else None))
+        t, r, codes, drop, n = self._pair_inputs(text1, recs1, text2, recs2, codes, drop)
+        self._chk(self.lib.qd_dev_cstats(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), n, _ptr(codes),
+                                         _ptr(drop) if drop is not None else None))
 
     def set_option(self, name, value):
         self._chk(self.lib.qd_set_option(self._h, name.encode(), int(value)))

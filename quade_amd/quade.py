@@ -335,102 +335,47 @@ class Quade(object):
             short, dropped = sum(p[2] for p in parts), sum(p[3] for p in parts)
         return keys, ucounts, short, dropped
 
-    def _collect_quality(self):
-        """[output] quality_report: the tables of every context of this process summed (chunk workers, devices); with several
-        ranks every rank publishes its sum in the rendezvous directory and adds all of them (rank 0 writes the file).
-        Returns uint64[2S+1, 2, 6]."""
+    def _collect(self, read, name, pack, unpack):
+        """A read stage's tables (read(engine) -> uint64 array) of every context of this process summed (chunk workers, devices);
+        with several ranks every rank publishes its sum in the rendezvous directory under `name` (pack / unpack: its bytes there)
+        and adds all of them (rank 0 writes the file)."""
         from . import dist
         table = None
         for eng in self.engines:
-            t = eng.qstats_read()
+            t = read(eng)
             table = t if table is None else table + t
         if self.world > 1:
-            got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, "quality", hb.pack_qstats(table))
-            tables = [hb.unpack_qstats(b) for b in got]
+            got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, name, pack(table))
+            tables = [unpack(b) for b in got]
             table = tables[0]
             for t in tables[1:]:
                 table = table + t
         return table
+
+    def _collect_quality(self):
+        """[output] quality_report: _collect's sum, uint64[2S+1, 2, 6]."""
+        return self._collect(lambda eng: eng.qstats_read(), "quality", hb.pack_qstats, hb.unpack_qstats)
 
     def _collect_clip(self):
-        """[trim] clipping: the counters of every context of this process summed (chunk workers, devices); with several ranks every
-        rank publishes its sum in the rendezvous directory and adds all of them (rank 0 writes the file).  Returns uint64[2, 12]."""
-        from . import dist
-        table = None
-        for eng in self.engines:
-            t = eng.clip_read()
-            table = t if table is None else table + t
-        if self.world > 1:
-            got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, "clip", hb.pack_clip(table))
-            tables = [hb.unpack_clip(b) for b in got]
-            table = tables[0]
-            for t in tables[1:]:
-                table = table + t
-        return table
+        """[trim] clipping: _collect's sum, uint64[2, 12]."""
+        return self._collect(lambda eng: eng.clip_read(), "clip", hb.pack_clip, hb.unpack_clip)
 
     def _collect_trim(self):
-        """[trim]: the counters of every context of this process summed (chunk workers, devices); with several ranks every rank
-        publishes its sum in the rendezvous directory and adds all of them (rank 0 writes the file).  Returns uint64[2, 8]."""
-        from . import dist
-        table = None
-        for eng in self.engines:
-            t = eng.trim_read()
-            table = t if table is None else table + t
-        if self.world > 1:
-            got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, "trim", hb.pack_trim(table))
-            tables = [hb.unpack_trim(b) for b in got]
-            table = tables[0]
-            for t in tables[1:]:
-                table = table + t
-        return table
+        """[trim]: _collect's sum, uint64[2, 8]."""
+        return self._collect(lambda eng: eng.trim_read(), "trim", hb.pack_trim, hb.unpack_trim)
 
     def _collect_pair_trim(self):
-        """[trim] pair_overlap: the tables of every context of this process summed (chunk workers, devices); with several ranks
-        every rank publishes its sum in the rendezvous directory and adds all of them (rank 0 writes the file).  Returns
-        uint64[1040]."""
-        from . import dist
-        table = None
-        for eng in self.engines:
-            t = eng.pairtrim_read()
-            table = t if table is None else table + t
-        if self.world > 1:
-            got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, "pairtrim", hb.pack_pairtrim(table))
-            tables = [hb.unpack_pairtrim(b) for b in got]
-            table = tables[0]
-            for t in tables[1:]:
-                table = table + t
-        return table
+        """[trim] pair_overlap: _collect's sum, uint64[1040]."""
+        return self._collect(lambda eng: eng.pairtrim_read(), "pairtrim", hb.pack_pairtrim, hb.unpack_pairtrim)
 
     def _collect_filter(self):
-        """[filter]: the tables of every context of this process summed (chunk workers, devices); with several ranks every rank
-        publishes its sum in the rendezvous directory and adds all of them (rank 0 writes the file).  Returns uint64[2S+1, 8]."""
-        from . import dist
-        table = None
-        for eng in self.engines:
-            t = eng.filter_read()
-            table = t if table is None else table + t
-        if self.world > 1:
-            got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, "filter", hb.pack_filter(table))
-            tables = [hb.unpack_filter(b) for b in got]
-            table = tables[0]
-            for t in tables[1:]:
-                table = table + t
-        return table
+        """[filter]: _collect's sum, uint64[2S+1, 8]."""
+        return self._collect(lambda eng: eng.filter_read(), "filter", hb.pack_filter, hb.unpack_filter)
 
     def _collect_cycles(self):
-        """[output] cycle_report: the tables of every context of this process summed (chunk workers, devices); with several
-        ranks every rank publishes its sum in the rendezvous directory and adds all of them (rank 0 writes the file).
-        Returns hip_backend.cstats_views' dict."""
-        from . import dist
-        flat = None
-        for eng in self.engines:
-            t = hb.cstats_flat(eng.cstats_read())
-            flat = t if flat is None else flat + t
-        if self.world > 1:
-            got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, "cycle", hb.pack_cstats(flat))
-            flat = hb.cstats_flat(hb.unpack_cstats(got[0]))
-            for b in got[1:]:
-                flat = flat + hb.cstats_flat(hb.unpack_cstats(b))
+        """[output] cycle_report: _collect's sum over the flat tables, as hip_backend.cstats_views' dict."""
+        flat = self._collect(lambda eng: hb.cstats_flat(eng.cstats_read()), "cycle", hb.pack_cstats,
+                             lambda b: hb.cstats_flat(hb.unpack_cstats(b)))
         return hb.cstats_views(flat)
 
     def double_index_parser(self):
