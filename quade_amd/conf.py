@@ -362,10 +362,8 @@ class QuadeConf(object):
         assert 0 <= self.top_unknown_barcodes <= 1000, "Authorized values for top_unknown_barcodes : 0 to 1000"
         assert 1 << 10 <= self.unknown_slots <= 1 << 28 and self.unknown_slots & (self.unknown_slots - 1) == 0, \
             "[gpu] unknown_slots : a power of two, 1024 to 268435456"
-        assert not self.quality_report or (self.device_pipeline and self.device_inflate and self.device_deflate
-                                           and self.gzip_level in (1, -1)), QUALITY_NEEDS
-        assert not self.cycle_report or (self.device_pipeline and self.device_inflate and self.device_deflate
-                                         and self.gzip_level in (1, -1)), CYCLE_NEEDS
+        assert not self.quality_report or self.can_pipe, QUALITY_NEEDS
+        assert not self.cycle_report or self.can_pipe, CYCLE_NEEDS
         for a in (self.adapter_R1, self.adapter_R2):
             assert len(a) <= 64 and not a.strip("ACGT"), TRIM_ADAPTER
         assert 0 <= self.quality_cutoff <= 93, TRIM_CUTOFF
@@ -373,30 +371,32 @@ class QuadeConf(object):
             TRIM_OVERLAP
         assert 0 <= self.max_mismatch_pct <= 50, TRIM_MISMATCH
         assert 0 <= self.min_length <= 65535, TRIM_LENGTH
-        assert not self.trim or (self.device_pipeline and self.device_inflate and self.device_deflate
-                                 and self.gzip_level in (1, -1)), TRIM_NEEDS
+        assert not self.trim or self.can_pipe, TRIM_NEEDS
         assert all(0 <= v <= 1000 for v in self.front_clip + self.tail_clip), CLIP_FIXED
         assert (self.window_size is None) == (self.window_quality is None), CLIP_WINDOW_BOTH
         assert self.window_size is None or 1 <= self.window_size <= 100, CLIP_WINDOW_SIZE
         assert self.window_quality is None or 1 <= self.window_quality <= 93, CLIP_WINDOW_QUALITY
         assert 6 <= self.poly_g_min_length <= 100, CLIP_POLY_G
-        assert not self.clip or (self.device_pipeline and self.device_inflate and self.device_deflate
-                                 and self.gzip_level in (1, -1)), CLIP_NEEDS
+        assert not self.clip or self.can_pipe, CLIP_NEEDS
         assert 8 <= self.pair_min_overlap <= 1000, PAIR_OVERLAP
         assert 0 <= self.pair_max_mismatches <= 64, PAIR_MISMATCHES
         assert 0 <= self.pair_max_mismatch_pct <= 50, PAIR_MISMATCH_PCT
-        assert not self.pair_trim or (self.device_pipeline and self.device_inflate and self.device_deflate
-                                      and self.gzip_level in (1, -1)), PAIR_NEEDS
+        assert not self.pair_trim or self.can_pipe, PAIR_NEEDS
         for name, value in self.filter_params().items():
             assert value is None or FILTER_RANGES[name][0] <= value <= FILTER_RANGES[name][1], filter_range_message(name)
-        assert not self.filter or (self.device_pipeline and self.device_inflate and self.device_deflate
-                                   and self.gzip_level in (1, -1)), FILTER_NEEDS
+        assert not self.filter or self.can_pipe, FILTER_NEEDS
         for pos in [self.idx1_pos, self.idx2_pos, self.mol1_pos, self.mol2_pos]:
             assert pos["start"] >= 0
             assert pos["end"] >= pos["start"]
         assert self.batch_pairs >= 1 and 1 <= self.slots <= 64 and -1 <= self.gzip_level <= 9 and \
             1 <= self.chunk_workers <= 64 and 0 <= self.io_threads <= 1024, \
             "[gpu] batch_pairs >= 1, 1 <= slots <= 64, -1 <= gzip_level <= 9, 1 <= chunk_workers <= 64, 0 <= io_threads <= 1024"
+
+    @property
+    def can_pipe(self):
+        """the device pipeline can run: every device stage is on and the gzip level is one the device codes; what the read
+        stages need (the *_NEEDS messages) and what Quade takes the pipeline for"""
+        return bool(self.device_pipeline and self.device_inflate and self.device_deflate and self.gzip_level in (1, -1))
 
     @property
     def trim(self):

@@ -12,13 +12,13 @@ len[0..c].  other(c) = reads(c) - A - C - G - T - N.
 from __future__ import annotations
 
 from . import QUADE_VERSION
-from .quality_report import ratio
+from .quality_report import ratio, write_lines
+from .stages import CSTATS_GROUPS as GROUPS  # the table's order; Total follows
 
 REPORT_NAME = "Quade_cycle_report.csv"
 PROGRAM = "Quade-cycle " + QUADE_VERSION.split()[-1]  # (no date: the file can be compared whole)
-GROUPS = ("pass", "fail", "Undetermined")  # the table's order (hip_backend.CSTATS_GROUPS); Total follows
 READS = ("R1", "R2")
-A, C, G, T, N, QUAL_SUM, Q20, Q30 = range(8)  # a cycle's counters (hip_backend.CSTATS_COUNTERS)
+A, C, G, T, N, QUAL_SUM, Q20, Q30 = range(8)  # a cycle's counters (stages.CSTATS_COUNTERS)
 CYCLE_COLUMNS = ("group", "read", "cycle", "reads", "A", "C", "G", "T", "N", "other", "percent_gc", "mean_quality", "q20", "q30",
                  "percent_q20", "percent_q30")
 LAST_LENGTH = ">=1024"  # the label of the last length bin
@@ -83,5 +83,4 @@ def report_lines(table):
 
 
 def write_report(path, table):
-    with open(path, "w") as fh:
-        fh.write("\n".join(report_lines(table)) + "\n")
+    write_lines(path, report_lines(table))

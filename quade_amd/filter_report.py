@@ -8,13 +8,13 @@ kept.  The reference has no counterpart.  Integer arithmetic only and no date, s
 from __future__ import annotations
 
 from . import QUADE_VERSION
-from .quality_report import ratio
+from .quality_report import ratio, write_lines
+from .stages import FILTER_COUNTERS as COUNTERS  # a destination's row of the table
+from .stages import FILTER_KEYS as PARAMS
+from .stages import FILTER_REASONS as REASONS
 
 REPORT_NAME = "Quade_filter_report.csv"
 PROGRAM = "Quade-filter " + QUADE_VERSION.split()[-1]
-REASONS = ("too_short", "too_many_n", "low_quality", "low_mean_quality", "low_complexity")
-COUNTERS = ("pairs",) + REASONS + ("bases_in", "bases_dropped")  # a destination's row of the table (hip_backend.FILTER_COUNTERS)
-PARAMS = ("min_length", "max_n", "max_unqualified_pct", "qualified_quality", "min_mean_quality", "min_complexity_pct")
 COLUMNS = ("destination", "pairs_in", "pairs_kept") + REASONS + ("bases_in", "bases_kept", "percent_pairs_kept", "percent_bases_kept")
 PAIRS, BASES_IN, BASES_DROPPED = 0, 6, 7
 
@@ -42,5 +42,4 @@ def report_lines(table, samples, params):
 
 
 def write_report(path, table, samples, params):
-    with open(path, "w") as fh:
-        fh.write("\n".join(report_lines(table, samples, params)) + "\n")
+    write_lines(path, report_lines(table, samples, params))

@@ -12,6 +12,12 @@ import os
 
 import numpy as np
 
+# the read stages' table layouts, their bytes in the ranks' exchange and the stage table live in stages.py; hb.X reaches them all
+from .stages import (CLIP_COUNTERS, CSTATS_COUNTERS, CSTATS_CYCLES, CSTATS_GC_BINS, CSTATS_GR_VALUES, CSTATS_GROUPS,  # noqa: F401
+                     CSTATS_LEN_BINS, CSTATS_MEANQ_BINS, CSTATS_SECTIONS, CSTATS_VALUES, FILTER_COUNTERS, FILTER_KEYS, FILTER_REASONS,
+                     PAIRTRIM_BINS, PAIRTRIM_COUNTERS, PAIRTRIM_PAIR_COUNTERS, PAIRTRIM_VALUES, QSTATS_COUNTERS, STAGE, STAGES,
+                     TRIM_COUNTERS, cstats_flat, cstats_views, pack_table, split_pairtrim, unpack_table)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libquade_hip.so")
 
@@ -466,152 +472,7 @@ def unpack_unknown(blob):
     return keys, counts, short, dropped
 
 
-QSTATS_COUNTERS = ("records", "bases", "qual_sum", "q20_bases", "q30_bases", "n_bases")  # per destination and read (qd_qstats_*)
-
-
-def pack_qstats(table):
-    """One context's or rank's quality table (uint64[2S+1, 2, 6]) as bytes (the ranks' exchange through the rendezvous
-    directory); unpack_qstats reverses it."""
-    table = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1, 2, len(QSTATS_COUNTERS))
-    return np.array([table.shape[0]], dtype=np.uint64).tobytes() + table.tobytes()
-
-
-def unpack_qstats(blob):
-    """-> uint64[n_dest, 2, 6] (a copy: tables are summed in place)"""
-    n_dest = int(np.frombuffer(blob, dtype=np.uint64, count=1)[0])
-    assert len(blob) == 8 + n_dest * 2 * len(QSTATS_COUNTERS) * 8, "quality table of the wrong size"
-    return np.frombuffer(blob, dtype=np.uint64, offset=8).reshape(n_dest, 2, len(QSTATS_COUNTERS)).copy()
-
-
-CLIP_COUNTERS = ("reads", "bases_in", "bases_out", "front_clipped_reads", "front_clipped_bases", "tail_clipped_reads", "tail_clipped_bases",
-                 "window_reads", "window_bases", "polyg_reads", "polyg_bases", "floored_reads")  # per read R1 / R2 (qd_clip_*)
-
-
-def pack_clip(table):
-    """One context's or rank's clip counters (uint64[2, 12]) as bytes (the ranks' exchange through the rendezvous directory);
-    unpack_clip reverses it."""
-    table = np.ascontiguousarray(table, dtype=np.uint64).reshape(2, len(CLIP_COUNTERS))
-    return table.tobytes()
-
-
-def unpack_clip(blob):
-    """-> uint64[2, 12] (a copy: tables are summed in place)"""
-    assert len(blob) == 2 * len(CLIP_COUNTERS) * 8, "clip counters of the wrong size"
-    return np.frombuffer(blob, dtype=np.uint64).reshape(2, len(CLIP_COUNTERS)).copy()
-
-
-TRIM_COUNTERS = ("reads", "bases_in", "bases_out", "quality_trimmed_reads", "quality_trimmed_bases", "adapter_reads", "adapter_bases",
-                 "floored_reads")  # per read R1 / R2 (qd_trim_*)
-
-
-def pack_trim(table):
-    """One context's or rank's trim counters (uint64[2, 8]) as bytes (the ranks' exchange through the rendezvous directory);
-    unpack_trim reverses it."""
-    table = np.ascontiguousarray(table, dtype=np.uint64).reshape(2, len(TRIM_COUNTERS))
-    return table.tobytes()
-
-
-def unpack_trim(blob):
-    """-> uint64[2, 8] (a copy: tables are summed in place)"""
-    assert len(blob) == 2 * len(TRIM_COUNTERS) * 8, "trim counters of the wrong size"
-    return np.frombuffer(blob, dtype=np.uint64).reshape(2, len(TRIM_COUNTERS)).copy()
-
-
-PAIRTRIM_COUNTERS = ("reads", "bases_in", "bases_out", "overlap_trimmed_reads", "overlap_trimmed_bases", "floored_reads")  # per read
-PAIRTRIM_PAIR_COUNTERS = ("pairs", "overlapped_pairs", "short_insert_pairs")
-PAIRTRIM_BINS = 1025  # insert sizes: bin I for I < 1024, the last bin for I >= 1024
-PAIRTRIM_VALUES = 2 * len(PAIRTRIM_COUNTERS) + len(PAIRTRIM_PAIR_COUNTERS) + PAIRTRIM_BINS  # qd_pairtrim_*'s table: 1040
-
-
-def pack_pairtrim(table):
-    """One context's or rank's overlap trimming table (uint64[1040]) as bytes (the ranks' exchange through the rendezvous
-    directory); unpack_pairtrim reverses it."""
-    table = np.ascontiguousarray(table, dtype=np.uint64).reshape(PAIRTRIM_VALUES)
-    return table.tobytes()
-
-
-def unpack_pairtrim(blob):
-    """-> uint64[1040] (a copy: tables are summed in place)"""
-    assert len(blob) == PAIRTRIM_VALUES * 8, "an overlap trimming table of the wrong size"
-    return np.frombuffer(blob, dtype=np.uint64).copy()
-
-
-def split_pairtrim(table):
-    """a table -> (per read [2][6], the three pair counters, the 1025 insert size bins), Python integers"""
-    t = [int(x) for x in np.asarray(table).reshape(PAIRTRIM_VALUES)]
-    k = len(PAIRTRIM_COUNTERS)
-    return [t[:k], t[k:2 * k]], t[2 * k:2 * k + 3], t[2 * k + 3:]
-
-
-# qd_filter_*: the reasons (the reason byte of a dropped pair is the index + 1), the table's columns and the parameters
-FILTER_REASONS = ("too_short", "too_many_n", "low_quality", "low_mean_quality", "low_complexity")
-FILTER_COUNTERS = ("pairs",) + FILTER_REASONS + ("bases_in", "bases_dropped")  # per destination
-FILTER_KEYS = ("min_length", "max_n", "max_unqualified_pct", "qualified_quality", "min_mean_quality", "min_complexity_pct")
 FILTER_KIND_LDS, FILTER_KIND_GLOBAL = 1, 2
-
-
-def pack_filter(table):
-    """One context's or rank's filter table (uint64[2S+1, 8]) as bytes (the ranks' exchange through the rendezvous directory);
-    unpack_filter reverses it."""
-    table = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1, len(FILTER_COUNTERS))
-    return np.uint64(table.shape[0]).tobytes() + table.tobytes()
-
-
-def unpack_filter(blob):
-    """-> uint64[2S+1, 8] (a copy: tables are summed in place)"""
-    n_dest = int(np.frombuffer(blob[:8], dtype=np.uint64)[0])
-    assert len(blob) == 8 + n_dest * len(FILTER_COUNTERS) * 8, "filter table of the wrong size"
-    return np.frombuffer(blob, dtype=np.uint64, offset=8).reshape(n_dest, len(FILTER_COUNTERS)).copy()
-
-
-# the per-cycle table (qd_cstats_*): uint64, group-major (pass, fail, Undetermined), then read; per (group, read) the sections
-CSTATS_GROUPS = ("pass", "fail", "Undetermined")
-CSTATS_COUNTERS = ("A", "C", "G", "T", "N", "qual_sum", "q20", "q30")  # per cycle
-CSTATS_CYCLES, CSTATS_LEN_BINS, CSTATS_MEANQ_BINS, CSTATS_GC_BINS = 1024, 1025, 94, 101
-CSTATS_SECTIONS = (("cycle", (CSTATS_CYCLES, len(CSTATS_COUNTERS))), ("len", (CSTATS_LEN_BINS,)), ("meanq", (CSTATS_MEANQ_BINS,)),
-                   ("gc", (CSTATS_GC_BINS,)))
-CSTATS_GR_VALUES = CSTATS_CYCLES * len(CSTATS_COUNTERS) + CSTATS_LEN_BINS + CSTATS_MEANQ_BINS + CSTATS_GC_BINS  # 9412
-CSTATS_VALUES = len(CSTATS_GROUPS) * 2 * CSTATS_GR_VALUES  # 56472
-
-
-def cstats_views(flat):
-    """The flat table (uint64[CSTATS_VALUES]) as a dict of views into it: cycle[3, 2, 1024, 8], len[3, 2, 1025],
-    meanq[3, 2, 94], gc[3, 2, 101] -- [group][R1, R2][...]"""
-    flat = np.asarray(flat)
-    assert flat.shape == (CSTATS_VALUES,) and flat.dtype == np.uint64, "cycle table of the wrong size"
-    per = flat.reshape(len(CSTATS_GROUPS), 2, CSTATS_GR_VALUES)
-    out, at = {}, 0
-    for name, shape in CSTATS_SECTIONS:
-        size = int(np.prod(shape))
-        out[name] = per[:, :, at:at + size].reshape((len(CSTATS_GROUPS), 2) + shape)
-        at += size
-    return out
-
-
-def cstats_flat(table):
-    """cstats_views' dict (or a flat table) -> the flat uint64[CSTATS_VALUES] layout of qd_cstats_read"""
-    if not isinstance(table, dict):
-        flat = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1)
-        assert flat.size == CSTATS_VALUES, "cycle table of the wrong size"
-        return flat
-    per = np.concatenate([np.asarray(table[name], dtype=np.uint64).reshape(len(CSTATS_GROUPS), 2, -1) for name, _ in CSTATS_SECTIONS],
-                         axis=2)
-    assert per.shape == (len(CSTATS_GROUPS), 2, CSTATS_GR_VALUES), "cycle table of the wrong size"
-    return np.ascontiguousarray(per).reshape(-1)
-
-
-def pack_cstats(table):
-    """One context's or rank's cycle table (cstats_views' dict or flat) as bytes (the ranks' exchange through the rendezvous
-    directory); unpack_cstats reverses it."""
-    flat = cstats_flat(table)
-    return np.array([flat.size], dtype=np.uint64).tobytes() + flat.tobytes()
-
-
-def unpack_cstats(blob):
-    """-> cstats_views' dict over a writable copy (tables are summed in place)"""
-    n = int(np.frombuffer(blob, dtype=np.uint64, count=1)[0])
-    assert n == CSTATS_VALUES and len(blob) == 8 + n * 8, "cycle table of the wrong size"
-    return cstats_views(np.frombuffer(blob, dtype=np.uint64, offset=8).copy())
 
 
 # ---- device context -------------------------------------------------------------------------------------

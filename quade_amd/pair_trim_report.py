@@ -8,14 +8,14 @@ has no counterpart.  Integer arithmetic only and no date, so that files can be c
 from __future__ import annotations
 
 from . import QUADE_VERSION
-from .quality_report import ratio
+from .quality_report import ratio, read_report_lines, write_lines
+from .stages import PAIRTRIM_BINS as BINS  # insert sizes 0 .. 1023 and ">=1024"
+from .stages import PAIRTRIM_COUNTERS as COUNTERS  # a row per read
+from .stages import PAIRTRIM_PAIR_COUNTERS as PAIR_COUNTERS
+from .stages import PAIRTRIM_VALUES as VALUES  # the table
 
 REPORT_NAME = "Quade_pair_trim_report.csv"
 PROGRAM = "Quade-pair-trim " + QUADE_VERSION.split()[-1]
-COUNTERS = ("reads", "bases_in", "bases_out", "overlap_trimmed_reads", "overlap_trimmed_bases", "floored_reads")  # a row per read
-PAIR_COUNTERS = ("pairs", "overlapped_pairs", "short_insert_pairs")
-BINS = 1025  # insert sizes 0 .. 1023 and ">=1024"
-VALUES = 2 * len(COUNTERS) + len(PAIR_COUNTERS) + BINS  # the table (hip_backend.PAIRTRIM_VALUES)
 COLUMNS = ("read",) + COUNTERS + ("percent_overlap_trimmed_reads", "percent_bases_trimmed")
 PARAMS = ("pair_min_overlap", "pair_max_mismatches", "pair_max_mismatch_pct", "min_length")
 KEYS = ("min_overlap", "max_mismatches", "max_mismatch_pct", "min_length")  # PARAMS as Engine.pairtrim_set's keywords
@@ -23,8 +23,8 @@ READS, BASES_IN, BASES_OUT, CUT_READS, CUT_BASES, FLOORED = range(6)
 PAIRS, OVERLAPPED, SHORT = range(3)
 
 
-def _row(name, c):
-    return "\t".join([name] + [str(x) for x in c] + [ratio(c[CUT_READS], c[READS], 100), ratio(c[BASES_IN] - c[BASES_OUT], c[BASES_IN], 100)])
+def _shares(c):
+    return [ratio(c[CUT_READS], c[READS], 100), ratio(c[BASES_IN] - c[BASES_OUT], c[BASES_IN], 100)]
 
 
 def report_lines(table, params):
@@ -33,11 +33,8 @@ def report_lines(table, params):
     assert len(t) == VALUES, "the table holds 1040 values"
     k = len(COUNTERS)
     rows, pairs, hist = [t[:k], t[k:2 * k]], t[2 * k:2 * k + 3], t[2 * k + 3:]
-    lines = ["Program " + PROGRAM, "", "pair_overlap\tTrue"]
-    lines += ["%s\t%s" % (name, params[key]) for name, key in zip(PARAMS, KEYS)]
-    lines += ["", "\t".join(COLUMNS)]
-    for name, c in (("R1", rows[0]), ("R2", rows[1]), ("Total", [a + b for a, b in zip(*rows)])):
-        lines.append(_row(name, c))
+    lines = read_report_lines(PROGRAM, ["pair_overlap\tTrue"] + ["%s\t%s" % (name, params[key]) for name, key in zip(PARAMS, KEYS)],
+                              COLUMNS, rows, _shares)
     lines.append("")
     lines += ["%s\t%d\t%s" % (name, v, ratio(v, pairs[PAIRS], 100)) for name, v in zip(PAIR_COUNTERS, pairs)]
     lines += ["", "insert_size\tpairs"]
@@ -47,5 +44,4 @@ def report_lines(table, params):
 
 
 def write_report(path, table, params):
-    with open(path, "w") as fh:
-        fh.write("\n".join(report_lines(table, params)) + "\n")
+    write_lines(path, report_lines(table, params))

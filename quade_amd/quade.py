@@ -147,7 +147,7 @@ class Quade(object):
         # with the text resident in HBM; a context drives one pipeline, several contexts (devices, chunk workers) one each
         # with the chunks dealt out to them.  Anything it does not cover (gzip levels the device does not code, the device
         # stages switched off) takes the batch pipeline over pinned slots below.
-        self.use_pipe = bool(cf.device_pipeline and cf.device_inflate and cf.device_deflate and cf.gzip_level in (-1, 1))
+        self.use_pipe = cf.can_pipe
         if self.use_pipe and self.workers * len(devices) > 1:
             self.parts = True  # several pipelines (one per context: devices x chunk workers) each take whole chunks: per-chunk part files
         # One chunk across several ranks (SURVEY.md 8e "large single chunks are split into contiguous row ranges"): with fewer chunks
@@ -167,18 +167,9 @@ class Quade(object):
                     eng.set_mismatches(cf.idx1_mismatches, cf.idx2_mismatches)
                 if cf.top_unknown_barcodes > 0:  # the barcodes of the Undetermined pairs are counted on the device
                     eng.unknown_enable(cf.unknown_slots)
-                if cf.quality_report:  # the insert reads are counted per destination while the pipeline holds their text
-                    eng.qstats_enable(True)
-                if cf.cycle_report:  # ... and per cycle, by pass / fail / Undetermined
-                    eng.cstats_enable(True)
-                if cf.clip:  # the insert reads are clipped (ends, window, poly-G) while the pipeline holds their text
-                    eng.clip_set(**cf.clip_params())
-                if cf.trim:  # ... trimmed at their 3' end while the pipeline holds their text
-                    eng.trim_set(**cf.trim_params())
-                if cf.pair_trim:  # ... and R1 and R2 of a pair together, behind it
-                    eng.pairtrim_set(**cf.pair_trim_params())
-                if cf.filter:  # ... and the pairs not worth keeping leave, behind both
-                    eng.filter_set(**cf.filter_params())
+                for stage in hb.STAGES:  # what the pipeline does to the insert reads while it holds their text, in its order
+                    if stage.on(cf):
+                        stage.enable(eng, cf)
                 if not self.use_pipe:
                     eng.slots_create(cf.slots, cf.batch_pairs)
                 group.append(eng)
@@ -203,13 +194,9 @@ class Quade(object):
         with _timed("drain gzip + close"):
             Sample.FLUSH_ALL()  # every rank's files are complete before its counters join the sum
         counts = self._reduce_counts(devices)
+        # (the unknown-barcode tally is no entry of the stage table: its tables merge by key, they are not added)
         unknown = self._collect_unknown() if cf.top_unknown_barcodes > 0 else None
-        quality = self._collect_quality() if cf.quality_report else None
-        cycles = self._collect_cycles() if cf.cycle_report else None
-        clipped = self._collect_clip() if cf.clip else None
-        trimmed = self._collect_trim() if cf.trim else None
-        pair_trimmed = self._collect_pair_trim() if cf.pair_trim else None
-        filtered = self._collect_filter() if cf.filter else None
+        tables = [(stage, self._collect(stage)) for stage in hb.STAGES if stage.on(cf)]
         for eng in self.engines:
             eng.close()
         self.engines = []
@@ -247,26 +234,8 @@ class Quade(object):
             w1 = cf.idx1_pos["end"] - cf.idx1_pos["start"]
             write_report(os.path.join(self.outdir, REPORT_NAME), keys, ucounts, short, dropped, int(counts[3]),
                          cf.top_unknown_barcodes, w1, bool(cf.idx2), [(s.name, s.index) for s in Sample.SAMPLE_LIST])
-        if quality is not None:
-            from . import quality_report
-            quality_report.write_report(os.path.join(self.outdir, quality_report.REPORT_NAME), quality,
-                                        [s.name for s in Sample.SAMPLE_LIST])
-        if cycles is not None:
-            from . import cycle_report
-            cycle_report.write_report(os.path.join(self.outdir, cycle_report.REPORT_NAME), cycles)
-        if clipped is not None:
-            from . import clip_report
-            clip_report.write_report(os.path.join(self.outdir, clip_report.REPORT_NAME), clipped, cf.clip_params())
-        if trimmed is not None:
-            from . import trim_report
-            trim_report.write_report(os.path.join(self.outdir, trim_report.REPORT_NAME), trimmed, cf.trim_params())
-        if pair_trimmed is not None:
-            from . import pair_trim_report
-            pair_trim_report.write_report(os.path.join(self.outdir, pair_trim_report.REPORT_NAME), pair_trimmed, cf.pair_trim_params())
-        if filtered is not None:
-            from . import filter_report
-            filter_report.write_report(os.path.join(self.outdir, filter_report.REPORT_NAME), filtered,
-                                       [s.name for s in Sample.SAMPLE_LIST], cf.filter_params())
+        for stage, table in tables:
+            stage.write_report(self.outdir, table, [s.name for s in Sample.SAMPLE_LIST], stage.conf_params(cf))
         print("Done in {}s".format(round(time() - start_time, 3)))
         if _PROFILE:
             for k, v in sorted(_T.items(), key=lambda kv: -kv[1]):
@@ -335,48 +304,23 @@ class Quade(object):
             short, dropped = sum(p[2] for p in parts), sum(p[3] for p in parts)
         return keys, ucounts, short, dropped
 
-    def _collect(self, read, name, pack, unpack):
-        """A read stage's tables (read(engine) -> uint64 array) of every context of this process summed (chunk workers, devices);
-        with several ranks every rank publishes its sum in the rendezvous directory under `name` (pack / unpack: its bytes there)
-        and adds all of them (rank 0 writes the file)."""
+    def _collect(self, stage):
+        """A read stage's tables (hip_backend.STAGES) of every context of this process summed (chunk workers, devices); with
+        several ranks every rank publishes its sum in the rendezvous directory under the stage's name and adds all of them (rank
+        0 writes the file)."""
         from . import dist
         table = None
         for eng in self.engines:
-            t = read(eng)
+            t = stage.read(eng)
             table = t if table is None else table + t
         if self.world > 1:
-            got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, name, pack(table))
-            tables = [unpack(b) for b in got]
-            table = tables[0]
-            for t in tables[1:]:
-                table = table + t
-        return table
-
-    def _collect_quality(self):
-        """[output] quality_report: _collect's sum, uint64[2S+1, 2, 6]."""
-        return self._collect(lambda eng: eng.qstats_read(), "quality", hb.pack_qstats, hb.unpack_qstats)
-
-    def _collect_clip(self):
-        """[trim] clipping: _collect's sum, uint64[2, 12]."""
-        return self._collect(lambda eng: eng.clip_read(), "clip", hb.pack_clip, hb.unpack_clip)
-
-    def _collect_trim(self):
-        """[trim]: _collect's sum, uint64[2, 8]."""
-        return self._collect(lambda eng: eng.trim_read(), "trim", hb.pack_trim, hb.unpack_trim)
-
-    def _collect_pair_trim(self):
-        """[trim] pair_overlap: _collect's sum, uint64[1040]."""
-        return self._collect(lambda eng: eng.pairtrim_read(), "pairtrim", hb.pack_pairtrim, hb.unpack_pairtrim)
-
-    def _collect_filter(self):
-        """[filter]: _collect's sum, uint64[2S+1, 8]."""
-        return self._collect(lambda eng: eng.filter_read(), "filter", hb.pack_filter, hb.unpack_filter)
-
-    def _collect_cycles(self):
-        """[output] cycle_report: _collect's sum over the flat tables, as hip_backend.cstats_views' dict."""
-        flat = self._collect(lambda eng: hb.cstats_flat(eng.cstats_read()), "cycle", hb.pack_cstats,
-                             lambda b: hb.cstats_flat(hb.unpack_cstats(b)))
-        return hb.cstats_views(flat)
+            got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, stage.name, hb.pack_table(stage, table))
+            table = None
+            for b in got:
+                t = hb.unpack_table(stage, b)
+                t = stage.flat(t) if stage.flat else t
+                table = t if table is None else table + t
+        return stage.view(table) if stage.view else table
 
     def double_index_parser(self):
         cf = self.cf

@@ -13,7 +13,7 @@ REPORT_NAME = "Quade_quality_report.csv"
 PROGRAM = "Quade-quality " + QUADE_VERSION.split()[-1]  # (no date: the file can be compared whole)
 COLUMNS = ("destination", "read", "reads", "bases", "mean_length", "q20_bases", "q30_bases", "percent_q20", "percent_q30",
            "mean_quality", "n_bases", "percent_n")
-RECORDS, BASES, QUAL_SUM, Q20, Q30, N_BASES = range(6)  # a table row (hip_backend.QSTATS_COUNTERS)
+RECORDS, BASES, QUAL_SUM, Q20, Q30, N_BASES = range(6)  # a table row (stages.QSTATS_COUNTERS)
 
 
 def ratio(x, y, scale=1):
@@ -22,6 +22,21 @@ def ratio(x, y, scale=1):
         return "0.00"
     v = int(x) * scale * 100 // int(y)
     return "%d.%02d" % (v // 100, v % 100)
+
+
+def write_lines(path, lines):
+    with open(path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+def read_report_lines(program, params, columns, table, shares):
+    """The body the read-scoped reports share: the program line, the parameters block (params: its lines), the column names, then
+    one row for R1, R2 and Total: the row's counters, then shares(counters), the ratio columns."""
+    lines = ["Program " + program, ""] + list(params) + ["", "\t".join(columns)]
+    rows = [[int(x) for x in t] for t in table]
+    for name, c in (("R1", rows[0]), ("R2", rows[1]), ("Total", [a + b for a, b in zip(*rows)])):
+        lines.append("\t".join([name] + [str(x) for x in c] + shares(c)))
+    return lines
 
 
 def _row(name, read, c):
@@ -51,5 +66,4 @@ def report_lines(table, samples):
 
 
 def write_report(path, table, samples):
-    with open(path, "w") as fh:
-        fh.write("\n".join(report_lines(table, samples)) + "\n")
+    write_lines(path, report_lines(table, samples))

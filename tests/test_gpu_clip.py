@@ -24,14 +24,15 @@ from tests import filter_model as FM
 from tests import pairtrim_model as PM
 from tests import qstats_model as QM
 from tests import trim_model as TM
-from tests.test_gpu_quality import BASES, QUALS
-from tests.test_gpu_trim import _text_from
+from tests import stage_support as SS
+from tests.run_support import _compare_dirs, _gz
+from tests.stage_support import (AD1, AD2, BASES, FILTER, P_F, P_PAIR, P_TRIM, QUALS, TRIM_KW, TRIMS, _cli, _rc, _read, _text_from,  # noqa: F401
+                                 torch_cuda)
+from tests.stage_support import LONG_LENS as LENS
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# 330: a line of 330 bytes fits its slab of 21 aligned words at offsets 0 .. 6 mod 16 only -- both paths in one launch
-LENS = (0, 1, 2, 3, 4, 15, 16, 17, 63, 64, 65, 151, 255, 256, 257, 300, 330, 2049)
 WINDOWS = (1, 4, 16, 17, 64, 100)
 POLY = (6, 10, 100)
 
@@ -43,13 +44,6 @@ def eng():
     assert torch.cuda.is_available(), "needs the MI355X"
     with hb.Engine(0) as e:
         yield e
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "needs the MI355X"
-    return torch
 
 
 def _rs(rng, L, alphabet=b"ACGT"):
@@ -330,7 +324,6 @@ def test_stage_pair_counts(eng, n):
 def test_the_read_the_stage_exists_for(eng):
     """insert + 10 bases of adapter + 8 G: the adapter rule alone leaves it (the G spend its mismatch budget); with the poly-G rule
     in front the tail goes and the adapter prefix with it -- the 5' offset and the new length reach qd_dev_trim through the tables"""
-    from tests.test_gpu_trim import AD1, AD2
     rng = np.random.default_rng(9)
     cases = [[("dark", _rs(rng, 60, b"ACT") + ad[:10].encode() + b"G" * 8, bytes([33 + 38]) * 78) for _ in range(40)] for ad in (AD1, AD2)]
     PT = TM.Params(AD1, AD2, min_length=20)
@@ -437,109 +430,61 @@ def test_state_and_errors(eng):
 
 
 # ---- the pipeline through the command line ---------------------------------------------------------------------------------------
-from tests.test_gpu_filter import AD1, AD2, FILTER, P_F, P_PAIR, P_TRIM, TRIM_KW, TRIMS  # noqa: E402
-
 CLIP = "front_clip_R2 : 5\ntail_clip_R1 : 1\nwindow_size : 4\nwindow_quality : 18\npoly_g : True\nmin_length : 25\n"
 P_CLIP = CM.Params(front_clip=(0, 5), tail_clip=(1, 0), window_size=4, window_quality=18, poly_g_min_length=10, min_length=25)
 
 
+def _inserts(g, i, sample, kind):
+    """the filter tests' fragments (stage_support._filter_inserts) with what this stage is for: a quarter of the reads end in
+    8 .. 40 high-quality G (a fifth of those behind the first 10 bases of the adapter), a seventh have a bad stretch in the middle
+    that good bases follow"""
+    rng, out = g.rng, []
+    I = int(rng.integers(15, 151)) if rng.integers(0, 2) else int(rng.integers(151, 331))
+    frag = g.rnd(I)
+    for ad, src in ((AD1, frag), (AD2, _rc(frag.encode()).decode())):
+        Lr = int(rng.integers(30, 45)) if i % 9 == 3 else int(rng.integers(60, 152))
+        s = SS._fragment_reads(g, i, Lr, ad, src)
+        qual = g.q(Lr, 22, 42)
+        if i % 4 == 1:
+            G = int(rng.integers(8, min(Lr, 41)))
+            s = s[:Lr - G] + "G" * G
+            if i % 20 == 1 and Lr - G > 10:
+                s = s[:Lr - G - 10] + ad[:10] + "G" * G
+        elif rng.integers(0, 2):
+            tail = int(rng.integers(0, min(Lr, 60) // 2))
+            qual = g.q(Lr - tail, 22, 42) + g.q(tail, 2, 24)
+        if i % 7 == 2:
+            at = int(rng.integers(10, Lr - 12))
+            qual = qual[:at] + g.q(6, 2, 10) + qual[at + 6:]
+        out.append((s.lower() if i % 11 == 0 else s, qual))
+    return out
+
+
 def _dataset(d, seed, n_chunks, n, bgzf):
-    """tests/test_gpu_filter.py's _dataset (dual 8 + 8 index; insert reads of a fragment of 15 .. 330 bases, the adapters read
-    through where it is shorter; substitutions, N, lower case, low-quality 3' tails; malformed records at the same places of all
-    four streams) with what this stage is for: a quarter of the reads end in 8 .. 40 high-quality G (a fifth of those behind the
-    first 10 bases of the adapter), a seventh have a bad stretch in the middle that good bases follow."""
-    from tests.test_gpu_e2e import _gz, _write_fastq
-    from tests.test_gpu_pairtrim import _rc
-    from tests.test_gpu_quality import MM_far_barcodes, N_SAMPLES
-    rng = np.random.default_rng(seed)
-    bcs = sorted(set(MM_far_barcodes()))[:N_SAMPLES]
-    os.makedirs(d, exist_ok=True)
-    files = {"seq_R1": [], "seq_R2": [], "index_R1": [], "index_R2": []}
-
-    def rnd(n_, alphabet="ACGT"):
-        return "".join(rng.choice(list(alphabet), n_))
-
-    def q(n_, lo, hi):
-        return "".join(chr(33 + int(v)) for v in rng.integers(lo, hi, n_))
-    for c in range(n_chunks):
-        names = ["SIM:1:FC:%d:%d:%d" % (c, i, i * 7) + "x" * (i % 5) for i in range(n)]
-        streams = {k: ([], []) for k in files}
-        for i in range(n):
-            sample = int(rng.integers(0, len(bcs)))
-            kind = int(rng.integers(0, 10))
-            I = int(rng.integers(15, 151)) if rng.integers(0, 2) else int(rng.integers(151, 331))
-            frag = rnd(I)
-            for key, ad, src in (("seq_R1", AD1, frag), ("seq_R2", AD2, _rc(frag.encode()).decode())):
-                Lr = int(rng.integers(30, 45)) if i % 9 == 3 else int(rng.integers(60, 152))
-                s = list((src + ad + rnd(151))[:Lr]) if i % 5 else list(rnd(Lr, "ACGTN"))
-                for _ in range(int(rng.integers(0, 4)) if i % 2 else 0):
-                    s[int(rng.integers(0, Lr))] = "ACGTNn"[int(rng.integers(0, 6))]
-                s = "".join(s)
-                qual = q(Lr, 22, 42)
-                if i % 4 == 1:
-                    G = int(rng.integers(8, min(Lr, 41)))
-                    s = s[:Lr - G] + "G" * G
-                    if i % 20 == 1 and Lr - G > 10:
-                        s = s[:Lr - G - 10] + ad[:10] + "G" * G
-                elif rng.integers(0, 2):
-                    tail = int(rng.integers(0, min(Lr, 60) // 2))
-                    qual = q(Lr - tail, 22, 42) + q(tail, 2, 24)
-                if i % 7 == 2:
-                    at = int(rng.integers(10, Lr - 12))
-                    qual = qual[:at] + q(6, 2, 10) + qual[at + 6:]
-                streams[key][0].append(s.lower() if i % 11 == 0 else s)
-                streams[key][1].append(qual)
-            for k, key in enumerate(("index_R1", "index_R2")):
-                streams[key][0].append(rnd(8) if kind == 0 else bcs[sample][k])
-                streams[key][1].append(q(8, 15 if kind in (2, 3) else 30, 41))
-        for i in (n // 2, n - 2):  # malformed: dropped
-            for key in streams:
-                streams[key][1][i] += "I"
-        for key, (ss, qs) in streams.items():
-            p = os.path.join(d, "C%d_%s.fastq.gz" % (c, key))
-            _write_fastq(p, names, ss, qs)
-            if bgzf:
-                text = _gz(p)
-                assert hb.load_library().qd_write_gzip_file(p.encode(), hb._ptr(np.frombuffer(text, dtype=np.uint8)), len(text), 1, -1) == 0
-            files[key].append(p)
-    return files, [("S%d" % i, b1, b2) for i, (b1, b2) in enumerate(bcs)]
+    return SS._dataset(d, seed, n_chunks, n, bgzf, _inserts, SS._same_places, sample_first=True)
 
 
 def _write_conf(path, files, samples, trim="[trim]\n" + CLIP, **kw):
-    from tests.test_gpu_pairtrim import _write_conf as base
-    base(path, files, samples, trim=trim, **kw)
+    SS._write_conf(path, files, samples, extra=trim, **kw)
 
 
 def _oracle(conf, ref_dir, P=P_CLIP):
     """the oracle's run of the conf without the stage -> ({file: clipped text}, the model's counters)"""
-    os.makedirs(ref_dir, exist_ok=True)
-    qo.run_quade(str(conf), outdir=str(ref_dir))
+    SS._oracle_run(conf, ref_dir)
     return CM.clipped_outputs(str(ref_dir), P)
 
 
-def _read(path):
-    with open(path) as fh:
-        return fh.read()
-
-
 def _check_run(mine, ref, texts, table, P=P_CLIP, only=None):
-    from tests.test_gpu_e2e import _gz
-    mine, ref = str(mine), str(ref)
-    want = sorted(f for f in texts if only is None or only(f))
-    assert sorted(f for f in os.listdir(mine) if f.endswith(".fastq.gz")) == want and len(want) >= 3
-    for f in want:
-        assert _gz(os.path.join(mine, f)) == texts[f], f
-    a, b = _read(os.path.join(mine, "Quade_report.csv")).split("\n"), _read(os.path.join(ref, "Quade_report.csv")).split("\n")
-    assert a[0].startswith("Program Quade 0.3.2\tDate ") and (only is not None or a[1:] == b[1:])  # as without the stage
-    assert _read(os.path.join(mine, cr.REPORT_NAME)) == "\n".join(cr.report_lines(table, P.keywords())) + "\n"
-    for other in (tr.REPORT_NAME, pr.REPORT_NAME, fr.REPORT_NAME):  # these options turn nothing else on
-        assert not os.path.exists(os.path.join(mine, other))
+    SS._check_files(mine, texts, only)
+    SS._check_main_report(mine, ref, only)  # as without the stage
+    SS._check_report(mine, cr, table, P.keywords())
+    for other in (tr, pr, fr):  # these options turn nothing else on
+        SS._check_report(mine, other, None)
 
 
 @pytest.fixture(scope="module")
 def bgzf_run(torch_cuda, tmp_path_factory):
     """2 chunks x 1 500 pairs in BGZF, run once with the stage alone; the model over the oracle's outputs"""
-    from tests.test_gpu_quality import _cli
     top = tmp_path_factory.mktemp("clip_bgzf")
     files, samples = _dataset(str(top / "data"), 61, 2, 1500, bgzf=True)
     plain = top / "plain.txt"
@@ -560,7 +505,6 @@ def test_cli_clip_alone_bgzf(bgzf_run):
 
 
 def test_cli_ordinary_gzip(torch_cuda, tmp_path):
-    from tests.test_gpu_quality import _cli
     files, samples = _dataset(str(tmp_path / "data"), 62, 1, 2000, bgzf=False)
     _write_conf(tmp_path / "plain.txt", files, samples, trim="")
     texts, table = _oracle(tmp_path / "plain.txt", tmp_path / "ref")
@@ -572,8 +516,6 @@ def test_cli_ordinary_gzip(torch_cuda, tmp_path):
 def test_cli_in_front_of_trim_pair_overlap_filter_and_both_reports(bgzf_run, tmp_path):
     """every stage on: the files and the reports are the models chained in the pipeline's order -- clip, [trim], pair_overlap,
     [filter], then the two counters over what is written.  The run that proves the 5' offset passes through every later kernel."""
-    from tests.test_gpu_e2e import _gz
-    from tests.test_gpu_quality import _cli
     run = bgzf_run
     names = [s[0] for s in run["samples"]]
     clipped = CM.write_outputs(run["texts"], str(tmp_path / "clipped"))
@@ -603,8 +545,6 @@ def test_cli_in_front_of_trim_pair_overlap_filter_and_both_reports(bgzf_run, tmp
 def test_cli_poly_g_uncovers_the_adapter_that_trim_alone_leaves(bgzf_run, tmp_path):
     """reads of insert + 10 bases of adapter + a G tail, one chunk: [trim] alone keeps adapter prefix and tail in most of them, with
     poly_g : True in front both go"""
-    from tests.test_gpu_e2e import _gz
-    from tests.test_gpu_quality import _cli
     run = bgzf_run
     ADS = "[trim]\nadapter_R1 : %s\nadapter_R2 : %s\n" % (AD1, AD2)
     PT = TM.Params(AD1, AD2)
@@ -631,7 +571,6 @@ def test_cli_poly_g_uncovers_the_adapter_that_trim_alone_leaves(bgzf_run, tmp_pa
 
 
 def test_cli_chunk_workers_and_write_flags(bgzf_run, tmp_path):
-    from tests.test_gpu_quality import _cli
     run = bgzf_run
     conf = tmp_path / "workers.txt"
     _write_conf(conf, run["files"], run["samples"], gpu="chunk_workers : 2\n")
@@ -645,7 +584,6 @@ def test_cli_chunk_workers_and_write_flags(bgzf_run, tmp_path):
 
 def test_cli_two_ranks_sharded_and_whole_chunks(bgzf_run, tmp_path):
     """2 ranks on GPU 0 (counters through the rendezvous files): each a pair range of ONE shared BGZF chunk, then a chunk each"""
-    from tests.test_gpu_quality import _cli
     run = bgzf_run
     _write_conf(tmp_path / "plain.txt", run["files"], run["samples"], trim="", chunks=[0])
     texts, table = _oracle(tmp_path / "plain.txt", tmp_path / "ref")
@@ -662,8 +600,6 @@ def test_cli_two_ranks_sharded_and_whole_chunks(bgzf_run, tmp_path):
 
 
 def test_cli_without_the_options_nothing_changes(bgzf_run, tmp_path):
-    from tests.test_gpu_e2e import _compare_dirs
-    from tests.test_gpu_quality import _cli
     run = bgzf_run
     _cli(run["plain"], tmp_path / "off")
     assert not os.path.exists(tmp_path / "off" / cr.REPORT_NAME)
@@ -693,7 +629,6 @@ def _bundled(tmp_path, bundled_dir, extra):
 
 def test_bundled_golden_run_with_the_stage_off(torch_cuda, tmp_path, bundled_dir):
     """the reference's own 299 pairs with a [trim] section that turns nothing on: the goldens, byte for byte"""
-    from tests.test_gpu_e2e import _compare_dirs
     work = _bundled(tmp_path, bundled_dir, "\n[trim]\nfront_clip_R1 : 0\npoly_g : False\npoly_g_min_length : 12\nmin_length : 30\n")
     _compare_dirs(str(work), os.path.join(bundled_dir, "result"))
     assert sorted(os.listdir(work)) == sorted(f for f in os.listdir(os.path.join(bundled_dir, "result")) if f != "Quade_conf_file.txt")

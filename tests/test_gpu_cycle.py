@@ -16,19 +16,14 @@ from quade_amd import hip_backend as hb
 from quade_amd import quality_report as qr
 from tests import cycle_model as CM
 from tests import qstats_model as QM
-from tests.test_gpu_quality import LENS, Stage, _barcodes, _cli, _dataset, _engine
-from tests.test_gpu_quality import _write_conf as _quality_conf
+from tests import stage_support as SS
+from tests.run_support import _compare_dirs
+from tests.stage_support import LENS, Stage, _barcodes, _cli, _engine, torch_cuda  # noqa: F401
+from tests.stage_support import _plain_dataset as _dataset
 
 pytestmark = pytest.mark.gpu
 UND = CM.UNDETERMINED
 WG_PAIRS = 4096  # pairs per workgroup of the kernel (quade_cstats.hip)
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "needs the MI355X"
-    return torch
 
 
 class CStage(Stage):
@@ -235,8 +230,7 @@ def test_cross_checks_against_the_quality_counters_of_the_same_call(torch_cuda):
 
 # ---- the pipeline through the command line ---------------------------------------------------------------------------------------
 def _write_conf(path, files, samples, cycle=True, **kw):
-    kw.setdefault("quality", False)
-    _quality_conf(path, files, samples, **kw)
+    SS._write_conf(path, files, samples, **kw)
     if cycle:
         text = open(path).read().replace("[output]\n", "[output]\ncycle_report : True\n", 1)
         open(path, "w").write(text)
@@ -276,7 +270,6 @@ def bgzf_run(torch_cuda, tmp_path_factory):
 
 
 def test_cli_report_equals_the_model_bgzf(bgzf_run):
-    from tests.test_gpu_e2e import _compare_dirs
     run = bgzf_run
     t = run["table"]
     assert (t["len"].sum(axis=2) > 0).all() and t["cycle"][:, :, :, 4].sum() > 0 and 5000 < t["len"][:, 0].sum() < 6000
@@ -288,7 +281,6 @@ def test_cli_report_equals_the_model_bgzf(bgzf_run):
 
 
 def test_cli_report_equals_the_model_ordinary_gzip(torch_cuda, tmp_path):
-    from tests.test_gpu_e2e import _compare_dirs
     files, samples = _dataset(str(tmp_path / "data"), 42, 2, 3000, bgzf=False)
     conf = tmp_path / "conf.txt"
     _write_conf(conf, files, samples)
@@ -329,10 +321,9 @@ def test_cli_two_ranks_sharded_and_whole_chunks(bgzf_run, tmp_path):
 def test_cli_behind_trim_pair_overlap_and_filter(torch_cuda, tmp_path):
     """[trim], pair_overlap and [filter] on, all write flags on: the report is the model over the files this run wrote (which
     tests/test_gpu_filter.py pins), and its totals are those of the Quade_quality_report.csv of the same run"""
-    from tests import test_gpu_filter as TF
-    files, samples = TF._dataset(str(tmp_path / "data"), 71, 2, 1500, bgzf=True)
+    files, samples = SS._filter_dataset(str(tmp_path / "data"), 71, 2, 1500, bgzf=True)
     conf = tmp_path / "conf.txt"
-    TF._write_conf(conf, files, samples, extra=TF.TRIMS + TF.FILTER, quality=True)
+    SS._write_conf(conf, files, samples, extra=SS.TRIMS + SS.FILTER, quality=True)
     text = open(conf).read().replace("[output]\n", "[output]\ncycle_report : True\n", 1)
     open(conf, "w").write(text)
     _cli(conf, tmp_path / "mine")
@@ -350,7 +341,6 @@ def test_cli_behind_trim_pair_overlap_and_filter(torch_cuda, tmp_path):
 
 
 def test_cli_option_off_writes_nothing_new(bgzf_run, tmp_path):
-    from tests.test_gpu_e2e import _compare_dirs
     run = bgzf_run
     conf = tmp_path / "off.txt"
     _write_conf(conf, run["files"], run["samples"], cycle=False)
@@ -363,7 +353,6 @@ def test_cli_option_off_writes_nothing_new(bgzf_run, tmp_path):
 def test_bundled_golden_run_with_the_option_on(torch_cuda, tmp_path, bundled_dir):
     """the reference's own 299 pairs: other outputs byte-identical, the report = the model over the reference's result files"""
     from quade_amd.quade import Quade
-    from tests.test_gpu_e2e import _compare_dirs
     shutil.copytree(os.path.join(bundled_dir, "dataset"), tmp_path / "dataset")
     with open(os.path.join(bundled_dir, "result", "Quade_conf_file.txt")) as fh:
         base = fh.read()

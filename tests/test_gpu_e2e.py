@@ -9,42 +9,9 @@ import numpy as np
 import pytest
 
 from oracle import quade_oracle as qo
+from tests.run_support import _LAST_PIPE_STATS, SCENARIOS, _compare_dirs, _conf, _make_dataset, _run_cli
 
 pytestmark = pytest.mark.gpu
-
-
-def _gz(path):
-    with gzip.open(path, "rb") as fh:
-        return fh.read()
-
-
-_LAST_PIPE_STATS = {}
-
-
-def _run_cli(conf, workdir):
-    from quade_amd.quade import Quade
-    old = os.getcwd()
-    os.chdir(workdir)
-    try:
-        q = Quade(conf_file=conf)
-        assert q() == 0
-        _LAST_PIPE_STATS["stats"] = getattr(q, "pipe_stats", None)
-    finally:
-        os.chdir(old)
-
-
-def _compare_dirs(mine, ref):
-    fm = sorted(f for f in os.listdir(mine) if f.endswith(".fastq.gz"))
-    fr = sorted(f for f in os.listdir(ref) if f.endswith(".fastq.gz"))
-    assert fm == fr
-    for f in fr:
-        assert _gz(os.path.join(mine, f)) == _gz(os.path.join(ref, f)), f
-    with open(os.path.join(mine, "Quade_report.csv")) as fh:
-        a = fh.read().split("\n")
-    with open(os.path.join(ref, "Quade_report.csv")) as fh:
-        b = fh.read().split("\n")
-    assert a[0].startswith("Program Quade 0.3.2\tDate ")
-    assert a[1:] == b[1:]
 
 
 def test_bundled_golden_replay_through_hip(tmp_path, bundled_dir):
@@ -74,125 +41,6 @@ def test_bundled_golden_replay_through_hip(tmp_path, bundled_dir):
 
 
 # ---- generated datasets ----------------------------------------------------------------------------
-def _write_fastq(path, names, seqs, quals, plus="+"):
-    with gzip.open(path, "wb") if str(path).endswith(".gz") else open(path, "wb") as fh:
-        for n, s, q in zip(names, seqs, quals):
-            fh.write(("@%s\n%s\n%s\n%s\n" % (n, s, plus, q)).encode("latin-1"))
-
-
-def _make_dataset(d, rng, n_chunks, n, dual, idx_len, barcodes, trunc=False, malformed=False, plain=False, bgzf=False):
-    """barcodes: list of (b1, b2) expected at the start of index read 1 / 2.  bgzf: the .gz files in bgzip's block layout (what the
-    device inflates) instead of one gzip member."""
-    ext = ".fastq" if plain else ".fastq.gz"
-    files = {"seq_R1": [], "seq_R2": [], "index_R1": [], "index_R2": []}
-    for c in range(n_chunks):
-        names = ["SIM:1:FC:%d:%d:%d %d:N:0:" % (c, i, i * 7, 1) for i in range(n)]
-        def rnd(L):
-            return "".join(rng.choice(list("ACGT"), L))
-        def q(L, lo=30):
-            return "".join(chr(33 + int(v)) for v in rng.integers(lo, 41, L))
-        r1 = [rnd(30) for _ in range(n)]
-        r2 = [rnd(30) for _ in range(n)]
-        i1, i2, q1, q2 = [], [], [], []
-        for i in range(n):
-            b = barcodes[int(rng.integers(0, len(barcodes)))]
-            kind = int(rng.integers(0, 10))
-            parts = []
-            for k in range(2 if dual else 1):
-                s = b[k] + rnd(idx_len - len(b[k]))
-                if kind == 0:
-                    p = int(rng.integers(0, len(b[k])))
-                    s = s[:p] + "N" + s[p + 1:]
-                elif kind == 1:
-                    s = s.lower()
-                elif kind == 2:
-                    s = rnd(idx_len)
-                if trunc and rng.integers(0, 4) == 0:
-                    s = s[:int(rng.integers(0, idx_len))]
-                qq = q(len(s), lo=20 if rng.integers(0, 3) == 0 else 30)
-                parts.append((s, qq))
-            i1.append(parts[0][0]); q1.append(parts[0][1])
-            if dual:
-                i2.append(parts[1][0]); q2.append(parts[1][1])
-        qr1 = [q(30) for _ in range(n)]
-        qr2 = [q(30) for _ in range(n)]
-        if malformed and n > 5:
-            qr1[3] = qr1[3] + "I"        # R1 record 3 dropped -> R1 shifts against the others
-            q1[n // 2] = q1[n // 2][:-1] if q1[n // 2] else "I"  # an index record dropped
-        for key, (nm, ss, qs) in {"seq_R1": (names, r1, qr1), "seq_R2": (names, r2, qr2),
-                                  "index_R1": (names, i1, q1), "index_R2": (names, i2, q2)}.items():
-            if key == "index_R2" and not dual:
-                continue
-            p = os.path.join(d, "C%d_%s%s" % (c, key, ext))
-            _write_fastq(p, nm, ss, qs, plus="+" if c % 2 == 0 else "+" + "x")
-            if bgzf and not plain:
-                from quade_amd import hip_backend as hb
-                text = _gz(p)
-                buf = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, np.uint8)
-                assert hb.load_library().qd_write_gzip_file(p.encode(), hb._ptr(buf), len(text), 1, -1) == 0
-            files[key].append(p)
-    return files
-
-
-def _conf(path, files, dual, pos, minq, samples, flags=(True, True, True), gpu=""):
-    i1, i2, m1, m2 = pos
-    txt = "[quality]\nminimal_qual : %d\n[fastq]\n" % minq
-    for k in ("seq_R1", "seq_R2", "index_R1") + (("index_R2",) if dual else ()):
-        txt += "%s : %s\n" % (k, "  ".join(files[k]))
-    txt += "[index]\nindex2 : %s\nmolecular1 : %s\nmolecular2 : %s\n" % (dual, bool(m1), bool(m2))
-    txt += "index1_start : %d\nindex1_end : %d\n" % i1
-    if dual:
-        txt += "index2_start : %d\nindex2_end : %d\n" % i2
-    if m1:
-        txt += "molecular1_start : %d\nmolecular1_end : %d\n" % m1
-    if m2:
-        txt += "molecular2_start : %d\nmolecular2_end : %d\n" % m2
-    txt += "[output]\nwrite_pass : %s\nwrite_fail : %s\nwrite_undetermined : %s\n" % flags
-    txt += gpu
-    for i, (name, b1, b2) in enumerate(samples):
-        txt += "[sample%d]\nname : %s\nindex1_seq : %s\n" % (i + 1, name, b1)
-        if dual:
-            txt += "index2_seq : %s\n" % b2
-    with open(path, "w") as fh:
-        fh.write(txt)
-
-
-SCENARIOS = {
-    # name: dual, idx_len, positions (1-based incl.), min_qual, flags, trunc, malformed, plain, gpu section
-    "single_plain": dict(dual=False, idx_len=8, pos=((1, 8), None, None, None), minq=0, plain=True),
-    "single_mol_ext": dict(dual=False, idx_len=12, pos=((1, 6), None, (7, 12), None), minq=25),
-    "dual_mol_fail": dict(dual=True, idx_len=14, pos=((1, 8), (1, 8), (9, 14), (9, 14)), minq=25,
-                          gpu="[gpu]\nbatch_pairs : 37\nslots : 2\n"),
-    "dual_offset_windows": dict(dual=True, idx_len=10, pos=((2, 7), (3, 9), (1, 3), None), minq=30),
-    "flags_off": dict(dual=True, idx_len=8, pos=((1, 8), (1, 8), None, None), minq=25, flags=(True, False, False)),
-    "truncated_generic": dict(dual=True, idx_len=8, pos=((1, 8), (1, 8), (5, 8), None), minq=20, trunc=True,
-                              gpu="[gpu]\nbatch_pairs : 50\n"),
-    "malformed_desync": dict(dual=True, idx_len=8, pos=((1, 8), (1, 8), None, None), minq=25, malformed=True,
-                             gpu="[gpu]\nbatch_pairs : 16\nslots : 3\n"),
-    # two contexts (both on GPU 0 here): batches fed round-robin over pinned slots / a pipeline each with the chunks dealt out --
-    # output order must still equal input order
-    "two_engines_round_robin": dict(dual=True, idx_len=8, pos=((1, 8), (1, 8), None, None), minq=25,
-                                    gpu="[gpu]\ndevices : 0 0\nbatch_pairs : 23\nslots : 2\n"),
-    # three host threads take chunks from a queue; per-chunk parts merged in chunk order
-    "chunk_workers_threads": dict(dual=True, idx_len=14, pos=((1, 8), (1, 8), (9, 14), None), minq=25, malformed=True,
-                                  gpu="[gpu]\nchunk_workers : 3\nbatch_pairs : 31\nslots : 2\n"),
-    # "all": every device the library sees (one on this box)
-    "devices_all": dict(dual=False, idx_len=8, pos=((1, 8), None, None, None), minq=20, gpu="[gpu]\ndevices : all\n"),
-    # dual 10 bp indexes (fused barcode of 20 bytes): the wide form of the fast kernel, incl. truncated reads
-    # (listed exceptions redone by the fixup kernel) and a molecular index behind the second barcode
-    "dual_10bp_wide_fast": dict(dual=True, idx_len=12, pos=((1, 10), (1, 10), None, None), minq=25),
-    "dual_10bp_umi_truncated": dict(dual=True, idx_len=16, pos=((1, 10), (2, 11), None, (12, 16)), minq=20, trunc=True,
-                                    gpu="[gpu]\nbatch_pairs : 64\n"),
-    # a molecular index of 11 bases behind the barcode of BOTH index reads (rows of 20 bytes in both streams, 22 molecular bytes per
-    # pair: the fast kernel's RowsU2 shape, r05), whole reads and truncated ones (the listed exceptions redone by the fixup kernel)
-    "dual_umi_in_both_reads": dict(dual=True, idx_len=19, pos=((1, 8), (1, 8), (9, 19), (9, 19)), minq=25),
-    "dual_umi_in_both_reads_truncated": dict(dual=True, idx_len=17, pos=((1, 8), (1, 8), (9, 17), (9, 17)), minq=20, trunc=True,
-                                             gpu="[gpu]\nbatch_pairs : 64\n"),
-    "wide_window_generic": dict(dual=False, idx_len=24, pos=((1, 20), None, (21, 24), None), minq=10),
-    # truncated reads on a plan the fast kernel does not take: the generic kernel needs every read's length
-    "wide_window_truncated": dict(dual=False, idx_len=24, pos=((1, 20), None, (21, 24), None), minq=10, trunc=True,
-                                  gpu="[gpu]\nbatch_pairs : 64\n"),
-}
 
 
 @pytest.mark.parametrize("path", ["device_pipeline", "pinned_slots"])
@@ -474,6 +322,6 @@ def test_c99_client_runs_the_hot_path(tmp_path):
     """examples/abi_client.c: fastq text -> pinned slot -> codes, molecular bytes, counters and name tags through
     the C ABI alone, from plain C."""
     import subprocess
-    from tests.test_host_cpu import _build_abi_client
+    from tests.run_support import _build_abi_client
     r = subprocess.run([_build_abi_client(tmp_path)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and r.stdout.startswith("ok: 4 pairs on "), (r.returncode, r.stdout, r.stderr)

@@ -20,14 +20,16 @@ from quade_amd import trim_report as tr
 from tests import filter_model as FM
 from tests import pairtrim_model as PM
 from tests import qstats_model as QM
-from tests import trim_model as TM
-from tests.test_gpu_quality import QUALS, _barcodes
+from tests import stage_support as SS
+from tests.run_support import _gz
+from tests.stage_support import (BASES, FILTER, P_F, P_PAIR, P_TRIM, POLY_G, QUALS, TRIM_KW, TRIMS, _barcodes, _cli,  # noqa: F401
+                                 torch_cuda)
+from tests.stage_support import _filter_dataset as _dataset
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 UND = FM.UNDETERMINED
 LENS = (0, 1, 2, 15, 16, 17, 31, 32, 33, 150, 151, 255, 256, 257, 300, 2049)
-BASES = b"ACGTNnacgtRYKM.*"
 S_STAGE = 3
 UPLOAD_SHIFT = 3  # qd_dev_filter uploads a text 3 bytes into an aligned buffer: byte o of the text lies at address o + 3 (mod 16)
 
@@ -44,13 +46,6 @@ RULES = {
     "complexity_100": dict(min_complexity_pct=100),
     "all": dict(min_length=16, max_n=3, max_unqualified_pct=40, qualified_quality=15, min_mean_quality=20, min_complexity_pct=30),
 }
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "needs the MI355X"
-    return torch
 
 
 def _with_diffs(rng, L, D):
@@ -447,80 +442,13 @@ def test_state_and_errors(torch_cuda):
 
 
 # ---- the pipeline through the command line ---------------------------------------------------------------------------------------
-AD1, AD2 = "AGATCGGAAGAGCACACGTCTGAACTCCAGTCA", "AGATCGGAAGAGCGTCGTGTAGGGAAAGAGTGT"
-FILTER = "[filter]\nmin_length : 40\nmax_n : 5\nmax_unqualified_pct : 40\nmin_mean_quality : 20\nmin_complexity_pct : 30\n"
-TRIMS = "[trim]\nadapter_R1 : %s\nadapter_R2 : %s\nquality_cutoff : 20\nmin_length : 25\npair_overlap : True\npair_max_mismatches : 3\n" % (AD1, AD2)
-P_F = FM.Params(min_length=40, max_n=5, max_unqualified_pct=40, min_mean_quality=20, min_complexity_pct=30)
-P_PAIR = PM.Params(max_mismatches=3, min_length=25)
-P_TRIM = TM.Params(AD1, AD2, quality_cutoff=20, min_length=25)
-TRIM_KW = dict(adapter_r1=AD1, adapter_r2=AD2, quality_cutoff=20, min_overlap=3, max_mismatch_pct=10, min_length=25)
-POLY_G = 0  # the sample all of whose insert reads are poly-G
-
-
-def _dataset(d, seed, n_chunks, n, bgzf):
-    """tests/test_gpu_pairtrim.py's _dataset (dual 8 + 8 index; insert reads of 30 .. 151 bases of a fragment of 15 .. 330 bases,
-    the adapters read through where it is shorter; a fifth unrelated and rich in N; substitutions, N, lower case, low-quality 3'
-    tails) with food for every rule of the filter: a ninth of the pairs has reads of 30 .. 44 bases and the others of 60 .. 151,
-    every insert read of sample 0 is poly-G, a thirteenth of the pairs has qualified but low qualities (15 .. 19) and another
-    thirteenth unqualified ones, both in front of 8 good bases at the 3' end, which keep a quality cutoff from trimming them away.  The malformed records sit at the
-    same places of all four streams: each stream drops its own, and the pairs stay together."""
-    from tests.test_gpu_e2e import _gz, _write_fastq
-    from tests.test_gpu_pairtrim import _rc
-    from tests.test_gpu_quality import MM_far_barcodes, N_SAMPLES
-    rng = np.random.default_rng(seed)
-    bcs = sorted(set(MM_far_barcodes()))[:N_SAMPLES]
-    os.makedirs(d, exist_ok=True)
-    files = {"seq_R1": [], "seq_R2": [], "index_R1": [], "index_R2": []}
-
-    def rnd(n_, alphabet="ACGT"):
-        return "".join(rng.choice(list(alphabet), n_))
-
-    def q(n_, lo, hi):
-        return "".join(chr(33 + int(v)) for v in rng.integers(lo, hi, n_))
-    for c in range(n_chunks):
-        names = ["SIM:1:FC:%d:%d:%d" % (c, i, i * 7) + "x" * (i % 5) for i in range(n)]
-        streams = {k: ([], []) for k in files}
-        for i in range(n):
-            sample = int(rng.integers(0, len(bcs)))
-            kind = int(rng.integers(0, 10))
-            I = int(rng.integers(15, 151)) if rng.integers(0, 2) else int(rng.integers(151, 331))
-            frag = rnd(I)
-            for key, ad, src in (("seq_R1", AD1, frag), ("seq_R2", AD2, _rc(frag.encode()).decode())):
-                Lr = int(rng.integers(30, 45)) if i % 9 == 3 else int(rng.integers(60, 152))
-                s = list((src + ad + rnd(151))[:Lr]) if i % 5 else list(rnd(Lr, "ACGTN"))
-                for _ in range(int(rng.integers(0, 4)) if i % 2 else 0):
-                    s[int(rng.integers(0, Lr))] = "ACGTNn"[int(rng.integers(0, 6))]
-                s = "".join(s)
-                if sample == POLY_G and kind != 0:
-                    s = "G" * Lr
-                tail = int(rng.integers(0, min(Lr, 60) // 2)) if rng.integers(0, 2) else 0
-                streams[key][0].append(s.lower() if i % 11 == 0 else s)
-                streams[key][1].append(q(Lr - 8, 15, 20) + q(8, 38, 42) if i % 13 == 1 else q(Lr - 8, 2, 24) + q(8, 38, 42) if i % 13 == 2 else q(Lr - tail, 22, 42) + q(tail, 2, 24))
-            for k, key in enumerate(("index_R1", "index_R2")):
-                streams[key][0].append(rnd(8) if kind == 0 else bcs[sample][k])
-                streams[key][1].append(q(8, 15 if kind in (2, 3) else 30, 41))
-        for i in (n // 2, n - 2):  # malformed: dropped
-            for key in streams:
-                streams[key][1][i] += "I"
-        for key, (ss, qs) in streams.items():
-            p = os.path.join(d, "C%d_%s.fastq.gz" % (c, key))
-            _write_fastq(p, names, ss, qs)
-            if bgzf:
-                text = _gz(p)
-                assert hb.load_library().qd_write_gzip_file(p.encode(), hb._ptr(np.frombuffer(text, dtype=np.uint8)), len(text), 1, -1) == 0
-            files[key].append(p)
-    return files, [("S%d" % i, b1, b2) for i, (b1, b2) in enumerate(bcs)]
-
-
 def _write_conf(path, files, samples, extra=FILTER, **kw):
-    from tests.test_gpu_pairtrim import _write_conf as base
-    base(path, files, samples, trim=extra, **kw)
+    SS._write_conf(path, files, samples, extra=extra, **kw)
 
 
 def _oracle(conf, ref_dir, samples, P=P_F, trim=None, pair=None):
     """the oracle's run of the conf without the sections -> filtered_outputs of the model"""
-    os.makedirs(ref_dir, exist_ok=True)
-    qo.run_quade(str(conf), outdir=str(ref_dir))
+    SS._oracle_run(conf, ref_dir)
     return FM.filtered_outputs(str(ref_dir), [s[0] for s in samples], P, trim, pair)
 
 
@@ -542,27 +470,16 @@ def _report_body(path):
 
 
 def _check_run(mine, ref, samples, texts, table, P=P_F, only=None, trim_table=None, pair_table=None, pair_kw=None):
-    from tests.test_gpu_e2e import _gz
-    mine, ref = str(mine), str(ref)
-    want = sorted(f for f in texts if only is None or only(f))
-    assert sorted(f for f in os.listdir(mine) if f.endswith(".fastq.gz")) == want
-    for f in want:
-        assert _gz(os.path.join(mine, f)) == texts[f], f
-    assert _report_body(os.path.join(mine, "Quade_report.csv")) == _report_body(os.path.join(ref, "Quade_report.csv"))  # assignments
-    with open(os.path.join(mine, fr.REPORT_NAME)) as fh:
-        assert fh.read() == "\n".join(fr.report_lines(table, [s[0] for s in samples], P.keywords())) + "\n"
-    for name, module, t, kw in ((tr.REPORT_NAME, tr, trim_table, TRIM_KW), (pr.REPORT_NAME, pr, pair_table, pair_kw or P_PAIR.keywords())):
-        if t is None:
-            assert not os.path.exists(os.path.join(mine, name))
-        else:
-            with open(os.path.join(mine, name)) as fh:
-                assert fh.read() == "\n".join(module.report_lines(t, kw)) + "\n"
+    SS._check_files(mine, texts, only, at_least=0)
+    assert _report_body(os.path.join(str(mine), "Quade_report.csv")) == _report_body(os.path.join(str(ref), "Quade_report.csv"))  # assignments
+    SS._check_report(mine, fr, table, [s[0] for s in samples], P.keywords())
+    SS._check_report(mine, tr, trim_table, TRIM_KW)
+    SS._check_report(mine, pr, pair_table, pair_kw or P_PAIR.keywords())
 
 
 @pytest.fixture(scope="module")
 def bgzf_run(torch_cuda, tmp_path_factory):
     """2 chunks x 1 500 pairs in BGZF, run once with the filter alone; the model over the oracle's outputs"""
-    from tests.test_gpu_quality import _cli
     top = tmp_path_factory.mktemp("filter_bgzf")
     files, samples = _dataset(str(top / "data"), 71, 2, 1500, bgzf=True)
     plain = top / "plain.txt"
@@ -585,7 +502,6 @@ def test_cli_filter_alone_bgzf(bgzf_run):
 
 
 def test_cli_with_quality_cutoff_adapters_and_pair_overlap(bgzf_run, tmp_path):
-    from tests.test_gpu_quality import _cli
     run = bgzf_run
     texts, table, first, second = FM.filtered_outputs(str(run["ref"]), [s[0] for s in run["samples"]], P_F, P_TRIM, P_PAIR)
     _input_is_fit(table)
@@ -597,7 +513,6 @@ def test_cli_with_quality_cutoff_adapters_and_pair_overlap(bgzf_run, tmp_path):
     _write_conf(conf, run["files"], run["samples"], extra=TRIMS + FILTER)
     _cli(conf, tmp_path / "both")
     _check_run(tmp_path / "both", run["ref"], run["samples"], texts, table, trim_table=first, pair_table=second)
-    from tests.test_gpu_e2e import _gz
     for f in texts:  # no read of fewer than 40 bases is left
         assert min(len(s) for s, _ in QM.fastq_records(str(tmp_path / "both" / f))) >= 40, f
 
@@ -605,7 +520,6 @@ def test_cli_with_quality_cutoff_adapters_and_pair_overlap(bgzf_run, tmp_path):
 def test_cli_a_dimer_that_pair_overlap_cuts_to_the_floor_is_dropped(bgzf_run, tmp_path):
     """pair_overlap without adapter sequences: the overlap trimming itself cuts the shortest inserts it can see (30 bases and more:
     pair_min_overlap) to its floor of 35 bases, and the filter's min_length 40 drops them"""
-    from tests.test_gpu_quality import _cli
     run = bgzf_run
     P = FM.Params(min_length=40)
     pair = PM.Params(max_mismatches=3, min_length=35)
@@ -620,7 +534,6 @@ def test_cli_a_dimer_that_pair_overlap_cuts_to_the_floor_is_dropped(bgzf_run, tm
 
 
 def test_cli_quality_report_counts_the_pairs_that_were_written(bgzf_run, tmp_path):
-    from tests.test_gpu_quality import _cli
     run = bgzf_run
     conf = tmp_path / "quality.txt"
     _write_conf(conf, run["files"], run["samples"], quality=True)
@@ -634,7 +547,6 @@ def test_cli_quality_report_counts_the_pairs_that_were_written(bgzf_run, tmp_pat
 
 
 def test_cli_ordinary_gzip(torch_cuda, tmp_path):
-    from tests.test_gpu_quality import _cli
     files, samples = _dataset(str(tmp_path / "data"), 72, 2, 1000, bgzf=False)
     _write_conf(tmp_path / "plain.txt", files, samples, extra="")
     texts, table, _, _ = _oracle(tmp_path / "plain.txt", tmp_path / "ref", samples)
@@ -644,7 +556,6 @@ def test_cli_ordinary_gzip(torch_cuda, tmp_path):
 
 
 def test_cli_chunk_workers_and_write_flags(bgzf_run, tmp_path):
-    from tests.test_gpu_quality import _cli
     run = bgzf_run
     conf = tmp_path / "workers.txt"
     _write_conf(conf, run["files"], run["samples"], gpu="chunk_workers : 2\n")
@@ -663,7 +574,6 @@ def test_cli_chunk_workers_and_write_flags(bgzf_run, tmp_path):
 
 def test_cli_two_ranks_sharded_and_whole_chunks(bgzf_run, tmp_path):
     """2 ranks on GPU 0 (tables through the rendezvous files): each a pair range of ONE shared BGZF chunk, then a chunk each"""
-    from tests.test_gpu_quality import _cli
     run = bgzf_run
     _write_conf(tmp_path / "plain.txt", run["files"], run["samples"], extra="", chunks=[0])
     texts, table, _, _ = _oracle(tmp_path / "plain.txt", tmp_path / "ref", run["samples"])
@@ -680,7 +590,6 @@ def test_cli_two_ranks_sharded_and_whole_chunks(bgzf_run, tmp_path):
 
 
 def test_cli_every_pair_dropped(bgzf_run, tmp_path):
-    from tests.test_gpu_quality import _cli
     run = bgzf_run
     P = FM.Params(min_length=100000)
     texts, table, _, _ = FM.filtered_outputs(str(run["ref"]), [s[0] for s in run["samples"]], P)
@@ -697,8 +606,6 @@ def test_cli_every_pair_dropped(bgzf_run, tmp_path):
 
 def test_cli_without_the_section_nothing_changes(bgzf_run, tmp_path):
     """a conf without the section, one with an empty section and one with every option empty: the same bytes"""
-    from tests.test_gpu_e2e import _gz
-    from tests.test_gpu_quality import _cli
     run = bgzf_run
     empty = "[filter]\n" + "".join("%s :\n" % k for k in FM.KEYS)
     runs = {}

@@ -128,7 +128,7 @@ def test_gzip_members_through_the_device(geometry, inflater_form):
 
 
 def _pipeline_run(base, files, samples):
-    from tests.test_gpu_text import _run_and_compare
+    from tests.run_support import _run_and_compare
     base.mkdir()
     return _run_and_compare(base, files, samples, "[gpu]\nbatch_pairs : 700\n")  # outputs byte-equal to oracle.run_quade, or it raises
 
@@ -139,7 +139,7 @@ def test_pipeline_with_a_forged_gzip_member_falls_back_and_with_forged_bgzf_does
     are the oracle's -- and the control run with zlib's framing never falls back.  One of four BGZF inputs rebuilt from forged blocks
     (empty stored and fixed blocks, far matches): the device takes every block."""
     import gzip
-    from tests.test_gpu_text import _dataset
+    from tests.run_support import _dataset
     rng = np.random.default_rng(23)
     for fmt in ("gz", "bgzf"):
         data = tmp_path / ("data_" + fmt)

@@ -32,7 +32,7 @@ needs_two = pytest.mark.skipif(N_DEV < 2, reason="needs at least two visible GPU
 
 
 def _dataset(tmp_path, n_chunks, n_reads, seed):
-    from tests.test_gpu_e2e import _conf, _make_dataset
+    from tests.run_support import _conf, _make_dataset
     rng = np.random.default_rng(seed)
     bcs = sorted({("".join(rng.choice(list("ACGT"), 8)), "".join(rng.choice(list("ACGT"), 8))) for _ in range(11)})
     data = tmp_path / "data"
@@ -190,8 +190,8 @@ def test_one_chunk_cut_across_real_ranks_matches_the_oracle(tmp_path):
     ranks (index pass per rank, tables exchanged, parts planned identically everywhere); records dropped upstream of the cuts keep
     their effect on the pairing -> the oracle's sequential run, byte for byte (the 1-GPU rehearsal:
     tests/test_gpu_text.py::test_shared_chunk_three_ranks_vs_oracle)."""
-    from tests.test_gpu_e2e import _conf
-    from tests.test_gpu_text import _dataset as _bgzf_dataset
+    from tests.run_support import _conf
+    from tests.run_support import _dataset as _bgzf_dataset
     rng = np.random.default_rng(92)
     data = tmp_path / "data"
     data.mkdir()

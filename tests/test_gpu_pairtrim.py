@@ -9,7 +9,6 @@ import os
 import numpy as np
 import pytest
 
-from oracle import quade_oracle as qo
 from quade_amd import hip_backend as hb
 from quade_amd import pair_trim_report as pr
 from quade_amd import quality_report as qr
@@ -17,23 +16,13 @@ from quade_amd import trim_report as tr
 from tests import pairtrim_model as PM
 from tests import qstats_model as QM
 from tests import trim_model as TM
-from tests.test_gpu_trim import _text_from
+from tests import stage_support as SS
+from tests.run_support import _gz
+from tests.stage_support import AD1, AD2, _cli, _rc, _text_from, torch_cuda  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RC = bytes.maketrans(b"ACGTacgt", b"TGCAtgca")
 L = 151
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "needs the MI355X"
-    return torch
-
-
-def _rc(s):
-    return bytes(s).translate(RC)[::-1]
 
 
 def _cases(rng, P):
@@ -378,7 +367,6 @@ def test_state_and_errors(torch_cuda):
 
 
 # ---- the pipeline through the command line ---------------------------------------------------------------------------------------
-AD1, AD2 = "AGATCGGAAGAGCACACGTCTGAACTCCAGTCA", "AGATCGGAAGAGCGTCGTGTAGGGAAAGAGTGT"
 PAIR = "[trim]\npair_overlap : True\npair_min_overlap : 20\n"
 BOTH = "[trim]\nadapter_R1 : %s\nadapter_R2 : %s\nquality_cutoff : 20\nmin_length : 25\npair_overlap : True\npair_max_mismatches : 3\n" % (AD1, AD2)
 P_PAIR = PM.Params(min_overlap=20)
@@ -387,95 +375,45 @@ T_BOTH = TM.Params(AD1, AD2, quality_cutoff=20, min_length=25)
 T_BOTH_KW = dict(adapter_r1=AD1, adapter_r2=AD2, quality_cutoff=20, min_overlap=3, max_mismatch_pct=10, min_length=25)
 
 
+def _inserts(g, i, sample, kind):
+    """pairs that belong together: insert reads of 30 .. 151 bases of a fragment of 15 .. 330 bases (half of them shorter than a
+    read: the adapters read through), a fifth unrelated, some with substitutions, N or lower case, half with a low-quality 3' tail"""
+    rng, out = g.rng, []
+    I = int(rng.integers(15, 151)) if rng.integers(0, 2) else int(rng.integers(151, 331))
+    frag = g.rnd(I)
+    for ad, src in ((AD1, frag), (AD2, _rc(frag.encode()).decode())):
+        Lr = int(rng.integers(30, 152))
+        s = SS._fragment_reads(g, i, Lr, ad, src)
+        tail = int(rng.integers(0, min(Lr, 60))) if rng.integers(0, 2) else 0
+        out.append((s.lower() if i % 11 == 0 else s, g.q(Lr - tail, 22, 42) + g.q(tail, 2, 24)))
+    return out
+
+
 def _dataset(d, seed, n_chunks, n, bgzf):
-    """tests/test_gpu_trim.py's _dataset with pairs that belong together: dual 8 + 8 index; insert reads of 30 .. 151 bases of a
-    fragment of 15 .. 330 bases (half of them shorter than a read: the adapters read through), a fifth unrelated, some with
-    substitutions, N or lower case, half with a low-quality 3' tail; a few malformed records (dropped inside their own stream,
-    which shifts the streams against each other: pairs that no longer belong together)."""
-    from tests.test_gpu_e2e import _gz, _write_fastq
-    from tests.test_gpu_quality import MM_far_barcodes, N_SAMPLES
-    rng = np.random.default_rng(seed)
-    bcs = sorted(set(MM_far_barcodes()))[:N_SAMPLES]
-    os.makedirs(d, exist_ok=True)
-    files = {"seq_R1": [], "seq_R2": [], "index_R1": [], "index_R2": []}
-
-    def rnd(n_, alphabet="ACGT"):
-        return "".join(rng.choice(list(alphabet), n_))
-
-    def q(n_, lo, hi):
-        return "".join(chr(33 + int(v)) for v in rng.integers(lo, hi, n_))
-    for c in range(n_chunks):
-        names = ["SIM:1:FC:%d:%d:%d" % (c, i, i * 7) + "x" * (i % 5) for i in range(n)]
-        streams = {k: ([], []) for k in files}
-        for i in range(n):
-            I = int(rng.integers(15, 151)) if rng.integers(0, 2) else int(rng.integers(151, 331))
-            frag = rnd(I)
-            for key, ad, src in (("seq_R1", AD1, frag), ("seq_R2", AD2, _rc(frag.encode()).decode())):
-                Lr = int(rng.integers(30, 152))
-                s = list((src + ad + rnd(151))[:Lr]) if i % 5 else list(rnd(Lr, "ACGTN"))
-                for _ in range(int(rng.integers(0, 4)) if i % 2 else 0):
-                    s[int(rng.integers(0, Lr))] = "ACGTNn"[int(rng.integers(0, 6))]
-                s = "".join(s)
-                tail = int(rng.integers(0, min(Lr, 60))) if rng.integers(0, 2) else 0
-                streams[key][0].append(s.lower() if i % 11 == 0 else s)
-                streams[key][1].append(q(Lr - tail, 22, 42) + q(tail, 2, 24))
-            b = bcs[int(rng.integers(0, len(bcs)))]
-            kind = int(rng.integers(0, 10))
-            for k, key in enumerate(("index_R1", "index_R2")):
-                streams[key][0].append(rnd(8) if kind == 0 else b[k])
-                streams[key][1].append(q(8, 15 if kind in (2, 3) else 30, 41))
-        for i in (n // 2, n - 2):  # malformed: dropped
-            streams["seq_R1"][1][i] += "I"
-        streams["seq_R2"][1][n // 2 + 40] += "I"
-        for key, (ss, qs) in streams.items():
-            p = os.path.join(d, "C%d_%s.fastq.gz" % (c, key))
-            _write_fastq(p, names, ss, qs)
-            if bgzf:
-                text = _gz(p)
-                assert hb.load_library().qd_write_gzip_file(p.encode(), hb._ptr(np.frombuffer(text, dtype=np.uint8)), len(text), 1, -1) == 0
-            files[key].append(p)
-    return files, [("S%d" % i, b1, b2) for i, (b1, b2) in enumerate(bcs)]
+    """the malformed records shift the streams against each other: pairs that no longer belong together"""
+    return SS._dataset(d, seed, n_chunks, n, bgzf, _inserts, lambda n: {"seq_R1": (n // 2, n - 2), "seq_R2": (n // 2 + 40,)})
 
 
-def _write_conf(path, files, samples, trim=PAIR, flags=(True, True, True), gpu="", quality=False, chunks=None):
-    from tests.test_gpu_quality import _write_conf as base
-    base(path, files, samples, flags=flags, gpu=gpu, quality=quality, chunks=chunks)
-    with open(path, "a") as fh:
-        fh.write(trim)
+def _write_conf(path, files, samples, trim=PAIR, **kw):
+    SS._write_conf(path, files, samples, extra=trim, **kw)
 
 
 def _oracle(conf, ref_dir, P=P_PAIR, trim=None):
     """the oracle's run of the conf without any trimming -> trimmed_outputs of the model"""
-    os.makedirs(ref_dir, exist_ok=True)
-    qo.run_quade(str(conf), outdir=str(ref_dir))
+    SS._oracle_run(conf, ref_dir)
     return PM.trimmed_outputs(str(ref_dir), P, trim)
 
 
 def _check_run(mine, ref, texts, table, P=P_PAIR, only=None, trim_table=None):
-    from tests.test_gpu_e2e import _gz
-    mine, ref = str(mine), str(ref)
-    want = sorted(f for f in texts if only is None or only(f))
-    assert sorted(f for f in os.listdir(mine) if f.endswith(".fastq.gz")) == want and len(want) >= 3
-    for f in want:
-        assert _gz(os.path.join(mine, f)) == texts[f], f
-    with open(os.path.join(mine, "Quade_report.csv")) as fh:
-        a = fh.read().split("\n")
-    with open(os.path.join(ref, "Quade_report.csv")) as fh:
-        b = fh.read().split("\n")
-    assert a[0].startswith("Program Quade 0.3.2\tDate ") and (only is not None or a[1:] == b[1:])  # as without trimming
-    with open(os.path.join(mine, pr.REPORT_NAME)) as fh:
-        assert fh.read() == "\n".join(pr.report_lines(table, P.keywords())) + "\n"
-    if trim_table is None:
-        assert not os.path.exists(os.path.join(mine, tr.REPORT_NAME))
-    else:
-        with open(os.path.join(mine, tr.REPORT_NAME)) as fh:
-            assert fh.read() == "\n".join(tr.report_lines(trim_table, T_BOTH_KW)) + "\n"
+    SS._check_files(mine, texts, only)
+    SS._check_main_report(mine, ref, only)  # as without trimming
+    SS._check_report(mine, pr, table, P.keywords())
+    SS._check_report(mine, tr, trim_table, T_BOTH_KW)
 
 
 @pytest.fixture(scope="module")
 def bgzf_run(torch_cuda, tmp_path_factory):
     """2 chunks x 1 500 pairs in BGZF, run once with pair_overlap alone; the model over the oracle's outputs"""
-    from tests.test_gpu_quality import _cli
     top = tmp_path_factory.mktemp("pairtrim_bgzf")
     files, samples = _dataset(str(top / "data"), 61, 2, 1500, bgzf=True)
     plain = top / "plain.txt"
@@ -497,7 +435,6 @@ def test_cli_pair_overlap_alone_bgzf(bgzf_run):
 
 
 def test_cli_with_quality_cutoff_adapters_and_min_length(bgzf_run, tmp_path):
-    from tests.test_gpu_quality import _cli
     run = bgzf_run
     texts, table, first = PM.trimmed_outputs(str(run["ref"]), P_BOTH, T_BOTH)
     assert all(first[r][k] > 0 for r in (0, 1) for k in range(8)) and table[14] > 0 and table[1] == first[0][2]
@@ -508,7 +445,6 @@ def test_cli_with_quality_cutoff_adapters_and_min_length(bgzf_run, tmp_path):
 
 
 def test_cli_quality_report_counts_the_final_lengths(bgzf_run, tmp_path):
-    from tests.test_gpu_quality import _cli
     run = bgzf_run
     conf = tmp_path / "quality.txt"
     _write_conf(conf, run["files"], run["samples"], quality=True)
@@ -522,7 +458,6 @@ def test_cli_quality_report_counts_the_final_lengths(bgzf_run, tmp_path):
 
 
 def test_cli_ordinary_gzip(torch_cuda, tmp_path):
-    from tests.test_gpu_quality import _cli
     files, samples = _dataset(str(tmp_path / "data"), 62, 2, 1000, bgzf=False)
     _write_conf(tmp_path / "plain.txt", files, samples, trim="")
     texts, table = _oracle(tmp_path / "plain.txt", tmp_path / "ref")
@@ -532,7 +467,6 @@ def test_cli_ordinary_gzip(torch_cuda, tmp_path):
 
 
 def test_cli_chunk_workers_and_write_flags(bgzf_run, tmp_path):
-    from tests.test_gpu_quality import _cli
     run = bgzf_run
     conf = tmp_path / "workers.txt"
     _write_conf(conf, run["files"], run["samples"], gpu="chunk_workers : 2\n")
@@ -546,7 +480,6 @@ def test_cli_chunk_workers_and_write_flags(bgzf_run, tmp_path):
 
 def test_cli_two_ranks_sharded_and_whole_chunks(bgzf_run, tmp_path):
     """2 ranks on GPU 0 (tables through the rendezvous files): each a pair range of ONE shared BGZF chunk, then a chunk each"""
-    from tests.test_gpu_quality import _cli
     run = bgzf_run
     _write_conf(tmp_path / "plain.txt", run["files"], run["samples"], trim="", chunks=[0])
     texts, table = _oracle(tmp_path / "plain.txt", tmp_path / "ref")
@@ -564,8 +497,6 @@ def test_cli_two_ranks_sharded_and_whole_chunks(bgzf_run, tmp_path):
 
 def test_cli_without_the_option_nothing_changes(bgzf_run, tmp_path):
     """a conf with a [trim] section, as written before the pair_* options existed, and the same with the options added but off"""
-    from tests.test_gpu_e2e import _gz
-    from tests.test_gpu_quality import _cli
     run = bgzf_run
     before = BOTH.split("pair_overlap")[0]
     assert "pair_" not in before and "quality_cutoff" in before

@@ -4,8 +4,6 @@ quality bytes, destination shapes on both accumulation paths, accumulation, stat
 (the report against the model over the oracle's per-destination output files)."""
 import os
 import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,76 +13,14 @@ from quade_amd import hip_backend as hb
 from quade_amd import quality_report as qr
 from tests import mismatch_model as MM
 from tests import qstats_model as QM
+from tests import stage_support as SS
+from tests.run_support import _compare_dirs, _scan
+from tests.stage_support import LENS, N_SAMPLES, QUALS, Stage, _barcodes, _cli, _engine, torch_cuda  # noqa: F401
+from tests.stage_support import _plain_dataset as _dataset
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 UND = QM.UNDETERMINED
-
-LENS = (0, 1, 3, 4, 5, 15, 16, 17, 63, 64, 65, 151, 300)
-# every printable quality, bytes below 33 and from 0x80 on (the clamp, the unsigned rule); never '\n' or '\r' (line ends)
-QUALS = bytes(range(33, 127)) + bytes([0, 1, 9, 31, 32, 127, 128, 129, 200, 254, 255])
-BASES = b"ACGTNnacgtRYKM.*"
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "needs the MI355X"
-    return torch
-
-
-def _barcodes(S):
-    """S distinct 16-base barcodes"""
-    return ["".join("ACGT"[(i >> (2 * k)) & 3] for k in range(16)) for i in range(S)]
-
-
-def _engine(S, enable=True):
-    eng = hb.Engine(0)
-    eng.set_plan(hb.make_plan(True, 25, (0, 8), (0, 8)))
-    eng.set_barcodes(_barcodes(S))
-    if enable:
-        eng.qstats_enable(True)
-    return eng
-
-
-def _text(rng, n, lens=LENS):
-    """A fastq text of n records with its record table (qd_dev_fastq_scan's layout) and the records' (seq, qual) bytes.  Names of
-    1 .. 24 bytes move the lines over every offset mod 16; a third of the records end their lines with CRLF; the first records'
-    qualities walk through QUALS."""
-    parts, recs, pairs, pos, walk = [], np.zeros((n, 6), dtype=np.uint32), [], 0, 0
-    for i in range(n):
-        L = int(lens[int(rng.integers(0, len(lens)))])
-        name = b"r%d" % i + b"x" * int(rng.integers(0, 20))
-        nl = b"\r\n" if rng.integers(0, 3) == 0 else b"\n"
-        seq = bytes(BASES[int(v)] for v in rng.integers(0, len(BASES), L))
-        if walk < len(QUALS):
-            qual = bytes(QUALS[(walk + k) % len(QUALS)] for k in range(L))
-            walk += L
-        else:
-            qual = bytes(QUALS[int(v)] for v in rng.integers(0, len(QUALS), L))
-        rec = b"@" + name + b" 1:N:0" + nl + seq + nl + b"+" + nl + qual + nl
-        seq_at = pos + 1 + len(name) + 6 + len(nl)
-        recs[i] = (pos, pos + 1, len(name), seq_at, L, seq_at + L + len(nl) + 1 + len(nl))
-        parts.append(rec)
-        pairs.append((seq, qual))
-        pos += len(rec)
-    return b"".join(parts), recs, pairs
-
-
-class Stage(object):
-    """n pairs: R1 and R2 texts drawn apart (a pair's two reads differ in length), tables, records"""
-
-    def __init__(self, seed, n, lens=LENS):
-        rng = np.random.default_rng(seed)
-        self.n = n
-        self.t1, self.r1, self.p1 = _text(rng, n, lens)
-        self.t2, self.r2, self.p2 = _text(rng, n, lens)
-
-    def model(self, S, codes):
-        return QM.table(S, [(int(c), a, b) for c, a, b in zip(codes, self.p1, self.p2)])
-
-    def run(self, eng, codes):
-        eng.dev_qstats(self.t1, self.r1, self.t2, self.r2, np.asarray(codes, dtype=np.uint16))
 
 
 def _check(eng, want):
@@ -95,7 +31,6 @@ def _check(eng, want):
 
 
 def test_the_tests_record_table_is_the_device_scans(torch_cuda):
-    from tests.test_gpu_text import _scan
     st = Stage(1, 1025)
     for text, recs, pairs in ((st.t1, st.r1, st.p1), (st.t2, st.r2, st.p2)):
         n, got, res = _scan(text)
@@ -271,88 +206,10 @@ def test_state_and_errors(torch_cuda):
 
 
 # ---- the pipeline through the command line ---------------------------------------------------------------------------------------
-N_SAMPLES = 6
 
 
-def _cli(conf, work, ranks=0, timeout=180):
-    """bin/Quade.py (or the launcher with `ranks` processes on GPU 0) in a child process under its own time limit"""
-    os.makedirs(work, exist_ok=True)
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
-        env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bin", "Quade.py"), "-c", str(conf)]
-    if ranks:
-        env.update(QUADE_DIST_TRANSPORT="files", QUADE_DEVICE="0")
-        cmd = [sys.executable, "-m", "quade_amd.launch", "-n", str(ranks), "-c", str(conf)]
-    r = subprocess.run(cmd, cwd=str(work), env=env, capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
-    return r
-
-
-def _dataset(d, seed, n_chunks, n, bgzf, one_off=False):
-    """dual 8 + 8 index, insert reads of 30 .. 151 bases with N and a wide quality range; a few malformed records (a quality line
-    one byte too long: dropped inside their own stream, the streams shift against each other as in the reference).
-    one_off: a tenth of the index reads one substitution from a sample's barcode (the mismatch rescue's food)."""
-    from tests.test_gpu_e2e import _gz, _write_fastq
-    rng = np.random.default_rng(seed)
-    bcs = sorted(set(MM_far_barcodes()))[:N_SAMPLES]
-    os.makedirs(d, exist_ok=True)
-    files = {"seq_R1": [], "seq_R2": [], "index_R1": [], "index_R2": []}
-
-    def rnd(L, alphabet="ACGT"):
-        return "".join(rng.choice(list(alphabet), L))
-
-    def q(L, lo, hi):
-        return "".join(chr(33 + int(v)) for v in rng.integers(lo, hi, L))
-    for c in range(n_chunks):
-        names = ["SIM:1:FC:%d:%d:%d" % (c, i, i * 7) + "x" * (i % 5) for i in range(n)]
-        streams = {k: ([], []) for k in files}
-        for i in range(n):
-            for key in ("seq_R1", "seq_R2"):
-                L = int(rng.integers(30, 152))
-                streams[key][0].append(rnd(L, "ACGTACGTACGTN" if i % 3 else "ACGTn"))
-                streams[key][1].append(q(L, 2, 42))
-            b = bcs[int(rng.integers(0, len(bcs)))]
-            kind = int(rng.integers(0, 10))
-            for k, key in enumerate(("index_R1", "index_R2")):
-                s = b[k]
-                if kind == 0:
-                    s = rnd(8)
-                elif kind == 1 and one_off:
-                    p = int(rng.integers(0, 8))
-                    s = s[:p] + ("A" if s[p] != "A" else "C") + s[p + 1:]
-                streams[key][0].append(s)
-                streams[key][1].append(q(8, 15 if kind in (2, 3) else 30, 41))
-        for i in (3, n // 2, n - 2):  # malformed: dropped
-            streams["seq_R1"][1][i] += "I"
-        streams["index_R2"][1][7] += "I"
-        for key, (ss, qs) in streams.items():
-            p = os.path.join(d, "C%d_%s.fastq.gz" % (c, key))
-            _write_fastq(p, names, ss, qs)
-            if bgzf:
-                text = _gz(p)
-                assert hb.load_library().qd_write_gzip_file(p.encode(), hb._ptr(np.frombuffer(text, dtype=np.uint8)), len(text), 1, -1) == 0
-            files[key].append(p)
-    return files, [("S%d" % i, b1, b2) for i, (b1, b2) in enumerate(bcs)]
-
-
-def MM_far_barcodes():
-    """8 + 8 base barcodes no two of which collide under the budgets (1, 1)"""
-    from quade_amd import synth
-    return [(b[:8], b[8:]) for b in synth.make_far_barcodes(N_SAMPLES, 8, 8, 1, 1, seed=3)]
-
-
-def _write_conf(path, files, samples, flags=(True, True, True), gpu="", quality=True, index_extra="", chunks=None):
-    from tests.test_gpu_e2e import _conf
-    if chunks is not None:
-        files = {k: [v[c] for c in chunks] for k, v in files.items()}
-    _conf(str(path), files, True, ((1, 8), (1, 8), None, None), 25, samples, flags, "[gpu]\nbatch_pairs : 1000\n" + gpu)
-    text = open(path).read()
-    if quality:
-        text = text.replace("[output]\n", "[output]\nquality_report : True\n", 1)
-    if index_extra:
-        text = text.replace("index2_end : 8\n", "index2_end : 8\n" + index_extra, 1)
-    open(path, "w").write(text)
+def _write_conf(path, files, samples, quality=True, **kw):
+    SS._write_conf(path, files, samples, quality=quality, **kw)
 
 
 def _oracle_report(conf, ref_dir, samples):
@@ -381,7 +238,6 @@ def bgzf_run(torch_cuda, tmp_path_factory):
 
 
 def test_cli_report_equals_the_model_bgzf(bgzf_run):
-    from tests.test_gpu_e2e import _compare_dirs
     run = bgzf_run
     t = run["table"]
     assert int(t[:, 0, 0].sum()) == run["counts"][0] < 6000  # malformed records were dropped
@@ -455,7 +311,6 @@ def test_cli_rescued_pairs_count_under_their_sample(torch_cuda, tmp_path, monkey
 
 
 def test_cli_option_off_writes_nothing_new(bgzf_run, tmp_path):
-    from tests.test_gpu_e2e import _compare_dirs
     run = bgzf_run
     conf = tmp_path / "off.txt"
     _write_conf(conf, run["files"], run["samples"], quality=False)
@@ -468,7 +323,6 @@ def test_cli_option_off_writes_nothing_new(bgzf_run, tmp_path):
 def test_bundled_golden_run_with_the_option_on(torch_cuda, tmp_path, bundled_dir):
     """the reference's own 299 pairs: S1_pass, S2_pass and Undetermined rows = the model over the reference's result files"""
     from quade_amd.quade import Quade
-    from tests.test_gpu_e2e import _compare_dirs
     shutil.copytree(os.path.join(bundled_dir, "dataset"), tmp_path / "dataset")
     with open(os.path.join(bundled_dir, "result", "Quade_conf_file.txt")) as fh:
         base = fh.read()

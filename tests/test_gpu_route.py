@@ -24,7 +24,7 @@ import pytest
 
 from quade_amd import hip_backend as hb
 from tests import route_model as RM
-from tests.test_host_route import NAME_BYTES, PLANS, build_fastq, make_plan, ragged_index_reads, rand_bytes, reads_of
+from tests.run_support import NAME_BYTES, PLANS, build_fastq, make_plan, ragged_index_reads, rand_bytes, reads_of
 
 pytestmark = pytest.mark.gpu
 

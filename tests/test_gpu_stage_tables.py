@@ -14,13 +14,13 @@ from tests import filter_model as FM
 from tests import pairtrim_model as PM
 from tests import qstats_model as QM
 from tests import trim_model as TM
-from tests.test_gpu_quality import _barcodes
-from tests.test_gpu_trim import _text_from
+from tests.stage_support import _barcodes, _text_from
 
 pytestmark = pytest.mark.gpu
 
 S, N, L = 2, 17, 20  # 17 pairs: one full step of a workgroup's 16 rows and one row of a ragged second step
-STAGES = ("qstats", "cstats", "clip", "trim", "pairtrim", "filter")  # stage k of the add test is STAGES[k - 1]
+BY_ENGINE = {s.engine: s for s in hb.STAGES}  # the product's stage table, by the prefix of the Engine methods
+STAGES = tuple(BY_ENGINE)  # qstats, cstats, clip, trim, pairtrim, filter: stage k of the add test is STAGES[k - 1]
 CODES = (0, 3, CYM.UNDETERMINED)  # sample 0 pass, sample 1 fail, Undetermined
 CLIP = CM.Params(front_clip=(1, 0), tail_clip=(0, 2), window_size=4, window_quality=20, poly_g_min_length=6, min_length=5)
 TRIM = TM.Params("AGATCGGAAG", "AGATCGGAAG", quality_cutoff=20, min_overlap=3, max_mismatch_pct=10, min_length=4)
@@ -89,8 +89,7 @@ def _configured():
 
 
 def _read(eng, stage):
-    t = getattr(eng, stage + "_read")()
-    return (hb.cstats_flat(t) if stage == "cstats" else np.asarray(t)).reshape(-1).copy()
+    return np.asarray(BY_ENGINE[stage].read(eng)).reshape(-1).copy()
 
 
 def _read_all(eng):

@@ -9,20 +9,9 @@ import numpy as np
 import pytest
 
 from oracle import quade_oracle as qo
+from tests.run_support import _bgzip, _dataset, _run_and_compare, _scan
 
 pytestmark = pytest.mark.gpu
-
-
-def _scan(text, at_eof=True, names=True, need=0, line_cap=None):
-    from quade_amd import hip_backend as hb
-    lib = hb.load_library()
-    buf = np.frombuffer(text, dtype=np.uint8) if len(text) else np.zeros(1, np.uint8)
-    cap = line_cap if line_cap is not None else (text.count(b"\n") + 8)
-    recs = np.zeros((cap // 4 + 2, 6), dtype=np.uint32)
-    res = np.zeros(8, dtype=np.uint32)
-    n = lib.qd_dev_fastq_scan(0, hb._ptr(buf), len(text), int(at_eof), int(names), int(need), max(cap, 4), hb._ptr(recs), recs.shape[0], hb._ptr(res))
-    assert n >= 0, n
-    return int(n), recs[:min(n, recs.shape[0])], res
 
 
 def _host_records(text, at_eof=True):
@@ -150,87 +139,6 @@ def test_device_sort_by_destination_is_stable(n_dest):
 
 
 # ---- whole chunks through the pipeline ---------------------------------------------------------------------------------------
-def _bgzip(path, data):
-    from quade_amd import hip_backend as hb
-    buf = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, np.uint8)
-    assert hb.load_library().qd_write_gzip_file(str(path).encode(), hb._ptr(buf), len(data), 1, -1) == 0
-
-
-def _dataset(d, rng, n_chunks, n, S, malformed=(), fmt="bgzf", read_len=60, trunc=False):
-    """Dual 8 + 8 bp index with a 6-base molecular index behind the first barcode; returns (files, samples)."""
-    bcs = set()
-    while len(bcs) < S:
-        bcs.add(("".join(rng.choice(list("ACGT"), 8)), "".join(rng.choice(list("ACGT"), 8))))
-    bcs = sorted(bcs)
-    files = {"seq_R1": [], "seq_R2": [], "index_R1": [], "index_R2": []}
-    A = np.frombuffer(b"ACGT", dtype=np.uint8)
-    for c in range(n_chunks):
-        pick = rng.integers(0, S, n)
-        kind = rng.integers(0, 12, n)
-        recs = {k: [] for k in files}
-        r1 = A[rng.integers(0, 4, (n, read_len))]
-        r2 = A[rng.integers(0, 4, (n, read_len))]
-        q1 = rng.integers(33 + 30, 33 + 41, (n, read_len)).astype(np.uint8)
-        q2 = rng.integers(33 + 30, 33 + 41, (n, read_len)).astype(np.uint8)
-        for i in range(n):
-            name = "SIM:1:FC:%d:%d:%d" % (c, i, i * 7)
-            b1, b2 = bcs[pick[i]]
-            i1 = b1 + "".join(rng.choice(list("ACGT"), 6))
-            i2 = b2
-            if kind[i] == 0:
-                i1 = "N" + i1[1:]
-            elif kind[i] == 1:
-                i1, i2 = i1.lower(), i2.lower()
-            elif kind[i] == 2:
-                i2 = "".join(rng.choice(list("ACGT"), 8))
-            if trunc and kind[i] == 3:
-                i1 = i1[:int(rng.integers(0, 14))]
-            qi1 = "".join(chr(33 + int(v)) for v in rng.integers(20 if kind[i] == 4 else 30, 41, len(i1)))
-            qi2 = "".join(chr(33 + int(v)) for v in rng.integers(30, 41, len(i2)))
-            rows = {"seq_R1": (r1[i].tobytes().decode(), q1[i].tobytes().decode(), "1"), "seq_R2": (r2[i].tobytes().decode(), q2[i].tobytes().decode(), "2"),
-                    "index_R1": (i1, qi1, "1"), "index_R2": (i2, qi2, "2")}
-            for k, (s, q, rd) in rows.items():
-                if (c, k, i) in malformed:
-                    q = q + "I"
-                recs[k].append("@%s %s:N:0:\n%s\n+\n%s\n" % (name, rd, s, q))
-        for k in files:
-            data = "".join(recs[k]).encode()
-            if fmt == "bgzf":
-                path = os.path.join(d, "C%d_%s.fastq.gz" % (c, k))
-                _bgzip(path, data)
-            elif fmt == "gz":
-                path = os.path.join(d, "C%d_%s.fastq.gz" % (c, k))
-                with gzip.open(path, "wb", compresslevel=1) as fh:
-                    fh.write(data)
-            else:
-                path = os.path.join(d, "C%d_%s.fastq" % (c, k))
-                with open(path, "wb") as fh:
-                    fh.write(data)
-            files[k].append(path)
-    return files, [("S%d" % i, b1, b2) for i, (b1, b2) in enumerate(bcs)]
-
-
-def _run_and_compare(tmp_path, files, samples, gpu, flags=(True, True, True), expect_stats=None):
-    from tests.test_gpu_e2e import _compare_dirs, _conf, _run_cli
-    conf = tmp_path / "conf.txt"
-    _conf(str(conf), files, True, ((1, 8), (1, 8), (9, 14), None), 25, samples, flags, gpu)
-    ref_dir, my_dir = tmp_path / "ref", tmp_path / "mine"
-    ref_dir.mkdir()
-    my_dir.mkdir()
-    sset, _ = qo.run_quade(str(conf), outdir=str(ref_dir))
-    from quade_amd.quade import Quade
-    old = os.getcwd()
-    os.chdir(my_dir)
-    try:
-        q = Quade(conf_file=str(conf))
-        assert q() == 0
-    finally:
-        os.chdir(old)
-    from quade_amd.sample import Sample
-    assert Sample.COUNTS() == sset.counts()
-    _compare_dirs(str(my_dir), str(ref_dir))
-    assert q.use_pipe
-    return q.pipe_stats
 
 
 @pytest.mark.parametrize("fmt", ["bgzf", "gz", "plain"])
@@ -320,7 +228,7 @@ def test_pipeline_falls_back_to_the_host_for_blocks_the_device_refuses(tmp_path)
     data = tmp_path / "data"
     data.mkdir()
     files, samples = _dataset(str(data), rng, 1, 20000, 5, fmt="bgzf")
-    from tests.test_gpu_e2e import _conf
+    from tests.run_support import _conf
     conf = tmp_path / "conf.txt"
     _conf(str(conf), files, True, ((1, 8), (1, 8), (9, 14), None), 25, samples, (True, True, True), "[gpu]\nbatch_pairs : 6000\n")
     ref_dir = tmp_path / "ref"
@@ -442,7 +350,7 @@ def test_shared_chunk_three_ranks_vs_oracle(tmp_path):
     outputs must equal oracle.run_quade's sequential run byte for byte (VERDICT r03 #6)."""
     import subprocess
     import sys
-    from tests.test_gpu_e2e import _compare_dirs, _conf
+    from tests.run_support import _compare_dirs, _conf
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     rng = np.random.default_rng(41)
     data = tmp_path / "data"
@@ -477,7 +385,7 @@ def test_shared_chunk_part_with_a_refused_block_in_its_first_window(tmp_path):
     from quade_amd import hip_backend as hb
     from quade_amd.conf import QuadeConf
     from quade_amd.sample import Sample, WriterSet
-    from tests.test_gpu_e2e import _conf
+    from tests.run_support import _conf
     rng = np.random.default_rng(43)
     data = tmp_path / "data"
     data.mkdir()

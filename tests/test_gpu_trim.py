@@ -5,33 +5,24 @@ accumulation, state and errors) and through the command line (every output file 
 the trim report, the quality report of the trimmed reads, chunk workers, write flags, ranks, the bundled golden run)."""
 import os
 import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from oracle import quade_oracle as qo
 from quade_amd import hip_backend as hb
 from quade_amd import quality_report as qr
 from quade_amd import trim_report as tr
 from tests import qstats_model as QM
 from tests import trim_model as TM
-from tests.test_gpu_quality import BASES, QUALS
+from tests import stage_support as SS
+from tests.run_support import _compare_dirs
+from tests.stage_support import AD1, AD2, BASES, QUALS, _cli, _text_from, torch_cuda  # noqa: F401
+from tests.stage_support import LONG_LENS as LENS
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-# 330: a line of 330 bytes fits its slab of 21 aligned words at offsets 0 .. 6 mod 16 only -- both paths in one stage
-LENS = (0, 1, 2, 3, 4, 15, 16, 17, 63, 64, 65, 151, 255, 256, 257, 300, 330, 2049)
 ADAPTER_LENS = (1, 3, 8, 19, 33, 64)
-
-
-@pytest.fixture(scope="module")
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "needs the MI355X"
-    return torch
 
 
 def _adapter(A, seed=0):
@@ -113,23 +104,6 @@ def _cases(rng, ad, mo, pct, C):
         for p in (30, 100, 140):
             out.append(("both", rs(p) + (ad + rs(151))[:151 - p], good(120) + bytes([35]) * 31))
     return out
-
-
-def _text_from(rng, cases):
-    """A fastq text of the cases' records with its record table (qd_dev_fastq_scan's layout), built as tests/test_gpu_quality.py's
-    _text builds it: names of 1 .. 24 bytes move the lines over every offset mod 16, a third of the records end their lines with
-    CRLF."""
-    parts, recs, pos = [], np.zeros((len(cases), 6), dtype=np.uint32), 0
-    for i, (_, seq, qual) in enumerate(cases):
-        L = len(seq)
-        name = b"r%d" % i + b"x" * int(rng.integers(0, 20))
-        nl = b"\r\n" if rng.integers(0, 3) == 0 else b"\n"
-        rec = b"@" + name + b" 1:N:0" + nl + seq + nl + b"+" + nl + qual + nl
-        seq_at = pos + 1 + len(name) + 6 + len(nl)
-        recs[i] = (pos, pos + 1, len(name), seq_at, L, seq_at + L + len(nl) + 1 + len(nl))
-        parts.append(rec)
-        pos += len(rec)
-    return b"".join(parts), recs
 
 
 class Stage(object):
@@ -350,96 +324,52 @@ def test_state_and_errors(torch_cuda):
 
 
 # ---- the pipeline through the command line ---------------------------------------------------------------------------------------
-AD1, AD2 = "AGATCGGAAGAGCACACGTCTGAACTCCAGTCA", "AGATCGGAAGAGCGTCGTGTAGGGAAAGAGTGT"
 TRIM = "[trim]\nadapter_R1 : %s\nadapter_R2 : %s\nquality_cutoff : 20\nmin_length : 25\n" % (AD1, AD2.lower())
 P_CLI = TM.Params(AD1, AD2, quality_cutoff=20, min_length=25)
 PARAMS_CLI = dict(adapter_r1=AD1, adapter_r2=AD2, quality_cutoff=20, min_overlap=3, max_mismatch_pct=10, min_length=25)
 
 
+def _inserts(g, i, sample, kind):
+    """what a trimmer is for: insert reads of 30 .. 151 bases, two in five with an insert shorter than the read (the adapter read
+    through, sometimes with a substitution or an N), half with a low-quality 3' tail"""
+    rng, out = g.rng, []
+    for ad in (AD1, AD2):
+        L = int(rng.integers(30, 152))
+        s = g.rnd(L, "ACGTACGTACGTN" if i % 3 else "ACGTn")
+        if rng.integers(0, 5) < 2:
+            p = int(rng.integers(0, L))
+            a = list(ad)
+            if rng.integers(0, 3) == 0:
+                a[int(rng.integers(0, len(a)))] = "N" if rng.integers(0, 2) else "a"
+            s = (s[:p] + "".join(a) + g.rnd(151))[:L]
+        tail = int(rng.integers(0, min(L, 60))) if rng.integers(0, 2) else 0
+        out.append((s, g.q(L - tail, 22, 42) + g.q(tail, 2, 24)))
+    return out
+
+
 def _dataset(d, seed, n_chunks, n, bgzf):
-    """tests/test_gpu_quality.py's _dataset with what a trimmer is for: dual 8 + 8 index; insert reads of 30 .. 151 bases, two in
-    five with an insert shorter than the read (the adapter read through, sometimes with a substitution or an N), half with a
-    low-quality 3' tail; a few malformed records (dropped inside their own stream)."""
-    from tests.test_gpu_e2e import _gz, _write_fastq
-    from tests.test_gpu_quality import MM_far_barcodes, N_SAMPLES
-    rng = np.random.default_rng(seed)
-    bcs = sorted(set(MM_far_barcodes()))[:N_SAMPLES]
-    os.makedirs(d, exist_ok=True)
-    files = {"seq_R1": [], "seq_R2": [], "index_R1": [], "index_R2": []}
-
-    def rnd(L, alphabet="ACGT"):
-        return "".join(rng.choice(list(alphabet), L))
-
-    def q(L, lo, hi):
-        return "".join(chr(33 + int(v)) for v in rng.integers(lo, hi, L))
-    for c in range(n_chunks):
-        names = ["SIM:1:FC:%d:%d:%d" % (c, i, i * 7) + "x" * (i % 5) for i in range(n)]
-        streams = {k: ([], []) for k in files}
-        for i in range(n):
-            for key, ad in (("seq_R1", AD1), ("seq_R2", AD2)):
-                L = int(rng.integers(30, 152))
-                s = rnd(L, "ACGTACGTACGTN" if i % 3 else "ACGTn")
-                if rng.integers(0, 5) < 2:
-                    p = int(rng.integers(0, L))
-                    a = list(ad)
-                    if rng.integers(0, 3) == 0:
-                        a[int(rng.integers(0, len(a)))] = "N" if rng.integers(0, 2) else "a"
-                    s = (s[:p] + "".join(a) + rnd(151))[:L]
-                tail = int(rng.integers(0, min(L, 60))) if rng.integers(0, 2) else 0
-                streams[key][0].append(s)
-                streams[key][1].append(q(L - tail, 22, 42) + q(tail, 2, 24))
-            b = bcs[int(rng.integers(0, len(bcs)))]
-            kind = int(rng.integers(0, 10))
-            for k, key in enumerate(("index_R1", "index_R2")):
-                streams[key][0].append(rnd(8) if kind == 0 else b[k])
-                streams[key][1].append(q(8, 15 if kind in (2, 3) else 30, 41))
-        for i in (3, n // 2, n - 2):  # malformed: dropped
-            streams["seq_R1"][1][i] += "I"
-        streams["index_R2"][1][7] += "I"
-        for key, (ss, qs) in streams.items():
-            p = os.path.join(d, "C%d_%s.fastq.gz" % (c, key))
-            _write_fastq(p, names, ss, qs)
-            if bgzf:
-                text = _gz(p)
-                assert hb.load_library().qd_write_gzip_file(p.encode(), hb._ptr(np.frombuffer(text, dtype=np.uint8)), len(text), 1, -1) == 0
-            files[key].append(p)
-    return files, [("S%d" % i, b1, b2) for i, (b1, b2) in enumerate(bcs)]
+    return SS._dataset(d, seed, n_chunks, n, bgzf, _inserts, SS._early_places)
 
 
-def _write_conf(path, files, samples, trim=TRIM, flags=(True, True, True), gpu="", quality=False, chunks=None):
-    from tests.test_gpu_quality import _write_conf as base
-    base(path, files, samples, flags=flags, gpu=gpu, quality=quality, chunks=chunks)
-    with open(path, "a") as fh:
-        fh.write(trim)
+def _write_conf(path, files, samples, trim=TRIM, **kw):
+    SS._write_conf(path, files, samples, extra=trim, **kw)
 
 
 def _oracle(conf, ref_dir, P=P_CLI):
     """the oracle's run of the conf without trimming -> ({file: trimmed text}, the model's counters)"""
-    os.makedirs(ref_dir, exist_ok=True)
-    qo.run_quade(str(conf), outdir=str(ref_dir))
+    SS._oracle_run(conf, ref_dir)
     return TM.trimmed_outputs(str(ref_dir), P)
 
 
 def _check_run(mine, ref, texts, table, params=PARAMS_CLI, only=None):
-    from tests.test_gpu_e2e import _gz
-    mine, ref = str(mine), str(ref)
-    want = sorted(f for f in texts if only is None or only(f))
-    assert sorted(f for f in os.listdir(mine) if f.endswith(".fastq.gz")) == want and len(want) >= 3
-    for f in want:
-        assert _gz(os.path.join(mine, f)) == texts[f], f
-    with open(os.path.join(mine, "Quade_report.csv")) as fh:
-        a = fh.read().split("\n")
-    with open(os.path.join(ref, "Quade_report.csv")) as fh:
-        b = fh.read().split("\n")
-    assert a[0].startswith("Program Quade 0.3.2\tDate ") and (only is not None or a[1:] == b[1:])  # as without trimming
-    with open(os.path.join(mine, tr.REPORT_NAME)) as fh:
-        assert fh.read() == "\n".join(tr.report_lines(table, params)) + "\n"
+    SS._check_files(mine, texts, only)
+    SS._check_main_report(mine, ref, only)  # as without trimming
+    SS._check_report(mine, tr, table, params)
 
 
 @pytest.fixture(scope="module")
 def bgzf_run(torch_cuda, tmp_path_factory):
     """2 chunks x 3 000 pairs in BGZF, run once with trimming and the quality report on; the model over the oracle's outputs"""
-    from tests.test_gpu_quality import _cli
     top = tmp_path_factory.mktemp("trim_bgzf")
     files, samples = _dataset(str(top / "data"), 51, 2, 3000, bgzf=True)
     plain = top / "plain.txt"
@@ -465,7 +395,6 @@ def test_cli_outputs_and_reports_equal_the_model_bgzf(bgzf_run):
 
 
 def test_cli_ordinary_gzip(torch_cuda, tmp_path):
-    from tests.test_gpu_quality import _cli
     files, samples = _dataset(str(tmp_path / "data"), 52, 2, 3000, bgzf=False)
     _write_conf(tmp_path / "plain.txt", files, samples, trim="")
     texts, table = _oracle(tmp_path / "plain.txt", tmp_path / "ref")
@@ -476,7 +405,6 @@ def test_cli_ordinary_gzip(torch_cuda, tmp_path):
 
 
 def test_cli_chunk_workers_and_write_flags(bgzf_run, tmp_path):
-    from tests.test_gpu_quality import _cli
     run = bgzf_run
     conf = tmp_path / "workers.txt"
     _write_conf(conf, run["files"], run["samples"], gpu="chunk_workers : 2\n")
@@ -490,7 +418,6 @@ def test_cli_chunk_workers_and_write_flags(bgzf_run, tmp_path):
 
 def test_cli_two_ranks_sharded_and_whole_chunks(bgzf_run, tmp_path):
     """2 ranks on GPU 0 (counters through the rendezvous files): each a pair range of ONE shared BGZF chunk, then a chunk each"""
-    from tests.test_gpu_quality import _cli
     run = bgzf_run
     _write_conf(tmp_path / "plain.txt", run["files"], run["samples"], trim="", chunks=[0])
     texts, table = _oracle(tmp_path / "plain.txt", tmp_path / "ref")
@@ -507,8 +434,6 @@ def test_cli_two_ranks_sharded_and_whole_chunks(bgzf_run, tmp_path):
 
 
 def test_cli_without_the_section_nothing_changes(bgzf_run, tmp_path):
-    from tests.test_gpu_e2e import _compare_dirs
-    from tests.test_gpu_quality import _cli
     run = bgzf_run
     _cli(run["plain"], tmp_path / "off")
     assert not os.path.exists(tmp_path / "off" / tr.REPORT_NAME)

@@ -218,7 +218,7 @@ def test_accumulation_over_slots_and_caller_streams(torch_cuda):
 # ---- 3. with budgets (1, 1) ---------------------------------------------------------------------------------------------------
 def test_rescued_pairs_are_not_tallied(torch_cuda, engine, monkeypatch):
     torch = torch_cuda
-    from tests.test_gpu_mismatch import SHAPES, make_reads, rows_on_device, sheet
+    from tests.mismatch_support import SHAPES, make_reads, rows_on_device, sheet
     bcs = sheet("dual8", 64, 1, 1)
     n = 20011
     streams = make_reads("dual8", bcs, n, 1, 1, seed=31, short_frac=0.05)
@@ -429,7 +429,7 @@ def _golden_truth(bundled_dir):
 
 @pytest.mark.parametrize("path", ["device_pipeline", "pinned_slots"])
 def test_cli_bundled_golden_run(torch_cuda, tmp_path, bundled_dir, path):
-    from tests.test_gpu_e2e import _compare_dirs
+    from tests.run_support import _compare_dirs
     truth = _golden_truth(bundled_dir)
     assert sum(truth.values()) == 247 and len(truth) == 19
     assert UM.report_order(truth)[:6] == [("GCCAGCCA", 53), ("CGATCGAT", 48), ("TGACTGAC", 40), ("CAGACAGA", 38), ("GTGAGTGA", 29),
@@ -466,7 +466,7 @@ def test_cli_bundled_golden_run(torch_cuda, tmp_path, bundled_dir, path):
 def test_merging_chunk_workers_and_ranks(torch_cuda, tmp_path):
     """3 chunks: one worker and one rank, chunk_workers : 2 (two contexts), and 2 ranks on GPU 0 over the files transport all
     write the same Quade_unknown_barcodes.csv; its rows are the oracle's Undetermined index slices."""
-    from tests.test_gpu_e2e import _conf, _make_dataset
+    from tests.run_support import _conf, _make_dataset
     rng = np.random.default_rng(99)
     bcs = sorted({("".join(rng.choice(list("ACGT"), 8)), "".join(rng.choice(list("ACGT"), 8))) for _ in range(7)})
     data = tmp_path / "data"

@@ -12,7 +12,7 @@ from quade_amd import clip_report as cr
 from quade_amd import conf as qconf
 from quade_amd import hip_backend as hb
 from tests import clip_model as CM
-from tests.test_host_trim import _conf
+from tests.stage_support import _one_sample_conf as _conf
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PARAMS = dict(front_clip_r1=2, front_clip_r2=0, tail_clip_r1=1, tail_clip_r2=0, window_size=4, window_quality=20, poly_g_min_length=10,
@@ -263,11 +263,11 @@ def test_pack_unpack_and_sum():
     a = rng.integers(0, 1 << 62, (2, 12), dtype=np.uint64)
     b = rng.integers(0, 1 << 62, (2, 12), dtype=np.uint64)
     a[1, 2], b[1, 2] = (1 << 63) - 1, 1 << 62
-    blob = hb.pack_clip(a)
+    blob = hb.pack_table("clip", a)
     assert isinstance(blob, bytes) and len(blob) == 192
-    a2 = hb.unpack_clip(blob)
+    a2 = hb.unpack_table("clip", blob)
     assert a2.dtype == np.uint64 and a2.shape == (2, 12) and (a2 == a).all()
-    a2 += hb.unpack_clip(hb.pack_clip(b.reshape(-1)))  # (a flat table packs alike; unpacked tables are writable copies)
+    a2 += hb.unpack_table("clip", hb.pack_table("clip", b.reshape(-1)))  # (a flat table packs alike; unpacked tables are writable copies)
     assert all(int(x) == int(y) + int(z) for x, y, z in zip(a2.reshape(-1), a.reshape(-1), b.reshape(-1)))
     with pytest.raises(AssertionError):
-        hb.unpack_clip(blob[:-8])
+        hb.unpack_table("clip", blob[:-8])

@@ -12,6 +12,7 @@ from oracle import quade_oracle as qo
 from quade_amd import hip_backend as hb
 from quade_amd.conf import QuadeConf, template_bytes, write_example_conf
 from quade_amd.sample import Sample
+from tests.run_support import _build_abi_client
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -351,18 +352,6 @@ def test_synthetic_generator_truth_equals_oracle():
         codes, _, _, counts = H.oracle_on_workload(w)
         assert (codes == w.expected.numpy().astype(np.uint16)).all()
         assert counts[0] == 3000 and counts[3] > 0 and (counts[2] > 0) == (synth.CONFIGS[name]["min_qual"] > 0)
-
-
-def _build_abi_client(tmp_path):
-    import subprocess
-    exe = str(tmp_path / "abi_client")
-    lib_dir = os.path.join(ROOT, "quade_amd", "lib")
-    cmd = ["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "examples", "abi_client.c"), "-L", lib_dir, "-lquade_hip", "-Wl,-rpath," + lib_dir,
-           "-Wl,-rpath-link,/opt/rocm/lib", "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return exe
 
 
 def test_c99_client_builds_against_the_header_and_fails_loudly_without_a_gpu(tmp_path):

@@ -213,15 +213,15 @@ def test_views_pack_unpack_and_sum():
     va["gc"][2, 1, 100] = (1 << 63) - 1  # a view: the flat table changes
     assert int(a[-1]) == (1 << 63) - 1
     b[-1] = 1 << 62
-    blob = hb.pack_cstats(va)
-    assert isinstance(blob, bytes) and blob == hb.pack_cstats(a)
-    a2 = hb.unpack_cstats(blob)
+    blob = hb.pack_table("cycle", va)
+    assert isinstance(blob, bytes) and blob == hb.pack_table("cycle", a)
+    a2 = hb.unpack_table("cycle", blob)
     assert all(a2[k].dtype == np.uint64 and (a2[k] == va[k]).all() for k in va)
-    total = hb.cstats_flat(a2) + hb.cstats_flat(hb.unpack_cstats(hb.pack_cstats(b)))
+    total = hb.cstats_flat(a2) + hb.cstats_flat(hb.unpack_table("cycle", hb.pack_table("cycle", b)))
     assert all(int(x) == int(y) + int(z) for x, y, z in zip(total[::97], a[::97], b[::97]))
     assert int(total[-1]) == (1 << 63) - 1 + (1 << 62)  # sums stay integers beyond 2^63
     with pytest.raises(AssertionError):
-        hb.unpack_cstats(blob[:-8])
+        hb.unpack_table("cycle", blob[:-8])
     with pytest.raises(AssertionError):
         hb.cstats_views(a[:-1])
     assert hb.CSTATS_GROUPS == ("pass", "fail", "Undetermined") == cr.GROUPS

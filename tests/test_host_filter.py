@@ -143,14 +143,14 @@ def test_pack_unpack_and_sum():
     a = rng.integers(0, 1 << 62, (13, 8), dtype=np.uint64)
     b = rng.integers(0, 1 << 62, (13, 8), dtype=np.uint64)
     a[12, 7], b[12, 7] = (1 << 63) + 5, 7
-    blob = hb.pack_filter(a)
+    blob = hb.pack_table("filter", a)
     assert isinstance(blob, bytes) and len(blob) == 8 + 13 * 8 * 8
-    a2 = hb.unpack_filter(blob)
+    a2 = hb.unpack_table("filter", blob)
     assert a2.dtype == np.uint64 and a2.shape == (13, 8) and (a2 == a).all()
-    a2 += hb.unpack_filter(hb.pack_filter(b.reshape(-1)))  # (a flat table packs alike; unpacked tables are writable copies)
+    a2 += hb.unpack_table("filter", hb.pack_table("filter", b.reshape(-1)))  # (a flat table packs alike; unpacked tables are writable copies)
     assert all(int(x) == int(y) + int(z) for x, y, z in zip(a2.ravel(), a.ravel(), b.ravel())) and int(a2[12, 7]) == (1 << 63) + 12
     with pytest.raises(AssertionError):
-        hb.unpack_filter(blob[:-8])
+        hb.unpack_table("filter", blob[:-8])
 
 
 def _conf(tmp_path, extra="", gpu=""):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from tests import deflate_forge as F
+from tests.run_support import write_corpus
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -91,15 +92,6 @@ def test_host_gunzip_on_the_forged_corpus(chunk):
             m = F.gzip_member(raw, text, extra=F.subfield(b"XY", b"abc"), name=b"reads.fastq", comment=b"forged", hcrc=True)
             rc, got, members = _gunzip(m + m, chunk, 2 * len(text) + 16)
             assert rc == 0 and got == text + text and members == 2, (name, rc)
-
-
-def write_corpus(d):
-    """the corpus as files for tests/native/inflate3_lane_test.cpp: cNN.deflate + cNN.txt | cNN.illegal + cNN.tags (name, tags)"""
-    for i, (name, raw, text, tags) in enumerate(F.corpus()):
-        stem = os.path.join(str(d), "c%02d" % i)
-        open(stem + ".deflate", "wb").write(raw)
-        open(stem + (".illegal" if text is None else ".txt"), "wb").write(text or b"")
-        open(stem + ".tags", "w").write(name + "\n" + " ".join("%s=%s" % (k, int(v)) for k, v in sorted(tags.items())) + "\n")
 
 
 def build_lane_test(tmp_path, header_dir=None):

@@ -304,15 +304,15 @@ def test_pack_unpack_and_sum():
     a = rng.integers(0, 1 << 62, 1040, dtype=np.uint64)
     b = rng.integers(0, 1 << 62, 1040, dtype=np.uint64)
     a[14], b[14], a[1039], b[1039] = (1 << 63) - 1, 1 << 62, (1 << 63) + 5, 7
-    blob = hb.pack_pairtrim(a)
+    blob = hb.pack_table("pairtrim", a)
     assert isinstance(blob, bytes) and len(blob) == 1040 * 8
-    a2 = hb.unpack_pairtrim(blob)
+    a2 = hb.unpack_table("pairtrim", blob)
     assert a2.dtype == np.uint64 and a2.shape == (1040,) and (a2 == a).all()
-    a2 += hb.unpack_pairtrim(hb.pack_pairtrim(b.reshape(2, 520)))  # (any shape of 1040 packs alike; unpacked tables are writable copies)
+    a2 += hb.unpack_table("pairtrim", hb.pack_table("pairtrim", b.reshape(2, 520)))  # (any shape of 1040 packs alike; unpacked tables are writable copies)
     assert all(int(x) == int(y) + int(z) for x, y, z in zip(a2, a, b))
     assert int(a2[14]) == (1 << 63) - 1 + (1 << 62) and int(a2[1039]) == (1 << 63) + 12  # sums stay integers beyond 2^63
     with pytest.raises(AssertionError):
-        hb.unpack_pairtrim(blob[:-8])
+        hb.unpack_table("pairtrim", blob[:-8])
     reads, pairs, hist = hb.split_pairtrim(a2)
     assert [len(reads[0]), len(reads[1]), len(pairs), len(hist)] == [6, 6, 3, 1025] and pairs[2] == int(a2[14]) and hist[-1] == int(a2[1039])
     assert hb.PAIRTRIM_COUNTERS == ("reads", "bases_in", "bases_out", "overlap_trimmed_reads", "overlap_trimmed_bases", "floored_reads")

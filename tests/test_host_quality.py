@@ -152,15 +152,15 @@ def test_pack_unpack_and_sum():
     b = rng.integers(0, 1 << 62, (2 * 7 + 1, 2, 6), dtype=np.uint64)
     a[3, 1, 2] = (1 << 63) - 1
     b[3, 1, 2] = 1 << 62
-    blob = hb.pack_qstats(a)
+    blob = hb.pack_table("quality", a)
     assert isinstance(blob, bytes)
-    a2 = hb.unpack_qstats(blob)
+    a2 = hb.unpack_table("quality", blob)
     assert a2.dtype == np.uint64 and a2.shape == a.shape and (a2 == a).all()
-    a2 += hb.unpack_qstats(hb.pack_qstats(b.reshape(-1)))  # (a flat table packs alike; unpacked tables are writable copies)
+    a2 += hb.unpack_table("quality", hb.pack_table("quality", b.reshape(-1)))  # (a flat table packs alike; unpacked tables are writable copies)
     assert all(int(x) == int(y) + int(z) for x, y, z in zip(a2.reshape(-1), a.reshape(-1), b.reshape(-1)))
     assert int(a2[3, 1, 2]) == (1 << 63) - 1 + (1 << 62)  # sums stay integers beyond 2^63
-    one = hb.unpack_qstats(hb.pack_qstats(np.zeros((1, 2, 6), np.uint64)))
+    one = hb.unpack_table("quality", hb.pack_table("quality", np.zeros((1, 2, 6), np.uint64)))
     assert one.shape == (1, 2, 6)
     with pytest.raises(AssertionError):
-        hb.unpack_qstats(blob[:-8])
+        hb.unpack_table("quality", blob[:-8])
     assert hb.QSTATS_COUNTERS == ("records", "bases", "qual_sum", "q20_bases", "q30_bases", "n_bases")

@@ -15,46 +15,10 @@ from oracle import quade_oracle as qo
 from quade_amd import hip_backend as hb
 from tests import helpers as H
 from tests import route_model as RM
-from tests.test_gpu_e2e import SCENARIOS, _conf
+from tests.run_support import (NAME_BYTES, ORACLE_PLANS, PLANS, SCENARIOS, _conf, build_fastq, make_plan, ragged_index_reads, rand_bytes,
+                               reads_of)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# the plans of the oracle comparison (single with extension, dual with offset windows, molecular part in both reads, truncated) and
-# the two more that the GPU sweep adds (dual 10 bp, the 20 + 4 wide window)
-ORACLE_PLANS = ("single_mol_ext", "dual_offset_windows", "dual_umi_in_both_reads_truncated")
-PLANS = ORACLE_PLANS + ("dual_10bp_wide_fast", "wide_window_generic")
-NAME_BYTES = b"ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789:_-/#"
-
-
-def make_plan(name):
-    sc = SCENARIOS[name]
-    z = [(p[0] - 1, p[1]) if p else (0, 0) for p in sc["pos"]]  # (1-based inclusive) -> (0-based start, end): src/Quade.py:105-116
-    return hb.make_plan(sc["dual"], sc["minq"], z[0], z[1], z[2], z[3])
-
-
-def rand_bytes(rng, L, alphabet):
-    return bytes(alphabet[int(v)] for v in rng.integers(0, len(alphabet), L))
-
-
-def build_fastq(reads, styles):
-    """[(name, seq, qual)] -> (fastq text, its record table uint32[n, 6] in qd_dev_fastq_scan's layout).  style bits: 1 = CRLF line
-    ends, 2 = text behind the '+', 4 = a comment behind the name (blanks behind the '@' of an empty name)."""
-    parts, table, pos = [], np.zeros((len(reads), 6), dtype=np.uint32), 0
-    for i, ((name, seq, qual), style) in enumerate(zip(reads, styles)):
-        nl = b"\r\n" if style & 1 else b"\n"
-        comment = (b" 1:N:0:" if name else b" \t") if style & 4 else b""
-        head = b"@" + name + comment
-        plus = b"+" + name if style & 2 else b"+"
-        rec = head + nl + seq + nl + plus + nl + qual + nl
-        seq_at = pos + len(head) + len(nl)
-        # (an empty name is found behind every blank of the header line, the '\r' included: where its '\n' is)
-        table[i] = (pos, pos + 1 if name else seq_at - 1, len(name), seq_at, len(seq), seq_at + len(seq) + len(nl) + len(plus) + len(nl))
-        parts.append(rec)
-        pos += len(rec)
-    return b"".join(parts), table
-
-
-def reads_of(text, table):
-    return [RM.read_of(text, r) for r in table]
 
 
 def ragged_inserts(rng, n, max_len=160):
@@ -64,29 +28,6 @@ def ragged_inserts(rng, n, max_len=160):
         name = rand_bytes(rng, int(rng.integers(1, 40)) if i % 17 else 0, NAME_BYTES)
         reads.append((name, rand_bytes(rng, L, b"ACGTNacgtn"), rand_bytes(rng, L, bytes(range(33, 75)))))
     return reads
-
-
-def ragged_index_reads(rng, n, start, width, barcodes, k):
-    """index reads of stream k: a sample's barcode at the window's start (or random bases), then as read, lower case, with an N,
-    truncated, or over-long; qualities on both sides of every threshold in use"""
-    out = []
-    for i in range(n):
-        b = barcodes[int(rng.integers(0, len(barcodes)))][k]
-        s = b"A" * start + b + rand_bytes(rng, int(rng.integers(0, 12)), b"ACGT")
-        kind = i % 10
-        if kind == 0:
-            s = s.lower()
-        elif kind == 1 and width:
-            p = start + int(rng.integers(0, width))
-            s = s[:p] + b"N" + s[p + 1:]
-        elif kind == 2:
-            s = rand_bytes(rng, len(s), b"ACGTacgtN")
-        elif kind == 3:
-            s = s[:(i // 10) % (len(s) + 1)]
-        elif kind == 4:
-            s = s + rand_bytes(rng, (255, 256, 300)[i % 3] - len(s), b"ACGTn")
-        out.append((b"idx%d" % i, s, rand_bytes(rng, len(s), bytes(range(33 + (18 if i % 3 == 0 else 31), 33 + 41)))))
-    return out
 
 
 class Dataset(object):

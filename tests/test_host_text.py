@@ -53,7 +53,7 @@ def test_inflate3_lane_decoder_against_zlib(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "all checks passed" in r.stdout, r.stdout[-2000:]
     # ... and against the forged corpus (tests/deflate_forge.py): DEFLATE that zlib never writes, and one stream per refusal
-    from tests.test_host_forge import write_corpus
+    from tests.run_support import write_corpus
     d = tmp_path / "corpus"
     d.mkdir()
     write_corpus(d)

@@ -12,6 +12,7 @@ from quade_amd import conf as qconf
 from quade_amd import hip_backend as hb
 from quade_amd import trim_report as tr
 from tests import trim_model as TM
+from tests.stage_support import _one_sample_conf as _conf
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEEDS = "[trim] needs the device pipeline (device_pipeline, device_inflate, device_deflate : True and gzip_level 1 or -1)"
@@ -96,18 +97,6 @@ def test_report_lines_beyond_53_bits():
     assert r1[11] == "%d.%02d" % (v // 100, v % 100) == "49.99"  # exact integers: a float would round to 50.00
     total = lines[-1].split("\t")
     assert total[1] == str((1 << 63) + 2) and total[2] == str((1 << 64) + 6)  # the sum of two rows passes 64 bits and stays exact
-
-
-def _conf(tmp_path, trim="", gpu=""):
-    f = tmp_path / "reads.fastq"
-    f.write_text("")
-    txt = "[quality]\nminimal_qual : 25\n[fastq]\nseq_R1 : {0}\nseq_R2 : {0}\nindex_R1 : {0}\nindex_R2 : {0}\n".format(f)
-    txt += "[index]\nindex2 : True\nmolecular1 : False\nmolecular2 : False\nindex1_start : 1\nindex1_end : 8\nindex2_start : 1\nindex2_end : 8\n"
-    txt += "[output]\nwrite_pass : True\nwrite_fail : True\nwrite_undetermined : True\n" + trim + gpu
-    txt += "[sample1]\nname : S1\nindex1_seq : ACAGACAG\nindex2_seq : CTTGCTTG\n"
-    p = tmp_path / "conf.txt"
-    p.write_text(txt)
-    return str(p)
 
 
 def test_conf_defaults_and_when_trimming_is_on(tmp_path):
@@ -212,14 +201,14 @@ def test_pack_unpack_and_sum():
     a = rng.integers(0, 1 << 62, (2, 8), dtype=np.uint64)
     b = rng.integers(0, 1 << 62, (2, 8), dtype=np.uint64)
     a[1, 2], b[1, 2] = (1 << 63) - 1, 1 << 62
-    blob = hb.pack_trim(a)
+    blob = hb.pack_table("trim", a)
     assert isinstance(blob, bytes) and len(blob) == 128
-    a2 = hb.unpack_trim(blob)
+    a2 = hb.unpack_table("trim", blob)
     assert a2.dtype == np.uint64 and a2.shape == (2, 8) and (a2 == a).all()
-    a2 += hb.unpack_trim(hb.pack_trim(b.reshape(-1)))  # (a flat table packs alike; unpacked tables are writable copies)
+    a2 += hb.unpack_table("trim", hb.pack_table("trim", b.reshape(-1)))  # (a flat table packs alike; unpacked tables are writable copies)
     assert all(int(x) == int(y) + int(z) for x, y, z in zip(a2.reshape(-1), a.reshape(-1), b.reshape(-1)))
     assert int(a2[1, 2]) == (1 << 63) - 1 + (1 << 62)  # sums stay integers beyond 2^63
     with pytest.raises(AssertionError):
-        hb.unpack_trim(blob[:-8])
+        hb.unpack_table("trim", blob[:-8])
     assert hb.TRIM_COUNTERS == ("reads", "bases_in", "bases_out", "quality_trimmed_reads", "quality_trimmed_bases", "adapter_reads",
                                 "adapter_bases", "floored_reads")

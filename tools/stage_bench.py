@@ -1,0 +1,502 @@
+#!/usr/bin/env python3
+"""Cost of one read stage's kernel over resident text: one batch of the device pipeline -- 2 M pairs of 2 x 150 bp insert reads
+as fastq text in HBM with their record tables (and routing codes) -- worked on by the kernel qd_pipe_run launches, through the
+pipeline's internal entry qd_<stage>_device.  Several contexts on one device take the same batch: one with the stage off, one
+with it on, and for some stages one that runs a comparison kernel; their calls alternate on one stream (off, on, off, on, ...) and
+each is timed by HIP events.  "off" does what process_batch does with the stage off, launches nothing and shows what the timing
+itself costs.  After the timed steps the stage's table is read back and checked against what the batch must have counted.  Prints
+one JSON line ("tool": "<stage>_bench"): per case the medians, the spread and the byte floor (the lines' bytes at 6.3 TB/s).
+
+usage: python tools/stage_bench.py --stage qstats|cycle|clip|trim|pairtrim|filter [--pairs N] [--bases L] [--steps K] [--warmup W]
+                                   [--once CASE] [--out FILE]
+  --once CASE  set up, run ONE launch and exit (for `rocprofv3 --kernel-trace --stats -- python ...`); CASE by stage:
+    qstats    hot | spread | off      routing: 96 samples with 90 % of the pairs to 8 destinations (per-workgroup partials in LDS) |
+                                      4 000 samples, uniform (64-bit global atomics); off: the context with the table off
+    cycle     pass | mix | long | off every pair to a pass file | a third each to pass, fail, Undetermined | reads of 2 x --bases;
+                                      interleaved with the quality counters' kernel over the same batch
+    clip      CASE:PCT                yardstick | window | poly_g | all, over a batch with PCT % of the reads ending in 30 G; the
+                                      yardstick is the 3' trimming kernel with a cutoff only
+    trim      PCT                     PCT % of the reads carry their adapter from a random position on
+    pairtrim  PCT | poly              PCT % of the pairs read from an insert of 30 .. --bases - 1 bases | poly-A against poly-T
+    filter    drop0 | drop10 | drop100 | spread | off   the share of pairs dropped (poly-G in R1), hot or spread routing;
+                                      interleaved with the quality counters' kernel over the same batch
+The end-to-end rates come from tools/e2e_bench.py with the stage's E2E_* switch against none."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from quade_amd import hip_backend as hb  # noqa: E402
+
+COPY_RATE = 6.3e12  # bytes/s an MI355X copies at (measured float4 copy)
+ADAPTERS = ("AGATCGGAAGAGCACACGTCTGAACTCCAGTCA", "AGATCGGAAGAGCGTCGTGTAGGGAAAGAGTGT")
+G_TAIL = 30
+PLAN = hb.make_plan(True, 25, (0, 8), (0, 8))
+
+
+# ---- the batch: resident text, record tables, routing codes -----------------------------------------------------------------------
+def generator(seed):
+    return torch.Generator(device="cuda").manual_seed(seed)
+
+
+def plain_seq(g, n, L):
+    """bases with an N in 16"""
+    return torch.tensor(list(b"ACGTACGTACGTACGN"), dtype=torch.uint8, device="cuda")[torch.randint(0, 16, (n, L), generator=g, device="cuda")]
+
+
+def plain_qual(g, n, L):
+    """Phred 2 .. 40"""
+    return torch.randint(35, 74, (n, L), generator=g, device="cuda", dtype=torch.uint8)
+
+
+def make_text(n, L, seed, plant=None):
+    """n records "@<20-byte name>\\n<L bases>\\n+\\n<L qualities>\\n" on the device, their record table (6 uint32 each) and a record's
+    bytes.  plant(g, n, L) -> (bases, qualities) uint8[n, L] is what a stage puts into the reads (adapters, G tails, short inserts),
+    drawn from the text's generator behind the names; None: plain_seq and plain_qual."""
+    g = generator(seed)
+    rec = 1 + 20 + 1 + L + 1 + 2 + L + 1
+    t = torch.empty((n, rec), dtype=torch.uint8, device="cuda")
+    t[:, 0] = ord("@")
+    t[:, 1:21] = torch.randint(48, 58, (n, 20), generator=g, device="cuda", dtype=torch.uint8)
+    t[:, 22:22 + L], t[:, 25 + L:25 + 2 * L] = plant(g, n, L) if plant else (plain_seq(g, n, L), plain_qual(g, n, L))
+    t[:, 21] = t[:, 22 + L] = t[:, 24 + L] = t[:, 25 + 2 * L] = 10
+    t[:, 23 + L] = ord("+")
+    head = torch.arange(n, device="cuda", dtype=torch.int64) * rec
+    recs = torch.stack([head, head + 1, torch.full_like(head, 20), head + 22, torch.full_like(head, L), head + 25 + L], dim=1)
+    assert n * rec < 1 << 31
+    return t.reshape(-1), recs.to(torch.int32).contiguous(), rec
+
+
+class Batch(object):
+    """R1 and R2 texts (seeds s1, s2; plant per read: plants[r]) with their tables, and tables for a stage's output"""
+
+    def __init__(self, n, L, s1=1, s2=2, plants=(None, None)):
+        self.n, self.L = n, L
+        self.t1, self.r1, self.rec = make_text(n, L, s1, plants[0])
+        self.t2, self.r2, _ = make_text(n, L, s2, plants[1])
+
+    def outputs(self):
+        self.o1, self.o2 = torch.empty_like(self.r1), torch.empty_like(self.r2)
+        return self.o1.data_ptr(), self.o2.data_ptr()
+
+    def kept_whole(self):
+        """a stage that writes new tables changed nothing but the lengths, and lengthened no read"""
+        return bool((self.o1[:, [0, 1, 2, 3, 5]] == self.r1[:, [0, 1, 2, 3, 5]]).all()) and int(self.o1[:, 4].max()) <= self.L
+
+
+def routed_codes(g, n, name):
+    """-> (samples, routing codes): hot = 96 samples, 90 % of the pairs to 8 destinations; spread = 4 000 samples, uniform over the
+    8 001 destinations"""
+    S = 96 if name == "hot" else 4000
+    codes = torch.randint(0, 2 * S + 1, (n,), generator=g, device="cuda")
+    if name == "hot":
+        hot = torch.rand(n, generator=g, device="cuda") < 0.9
+        codes[hot] = torch.randint(0, 8, (int(hot.sum()),), generator=g, device="cuda") * 2
+    codes[codes == 2 * S] = 0xFFFF
+    return S, codes.to(torch.int16).contiguous()
+
+
+def contexts(kinds, S=None):
+    """{name: a context set up by kinds[name](engine) (None: left as it is)}, in kinds' order; S: with the plan and S barcodes"""
+    engines = {}
+    for k, setup in kinds.items():
+        eng = hb.Engine(0)
+        if S is not None:
+            eng.set_plan(PLAN)
+            eng.set_barcodes(["".join("ACGT"[(i >> (2 * j)) & 3] for j in range(16)) for i in range(S)])
+        if setup:
+            setup(eng)
+        engines[k] = eng
+    return engines
+
+
+def close(engines):
+    for eng in engines.values():
+        eng.close()
+
+
+# ---- launching and timing -----------------------------------------------------------------------------------------------------------
+class Bench(object):
+    def __init__(self, a):
+        self.a, self.lib, self.st = a, hb.load_library(), torch.cuda.current_stream()
+
+    def entry(self, name):
+        """the pipeline's internal entry qd_<name>_device: a context, device pointers of the batch, two more and a stream"""
+        f = getattr(self.lib, "qd_%s_device" % name)
+        f.restype, f.argtypes = C.c_int, [C.c_void_p] * 5 + [C.c_uint32] + [C.c_void_p] * 3
+        return f
+
+    def asker(self, name):
+        """qd_<name>_active: what process_batch asks before it launches"""
+        f = getattr(self.lib, "qd_%s_active" % name)
+        f.restype, f.argtypes = C.c_int, [C.c_void_p]
+        return f
+
+    def launch(self, f, eng, b, x, y):
+        rc = f(eng._h, b.t1.data_ptr(), b.r1.data_ptr(), b.t2.data_ptr(), b.r2.data_ptr(), b.n, x, y, self.st.cuda_stream)
+        assert rc == 0, rc
+
+    def timed(self, run):
+        """run: {name: launcher}, called in this order in every step, each between two events -> {name: sorted milliseconds}"""
+        for _ in range(self.a.warmup):
+            for f in run.values():
+                f()
+        ev = {k: [] for k in run}
+        for _ in range(self.a.steps):
+            for k, f in run.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(self.st)
+                f()
+                e1.record(self.st)
+                ev[k].append((e0, e1))
+        torch.cuda.synchronize()
+        return {k: sorted(e0.elapsed_time(e1) for e0, e1 in v) for k, v in ev.items()}
+
+    def once_in(self, values):
+        if self.a.once not in values:
+            sys.exit("--once for --stage %s: %s" % (self.a.stage, " | ".join(v for v in values if v)))
+
+    def once(self, f, result):
+        f()
+        torch.cuda.synchronize()
+        return result
+
+    def floor_ms(self, lines, L=None):
+        """reading `lines` lines of every pair once at COPY_RATE"""
+        return float(lines) * self.a.pairs * (L or self.a.bases) / COPY_RATE * 1e3
+
+    def head(self, tool, **more):
+        out = {"tool": tool, "device": torch.cuda.get_device_name(0), "pairs_per_launch": self.a.pairs, "bases_per_read": self.a.bases}
+        out.update(more)
+        return out
+
+
+def median(v):
+    return v[len(v) // 2]
+
+
+def off_on(ms):
+    return {"off_median_ms": median(ms["off"]), "on_median_ms": median(ms["on"]), "off_min_ms": ms["off"][0], "off_max_ms": ms["off"][-1],
+            "on_min_ms": ms["on"][0], "on_max_ms": ms["on"][-1]}
+
+
+def by_name(ms):
+    out = {}
+    for k, v in ms.items():
+        out.update({k + "_median_ms": median(v), k + "_min_ms": v[0], k + "_max_ms": v[-1]})
+    return out
+
+
+# ---- the stages: their cases, launchers and the checks on the table ---------------------------------------------------------------
+def qstats(B):
+    a, n, L = B.a, B.a.pairs, B.a.bases
+    B.once_in((None, "hot", "spread", "off"))
+    launch, b, g = B.entry("qstats"), Batch(n, L), generator(7)
+
+    def measure(name):
+        S, codes = routed_codes(g, n, name)
+        engines = contexts({"off": None, "on": lambda e: e.qstats_enable(True)}, S)
+        run = {k: (lambda k=k: B.launch(launch, engines[k], b, codes.data_ptr(), None)) for k in engines}  # (no drop bytes)
+        if a.once:
+            return B.once(run["off" if a.once == "off" else "on"], {"once": a.once, "pairs": n, "bases": L, "path": engines["on"].qstats_kind()})
+        ms = B.timed(run)
+        table, launches = engines["on"].qstats_read(), a.steps + a.warmup
+        assert int(table[:, 0, 0].sum()) == launches * n and int(table[:, :, 1].sum()) == 2 * launches * n * L
+        out = {"routing": name, "samples": S, "path": engines["on"].qstats_kind(), **off_on(ms), "byte_floor_ms": B.floor_ms(4),
+               "busiest_destination_share": float(table[:, 0, 0].max()) / (launches * n)}
+        close(engines)
+        return out
+
+    if a.once:
+        return measure("hot" if a.once == "off" else a.once)
+    return B.head("qstats_bench", text_bytes=2 * n * b.rec, line_bytes=4 * n * L, steps=a.steps, hot=measure("hot"), spread=measure("spread"))
+
+
+def cycle(B):
+    a, n, S = B.a, B.a.pairs, 96
+    cases = {"pass": ("pass", 1), "mix": ("mix", 1), "long": ("pass", 2)}  # routing, read length in units of --bases
+    B.once_in([None, "off"] + sorted(cases))
+    launch, g = {"off": B.entry("cstats"), "cycle": B.entry("cstats"), "qstats": B.entry("qstats")}, generator(7)
+    kinds = {"off": None, "cycle": lambda e: e.cstats_enable(True), "qstats": lambda e: e.qstats_enable(True)}
+
+    def measure(case):
+        route, mult = cases[case]
+        L = a.bases * mult
+        b = Batch(n, L)
+        codes = torch.randint(0, S, (n,), generator=g, device="cuda") * 2  # pass
+        if route == "mix":
+            third = torch.randint(0, 3, (n,), generator=g, device="cuda")
+            codes[third == 1] += 1
+            codes[third == 2] = 0xFFFF
+        codes = codes.to(torch.int16).contiguous()
+        engines = contexts({k: kinds[k] for k in (("off",) if a.once == "off" else ("cycle",) if a.once else kinds)}, S)
+        # "off": what process_batch does with the table off -- the same call, which launches nothing
+        run = {k: (lambda k=k: B.launch(launch[k], engines[k], b, codes.data_ptr(), None)) for k in engines}
+        if a.once:
+            out = B.once(run["off" if a.once == "off" else "cycle"], {"once": a.once, "pairs": n, "bases": L})
+            close(engines)
+            return out
+        ms = B.timed(run)
+        launches = a.steps + a.warmup
+        t, q = engines["cycle"].cstats_read(), engines["qstats"].qstats_read()
+        assert int(t["len"].sum()) == 2 * launches * n and int(t["len"][:, :, L].sum()) == 2 * launches * n  # the one hot length bin
+        groups = [int(t["len"][k].sum()) for k in range(3)]
+        assert (groups[1] == groups[2] == 0) if route == "pass" else min(groups) > 0.3 * 2 * launches * n
+        for k, col in ((4, 5), (5, 2), (6, 3), (7, 4)):  # N, qual_sum, q20, q30 against the quality counters of the same batch
+            assert int(t["cycle"][:, :, :, k].sum()) == int(q[:, :, col].sum()), (k, col)
+        floor = B.floor_ms(4, L)
+        out = {"case": case, "samples": S, "bases_per_read": L, "byte_floor_ms": floor,
+               "cycle_over_qstats": median(ms["cycle"]) / median(ms["qstats"]), "cycle_over_floor": median(ms["cycle"]) / floor, **by_name(ms)}
+        close(engines)
+        return out
+
+    if a.once:
+        return measure("pass" if a.once == "off" else a.once)
+    out = B.head("cycle_bench", steps=a.steps, lds_cycles=B.lib.qd_cstats_lds_cycles())
+    for case in cases:
+        out[case] = measure(case)
+    return out
+
+
+def g_tails(share):
+    """a `share` of the reads ends in G_TAIL bases G; qualities 30 .. 40, on half the reads a 3' tail of 0 .. 40 bases at 2 .. 19 (not
+    under a G tail: a dark cluster reads as high-quality G)"""
+    def plant(g, n, L):
+        seq = plain_seq(g, n, L)
+        col = torch.arange(L, device="cuda").reshape(1, L)
+        has = (torch.rand(n, generator=g, device="cuda") < share).reshape(n, 1)
+        seq = torch.where(has & (col >= L - G_TAIL), torch.full_like(seq, ord("G")), seq)
+        qual = torch.randint(33 + 30, 33 + 41, (n, L), generator=g, device="cuda", dtype=torch.uint8)
+        low = torch.randint(33 + 2, 33 + 20, (n, L), generator=g, device="cuda", dtype=torch.uint8)
+        tail = torch.randint(0, 41, (n, 1), generator=g, device="cuda") * (torch.rand(n, 1, generator=g, device="cuda") < 0.5)
+        return seq, torch.where(~has & (col >= L - tail), low, qual)
+    return plant
+
+
+def clip(B):
+    a, n, L = B.a, B.a.pairs, B.a.bases
+    launch = {"yardstick": B.entry("trim"), "window": B.entry("clip"), "poly_g": B.entry("clip"), "all": B.entry("clip")}
+    engines = contexts({"yardstick": lambda e: e.trim_set(quality_cutoff=20), "window": lambda e: e.clip_set(window_size=4, window_quality=20),
+                        "poly_g": lambda e: e.clip_set(poly_g_min_length=10),
+                        "all": lambda e: e.clip_set(tail_clip_r1=1, tail_clip_r2=1, window_size=4, window_quality=20, poly_g_min_length=10)})
+    floor = B.floor_ms(4)
+
+    def measure(pct, only=None):
+        b = Batch(n, L, plants=(g_tails(pct / 100.0),) * 2)
+        o1, o2 = b.outputs()
+        run = {k: (lambda k=k: B.launch(launch[k], engines[k], b, o1, o2)) for k in engines}
+        if only is not None:
+            return B.once(run[only], {"once": only, "g_tail_percent": pct, "pairs": n, "bases": L})
+        for eng in engines.values():
+            eng.reset_counts()
+        ms = B.timed(run)
+        runs = a.steps + a.warmup
+        out = {"g_tail_percent": pct, "byte_floor_ms": floor, "cases": {}}
+        for k in engines:
+            table = engines[k].trim_read() if k == "yardstick" else engines[k].clip_read()
+            assert int(table[0, 0]) == int(table[1, 0]) == runs * n and int(table[:, 1].sum()) == 2 * runs * n * L
+            per = lambda c: float(table[:, c].sum()) / (2 * runs * n)  # noqa: E731
+            row = {"median_ms": median(ms[k]), "min_ms": ms[k][0], "max_ms": ms[k][-1], "over_yardstick": median(ms[k]) / median(ms["yardstick"]),
+                   "over_floor": median(ms[k]) / floor, "mean_bases_out": per(2)}
+            if k != "yardstick":
+                row.update(window_read_share=per(7), polyg_read_share=per(9))
+            out["cases"][k] = row
+        return out
+
+    if a.once is not None:
+        case, pct = a.once.split(":")
+        assert case in engines, "--once yardstick|window|poly_g|all:PCT"
+        return measure(int(pct), only=case)
+    out = B.head("clip_bench", line_bytes=4 * n * L, steps=a.steps, yardstick="trim_reads, quality_cutoff 20, no adapter",
+                 params={k: engines[k].clip_get() for k in list(engines)[1:]}, batches=[measure(pct) for pct in (0, 10, 100)])
+    close(engines)
+    return out
+
+
+def adapters(adapter, share):
+    """a `share` of the reads holds the adapter (cut at the read's end) from a random position on"""
+    def plant(g, n, L):
+        seq = plain_seq(g, n, L)
+        if share > 0:
+            ad = torch.tensor(list(adapter.encode()), dtype=torch.uint8, device="cuda")
+            has = torch.rand(n, generator=g, device="cuda") < share
+            p = torch.randint(0, L, (n, 1), generator=g, device="cuda")
+            col = torch.arange(L, device="cuda").reshape(1, L)
+            inside = has.reshape(n, 1) & (col >= p) & (col < p + len(ad))
+            seq = torch.where(inside, ad[(col - p).clamp(0, len(ad) - 1)], seq)
+        return seq, plain_qual(g, n, L)
+    return plant
+
+
+def rewriting(B, name, engines, b):
+    """{off, on} launchers of a stage that writes new record tables (trim, pairtrim) as process_batch runs it: it asks whether the
+    stage is on and launches only then"""
+    launch, active, (o1, o2) = B.entry(name), B.asker(name), b.outputs()
+    return {k: (lambda k=k: B.launch(launch, engines[k], b, o1, o2) if active(engines[k]._h) else None) for k in engines}
+
+
+def trim(B):
+    a, n, L = B.a, B.a.pairs, B.a.bases
+    engines = contexts({"off": None, "on": lambda e: e.trim_set(ADAPTERS[0], ADAPTERS[1], quality_cutoff=20)})
+    floor = B.floor_ms(4)
+
+    def measure(pct):
+        b = Batch(n, L, plants=(adapters(ADAPTERS[0], pct / 100.0), adapters(ADAPTERS[1], pct / 100.0)))
+        run = rewriting(B, "trim", engines, b)
+        if a.once is not None:
+            return B.once(run["on"], {"once": pct, "pairs": n, "bases": L})
+        engines["on"].reset_counts()
+        ms = B.timed(run)
+        table, launches = engines["on"].trim_read(), a.steps + a.warmup
+        assert int(table[0, 0]) == int(table[1, 0]) == launches * n and int(table[:, 1].sum()) == 2 * launches * n * L
+        assert b.kept_whole()
+        per = lambda k: float(table[:, k].sum()) / (2 * launches * n)  # noqa: E731
+        return {"adapter_percent": pct, **off_on(ms), "byte_floor_ms": floor, "on_over_floor": median(ms["on"]) / floor,
+                "quality_trimmed_read_share": per(3), "adapter_read_share": per(5), "mean_bases_out": per(2)}
+
+    if a.once is not None:
+        return measure(int(a.once))
+    out = B.head("trim_bench", line_bytes=4 * n * L, steps=a.steps, params=engines["on"].trim_get(),
+                 batches=[measure(pct) for pct in (0, 10, 100)])
+    close(engines)
+    return out
+
+
+def insert_pairs(n, L, seed, case):
+    """-> (R1, R2) base codes [n, L] on the device (0 .. 3 = A C G T); case: the percentage of pairs read from an insert of
+    30 .. L - 1 bases, or "poly" """
+    g = generator(seed)
+    if case == "poly":
+        return torch.zeros((n, L), dtype=torch.int64, device="cuda"), torch.full((n, L), 3, dtype=torch.int64, device="cuda")
+    frag = torch.randint(0, 4, (n, L), generator=g, device="cuda")
+    r1 = frag.clone()
+    r2 = torch.randint(0, 4, (n, L), generator=g, device="cuda")
+    if case > 0:
+        short = torch.rand(n, generator=g, device="cuda") < case / 100.0
+        insert = torch.randint(30, L, (n, 1), generator=g, device="cuda")
+        col = torch.arange(L, device="cuda").reshape(1, L)
+        inside = short.reshape(n, 1) & (col < insert)
+        rc = 3 - torch.gather(frag, 1, (insert - 1 - col).clamp(0, L - 1))
+        r2 = torch.where(inside, rc, r2)
+        r1 = torch.where(short.reshape(n, 1) & (col >= insert), torch.randint(0, 4, (n, L), generator=g, device="cuda"), r1)
+    return r1, r2
+
+
+def pairtrim(B):
+    a, n, L = B.a, B.a.pairs, B.a.bases
+    engines = contexts({"off": None, "on": lambda e: e.pairtrim_set()})
+    floor = B.floor_ms(2)
+    acgt = lambda codes: lambda g, n_, L_: (torch.tensor(list(b"ACGT"), dtype=torch.uint8, device="cuda")[codes], plain_qual(g, n_, L_))  # noqa: E731
+
+    def measure(case):
+        c1, c2 = insert_pairs(n, L, 1, case)
+        b = Batch(n, L, 2, 3, plants=(acgt(c1), acgt(c2)))
+        del c1, c2
+        run = rewriting(B, "pairtrim", engines, b)
+        if a.once is not None:
+            return B.once(run["on"], {"once": case, "pairs": n, "bases": L})
+        engines["on"].reset_counts()
+        ms = B.timed(run)
+        reads, pairs, hist = hb.split_pairtrim(engines["on"].pairtrim_read())
+        launches = a.steps + a.warmup
+        assert pairs[0] == reads[0][0] == reads[1][0] == launches * n and reads[0][1] == reads[1][1] == launches * n * L
+        assert sum(hist) == pairs[1] and b.kept_whole()
+        if case != "poly":  # an unrelated pair is next to never accepted, an insert always found
+            assert abs(pairs[2] / pairs[0] - case / 100.0) < 0.01, pairs
+        return {"case": case, **off_on(ms), "byte_floor_ms": floor, "on_over_floor": median(ms["on"]) / floor,
+                "overlapped_pair_share": pairs[1] / pairs[0], "short_insert_pair_share": pairs[2] / pairs[0],
+                "mean_bases_out": (reads[0][2] + reads[1][2]) / (2.0 * pairs[0])}
+
+    if a.once is not None:
+        out = measure(a.once if a.once == "poly" else int(a.once))
+    else:
+        out = B.head("pairtrim_bench", line_bytes=2 * n * L, steps=a.steps, params=engines["on"].pairtrim_get(),
+                     batches=[measure(case) for case in (0, 10, 100, "poly")])
+    close(engines)
+    return out
+
+
+def filter_(B):
+    a, n, L = B.a, B.a.pairs, B.a.bases
+    cases = {"drop0": (0.0, "hot"), "drop10": (0.1, "hot"), "drop100": (1.0, "hot"), "spread": (0.1, "spread")}
+    rules = dict(min_length=30, max_n=5, max_unqualified_pct=40, min_mean_quality=20, min_complexity_pct=30)
+    B.once_in([None, "off"] + sorted(cases))
+    f_launch, q_launch, active, g = B.entry("filter"), B.entry("qstats"), B.asker("filter"), generator(7)
+    kinds = {"off": None, "filter": lambda e: e.filter_set(**rules), "qstats": lambda e: e.qstats_enable(True)}
+    reason = torch.zeros(n + 64, dtype=torch.uint8, device="cuda")
+    floor = B.floor_ms(4)
+
+    def texts(share):
+        """the batch with `share` of its pairs poly-G in R1; the other reads are drawn so that every rule passes them (bases from ACGT
+        where make_text has an N in 16, Phred 20 .. 40 where it has 2 .. 40): the dropped share is exactly the poly-G share"""
+        b = Batch(n, L)
+        bases = torch.tensor(list(b"ACGT"), dtype=torch.uint8, device="cuda")
+        for t in (b.t1, b.t2):
+            v = t.view(n, b.rec)
+            v[:, 22:22 + L] = bases[torch.randint(0, 4, (n, L), generator=g, device="cuda")]
+            v[:, 25 + L:25 + 2 * L] = torch.randint(53, 74, (n, L), generator=g, device="cuda", dtype=torch.uint8)
+        poly = torch.rand(n, generator=g, device="cuda") < share if 0 < share < 1 else torch.full((n,), share >= 1, device="cuda")
+        b.t1.view(n, b.rec)[poly, 22:22 + L] = ord("G")
+        return b, int(poly.sum())
+
+    def measure(case):
+        share, route = cases[case]
+        b, n_poly = texts(share)
+        S, codes = routed_codes(g, n, route)
+        engines = contexts({k: kinds[k] for k in (("off",) if a.once == "off" else ("filter",) if a.once else kinds)}, S)
+
+        def off():  # what process_batch does with the stage off: it asks, and launches nothing
+            assert active(engines["off"]._h) == 0
+        run = {"off": off, "filter": lambda: B.launch(f_launch, engines["filter"], b, codes.data_ptr(), reason.data_ptr()),
+               "qstats": lambda: B.launch(q_launch, engines["qstats"], b, codes.data_ptr(), None)}
+        run = {k: run[k] for k in engines}
+        if a.once:
+            out = B.once(run["off" if a.once == "off" else "filter"],
+                         {"once": a.once, "pairs": n, "bases": L, "path": engines["filter"].filter_kind() if "filter" in engines else None})
+            close(engines)
+            return out
+        ms = B.timed(run)
+        table, launches = engines["filter"].filter_read(), a.steps + a.warmup
+        assert int(table[:, 0].sum()) == launches * n and int(table[:, 6].sum()) == 2 * launches * n * L
+        assert int(table[:, 5].sum()) == launches * n_poly and int(table[:, 1:5].sum()) == 0 and int(reason[:n].count_nonzero()) == n_poly
+        out = {"case": case, "samples": S, "path": engines["filter"].filter_kind(), "dropped_share": n_poly / n, "byte_floor_ms": floor,
+               "filter_over_qstats": median(ms["filter"]) / median(ms["qstats"]), "filter_over_floor": median(ms["filter"]) / floor, **by_name(ms)}
+        close(engines)
+        return out
+
+    if a.once:
+        return measure("drop10" if a.once == "off" else a.once)
+    out = B.head("filter_bench", line_bytes=4 * n * L, steps=a.steps, rules=rules)
+    for case in cases:
+        out[case] = measure(case)
+    return out
+
+
+STAGES = {"qstats": qstats, "cycle": cycle, "clip": clip, "trim": trim, "pairtrim": pairtrim, "filter": filter_}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--stage", required=True, choices=sorted(STAGES))
+    ap.add_argument("--pairs", type=int, default=2_000_000)
+    ap.add_argument("--bases", type=int, default=150)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--once", default=None)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    line = json.dumps(STAGES[a.stage](Bench(a)))
+    print(line)
+    if a.out and a.once is None:
+        with open(a.out, "w") as fh:
+            fh.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
