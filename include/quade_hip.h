@@ -168,7 +168,8 @@ int qd_kernel_kind(const qd_ctx* ctx, int has_len);
  *                             maximum 2^32 - 1; tests lower it)
  *   "unknown_tag_bits"        (tests only: the unknown-barcode tally keeps the low b bits of a key's 64-bit tag, 1..64,
  *                             default 64, so that tag collisions can be produced at will; set it before the first
- *                             tallied launch or right after qd_reset_counts) */
+ *                             tallied launch or right after qd_reset_counts)
+ *   "dup_tag_bits"            (tests only: the same knob for the duplication tally's table, qd_dup_set) */
 int qd_set_option(qd_ctx* ctx, const char* name, int64_t value);
 
 /* ---- mismatch-tolerant matching (opt-in; no reference counterpart: Quade 0.3.2 matches exactly) ---------
@@ -493,6 +494,60 @@ int qd_cstats_enable(qd_ctx* ctx, int32_t on);
 int qd_cstats_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
 int qd_cstats_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
 int qd_cstats_lds_cycles(void);
+
+/* ---- duplication report: read-pair keys tallied on the device (opt-in; no reference counterpart) -------------------------------
+ * The library duplication rate: how many of a destination's pairs repeat an earlier pair's first bases.  It is no sum of per-read
+ * counters: a device-resident hash table, fed by every batch, counts the pairs per key.  The pairs are those the output stages
+ * see -- behind the trimming stages, without the pairs the read filter dropped, every destination whatever its write flag:
+ * exactly the pairs the quality counters (qd_qstats_enable) count.
+ *
+ * Definition (quade_amd/csrc/quade_dup.h and tests/dup_model.py state the same; the kernels implement exactly this).
+ * Parameters: B = bases (8 .. 32), sample (a power of two, 1 .. 1024), slots (a power of two, 2^10 .. 2^28).  Per pair that
+ * carries no filter reason, with reads s1, s2 of current lengths L1, L2 and starts as the record tables in force give them (a
+ * front clip moves the start):
+ *   fold     u(b) = b & 0xDF; a base is valid when u(b) is one of A, C, G, T
+ *   code     c(b) = (u(b) >> 1) & 3, which gives A 0, C 1, T 2, G 3
+ *   class    the first that applies: short (L1 < B or L2 < B); with_n (an invalid base among the first B of either read); keyed
+ *   key      three 64-bit words (w1, w2, d): w_r = sum over i < B of c(s_r[i]) << (2 i) (there is no shift by 64 at B = 32);
+ *            d = the destination as qd_qstats numbers it (the routing code, 0xFFFF -> 2 * S).  Equal sequences in two
+ *            destinations are two keys: duplicates are a per-library matter
+ *   hash     h = the unknown tally's 64-bit tag function over the four words {w1, w2, d, 0}: h0 = 0x9E3779B97F4A7C15; per word
+ *            h = (h ^ w) * 0xFF51AFD7ED558CCD, h ^= h >> 32; then h *= 0xC4CEB9FE1A85EC53, h ^= h >> 29 (mod 2^64)
+ *   sampled  sample == 1, or h >> (64 - log2 sample) == 0.  This is key-space sampling: a sampled key keeps its exact
+ *            multiplicity, and every context and rank samples the same keys because the test is a pure function of the key.
+ *            Table and merge traffic fall by the factor `sample`; rates over the sample are unbiased estimates of the library's
+ *   tally    sampled pairs are counted per key in a table of `slots` entries per context.  The slot tag is h (0 replaced by 1;
+ *            the low dup_tag_bits of it under the test knob), the home slot and the probe limit min(slots, 1024) are the unknown
+ *            tally's.  A pair that finds no entry within the probe limit, or whose tag belongs to another key, is not_tallied
+ * Counters: uint64[2 * S + 1][QD_DUP_VALUES], destination-major as qd_qstats_read's:
+ *   0 pairs   1 short   2 with_n   3 sampled   4 not_tallied      (keyed = pairs - short - with_n)
+ * Per destination sampled == not_tallied + the sum of the counts of the table's entries with that d; every entry's count is exact.
+ *
+ * With the stage on, qd_pipe_run runs it over every pair it routes beside the quality counters (three launches per batch on its
+ * compute stream, no host sync; launches of one context on different streams are ordered among themselves as the unknown tally's
+ * are).  Off, nothing is allocated or launched.
+ *
+ * qd_dup_set: NULL turns the stage off and frees both tables; otherwise the values are checked (QD_ERR_INVALID, the state as
+ * before) and zeroed tables allocated (20 bytes per destination and 48 bytes per slot), which needs the plan and the barcodes
+ * (QD_ERR_STATE); a new plan or new barcodes turn the stage off, as they do the read filter.  Waits for the context's work.
+ * qd_dup_get: the parameters in force (all 0 and QD_OK when off).
+ * qd_dup_stats: waits for the context's work, writes n_values = (2 * S + 1) * 5 counters (QD_ERR_INVALID on another size,
+ * QD_ERR_STATE when off).
+ * qd_dup_read: the occupied entries are packed on the device and only they are downloaded; entry i is keys[3 i .. 3 i + 2] =
+ * (w1, w2, d) with counts[i], in no particular order.  Returns the number of entries, or -(entries needed) when cap is too small
+ * (cap 0 with NULL arrays asks for the size), or a value <= QD_DUP_READ_ERROR on failure: QD_DUP_READ_ERROR + QD_ERR_*.
+ * qd_reset_counts empties both tables.  Tables of several contexts or ranks are merged on the host: equal keys summed. */
+#define QD_DUP_VALUES 5
+#define QD_DUP_READ_ERROR (-((int64_t)1 << 40))
+typedef struct qd_dup_params {
+    int32_t bases;  /* 8 .. 32 */
+    int32_t sample; /* a power of two, 1 .. 1024 */
+    int64_t slots;  /* a power of two, 2^10 .. 2^28 */
+} qd_dup_params;
+int qd_dup_set(qd_ctx* ctx, const qd_dup_params* params);
+int qd_dup_get(const qd_ctx* ctx, qd_dup_params* out);
+int qd_dup_stats(qd_ctx* ctx, uint64_t* out, int64_t n_values);
+int64_t qd_dup_read(qd_ctx* ctx, uint64_t* keys, uint64_t* counts, int64_t cap);
 
 /* ---- counters: replace the class counters of src/Sample.py:32,144 and feed Sample.REPORT ---------
  * qd_get_counts waits for outstanding work of this context (only), then writes 2*S+4 values. */
@@ -922,6 +977,14 @@ int qd_dev_filter(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_
  * Returns when the launch has finished. */
 int qd_dev_cstats(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                   const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes, const uint8_t* drop);
+/* the duplication tally (qd_dup_set above; no reference counterpart) over host buffers, as qd_dev_cstats: pairs [0, n_pairs) of
+ * two texts with their record tables and routing codes are uploaded (the texts 3 bytes off alignment), keyed, listed and tallied
+ * by the kernels qd_pipe_run launches, and added to the context's two tables.  drop may be NULL; otherwise pair j is skipped where
+ * drop[j] != 0 (the read filter's reason bytes).  Every record's sequence and quality range is checked against len1 / len2 and
+ * every code against 2 * S (0xFFFF apart) before anything is launched: QD_ERR_INVALID.  QD_ERR_STATE when the stage is off.
+ * Returns when the launches have finished. */
+int qd_dev_dup(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+               const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes, const uint8_t* drop);
 /* ---- the routing and format stages of qd_pipe_run one at a time (additive: QD_ABI_VERSION stays 6) ----------------------------
  * These three run the kernels between the record tables and the packed members on host buffers, for tests that compare every stage
  * with a plain model (tests/route_model.py).  They are stage harnesses: no reference counterpart (what the stages themselves

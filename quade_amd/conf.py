@@ -7,7 +7,7 @@ file written by `-i` is the reference's template byte for byte (src/Conf_file.py
 package data, quade_amd/data/Quade_conf_file.txt).  An optional [gpu] section that reference conf
 files simply do not have is read when present (defaults apply otherwise; see GPU_SECTION_HELP), and so are the optional
 mismatch budgets of the [index] section (MISMATCH_HELP), the unknown-barcode report (UNKNOWN_HELP) and the quality report
-(QUALITY_HELP) and the per-cycle report (CYCLE_HELP) of the [output] section, an optional [trim] section (CLIP_HELP, TRIM_HELP, PAIR_HELP) and an optional [filter] section
+(QUALITY_HELP), the per-cycle report (CYCLE_HELP) and the duplication report (DUPLICATION_HELP) of the [output] section, an optional [trim] section (CLIP_HELP, TRIM_HELP, PAIR_HELP) and an optional [filter] section
 (FILTER_HELP).
 """
 from __future__ import annotations
@@ -95,6 +95,33 @@ Optional [output] option (not in Quade 0.3.2, whose parser ignores it; absent, e
 """
 
 CYCLE_NEEDS = "cycle_report needs the device pipeline (device_pipeline, device_inflate, device_deflate : True and gzip_level 1 or -1)"
+
+DUPLICATION_HELP = """\
+Optional [output] options (not in Quade 0.3.2, whose parser ignores them; absent, empty or False = no report):
+  duplication_report : False  True: write Quade_duplication_report.csv next to the report -- for every destination (<sample>_pass,
+                            <sample>_fail, Undetermined) and Total: the pairs, those too short or with an N to be keyed, the keyed,
+                            sampled and tallied pairs, the distinct keys, duplicate_pairs = tallied - distinct and their percentage;
+                            then how many keys and pairs of the run occur once, twice, ... (levels 1 to 31 and >=32).  A pair's
+                            key is the first duplication_bases bases of R1 and of R2 (case folded; A, C, G, T only) and its
+                            destination: equal sequences in two destinations are two keys, duplicates are a per-library matter.
+                            The pairs are those the output stages see (behind [trim], pair_overlap and [filter]), whatever the
+                            write flags say: the pairs quality_report counts.  They are counted on the GPU, in a hash table that
+                            every batch feeds, so the option needs the device pipeline: [gpu] device_pipeline, device_inflate and
+                            device_deflate True (the defaults) and gzip_level 1 or -1
+  duplication_bases : 32    8 to 32: a pair whose R1 or R2 is shorter is counted as short, one with another letter among these
+                            bases as with_n; neither is keyed
+  duplication_sample : 16   a power of two, 1 to 1024: one key in this many is counted (chosen by a hash of the key, so a counted
+                            key keeps its exact multiplicity and every GPU and rank counts the same keys).  Rates over the sample
+                            are unbiased estimates of the library's; 1 counts every key
+Optional [gpu] option:
+  duplicate_slots : 16777216  entries of the hash table per context: a power of two, 1024 to 268435456 (48 bytes each).  Pairs
+                            whose key finds no room are counted as not_tallied
+"""
+
+DUPLICATION_NEEDS = "duplication_report needs the device pipeline (device_pipeline, device_inflate, device_deflate : True and gzip_level 1 or -1)"
+DUPLICATION_BASES = "Authorized values for duplication_bases : 8 to 32"
+DUPLICATION_SAMPLE = "Authorized values for duplication_sample : a power of two, 1 to 1024"
+DUPLICATION_SLOTS = "[gpu] duplicate_slots : a power of two, 1024 to 268435456"
 
 TRIM_HELP = """\
 Optional [trim] section (not in Quade 0.3.2, whose parser ignores it; absent = the insert reads leave as they came): 3' trimming of
@@ -265,6 +292,18 @@ class QuadeConf(object):
         if cp.has_option("output", "quality_report") and cp.get("output", "quality_report") not in (None, ""):
             self.quality_report = cp.get("output", "quality_report").strip().lower() in ("true", "1", "yes", "on")
 
+        # optional duplication report (extension, DUPLICATION_HELP)
+        def out(name, default):
+            if cp.has_option("output", name) and cp.get("output", name) not in (None, ""):
+                return cp.getint("output", name)
+            return default
+
+        self.duplication_report = False
+        if cp.has_option("output", "duplication_report") and cp.get("output", "duplication_report") not in (None, ""):
+            self.duplication_report = cp.get("output", "duplication_report").strip().lower() in ("true", "1", "yes", "on")
+        self.duplication_bases = out("duplication_bases", 32)
+        self.duplication_sample = out("duplication_sample", 16)
+
         # optional [trim] section (extension, TRIM_HELP): 3' quality and adapter trimming of the insert reads
         def trim(name, default, conv=int):
             if cp.has_section("trim") and cp.has_option("trim", name) and cp.get("trim", name) not in (None, ""):
@@ -329,6 +368,7 @@ class QuadeConf(object):
         self.chunk_workers = opt("chunk_workers", 1)
         self.io_threads = opt("io_threads", 0)
         self.unknown_slots = opt("unknown_slots", 1 << 24)
+        self.duplicate_slots = opt("duplicate_slots", 1 << 24)
         self.device_inflate = opt("device_inflate", "True", str).strip().lower() in ("true", "1", "yes", "on")
         self.device_deflate = opt("device_deflate", "True", str).strip().lower() in ("true", "1", "yes", "on")
         # the whole chunk loop on the device (qd_pipe_*): text stays in HBM from the inflater to the coder.  Needs the device's
@@ -364,6 +404,10 @@ class QuadeConf(object):
             "[gpu] unknown_slots : a power of two, 1024 to 268435456"
         assert not self.quality_report or self.can_pipe, QUALITY_NEEDS
         assert not self.cycle_report or self.can_pipe, CYCLE_NEEDS
+        assert 8 <= self.duplication_bases <= 32, DUPLICATION_BASES
+        assert 1 <= self.duplication_sample <= 1024 and self.duplication_sample & (self.duplication_sample - 1) == 0, DUPLICATION_SAMPLE
+        assert 1 << 10 <= self.duplicate_slots <= 1 << 28 and self.duplicate_slots & (self.duplicate_slots - 1) == 0, DUPLICATION_SLOTS
+        assert not self.duplication_report or self.can_pipe, DUPLICATION_NEEDS
         for a in (self.adapter_R1, self.adapter_R2):
             assert len(a) <= 64 and not a.strip("ACGT"), TRIM_ADAPTER
         assert 0 <= self.quality_cutoff <= 93, TRIM_CUTOFF
@@ -397,6 +441,10 @@ class QuadeConf(object):
         """the device pipeline can run: every device stage is on and the gzip level is one the device codes; what the read
         stages need (the *_NEEDS messages) and what Quade takes the pipeline for"""
         return bool(self.device_pipeline and self.device_inflate and self.device_deflate and self.gzip_level in (1, -1))
+
+    def duplication_params(self):
+        """what Engine.dup_set takes"""
+        return dict(bases=self.duplication_bases, sample=self.duplication_sample, slots=self.duplicate_slots)
 
     @property
     def trim(self):

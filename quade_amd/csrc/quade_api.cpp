@@ -27,6 +27,7 @@
 #include "quade_trim.h"
 #include "quade_pairtrim.h"
 #include "quade_filter.h"
+#include "quade_dup.h"
 #include "quade_pool.h"
 
 typedef uint64_t u64;
@@ -170,6 +171,26 @@ struct qd_ctx {
     qd_filter_params filter{-1, -1, -1, 15, -1, -1};
     qd_filter_dev filter_dev{-1, -1, -1, 33 + 15, -1, -1};
     u64* d_filter = nullptr;
+
+    // duplication tally (qd_dup_set): the parameters as given and as the kernels take them, the counters
+    // uint64[(2 * S + 1)][5] (d_dup == nullptr = off), the key table (one allocation, the unknown tally's layout), per stream the
+    // batch list (quade_dup.h), and the event behind the last launch's dup_count that a launch on another stream waits for
+    // before its dup_claim
+    qd_dup_params dup{0, 0, 0};
+    qd_dup_dev dup_dev{0, 0};
+    u64* d_dup = nullptr;
+    void* d_dup_keys = nullptr;
+    UnknownTable dup_t{};
+    int dup_tag_bits = 64;  // option "dup_tag_bits" (tests)
+    hipEvent_t dup_done = nullptr;
+    hipStream_t dup_last = nullptr;
+    bool dup_recorded = false;
+    struct DupScratch {
+        hipStream_t stream;
+        uint8_t* buf;
+        size_t pairs;  // qd_dup_list_bytes(pairs) bytes
+    };
+    std::vector<DupScratch> dup_scratch;
 };
 
 namespace {
@@ -603,6 +624,20 @@ void free_filter(qd_ctx* c) {
     c->filter_dev = qd_filter_dev{-1, -1, -1, 33 + 15, -1, -1};
 }
 
+// the duplication tally off and its memory freed (the caller waited for the context's work)
+void free_dup(qd_ctx* c) {
+    table_free(c->d_dup);
+    if (c->d_dup_keys) (void)hipFree(c->d_dup_keys);
+    c->d_dup_keys = nullptr;
+    c->dup = qd_dup_params{0, 0, 0};
+    c->dup_dev = qd_dup_dev{0, 0};
+    c->dup_recorded = false;
+    for (auto& m : c->dup_scratch) (void)hipFree(m.buf);
+    c->dup_scratch.clear();
+    if (c->dup_done) (void)hipEventDestroy(c->dup_done);
+    c->dup_done = nullptr;
+}
+
 // (re)build the device table from the host barcodes and the current plan
 int rebuild(qd_ctx* c) {
     HIPCHK(c, hipSetDevice(c->device));
@@ -959,6 +994,7 @@ int qd_destroy(qd_ctx* c) {
     free_trim(c);
     free_pairtrim(c);
     free_filter(c);
+    free_dup(c);
     for (auto& t : c->tracked) (void)hipEventDestroy(t.second);
     c->tracked.clear();
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -981,13 +1017,14 @@ int qd_set_plan(qd_ctx* c, const qd_plan* plan) {
     if (r != QD_OK) return fail(c, r, "plan rejected: positions must satisfy 0 <= start <= end <= 255, window <= 64, "
                                        "fused barcode <= 32, 0 <= minimal_qual <= 40");
     if (!c->slots.empty()) return fail(c, QD_ERR_STATE, "destroy the slots before changing the plan");
-    if (c->mm_m1 + c->mm_m2 > 0 || c->uk_slots || c->d_qs || c->d_filter) {  // a new plan resets the mismatch budgets and turns the unknown tally, the quality counters and the read filter off
+    if (c->mm_m1 + c->mm_m2 > 0 || c->uk_slots || c->d_qs || c->d_filter || c->d_dup) {  // a new plan resets the mismatch budgets and turns the unknown tally, the quality counters, the read filter and the duplication tally off
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, wait_all(c));
         free_mismatch(c, false);
         free_unknown(c);
         free_qstats(c);
         free_filter(c);
+        free_dup(c);
     }
     c->plan = *plan;
     c->lay = L;
@@ -1022,13 +1059,14 @@ int qd_set_barcodes(qd_ctx* c, int32_t S, const uint8_t* barcodes, const int32_t
     if (!c->have_plan) return fail(c, QD_ERR_STATE, "qd_set_plan first");
     for (int i = 0; i < S; ++i)
         if (offsets[i + 1] < offsets[i]) return fail(c, QD_ERR_INVALID, "offsets must be non-decreasing");
-    if (c->mm_m1 + c->mm_m2 > 0 || c->uk_slots || c->d_qs || c->d_filter) {  // new barcodes reset the mismatch budgets, as they reset the counters, and turn the unknown tally, the quality counters and the read filter off
+    if (c->mm_m1 + c->mm_m2 > 0 || c->uk_slots || c->d_qs || c->d_filter || c->d_dup) {  // new barcodes reset the mismatch budgets, as they reset the counters, and turn the unknown tally, the quality counters, the read filter and the duplication tally off
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, wait_all(c));
         free_mismatch(c, false);
         free_unknown(c);
         free_qstats(c);
         free_filter(c);
+        free_dup(c);
     }
     c->S = S;
     c->bc.assign(barcodes, barcodes + (S ? offsets[S] : 0));
@@ -1589,6 +1627,148 @@ int qd_dev_filter(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t*
     return up.close(qd_filter_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), up.codes(), up.reason(), QD_STREAM_CONTEXT));
 }
 
+static_assert(QD_DUP_VALUES == QD_DP_VALUES, "the public row size is the kernels'");
+static_assert(QD_DUP_READ_ERROR == QD_UNKNOWN_READ_ERROR, "one sizing protocol");
+
+int qd_dup_set(qd_ctx* c, const qd_dup_params* params) {
+    if (!c) return QD_ERR_INVALID;
+    int sample_lg = 0;
+    if (params) {  // checked as the configuration file's values are, before anything changes
+        const qd_dup_params& P = *params;
+        if (P.bases < 8 || P.bases > 32) return fail(c, QD_ERR_INVALID, "duplication bases: 8 to 32");
+        if (P.sample < 1 || P.sample > 1024 || (P.sample & (P.sample - 1))) return fail(c, QD_ERR_INVALID, "duplication sample: a power of two, 1 to 1024");
+        if (P.slots < ((int64_t)1 << QD_UK_MIN_LG) || P.slots > ((int64_t)1 << QD_UK_MAX_LG) || (P.slots & (P.slots - 1)))
+            return fail(c, QD_ERR_INVALID, "duplication slots: a power of two in 2^10 .. 2^28");
+        while ((1 << sample_lg) < P.sample) ++sample_lg;
+        if (!c->have_plan || !c->have_table) return fail(c, QD_ERR_STATE, "qd_set_plan and qd_set_barcodes first");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));  // nothing of this context may still use the old tables
+    free_dup(c);
+    if (!params) return QD_OK;
+    int rc = table_alloc(c, c->d_dup, qd_dup_values((uint32_t)c->S), "duplication counters");
+    if (rc != QD_OK) return rc;
+    hipError_t e = uk_malloc(&c->d_dup_keys, qd_uk_bytes(params->slots));
+    if (e == hipSuccess) e = hipMemsetAsync(c->d_dup_keys, 0, qd_uk_bytes(params->slots), c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->dup_done, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        free_dup(c);
+        return fail(c, QD_ERR_HIP, std::string("duplication table: ") + hipGetErrorString(e));
+    }
+    qd_uk_carve(c->d_dup_keys, params->slots, c->dup_t);
+    c->dup = *params;
+    c->dup_dev = qd_dup_dev{params->bases, sample_lg};
+    return QD_OK;
+}
+
+int qd_dup_get(const qd_ctx* c, qd_dup_params* out) {
+    if (!c || !out) return QD_ERR_INVALID;
+    *out = c->dup;
+    return QD_OK;
+}
+
+int qd_dup_active(const qd_ctx* c) { return c && c->d_dup ? 1 : 0; }
+
+int qd_stream_retired(qd_ctx* c, void* stream) {
+    if (!c) return QD_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    forget_stream(c, st);  // (the caller waited for the stream: nothing of it is outstanding)
+    if (c->uk_last == st) c->uk_recorded = false;
+    if (c->dup_last == st) c->dup_recorded = false;
+    return QD_OK;
+}
+
+int qd_dup_stats(qd_ctx* c, uint64_t* out, int64_t n_values) {
+    if (!c) return QD_ERR_INVALID;
+    return table_read(c, c->d_dup, qd_dup_values((uint32_t)c->S), out, n_values, "the duplication tally is not on", "n_values must be (2*S+1)*5");
+}
+
+int64_t qd_dup_read(qd_ctx* c, uint64_t* keys, uint64_t* counts, int64_t cap) {
+    auto bad = [&](int code, const std::string& msg) { return QD_DUP_READ_ERROR + (int64_t)fail(c, code, msg); };
+    if (!c || cap < 0 || (cap > 0 && (!keys || !counts))) return bad(QD_ERR_INVALID, "bad arguments");
+    if (!c->d_dup) return bad(QD_ERR_STATE, "the duplication tally is not on");
+    uint64_t tot[4];
+    hipError_t e = hipSetDevice(c->device);
+    if (e == hipSuccess) e = wait_all(c);
+    if (e == hipSuccess) e = hipMemcpy(tot, c->dup_t.totals, sizeof tot, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return bad(QD_ERR_HIP, std::string("duplication read: ") + hipGetErrorString(e));
+    const int64_t D = (int64_t)tot[QD_UK_DISTINCT];
+    if (D > cap) return -D;
+    if (D == 0) return 0;
+    // the occupied entries packed on the device (the unknown tally's gather: it works on the table alone): only they cross the link
+    uint8_t* d_out = nullptr;
+    const size_t kbytes = (size_t)D * QD_KEY_WORDS * 8, cbytes = (size_t)D * 8;
+    if ((e = uk_malloc(reinterpret_cast<void**>(&d_out), kbytes + cbytes + 16)) != hipSuccess)
+        return bad(QD_ERR_HIP, std::string("duplication read: ") + hipGetErrorString(e));
+    u64* d_keys = reinterpret_cast<u64*>(d_out);
+    u64* d_counts = reinterpret_cast<u64*>(d_out + kbytes);
+    uint32_t* d_n = reinterpret_cast<uint32_t*>(d_out + kbytes + cbytes);
+    std::vector<u64> hk((size_t)D * QD_KEY_WORDS);
+    uint32_t got = 0;
+    e = qd_launch_unknown_gather(c->dup_t, d_keys, d_counts, d_n, (uint32_t)D, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hk.data(), d_keys, kbytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, cbytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&got, d_n, 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d_out);
+    if (e != hipSuccess) return bad(QD_ERR_HIP, std::string("duplication read: ") + hipGetErrorString(e));
+    if ((int64_t)got != D) return bad(QD_ERR_HIP, "duplication read: the table's entry count and its occupied entries differ");
+    for (int64_t i = 0; i < D; ++i)
+        for (int q = 0; q < QD_DUP_KEY_WORDS; ++q) keys[i * QD_DUP_KEY_WORDS + q] = hk[(size_t)i * QD_KEY_WORDS + q];
+    return D;
+}
+
+int qd_dup_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
+                  const uint16_t* codes, const uint8_t* drop, void* stream) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_dup || !n) return QD_OK;
+    hipStream_t st = resolve_stream(c, stream);
+    qd_ctx::DupScratch* sc = nullptr;
+    for (auto& m : c->dup_scratch)
+        if (m.stream == st) sc = &m;
+    if (!sc) {
+        c->dup_scratch.push_back(qd_ctx::DupScratch{st, nullptr, 0});
+        sc = &c->dup_scratch.back();
+    }
+    if (sc->pairs < (size_t)n) {
+        HIPCHK(c, hipStreamSynchronize(st));  // the old list may still be read by this stream's previous batch
+        if (sc->buf) (void)hipFree(sc->buf);
+        sc->buf = nullptr;
+        const size_t pairs = std::max<size_t>((size_t)n, sc->pairs * 2);
+        sc->pairs = 0;
+        HIPCHK(c, uk_malloc(reinterpret_cast<void**>(&sc->buf), qd_dup_list_bytes(pairs)));
+        sc->pairs = pairs;
+    }
+    qd_dup_args a{};
+    fill_pair_args(a, text1, recs1, text2, recs2);
+    a.codes = codes;
+    a.drop = drop;
+    a.table = c->d_dup;
+    a.list_n = reinterpret_cast<uint32_t*>(sc->buf);
+    a.list = reinterpret_cast<uint64_t*>(sc->buf + QD_DUP_LIST_HEAD);
+    a.where = reinterpret_cast<uint32_t*>(sc->buf + QD_DUP_LIST_HEAD + sc->pairs * QD_DUP_KEY_WORDS * 8);
+    a.t = c->dup_t;
+    a.t.tag_mask = c->dup_tag_bits >= 64 ? ~0ull : ((1ull << c->dup_tag_bits) - 1);
+    hipError_t e = qd_dup_launch(c->dup_dev, a, (uint32_t)c->S, n, c->cu, c->dup_recorded && c->dup_last != st ? c->dup_done : nullptr, st);
+    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("duplication tally launch: ") + hipGetErrorString(e));
+    HIPCHK(c, hipEventRecord(c->dup_done, st));
+    c->dup_recorded = true;
+    c->dup_last = st;
+    HIPCHK(c, track(c, st));
+    return QD_OK;
+}
+
+int qd_dev_dup(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+               const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes, const uint8_t* drop) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_dup) return fail(c, QD_ERR_STATE, "the duplication tally is not on");
+    PairUpload up(c);
+    const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::CODES, codes, drop, nullptr, nullptr, nullptr);
+    if (rc != QD_OK || up.empty()) return rc;
+    return up.close(qd_dup_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), up.codes(), up.drop(), QD_STREAM_CONTEXT));
+}
+
 int qd_kernel_kind(const qd_ctx* c, int has_len) {
     if (!c || !c->have_table) return QD_ERR_STATE;
     return pick_kernel(c, has_len != 0);
@@ -1633,6 +1813,11 @@ int qd_set_option(qd_ctx* c, const char* name, int64_t value) {
     if (!strcmp(name, "unknown_tag_bits")) {  // test knob: the tally keeps this many low bits of a key's tag (default 64), so tag collisions can be made
         if (value < 1 || value > 64) return fail(c, QD_ERR_INVALID, "unknown_tag_bits must be 1..64");
         c->uk_tag_bits = (int)value;
+        return QD_OK;
+    }
+    if (!strcmp(name, "dup_tag_bits")) {  // test knob: the same for the duplication tally's table
+        if (value < 1 || value > 64) return fail(c, QD_ERR_INVALID, "dup_tag_bits must be 1..64");
+        c->dup_tag_bits = (int)value;
         return QD_OK;
     }
     return fail(c, QD_ERR_INVALID, std::string("unknown option ") + name);
@@ -1750,6 +1935,10 @@ int qd_reset_counts(qd_ctx* c) {
     if (c->d_trim) HIPCHK(c, hipMemsetAsync(c->d_trim, 0, QD_TRIM_VALUES * 8, c->stream));
     if (c->d_pairtrim) HIPCHK(c, hipMemsetAsync(c->d_pairtrim, 0, QD_PT_VALUES * 8, c->stream));
     if (c->d_filter) HIPCHK(c, hipMemsetAsync(c->d_filter, 0, qd_filter_values((uint32_t)c->S) * 8, c->stream));
+    if (c->d_dup) {  // both tables: sampled == tallied + not_tallied stays true
+        HIPCHK(c, hipMemsetAsync(c->d_dup, 0, qd_dup_values((uint32_t)c->S) * 8, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->d_dup_keys, 0, qd_uk_bytes(c->dup.slots), c->stream));
+    }
     HIPCHK(c, track(c, c->stream));  // later launches on other streams are not ordered behind this: wait here
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->total_pairs = 0;

@@ -46,6 +46,7 @@
 #include "quade_pool.h"
 #include "quade_qstats.h"
 #include "quade_cstats.h"
+#include "quade_dup.h"
 #include "quade_text.h"
 #include "quade_clip.h"
 #include "quade_trim.h"
@@ -1784,6 +1785,12 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
                                         ins[1], n, p->codes.as<uint16_t>(), drop, p->cs);
         if (rc != QD_OK) return pfail(p, rc, std::string("cycle counters: ") + qd_last_error(p->ctx));
     }
+    // opt-in duplication tally (qd_dup_set): the same pairs keyed by their first bases and counted in the context's hash table
+    if (qd_dup_active(p->ctx)) {
+        const int rc = qd_dup_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p, ins[1], n,
+                                     p->codes.as<uint16_t>(), drop, p->cs);
+        if (rc != QD_OK) return pfail(p, rc, std::string("duplication tally: ") + qd_last_error(p->ctx));
+    }
     // 3. destinations, output lengths, stable sort by destination, output offsets
     PCHK(p, p->dest.need((size_t)n * 2 + 64, 0, p->cs));
     PCHK(p, p->len1.need((size_t)n * 4 + 64, 0, p->cs));
@@ -2547,6 +2554,8 @@ int qd_pipe_run(qd_pipe* p, const qd_pipe_chunk* chunks, int32_t n_chunks, qd_pi
     }
     p->collector.join();
     (void)hipStreamSynchronize(p->cs);
+    // the compute stream is idle and is destroyed with the pipeline, often before the context is read: the context keeps no event on it
+    (void)qd_stream_retired(p->ctx, p->cs);
     for (auto& f : feeders) f->stop();
     {
         std::lock_guard<std::mutex> g(p->cm);

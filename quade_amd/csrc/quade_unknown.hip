@@ -23,15 +23,13 @@
 
 #include "quade_kernels.h"
 #include "quade_rowkey.h"
+#include "quade_tally.h"
 #include "quade_unknown.h"
 
 namespace {
 
-constexpr int UK_BLOCK = 256;
-constexpr int UK_LDS = 1024;      // entries of the workgroup's slot -> count hash
-constexpr int UK_LDS_PROBES = 8;  // then the add goes to global memory directly
+// (the block size, the claim, the wave and LDS combining: quade_tally.h, shared with quade_dup.hip)
 constexpr int UK_GATHER_ITERS = 8;
-constexpr uint32_t UK_LDS_EMPTY = 0xFFFFFFFFu;
 
 // canonical key of pair r; false: a read ends inside its index window (the row is zero padded there)
 template <int KW>
@@ -61,12 +59,6 @@ __device__ __forceinline__ bool uk_key(const UnknownParams& p, int64_t r, u64 (&
     return full;
 }
 
-__device__ __forceinline__ uint32_t uk_wave_sum(uint32_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 template <int KW>
 __global__ __launch_bounds__(UK_BLOCK) void uk_claim(const UnknownParams p) {
     __shared__ uint32_t installs_wg;
@@ -87,51 +79,12 @@ __global__ __launch_bounds__(UK_BLOCK) void uk_claim(const UnknownParams p) {
 #pragma unroll
                 for (int q = 0; q < KW; ++q) k4[q] = w[q];
                 const u64 tag = qd_uk_trim(qd_uk_tag(k4), t.tag_mask);
-                uint32_t s = qd_uk_home(tag, t.lg);
-                res = QD_UK_NONE;
-                for (uint32_t probe = 0; probe < t.probes; ++probe) {
-                    // a stale 0 is corrected by the swap; a tag word changes once only (0 -> tag), so a non-zero value read is final
-                    u64 cur = __hip_atomic_load(&t.tags[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (cur == 0) {
-                        cur = atomicCAS(reinterpret_cast<unsigned long long*>(&t.tags[s]), 0ull, (unsigned long long)tag);
-                        if (cur == 0) {  // this lane owns the entry: its key words, 2 x 16 bytes
-                            ulonglong2* kp = reinterpret_cast<ulonglong2*>(t.keys + (size_t)s * QD_KEY_WORDS);
-                            kp[0] = make_ulonglong2(k4[0], k4[1]);
-                            kp[1] = make_ulonglong2(k4[2], k4[3]);
-                            ++installs;
-                            res = s;
-                            break;
-                        }
-                    }
-                    if (cur == tag) {
-                        res = s;
-                        break;
-                    }
-                    s = (s + 1) & t.mask;
-                }
+                res = tally_claim(t, k4, tag, installs);
             }
         }
         p.where[i] = res;
     }
-    installs = uk_wave_sum(installs);
-    if ((threadIdx.x & 63) == 0 && installs) atomicAdd(&installs_wg, installs);
-    __syncthreads();
-    if (threadIdx.x == 0 && installs_wg)
-        atomicAdd(reinterpret_cast<unsigned long long*>(&t.totals[QD_UK_DISTINCT]), (unsigned long long)installs_wg);
-}
-
-// c more pairs of `slot`: into the workgroup's hash, or to global memory when its probe sequence is taken
-__device__ __forceinline__ void uk_add(uint32_t* lslot, uint32_t* lcnt, u64* counts, uint32_t slot, uint32_t c) {
-    uint32_t h = (slot * 0x9E3779B1u) >> 22;  // 10 bits: UK_LDS entries
-    for (int j = 0; j < UK_LDS_PROBES; ++j) {
-        const uint32_t old = atomicCAS(&lslot[h], UK_LDS_EMPTY, slot);
-        if (old == UK_LDS_EMPTY || old == slot) {
-            atomicAdd(&lcnt[h], c);
-            return;
-        }
-        h = (h + 1) & (UK_LDS - 1);
-    }
-    atomicAdd(reinterpret_cast<unsigned long long*>(&counts[slot]), (unsigned long long)c);
+    tally_installs(t, installs, &installs_wg);
 }
 
 template <int KW>
@@ -139,10 +92,7 @@ __global__ __launch_bounds__(UK_BLOCK) void uk_count(const UnknownParams p) {
     __shared__ uint32_t lslot[UK_LDS];
     __shared__ uint32_t lcnt[UK_LDS];
     __shared__ uint32_t tot[3];  // tallied, short, dropped of this workgroup
-    for (int i = threadIdx.x; i < UK_LDS; i += UK_BLOCK) {
-        lslot[i] = UK_LDS_EMPTY;
-        lcnt[i] = 0;
-    }
+    tally_lds_init(lslot, lcnt);
     if (threadIdx.x < 3) tot[threadIdx.x] = 0;
     __syncthreads();
     const uint32_t nm = p.miss[0];
@@ -172,18 +122,7 @@ __global__ __launch_bounds__(UK_BLOCK) void uk_count(const UnknownParams p) {
                 ++n_drop;  // another key holds this tag's entry
             }
         }
-#pragma unroll
-        for (int round = 0; round < 2; ++round) {
-            const u64 m = __ballot(pend);
-            if (m == 0) break;
-            const int leader = __ffsll((unsigned long long)m) - 1;
-            const uint32_t ls = __shfl(res, leader, 64);
-            const bool mine = pend && res == ls;
-            const u64 sm = __ballot(mine);
-            if (lane == leader) uk_add(lslot, lcnt, t.counts, ls, (uint32_t)__popcll(sm));
-            if (mine) pend = false;
-        }
-        if (pend) uk_add(lslot, lcnt, t.counts, res, 1u);
+        tally_combine(lslot, lcnt, t.counts, pend, res, lane);
     }
     n_tal = uk_wave_sum(n_tal);
     n_short = uk_wave_sum(n_short);
@@ -194,10 +133,7 @@ __global__ __launch_bounds__(UK_BLOCK) void uk_count(const UnknownParams p) {
         if (n_drop) atomicAdd(&tot[2], n_drop);
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < UK_LDS; i += UK_BLOCK) {
-        const uint32_t c = lcnt[i];
-        if (c) atomicAdd(reinterpret_cast<unsigned long long*>(&t.counts[lslot[i]]), (unsigned long long)c);
-    }
+    tally_lds_flush(lslot, lcnt, t.counts);
     if (threadIdx.x < 3 && tot[threadIdx.x])  // QD_UK_TALLIED, _SHORT, _DROPPED = 0, 1, 2
         atomicAdd(reinterpret_cast<unsigned long long*>(&t.totals[threadIdx.x]), (unsigned long long)tot[threadIdx.x]);
 }

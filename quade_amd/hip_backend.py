@@ -25,6 +25,8 @@ QD_OK = 0
 QD_ERR_INVALID, QD_ERR_NO_DEVICE, QD_ERR_HIP, QD_ERR_STATE = -1, -2, -3, -4
 QD_ERR_UNSUPPORTED, QD_ERR_BARCODE, QD_ERR_FORMAT = -5, -6, -7
 QD_UNKNOWN_READ_ERROR = -(1 << 40)  # qd_unknown_read: a value <= this is this + QD_ERR_*
+QD_DUP_READ_ERROR = QD_UNKNOWN_READ_ERROR  # qd_dup_read follows the same protocol
+DUP_COUNTERS = ("pairs", "short", "with_n", "sampled", "not_tallied")  # a destination's row of qd_dup_stats
 CODE_UNDETERMINED = 0xFFFF
 
 
@@ -70,6 +72,10 @@ class qd_pairtrim_params(C.Structure):
 class qd_filter_params(C.Structure):
     _fields_ = [("min_length", C.c_int32), ("max_n", C.c_int32), ("max_unqualified_pct", C.c_int32), ("qualified_quality", C.c_int32),
                 ("min_mean_quality", C.c_int32), ("min_complexity_pct", C.c_int32)]
+
+
+class qd_dup_params(C.Structure):
+    _fields_ = [("bases", C.c_int32), ("sample", C.c_int32), ("slots", C.c_int64)]
 
 
 class qd_text_batch(C.Structure):
@@ -153,6 +159,10 @@ SYMBOLS = [
     ("qd_cstats_read", C.c_int, [_P, _P, C.c_int64]),
     ("qd_cstats_add", C.c_int, [_P, _P, C.c_int64]),
     ("qd_cstats_lds_cycles", C.c_int, []),
+    ("qd_dup_set", C.c_int, [_P, C.POINTER(qd_dup_params)]),
+    ("qd_dup_get", C.c_int, [_P, C.POINTER(qd_dup_params)]),
+    ("qd_dup_stats", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_dup_read", C.c_int64, [_P, _P, _P, C.c_int64]),
     ("qd_get_counts", C.c_int, [_P, _P, C.c_int32]),
     ("qd_reset_counts", C.c_int, [_P]),
     ("qd_add_counts", C.c_int, [_P, _P, C.c_int32]),
@@ -237,6 +247,7 @@ SYMBOLS = [
     ("qd_dev_pairtrim", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_filter", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_cstats", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
+    ("qd_dev_dup", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_pack_rows", C.c_int, [C.c_int, C.POINTER(qd_layout), _P * 2, C.c_int64 * 2, _P * 2, C.c_int64, C.c_int64, _P * 2, _P * 2, _P * 2,
                                    _P, C.c_int64, C.POINTER(C.c_uint32)]),
     ("qd_dev_route_format", C.c_int, [C.c_int, C.POINTER(qd_plan), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P * 4, C.c_int64 * 4, _P * 4, _P, _P,
@@ -470,6 +481,52 @@ def unpack_unknown(blob):
     keys = np.frombuffer(blob, dtype=np.uint8, count=n * K, offset=32).reshape(n, K)
     counts = np.frombuffer(blob, dtype=np.uint64, count=n, offset=32 + n * K)
     return keys, counts, short, dropped
+
+
+def merge_dup(tables):
+    """Host: duplication tables (keys uint64[n, 3] = (w1, w2, d), counts uint64[n]) of several contexts or ranks -> one table with
+    the counts of equal keys summed, rows ascending by (d, w1, w2); a single table holds every key once already and is returned as
+    it is.  Returns (keys, counts)."""
+    tables = [(np.asarray(k, dtype=np.uint64).reshape(-1, 3), np.asarray(c, dtype=np.uint64).reshape(-1)) for k, c in tables]
+    assert all(k.shape[0] == c.size for k, c in tables), "one count per key"
+    tables = [(k, c) for k, c in tables if c.size]
+    if not tables:
+        return np.zeros((0, 3), dtype=np.uint64), np.zeros(0, dtype=np.uint64)
+    if len(tables) == 1:
+        return tables[0]
+    keys = np.concatenate([k for k, _ in tables])
+    counts = np.concatenate([c for _, c in tables])
+    uniq, inv = np.unique(keys[:, [2, 0, 1]], axis=0, return_inverse=True)
+    total = np.zeros(uniq.shape[0], dtype=np.uint64)
+    np.add.at(total, inv.reshape(-1), counts)
+    return np.ascontiguousarray(uniq[:, [1, 2, 0]]), total
+
+
+_DUP_MAGIC = 0x3150554445445551  # "QUDEDUP1"
+
+
+def pack_dup(keys, counts, stats):
+    """One context's or rank's tally as bytes (the ranks' exchange through the rendezvous directory): keys uint64[n, 3], counts
+    uint64[n], stats uint64[2S+1, 5] (dup_stats); unpack_dup reverses it."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint64).reshape(-1)
+    keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(counts.size, 3)
+    stats = np.ascontiguousarray(stats, dtype=np.uint64).reshape(-1, len(DUP_COUNTERS))
+    head = np.array([_DUP_MAGIC, counts.size, stats.shape[0]], dtype=np.uint64)
+    return head.tobytes() + stats.tobytes() + keys.tobytes() + counts.tobytes()
+
+
+def unpack_dup(blob):
+    """-> (keys uint64[n, 3], counts uint64[n], stats uint64[rows, 5]); ValueError when the blob is not whole"""
+    if len(blob) < 24:
+        raise ValueError("a duplication table of %d bytes has no head" % len(blob))
+    magic, n, rows = (int(x) for x in np.frombuffer(blob, dtype=np.uint64, count=3))
+    V = len(DUP_COUNTERS)
+    if magic != _DUP_MAGIC or len(blob) != 24 + 8 * (rows * V + 4 * n):
+        raise ValueError("a duplication table of %d bytes does not hold the %d entries and %d rows its head names" % (len(blob), n, rows))
+    stats = np.frombuffer(blob, dtype=np.uint64, count=rows * V, offset=24).reshape(rows, V)
+    keys = np.frombuffer(blob, dtype=np.uint64, count=3 * n, offset=24 + 8 * rows * V).reshape(n, 3)
+    counts = np.frombuffer(blob, dtype=np.uint64, count=n, offset=24 + 8 * (rows * V + 3 * n))
+    return keys, counts, stats
 
 
 FILTER_KIND_LDS, FILTER_KIND_GLOBAL = 1, 2
@@ -804,6 +861,52 @@ class Engine(object):
         t, r, codes, drop, n = self._pair_inputs(text1, recs1, text2, recs2, codes, drop)
         self._chk(self.lib.qd_dev_cstats(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), n, _ptr(codes),
                                          _ptr(drop) if drop is not None else None))
+
+    def dup_set(self, bases=32, sample=16, slots=1 << 24, on=True):
+        """The duplication tally in the device pipeline (qd_dup_set; conf.DUPLICATION_HELP has the definition): `bases` 8 .. 32
+        of either read make a pair's key, keys are sampled one in `sample` (a power of two, 1 .. 1024) and counted in a table of
+        `slots` entries (a power of two, 2^10 .. 2^28).  on=False turns the stage off and frees both tables; a value out of range
+        is QD_ERR_INVALID and changes nothing.  Needs the plan and the barcodes."""
+        if not on:
+            self._chk(self.lib.qd_dup_set(self._h, None))
+            return
+        P = qd_dup_params(int(bases), int(sample), int(slots))
+        self._chk(self.lib.qd_dup_set(self._h, C.byref(P)))
+
+    def dup_get(self):
+        """The parameters in force, as dup_set's keywords; None when the stage is off."""
+        P = qd_dup_params()
+        self._chk(self.lib.qd_dup_get(self._h, C.byref(P)))
+        return dict(bases=int(P.bases), sample=int(P.sample), slots=int(P.slots)) if P.slots else None
+
+    def dup_stats(self):
+        """numpy uint64[2S+1, 5]: [destination (code; Undetermined last)][DUP_COUNTERS]"""
+        out = np.zeros((2 * self.n_samples + 1, len(DUP_COUNTERS)), dtype=np.uint64)
+        self._chk(self.lib.qd_dup_stats(self._h, _ptr(out), out.size))
+        return out
+
+    def dup_read(self):
+        """The key table's entries in no particular order: (keys uint64[n, 3] = (w1, w2, d), counts uint64[n])."""
+        n = self.lib.qd_dup_read(self._h, None, None, 0)
+        while True:
+            if n <= QD_DUP_READ_ERROR:
+                self._chk(int(n - QD_DUP_READ_ERROR))
+            if n == 0:
+                return np.zeros((0, 3), dtype=np.uint64), np.zeros(0, dtype=np.uint64)
+            cap = int(-n)
+            keys = np.zeros((cap, 3), dtype=np.uint64)
+            counts = np.zeros(cap, dtype=np.uint64)
+            n = self.lib.qd_dup_read(self._h, _ptr(keys), _ptr(counts), cap)
+            if n > 0:
+                return keys[:n], counts[:n]
+
+    def dev_dup(self, text1, recs1, text2, recs2, codes, drop=None):
+        """The duplication tally over host buffers (qd_dev_dup): texts as bytes or uint8 arrays, recs uint32[n, 6] in
+        dev_fastq_scan's layout, codes uint16[n], drop None or uint8[n] (non-zero = the pair is skipped); adds to the context's
+        two tables."""
+        t, r, codes, drop, n = self._pair_inputs(text1, recs1, text2, recs2, codes, drop)
+        self._chk(self.lib.qd_dev_dup(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), n, _ptr(codes),
+                                      _ptr(drop) if drop is not None else None))
 
     def set_option(self, name, value):
         self._chk(self.lib.qd_set_option(self._h, name.encode(), int(value)))

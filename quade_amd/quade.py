@@ -167,6 +167,8 @@ class Quade(object):
                     eng.set_mismatches(cf.idx1_mismatches, cf.idx2_mismatches)
                 if cf.top_unknown_barcodes > 0:  # the barcodes of the Undetermined pairs are counted on the device
                     eng.unknown_enable(cf.unknown_slots)
+                if cf.duplication_report:  # the read-pair keys are tallied on the device, beside the quality counters
+                    eng.dup_set(**cf.duplication_params())
                 for stage in hb.STAGES:  # what the pipeline does to the insert reads while it holds their text, in its order
                     if stage.on(cf):
                         stage.enable(eng, cf)
@@ -196,6 +198,8 @@ class Quade(object):
         counts = self._reduce_counts(devices)
         # (the unknown-barcode tally is no entry of the stage table: its tables merge by key, they are not added)
         unknown = self._collect_unknown() if cf.top_unknown_barcodes > 0 else None
+        with _timed("duplication gather + merge"):  # (nor is the duplication tally a stage of the table: it merges by key too)
+            dup = self._collect_dup() if cf.duplication_report else None
         tables = [(stage, self._collect(stage)) for stage in hb.STAGES if stage.on(cf)]
         for eng in self.engines:
             eng.close()
@@ -234,6 +238,11 @@ class Quade(object):
             w1 = cf.idx1_pos["end"] - cf.idx1_pos["start"]
             write_report(os.path.join(self.outdir, REPORT_NAME), keys, ucounts, short, dropped, int(counts[3]),
                          cf.top_unknown_barcodes, w1, bool(cf.idx2), [(s.name, s.index) for s in Sample.SAMPLE_LIST])
+        if dup is not None:
+            from .duplication_report import REPORT_NAME, write_report
+            keys, dcounts, stats = dup
+            write_report(os.path.join(self.outdir, REPORT_NAME), stats, keys, dcounts, [s.name for s in Sample.SAMPLE_LIST],
+                         cf.duplication_params())
         for stage, table in tables:
             stage.write_report(self.outdir, table, [s.name for s in Sample.SAMPLE_LIST], stage.conf_params(cf))
         print("Done in {}s".format(round(time() - start_time, 3)))
@@ -303,6 +312,26 @@ class Quade(object):
             keys, ucounts = hb.merge_unknown([(k, c) for k, c, _, _ in parts])
             short, dropped = sum(p[2] for p in parts), sum(p[3] for p in parts)
         return keys, ucounts, short, dropped
+
+    def _collect_dup(self):
+        """[output] duplication_report: the key tables of every context of this process merged (equal keys summed) and their
+        destination counters added; with several ranks every rank publishes its merged tally in the rendezvous directory and
+        merges all of them (rank 0 writes the file).  Returns (keys uint64[n, 3], counts uint64[n], stats uint64[2S+1, 5])."""
+        from . import dist
+        t0 = time()
+        tables, stats = [], None
+        for eng in self.engines:
+            st = eng.dup_stats()
+            stats = st if stats is None else stats + st
+            tables.append(eng.dup_read())
+        keys, dcounts = hb.merge_dup(tables)
+        if self.world > 1:
+            got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, "duplication", hb.pack_dup(keys, dcounts, stats))
+            parts = [hb.unpack_dup(b) for b in got]
+            keys, dcounts = hb.merge_dup([(k, c) for k, c, _ in parts])
+            stats = sum(p[2].astype("uint64") for p in parts)
+        self.dup_merge_seconds = time() - t0  # the end-of-run gather and merge (tools/e2e_bench.py reports it)
+        return keys, dcounts, stats
 
     def _collect(self, stage):
         """A read stage's tables (hip_backend.STAGES) of every context of this process summed (chunk workers, devices); with

@@ -7,7 +7,7 @@ each is timed by HIP events.  "off" does what process_batch does with the stage 
 itself costs.  After the timed steps the stage's table is read back and checked against what the batch must have counted.  Prints
 one JSON line ("tool": "<stage>_bench"): per case the medians, the spread and the byte floor (the lines' bytes at 6.3 TB/s).
 
-usage: python tools/stage_bench.py --stage qstats|cycle|clip|trim|pairtrim|filter [--pairs N] [--bases L] [--steps K] [--warmup W]
+usage: python tools/stage_bench.py --stage qstats|cycle|clip|trim|pairtrim|filter|dup [--pairs N] [--bases L] [--steps K] [--warmup W]
                                    [--once CASE] [--out FILE]
   --once CASE  set up, run ONE launch and exit (for `rocprofv3 --kernel-trace --stats -- python ...`); CASE by stage:
     qstats    hot | spread | off      routing: 96 samples with 90 % of the pairs to 8 destinations (per-workgroup partials in LDS) |
@@ -19,6 +19,9 @@ usage: python tools/stage_bench.py --stage qstats|cycle|clip|trim|pairtrim|filte
     trim      PCT                     PCT % of the reads carry their adapter from a random position on
     pairtrim  PCT | poly              PCT % of the pairs read from an insert of 30 .. --bases - 1 bases | poly-A against poly-T
     filter    drop0 | drop10 | drop100 | spread | off   the share of pairs dropped (poly-G in R1), hot or spread routing;
+                                      interleaved with the quality counters' kernel over the same batch
+    dup       sSAMPLE_dPCT | off      the duplication tally with duplication_sample SAMPLE (16 | 1) over a batch in which PCT (0 |
+                                      30 | 100) % of the pairs repeat another pair's reads and destination, 8 hot destinations;
                                       interleaved with the quality counters' kernel over the same batch
 The end-to-end rates come from tools/e2e_bench.py with the stage's E2E_* switch against none."""
 import argparse
@@ -478,7 +481,77 @@ def filter_(B):
     return out
 
 
-STAGES = {"qstats": qstats, "cycle": cycle, "clip": clip, "trim": trim, "pairtrim": pairtrim, "filter": filter_}
+def dup(B):
+    """The duplication tally's three launches (dup_keys, dup_claim, dup_count) against the quality counters' kernel.  The byte floor:
+    the two records, the code and the reason byte of every pair, the aligned 16-byte words that hold the first 32 bases of both
+    reads, and 24 bytes per listed pair."""
+    a, n, L = B.a, B.a.pairs, B.a.bases
+    cases = {"s%d_d%d" % (s, d): (s, d) for s in (16, 1) for d in (0, 30, 100)}
+    B.once_in([None, "off"] + sorted(cases))
+    d_launch, q_launch, active, g = B.entry("dup"), B.entry("qstats"), B.asker("dup"), generator(7)
+    reason = torch.zeros(n + 64, dtype=torch.uint8, device="cuda")
+    TEMPLATES = 1024  # at 100 % every pair repeats one of these
+
+    def texts(pct, codes):
+        """the batch (bases from ACGT: every pair is keyed) with pct % of its pairs a copy of another pair -- reads and code"""
+        b = Batch(n, L)
+        bases = torch.tensor(list(b"ACGT"), dtype=torch.uint8, device="cuda")
+        for t in (b.t1, b.t2):
+            t.view(n, b.rec)[:, 22:22 + L] = bases[torch.randint(0, 4, (n, L), generator=g, device="cuda")]
+        if pct >= 100:
+            copy = torch.arange(n, device="cuda") >= TEMPLATES
+            src = torch.randint(0, TEMPLATES, (n,), generator=g, device="cuda")
+        else:
+            copy = torch.rand(n, generator=g, device="cuda") < pct / 100.0
+            src = torch.randint(0, n, (n,), generator=g, device="cuda")
+        if pct:
+            for t in (b.t1, b.t2):
+                v = t.view(n, b.rec)
+                v[copy] = v[src[copy]]
+            codes[copy] = codes[src[copy]]
+        words = sum(int((((r[:, 3].to(torch.int64) + t.data_ptr()) % 16 + 32 + 15) // 16).sum()) for t, r in ((b.t1, b.r1), (b.t2, b.r2)))
+        return b, 16 * words
+
+    def measure(case):
+        sample, pct = cases[case]
+        S, codes = routed_codes(g, n, "hot")
+        b, word_bytes = texts(pct, codes)
+        kinds = {"off": None, "dup": lambda e: e.dup_set(bases=32, sample=sample), "qstats": lambda e: e.qstats_enable(True)}
+        engines = contexts({k: kinds[k] for k in (("off",) if a.once == "off" else ("dup",) if a.once else kinds)}, S)
+
+        def off():  # what process_batch does with the stage off: it asks, and launches nothing
+            assert active(engines["off"]._h) == 0
+        run = {"off": off, "dup": lambda: B.launch(d_launch, engines["dup"], b, codes.data_ptr(), reason.data_ptr()),
+               "qstats": lambda: B.launch(q_launch, engines["qstats"], b, codes.data_ptr(), None)}
+        run = {k: run[k] for k in engines}
+        if a.once:
+            out = B.once(run["off" if a.once == "off" else "dup"], {"once": a.once, "pairs": n, "bases": L})
+            close(engines)
+            return out
+        ms = B.timed(run)
+        stats, launches = engines["dup"].dup_stats(), a.steps + a.warmup
+        keys, counts = engines["dup"].dup_read()
+        tot = [int(x) for x in stats.sum(axis=0)]
+        assert tot[0] == launches * n and tot[1] == tot[2] == 0 and tot[3] == int(counts.sum()) + tot[4] and tot[3] % launches == 0
+        listed = tot[3] // launches  # the same batch every launch: its sampled pairs
+        assert int(counts.min()) % launches == 0 and (sample > 1 or listed == n)
+        floor = (n * (2 * 24 + 2 + 1) + word_bytes + 24 * listed) / COPY_RATE * 1e3
+        out = {"case": case, "sample": sample, "duplicate_pct_planted": pct, "samples": S, "listed_pairs": listed, "distinct_keys": len(counts),
+               "duplicate_pairs_share": 1.0 - len(counts) / max(listed, 1), "not_tallied": tot[4], "byte_floor_ms": floor,
+               "qstats_byte_floor_ms": B.floor_ms(4), "dup_over_qstats": median(ms["dup"]) / median(ms["qstats"]),
+               "dup_over_floor": median(ms["dup"]) / floor, **by_name(ms)}
+        close(engines)
+        return out
+
+    if a.once:
+        return measure("s16_d30" if a.once == "off" else a.once)
+    out = B.head("dup_bench", steps=a.steps, slots=1 << 24)
+    for case in cases:
+        out[case] = measure(case)
+    return out
+
+
+STAGES = {"dup": dup, "qstats": qstats, "cycle": cycle, "clip": clip, "trim": trim, "pairtrim": pairtrim, "filter": filter_}
 
 
 def main():
