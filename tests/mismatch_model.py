@@ -7,7 +7,8 @@ barcode whose length is not K, match exactly only.  Two K-long barcodes collide 
 
 tolerant_sampleset(qo, ...) returns a subclass of the oracle's SampleSet whose INDEX_TO_SAMPLE resolves exactly first and
 then by this rule, so that the unmodified oracle (qo.demux_reads, qo.run_quade) produces tolerant codes, outputs and reports
-when the tests monkeypatch qo.SampleSet with it.
+when the tests monkeypatch qo.SampleSet with it.  codes_for_keys states the same rule once more for whole corpora of keys at
+once (numpy, no oracle, no product code); tests/test_host_mismatch.py holds the two to each other.
 """
 import numpy as np
 
@@ -70,6 +71,71 @@ class TolerantIndex(dict):
         if v is None:
             raise KeyError(key)
         return v
+
+
+UNDETERMINED = 0xFFFF
+
+
+def _part_values(rows):
+    """the distinct rows of a byte matrix and every row's place among them (a part of no width: one empty value)"""
+    if rows.shape[1] == 0:
+        return rows[:1], np.zeros(rows.shape[0], dtype=np.int64)
+    values, where = np.unique(rows, axis=0, return_inverse=True)
+    return values, where.reshape(-1)
+
+
+def codes_for_keys(keys, quals, sheet, K, w1, m1, m2, min_qual, chunk_bytes=1 << 25):
+    """Routing codes (uint16) of fused keys by the rule above, brute force.  keys: uint8 [n, K], upper-cased; quals: uint8 [n, K],
+    the slice's quality bytes (Phred + 33); sheet: the barcodes in ordinal order (those not K long match exactly only, so no K-long
+    key reaches them).  2 * sample (+ 1 when a slice quality is below min_qual), 0xFFFF when no K-long barcode is within (m1, m2)
+    per part.  An exact hit is taken first; otherwise at most one barcode may qualify (asserted: the collision rule).
+
+    Every key is compared with every K-long barcode: its first part with the distinct first parts of the sheet and its second
+    part with the distinct second parts ([n, U, w] byte compares, chunked), and the barcodes -- a grid over those two lists of
+    values -- are then counted per key wherever both parts are within budget."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint8).reshape(-1, K)
+    quals = np.ascontiguousarray(quals, dtype=np.uint8).reshape(-1, K)
+    n = keys.shape[0]
+    ids = [i for i, b in enumerate(sheet) if len(b) == K]
+    fail = (quals.astype(np.int32) - 33 < min_qual).any(axis=1)
+    out = np.full(n, UNDETERMINED, dtype=np.uint16)
+    if not ids or n == 0:
+        return out
+    bc = np.array([np.frombuffer(sheet[i].encode("latin-1"), np.uint8) for i in ids], dtype=np.uint8).reshape(len(ids), K)
+    v1, at1 = _part_values(bc[:, :w1])
+    v2, at2 = _part_values(bc[:, w1:])
+    grid = np.zeros((v1.shape[0], v2.shape[0]), dtype=np.float64)  # ordinal + 1 of the barcode made of (first part, second part)
+    assert len({(int(a), int(b)) for a, b in zip(at1, at2)}) == len(ids), "equal barcodes"
+    grid[at1, at2] = np.asarray(ids, dtype=np.float64) + 1
+    there = (grid > 0).astype(np.float64)
+    step = max(1, chunk_bytes // (max(v1.shape[0], v2.shape[0]) * K))
+    for a in range(0, n, step):
+        k = keys[a:a + step]
+        d1 = (k[:, None, :w1] != v1[None, :, :]).sum(axis=2)
+        d2 = (k[:, None, w1:] != v2[None, :, :]).sum(axis=2)
+        exact = (((d1 == 0).astype(np.float64) @ grid) * (d2 == 0)).sum(axis=1)
+        in1, in2 = (d1 <= m1).astype(np.float64), (d2 <= m2)
+        hits = ((in1 @ there) * in2).sum(axis=1)
+        near = ((in1 @ grid) * in2).sum(axis=1)
+        assert (hits[exact == 0] <= 1).all(), "colliding sample sheet"
+        found = np.where(exact > 0, exact, np.where(hits == 1, near, 0)).astype(np.int64)
+        code = (found - 1) * 2 + fail[a:a + step]
+        out[a:a + step] = np.where(found > 0, code, UNDETERMINED).astype(np.uint16)
+    return out
+
+
+def counts_for_codes(codes, S):
+    """the ABI's counter vector uint64[2S + 4] of a batch's codes: [total, pass, fail, undetermined, pass_0, fail_0, pass_1, ...]"""
+    codes = np.asarray(codes, dtype=np.uint16)
+    per = np.bincount(codes[codes != UNDETERMINED].astype(np.int64), minlength=2 * S)
+    assert per.size == 2 * S
+    out = np.zeros(2 * S + 4, dtype=np.uint64)
+    out[0] = codes.size
+    out[1] = per[0::2].sum()
+    out[2] = per[1::2].sum()
+    out[3] = int((codes == UNDETERMINED).sum())
+    out[4:] = per
+    return out
 
 
 def tolerant_sampleset(qo, K, w1, m1, m2):

@@ -1,6 +1,8 @@
 """Mismatch-tolerant matching on the MI355X: routing codes, molecular bytes and counters equal to the oracle with the tolerant
 lookup of tests/mismatch_model.py installed (qo.SampleSet monkeypatched; the oracle itself is unmodified), on every path that
-launches the match kernels: fast and generic kernels, ragged batches, pinned slots, and the command line's device pipeline."""
+launches the match kernels: fast and generic kernels, ragged batches, pinned slots, and the command line's device pipeline; and, on
+tight and combinatorial sheets, equal to the brute-force model of tests/mismatch_model.py on every key within budget of a barcode
+and on the keys one substitution too far (tests/mismatch_support.py; tests/test_host_mismatch.py pins that model to the oracle)."""
 import gzip
 import os
 
@@ -12,6 +14,7 @@ from quade_amd import hip_backend as hb
 from quade_amd import synth
 from tests import helpers as H
 from tests import mismatch_model as MM
+from tests import mismatch_support as MS
 from tests.mismatch_support import SHAPES, make_reads, rows_on_device, sheet
 
 pytestmark = pytest.mark.gpu
@@ -221,6 +224,220 @@ def test_api_state_and_resets(torch_cuda, monkeypatch):
             else:
                 eng.set_mismatches(0, 0)  # (0, 0) set explicitly: today's codes
             assert (check(eng, torch_cuda, streams, exact, n) == exact[3]).all()
+
+
+# ---- tight and combinatorial sheets: every key within budget, and the keys one substitution too far, against the model ---------
+def _launch(engine, torch, dev, n, mode, short=None):
+    """one launch over the first n pairs of the rows on the device (plain: whole rows; lens: a length per read, the generic
+    kernel; ragged: the short pairs listed) behind a counter reset -> (codes, molecular rows, counters)"""
+    seq, qual, lens = dev
+    engine.reset_counts()
+    if mode != "ragged":
+        codes, mol = H.hip_on_device(engine, seq, qual, n, lens=lens if mode == "lens" else None)
+        return codes, mol, engine.counts()
+    M = engine.layout.mol_width
+    codes = torch.full((max(n, 1),), 0x7777, dtype=torch.int16, device="cuda")
+    mol = torch.full((max(n, 1), max(M, 1)), 0x55, dtype=torch.uint8, device="cuda")
+    ptr = lambda ts: [t.data_ptr() for t in ts]  # noqa: E731
+    engine.demux_device_ragged(n, ptr(seq), ptr(qual), codes.data_ptr(), mol.data_ptr() if M else None, ptr(lens), short.numel(),
+                               short.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    return codes.cpu().numpy().view(np.uint16)[:n], (mol.cpu().numpy()[:n] if M else None), engine.counts()
+
+
+def _same(got, want, c, what):
+    bad = np.flatnonzero(got != want)
+    assert bad.size == 0, (c.name, what, bad.size, [(int(r), c.keys[r].tobytes(), c.sheet[c.origin[r]], hex(int(got[r])), hex(int(want[r])))
+                                                   for r in bad[:5]])
+
+
+def _corpus_against_the_model(torch, engine, c):
+    """the corpus's reads under every kernel the plan has: codes and counters equal the model's on every pair; and without
+    budgets exactly the pairs that the model rescues are Undetermined"""
+    engine.set_plan(c.shape.plan)
+    engine.set_barcodes(c.sheet)
+    seq, qual, lens, full = rows_on_device(torch, engine.layout, c.streams)
+    assert full == (not c.short.any())
+    short = None if full else torch.from_numpy(np.flatnonzero(c.short).astype(np.uint32)).cuda()
+    modes = ("plain",) if full else ("ragged", "lens")
+    want_mol = None
+    if engine.layout.mol_width:
+        want_mol = np.frombuffer(b"".join(c.molecular()), np.uint8).reshape(c.n, engine.layout.mol_width)
+    engine.set_option("kernel", 0)
+    has_fast = engine.kernel_kind() == "fast"
+    try:
+        for kernel in (0, 2) + ((1,) if has_fast else ()):
+            engine.set_option("kernel", kernel)
+            engine.set_mismatches(c.m1, c.m2)
+            assert engine.kernel_kind() == ("generic" if kernel == 2 or not has_fast else "fast")
+            for mode in modes:
+                assert mode != "lens" or engine.kernel_kind(has_len=True) == "generic"
+                codes, mol, counts = _launch(engine, torch, (seq, qual, lens), c.n, mode, short)
+                _same(codes, c.codes, c, (kernel, mode))
+                assert (counts == c.counts()).all(), (c.name, kernel, mode)
+                if want_mol is not None:  # the molecular bytes are the reads' slice, and rescued pairs keep them
+                    assert (mol == want_mol).all() and (mol[c.rescued] == want_mol[c.rescued]).all() and c.rescued.any()
+            engine.set_mismatches(0, 0)
+            for mode in modes:
+                codes, _, counts = _launch(engine, torch, (seq, qual, lens), c.n, mode, short)
+                _same(codes, c.exact, c, (kernel, mode, "no budgets"))
+                assert (codes[c.rescued] == 0xFFFF).all() and (counts == c.counts(c.exact)).all()
+    finally:
+        engine.set_option("kernel", 0)
+
+
+@pytest.mark.parametrize("name", sorted(MS.CORPORA))
+def test_neighbourhoods_equal_the_model(torch_cuda, engine, name):
+    """Sheets as tight as the collision rule allows, whose samples share whole parts (candidate lists longer than one), with
+    every key within budget of every barcode and a sample of the keys one substitution too far (tests/test_host_mismatch.py
+    holds the corpora to their conditions and the model to the oracle).  Slices at an offset, parts of unequal width, unequal
+    budgets, barcodes with N, barcodes of several lengths, and a sheet past the per-workgroup histogram are among them."""
+    _corpus_against_the_model(torch_cuda, engine, MS.corpus(name))
+
+
+@pytest.mark.parametrize("shape", sorted(MS.NO_SEGMENTS))
+def test_the_branch_without_segments(torch_cuda, engine, shape):
+    """parts narrower than budget + 1: no pigeonhole, the rescue compares with every barcode.  One sample and all 5^K keys: every
+    full-length key is its sample's, pass or fail by the gate; the same keys in reads cut inside the slice stay Undetermined"""
+    c = MS.no_segments_corpus(shape)
+    gate_fails = (c.quals.astype(np.int64) - 33 < c.shape.plan.min_qual).any(axis=1)
+    assert (c.codes[~c.short] == gate_fails[~c.short]).all() and (c.codes[c.short] == 0xFFFF).all()
+    assert c.short.sum() == (~c.short).sum() == 4 * 5 ** c.K and gate_fails[~c.short].any() and not gate_fails[~c.short].all()
+    _corpus_against_the_model(torch_cuda, engine, c)
+
+
+def test_compact_boundaries(torch_cuda, engine):
+    """mm_compact lists 8 codes per lane step and 32 768 per workgroup: batches that end just before, at and just behind both,
+    all to be rescued, none (every pair exact), and all listed but none rescued (every pair unrelated)"""
+    c = MS.corpus("comb_8x12")
+    rng = np.random.default_rng(3)
+    N, plan = 32769, c.shape.plan
+    engine.set_plan(plan)
+    engine.set_barcodes(c.sheet)
+    batches = {}
+    for what, rows in (("one off", np.flatnonzero(c.d1 + c.d2 == 1)), ("exact", np.flatnonzero(c.d1 + c.d2 == 0))):
+        pick = rng.choice(rows, N, replace=True)
+        batches[what] = ([([s[r] for r in pick], [q[r] for r in pick]) for s, q in c.streams], c.codes[pick])
+    keys = MS.ACGT[rng.integers(0, 4, (N + 2000, c.K))]
+    streams, quals = MS.reads_from_keys(c.shape, keys, np.zeros(keys.shape, bool), rng)
+    codes = MM.codes_for_keys(keys, quals, c.sheet, c.K, c.w1, c.m1, c.m2, plan.min_qual)
+    far = np.flatnonzero(codes == 0xFFFF)[:N]
+    batches["unrelated"] = ([([s[r] for r in far], [q[r] for r in far]) for s, q in streams], codes[far])
+    assert far.size == N and (batches["one off"][1] != 0xFFFF).all() and (batches["exact"][1] != 0xFFFF).all()
+    try:
+        for kernel in (1, 2):
+            engine.set_option("kernel", kernel)
+            engine.set_mismatches(c.m1, c.m2)
+            assert engine.kernel_kind() == {1: "fast", 2: "generic"}[kernel]
+            for what, (reads, want) in batches.items():
+                seq, qual, lens, full = rows_on_device(torch_cuda, engine.layout, reads)
+                assert full
+                for n in (7, 8, 9, 32767, 32768, 32769):
+                    got, _, counts = _launch(engine, torch_cuda, ([t[:n] for t in seq], [t[:n] for t in qual], None), n, "plain")
+                    assert (got == want[:n]).all(), (kernel, what, n, np.flatnonzero(got != want[:n])[:10])
+                    assert (counts == MM.counts_for_codes(want[:n], len(c.sheet))).all(), (kernel, what, n)
+    finally:
+        engine.set_option("kernel", 0)
+
+
+def test_counters_accumulate_across_launches_and_folds(torch_cuda, engine):
+    """the rescue's signed move out of UNDETERMINED into the 64-bit totals, over launches without a reset and across folds of the
+    32-bit rows (a fold in front of every launch: fold_pairs below the batch size)"""
+    c = MS.corpus("comb_8x12")
+    engine.set_plan(c.shape.plan)
+    engine.set_barcodes(c.sheet)
+    seq, qual, _, _ = rows_on_device(torch_cuda, engine.layout, c.streams)
+    want = c.counts()
+    assert want[3] > 0 and c.rescued.sum() > 40000 and c.n > 40000
+    ptr = lambda ts: [t.data_ptr() for t in ts]  # noqa: E731
+    codes = torch_cuda.full((c.n,), 0x7777, dtype=torch_cuda.int16, device="cuda")
+    try:
+        for kernel in (0, 2):
+            engine.set_option("kernel", kernel)
+            engine.set_mismatches(c.m1, c.m2)
+            engine.set_option("fold_pairs", 40000)
+            engine.reset_counts()
+            for launches in (1, 2, 3, 1):
+                if launches == 1:
+                    engine.reset_counts()
+                    assert not engine.counts().any()
+                engine.demux_device(c.n, ptr(seq), ptr(qual), codes.data_ptr(), None, stream=torch_cuda.cuda.current_stream().cuda_stream)
+                counts = engine.counts()
+                assert (counts.view(np.int64) >= 0).all() and (counts == launches * want).all(), (kernel, launches, counts[:4], want[:4])
+            assert (codes.cpu().numpy().view(np.uint16) == c.codes).all()
+    finally:
+        engine.set_option("fold_pairs", 0xFFFFFFFF)
+        engine.set_option("kernel", 0)
+
+
+def test_cli_rescued_pairs_in_every_per_destination_report(torch_cuda, tmp_path, monkeypatch):
+    """One command-line run at (1, 1) over 2 BGZF chunks x 1 500 pairs, a tenth of the index reads one substitution from a
+    barcode, with [filter] and every per-destination report on: the fastq outputs are the tolerant oracle's with the filter's
+    model applied, and the quality, cycle, filter, duplication and unknown-barcode reports equal their models fed from those
+    outputs -- a rescued pair counts under its sample everywhere.  Then the same with two chunk workers."""
+    from collections import Counter
+    from quade_amd import cycle_report as cyr
+    from quade_amd import duplication_report as dr
+    from quade_amd import filter_report as fr
+    from quade_amd import quality_report as qr
+    from tests import cycle_model as CYM
+    from tests import dup_model as DM
+    from tests import filter_model as FM
+    from tests import qstats_model as QM
+    from tests import stage_support as SS
+    from tests import unknown_model as UM
+    # (malformed records at the same places of all four streams: the pairs stay together, so the index reads keep their meaning)
+    files, samples = SS._dataset(str(tmp_path / "data"), 47, 2, 1500, True, SS._plain_inserts, SS._same_places, one_off=True)
+    names, slots = [s[0] for s in samples], 1 << 16
+    budgets = "index1_mismatches : 1\nindex2_mismatches : 1\n"
+    plain = tmp_path / "plain.txt"
+    SS._write_conf(plain, files, samples, index_extra=budgets)
+    counts0 = np.array(SS._oracle_run(plain, tmp_path / "ref0").counts(), dtype=np.int64)
+    monkeypatch.setattr(qo, "SampleSet", MM.tolerant_sampleset(qo, 16, 8, 1, 1))
+    counts1 = np.array(SS._oracle_run(plain, tmp_path / "ref1").counts(), dtype=np.int64)
+    # pairs were rescued into every sample; nothing else moved
+    moved = counts1[4:] - counts0[4:]
+    assert counts0[0] == counts1[0] < 3000 and (moved >= 0).all() and (moved.reshape(-1, 2).sum(axis=1) > 0).all()
+    assert 100 < moved.sum() == counts0[3] - counts1[3] and counts1[3] > 100
+    texts, ftable, _, _ = FM.filtered_outputs(str(tmp_path / "ref1"), names, SS.P_F)
+    exact_texts = FM.filtered_outputs(str(tmp_path / "ref0"), names, SS.P_F)[0]
+    size = lambda t, part: sum(len(v) for f, v in t.items() if part in f)  # noqa: E731
+    assert size(texts, "_pass_R1") > size(exact_texts, "_pass_R1") and size(texts, "Undetermined_R1") < size(exact_texts, "Undetermined_R1")  # some get past the filter
+    want = tmp_path / "want"
+    want.mkdir()
+    for f, text in texts.items():
+        with gzip.open(want / f, "wb") as fh:
+            fh.write(text)
+    pairs = []
+    for d, stem in enumerate([n + q for n in names for q in ("_pass", "_fail")] + ["Undetermined"]):
+        r1, r2 = (QM.fastq_records(str(want / (stem + r + ".fastq.gz"))) if stem + r + ".fastq.gz" in texts else [] for r in ("_R1", "_R2"))
+        pairs += [(0xFFFF if d == 2 * len(names) else d, a[0], b[0], 0) for a, b in zip(r1, r2)]
+    table, stats = DM.tally(len(names), pairs, DM.Params(32, 1, slots))
+    unknown = Counter()
+    with gzip.open(tmp_path / "ref1" / "Undetermined_R1.fastq.gz", "rt") as fh:  # (the tally sees every Undetermined pair, filtered or not)
+        unknown.update(ln.strip().rsplit(":", 1)[1].upper() for i, ln in enumerate(fh) if i % 4 == 0)
+    assert sum(unknown.values()) == counts1[3] and all(len(k) == 16 for k in unknown)
+    for work, gpu in (("mine", ""), ("workers", "chunk_workers : 2\n")):
+        conf = tmp_path / (work + ".txt")
+        SS._write_conf(conf, files, samples, quality=True, index_extra=budgets, extra=SS.FILTER, gpu="duplicate_slots : %d\n" % slots + gpu)
+        conf.write_text(conf.read_text().replace("[output]\n", "[output]\ncycle_report : True\nduplication_report : True\n"
+                                                 "duplication_sample : 1\ntop_unknown_barcodes : 1000\n", 1))
+        mine = tmp_path / work
+        SS._cli(conf, mine)
+        SS._check_files(mine, texts)
+        SS._check_main_report(mine, tmp_path / "ref1")
+        SS._check_report(mine, fr, ftable, names, SS.P_F.keywords())
+        SS._check_report(mine, qr, QM.table_from_outputs(str(want), names), names)
+        SS._check_report(mine, cyr, CYM.table_from_outputs(str(want), names))
+        SS._check_report(mine, dr, stats, *DM.arrays(table), names, dict(bases=32, sample=1, slots=slots))
+        head, _, rows = UM.parse_report(str(mine / "Quade_unknown_barcodes.csv"))
+        assert head == {"Pair Undetermined": str(counts1[3]), "Short index slice": "0", "Not tallied": "0",
+                        "Distinct barcodes tallied": str(len(unknown))}
+        fused = [(s[0], s[1] + s[2]) for s in samples]
+        assert len(rows) == len(unknown) <= 1000
+        for r, (key, c) in zip(rows, UM.report_order(unknown)):
+            name, d1, d2 = UM.nearest_brute(key, fused, 8)
+            assert r == [key[:8], key[8:], str(c), str(c * 100 // counts1[3]), name, str(d1), str(d2)] and (d1 > 1 or d2 > 1)
 
 
 def _decompressed(d):

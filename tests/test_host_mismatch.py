@@ -1,5 +1,8 @@
 """Mismatch-tolerant matching, host side (no GPU): the [index] options, the host-only collision check against a brute force
-written from the rule (tests/mismatch_model.py), and the command line on a colliding sample sheet."""
+written from the rule (tests/mismatch_model.py), and the command line on a colliding sample sheet; and the ground the GPU tests of the
+tight and combinatorial sheets stand on: the brute-force model of the routing codes pinned to the unmodified oracle with the tolerant
+lookup installed, and the conditions that keep every corpus of tests/mismatch_support.py from going hollow."""
+import math
 import os
 import subprocess
 import sys
@@ -7,10 +10,13 @@ import sys
 import numpy as np
 import pytest
 
+from oracle import quade_oracle as qo
 from quade_amd import hip_backend as hb
 from quade_amd import synth
 from quade_amd.conf import MISMATCH_HELP, QuadeConf, template_bytes
+from tests import helpers as H
 from tests import mismatch_model as MM
+from tests import mismatch_support as MS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -121,6 +127,131 @@ def test_far_sheet_generator_does_not_collide():
     # the existing generator is untouched: cfg5's uniform sheet collides under (1, 1)
     w = synth.generate("cfg5", 16, seed=3)
     assert hb.check_mismatch_collisions(w.barcode_strings(), 16, 8, 1, 1) is not None
+
+
+# ---- the tight and combinatorial corpora of the GPU tests: the model pinned to the oracle, and the corpora kept from going hollow ----
+def test_model_by_hand():
+    K, w1, q40 = 4, 2, np.full((1, 4), 73, np.uint8)
+    one = lambda key, sheet, m1, m2, quals=q40: int(MM.codes_for_keys(np.frombuffer(key, np.uint8)[None, :], quals, sheet, K, w1, m1, m2, 25)[0])  # noqa: E731
+    sheet = ["ACGT", "TTTTT", "GGCC"]
+    assert one(b"GGCC", sheet, 0, 0) == 4 and one(b"GGCA", sheet, 0, 0) == 0xFFFF
+    assert one(b"GGCA", sheet, 0, 1) == 4 and one(b"GGCA", sheet, 1, 0) == 0xFFFF  # the budgets are per part
+    assert one(b"GGAA", sheet, 1, 1) == 0xFFFF and one(b"GGAA", sheet, 0, 2) == 4 and one(b"ANGN", sheet, 1, 1) == 0  # N is a symbol
+    assert one(b"TTTT", ["TTTTT", "TTT"], 2, 2) == 0xFFFF == one(b"TTTT", sheet, 1, 1)  # a barcode of another length matches exactly only
+    low = q40.copy()
+    low[0, 3] = 24 + 33
+    at = q40.copy()
+    at[0, 0] = 25 + 33
+    assert one(b"ACGA", sheet, 0, 1, low) == 1 and one(b"ACGA", sheet, 0, 1, at) == 0
+    # an exact hit is taken first, whatever else is within budget; without one, two barcodes within budget are a colliding sheet
+    assert one(b"ACGT", ["ACGA", "ACGT"], 0, 1) == 2
+    with pytest.raises(AssertionError):
+        one(b"ACGC", ["ACGA", "ACGT"], 0, 1)
+    codes = np.array([0, 3, 0xFFFF, 3, 4], dtype=np.uint16)
+    assert MM.counts_for_codes(codes, 3).tolist() == [5, 2, 2, 1, 1, 0, 0, 2, 1, 0]
+
+
+def _spheres(w, m):
+    """how many strings over five symbols lie at exactly m substitutions from one of w bases"""
+    return math.comb(w, m) * 4 ** m if m <= w else 0
+
+
+@pytest.mark.parametrize("name", sorted(MS.CORPORA))
+def test_corpus_conditions(name):
+    c = MS.corpus(name)
+    shape, (m1, m2), sizes, cap, alphabet = MS.CORPORA[name]
+    w = (c.w1, c.K - c.w1)
+    assert hb.check_mismatch_collisions(c.sheet, c.K, c.w1, m1, m2) is None
+    assert len(set(c.sheet)) == len(c.sheet) == int(np.prod(sizes)) + (3 if name == "mixed_len" else 0)
+    for codes, width, m in zip(c.lists, w, (m1, m2)):  # tight: no pair closer than 2m + 1 (1 at m = 0), the first pair exactly there
+        d = [[MM.part_distances(a, b, width)[0] for b in codes] for a in codes]
+        assert min(d[i][j] for i in range(len(codes)) for j in range(i)) == d[0][1] == max(1, 2 * m + 1)
+    # every key within budget of every barcode with a neighbourhood: the whole product of the two balls, each key once
+    made = np.unique(c.origin[~c.short])
+    inside = (c.d1 <= m1) & (c.d2 <= m2) & ~c.short
+    ball = [sum(_spheres(w[p], d) for d in range(m + 1)) for p, m in enumerate((m1, m2))]
+    assert made.size == (68 if name == "comb_96x96" else int(np.prod(sizes)))
+    for s in made[:: max(1, made.size // 8)]:
+        mine = c.keys[inside & (c.origin == s)]
+        assert mine.shape[0] == ball[0] * ball[1] == np.unique(mine, axis=0).shape[0]
+    assert int(inside.sum()) == made.size * ball[0] * ball[1]
+    corner = int(((c.d1 == m1) & (c.d2 == m2) & ~c.short).sum())
+    assert corner == made.size * _spheres(w[0], m1) * _spheres(w[1], m2) and (corner >= 1000 or name == "single8_m1")
+    # the two shells: exactly one substitution over budget on one part, within budget on the other, `cap` of each per barcode at most
+    for over1, over2 in ((1, 0), (0, 1)):
+        shell = (c.d1 == m1 + over1 if over1 else c.d1 <= m1) & (c.d2 == m2 + over2 if over2 else c.d2 <= m2) & ~c.short
+        full = (_spheres(w[0], m1 + 1) * ball[1]) if over1 else (ball[0] * _spheres(w[1], m2 + 1))
+        assert int(shell.sum()) == made.size * min(cap, full)
+    outside = ((c.d1 > m1) | (c.d2 > m2)) & ~c.short
+    assert int((inside | outside).sum()) == int((~c.short).sum())
+    # within budget of its own barcode: that sample; some keys just outside belong to ANOTHER sample, the tight neighbour
+    assert (c.codes[inside] // 2 == c.origin[inside]).all()
+    assert int((outside & (c.codes != 0xFFFF) & (c.codes // 2 != c.origin)).sum()) >= 40
+    assert not (outside & (c.codes // 2 == c.origin)).any()
+    determined = c.codes != 0xFFFF
+    for what in (c.rescued, ~determined, determined & (c.codes % 2 == 0), determined & (c.codes % 2 == 1)):
+        assert int(what.sum()) >= 100
+    assert (c.exact[~c.rescued] == c.codes[~c.rescued]).all()
+    if name == "with_N":
+        assert sum("N" in b for b in c.sheet) >= 2
+    if name == "mixed_len":
+        assert sorted(len(b) for b in c.sheet[-3:]) == [8, 13, 15] and c.sheet[:-3] == MS.corpus("comb_8x12").sheet
+        cut = np.flatnonzero(c.short)
+        assert cut.size == -(-(c.n - cut.size) // 10) and(c.keys[:c.n - cut.size] == MS.corpus("comb_8x12").keys).all()
+        assert 0.4 < float((c.codes[cut] == 0xFFFF).mean()) < 0.6 and set(c.codes[cut].tolist()) == {0xFFFF} | set(range(192, 198))
+    if name == "comb_96x96":
+        assert 2 * len(c.sheet) > 16000  # past the rescue's per-workgroup histogram: counted in global memory
+        assert min(MS.longest_candidate_lists(c.sheet, c.K, c.w1, m1, m2)) >= 96  # whichever part: lists of 96 and more
+
+
+def test_which_part_the_candidate_lists_come_from():
+    """the part whose longest candidate list is shorter.  Lists longer than one -- what uniform sheets never have"""
+    a = MS.corpus("comb_8x12")
+    # index read 1's part: its 8 codes share no half, so 12 samples per list; three of the other part's 12 codes share a half (3 x 8)
+    assert MS.longest_candidate_lists(a.sheet, 16, 8, 1, 1) == [12, 24]
+    b = MS.corpus("comb_12x8_m10")
+    # index read 2's part, whole (budget 0: one segment), 8 codes in 12 samples each; two of the 12 codes of part 1 share a half (2 x 8)
+    assert MS.longest_candidate_lists(b.sheet, 16, 8, 1, 0) == [16, 12]
+    c = MS.corpus("comb_12x8_m01")
+    assert MS.longest_candidate_lists(c.sheet, 16, 8, 0, 1) == [12, 16]   # the mirror image: index read 1's part, whole
+    assert MS.longest_candidate_lists(MS.corpus("comb_96x96").sheet, 16, 8, 1, 1) == [384, 288]  # index read 2's part
+    far = synth.make_far_barcodes(96, 8, 8, 1, 1, seed=1)
+    assert MS.longest_candidate_lists(far, 16, 8, 1, 1) == [4, 3]  # uniform draws: the few that share a 4-base half by chance
+    for shape, (m1, m2) in MS.NO_SEGMENTS.items():
+        s = MS.TIGHT[shape]
+        assert MS.longest_candidate_lists(["AC"], s.w1 + s.w2, s.w1, m1, m2) == [None, None]
+
+
+def _oracle_on(monkeypatch, c, rows):
+    monkeypatch.setattr(qo, "SampleSet", MM.tolerant_sampleset(qo, c.K, c.w1, c.m1, c.m2))
+    reads = []
+    for s, q in c.streams:
+        reads += [[s[r].decode() for r in rows], [q[r].decode() for r in rows]]
+    if len(c.streams) == 1:
+        reads += [None, None]
+    return H.oracle_on_reads(c.sheet, c.shape.plan, *reads)
+
+
+@pytest.mark.parametrize("name", sorted(MS.CORPORA) + ["no_segments_" + s for s in sorted(MS.NO_SEGMENTS)])
+def test_model_agrees_with_the_tolerant_oracle(monkeypatch, name):
+    """the unmodified oracle with TolerantIndex installed, on a seeded sub-sample of every corpus's reads: every code, the
+    fused slice, the molecular bytes and the counter vector"""
+    c = MS.no_segments_corpus(name[len("no_segments_"):]) if name.startswith("no_segments_") else MS.corpus(name)
+    rows = c.sample(4000, seed=11)
+    assert rows.size == min(4000, c.n) and (not c.short.any() or c.short[rows].sum() >= min(100, c.short.sum()))
+    codes, idx, mol, counts = _oracle_on(monkeypatch, c, rows)
+    assert (codes == c.codes[rows]).all(), rows[np.flatnonzero(codes != c.codes[rows])[:10]]
+    assert (counts == c.counts(c.codes[rows])).all()
+    full = rows[~c.short[rows]]
+    assert [i.upper().encode() for i, r in zip(idx, rows) if not c.short[r]] == [c.keys[r].tobytes() for r in full]
+    if c.shape.plan.mol1_end:
+        want = c.molecular()
+        assert mol == [want[r].decode() for r in rows] and len(want[0]) == 3
+    # and without budgets: what the model calls rescued is Undetermined, everything else keeps its code
+    monkeypatch.setattr(c, "m1", 0)
+    monkeypatch.setattr(c, "m2", 0)
+    codes0 = _oracle_on(monkeypatch, c, rows)[0]
+    assert (codes0 == c.exact[rows]).all() and (codes0[c.rescued[rows]] == 0xFFFF).all()
 
 
 def _run_cli(conf, cwd):
