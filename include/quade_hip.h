@@ -809,7 +809,10 @@ int64_t qd_huffman_member_bound(int64_t text_len);
 /* ABI v4.  Which members the deflater makes: -1 (the default) = Huffman only, as above; 1 = LZ77 + dynamic Huffman, the
  * driver's `gzip_level : 1` (greedy parse, 4-byte hash of last positions + runs, 32 KiB window; the piece is coded as 64 KiB
  * dynamic-Huffman blocks joined by empty stored blocks in ONE member).  Same slots, same bound, same fallback rule
- * (member_len 0); other levels stay with the host's libdeflate / zlib: QD_ERR_INVALID. */
+ * (member_len 0); other levels stay with the host's libdeflate / zlib: QD_ERR_INVALID.
+ * At level 1 qd_deflater_run accepts crc32 == NULL: every member's CRC-32 then comes from the coder itself (each sub-block's,
+ * taken while its text is staged, combined per piece on the device), as in the device pipeline.  At level -1 NULL stays
+ * QD_ERR_INVALID. */
 int qd_deflater_set_level(qd_deflater* deflater, int32_t level);
 int qd_deflater_destroy(qd_deflater* deflater);
 const char* qd_deflater_last_error(const qd_deflater* deflater);

@@ -19,6 +19,7 @@
 #include "quade_inflate.h"
 #include "quade_inflate3.h"
 #include "quade_deflate.h"
+#include "quade_text.h"
 #include "quade_mismatch.h"
 #include "quade_unknown.h"
 #include "quade_qstats.h"
@@ -2592,7 +2593,11 @@ struct qd_deflater {
     size_t cap_sub = 0, cap_first = 0;
     uint32_t *d_tokens = nullptr, *d_sub_bytes = nullptr;
     uint8_t* d_sub_out = nullptr;
-    size_t cap_scratch = 0;  // sub-blocks the three scratch arrays hold
+    size_t cap_scratch = 0;  // sub-blocks the scratch arrays hold
+    // crc32 == NULL at level 1: the sub-blocks' CRC-32s out of the coder, their lengths for the combine
+    uint32_t* d_sub_crc = nullptr;
+    qd_crc_range *h_rg = nullptr, *d_rg = nullptr;
+    size_t cap_rg = 0;
 };
 
 namespace {
@@ -2666,6 +2671,9 @@ int qd_deflater_destroy(qd_deflater* f) {
     if (f->d_tokens) (void)hipFree(f->d_tokens);
     if (f->d_sub_bytes) (void)hipFree(f->d_sub_bytes);
     if (f->d_sub_out) (void)hipFree(f->d_sub_out);
+    if (f->d_sub_crc) (void)hipFree(f->d_sub_crc);
+    if (f->h_rg) (void)hipHostFree(f->h_rg);
+    if (f->d_rg) (void)hipFree(f->d_rg);
     delete f;
     return QD_OK;
 }
@@ -2678,9 +2686,10 @@ int qd_deflater_set_level(qd_deflater* f, int32_t level) {
 
 int qd_deflater_run(qd_deflater* f, int32_t n_pieces, const uint8_t* const* text, const int64_t* text_len, const uint32_t* crc32,
                     int32_t text_pinned, uint8_t* out, int64_t out_stride, int64_t* member_len) {
-    if (!f || n_pieces < 0 || (n_pieces && (!text || !text_len || !crc32 || !out || !member_len)) || out_stride < 64 || (out_stride & 3))
+    if (!f || n_pieces < 0 || (n_pieces && (!text || !text_len || !out || !member_len)) || out_stride < 64 || (out_stride & 3))
         return def_fail(f, QD_ERR_INVALID, "bad arguments");
     if (n_pieces == 0) return QD_OK;
+    if (!crc32 && f->level != 1) return def_fail(f, QD_ERR_INVALID, "only the level-1 coder makes the members' CRC-32s itself");
     size_t total = 0;
     for (int i = 0; i < n_pieces; ++i) {
         if (text_len[i] < 0 || text_len[i] > (int64_t)0x7FFFFFFF || (text_len[i] && !text[i])) return def_fail(f, QD_ERR_INVALID, "bad piece");
@@ -2702,7 +2711,7 @@ int qd_deflater_run(qd_deflater* f, int32_t n_pieces, const uint8_t* const* text
     if (!text_pinned && !f->h_text) DEFCHK(f, hipHostMalloc((void**)&f->h_text, f->cap_text, hipHostMallocDefault));
     size_t at = 0;
     for (int i = 0; i < n_pieces; ++i) {
-        f->h_pc[i] = qd_deflate_piece{(uint64_t)at, (uint32_t)text_len[i], crc32[i]};
+        f->h_pc[i] = qd_deflate_piece{(uint64_t)at, (uint32_t)text_len[i], crc32 ? crc32[i] : 0u};
         if (text_len[i]) {
             const uint8_t* src = text[i];
             if (!text_pinned) {
@@ -2724,13 +2733,15 @@ int qd_deflater_run(qd_deflater* f, int32_t n_pieces, const uint8_t* const* text
             if (f->d_tokens) (void)hipFree(f->d_tokens);
             if (f->d_sub_bytes) (void)hipFree(f->d_sub_bytes);
             if (f->d_sub_out) (void)hipFree(f->d_sub_out);
-            f->d_tokens = f->d_sub_bytes = nullptr;
+            if (f->d_sub_crc) (void)hipFree(f->d_sub_crc);
+            f->d_tokens = f->d_sub_bytes = f->d_sub_crc = nullptr;
             f->d_sub_out = nullptr;
             f->cap_scratch = 0;
             const size_t n = n_subs + n_subs / 4 + 16;
             DEFCHK(f, hipMalloc((void**)&f->d_tokens, n * (size_t)QD_LZ_SUB * 4));
             DEFCHK(f, hipMalloc((void**)&f->d_sub_bytes, n * 4));
             DEFCHK(f, hipMalloc((void**)&f->d_sub_out, n * (size_t)sub_stride));
+            DEFCHK(f, hipMalloc((void**)&f->d_sub_crc, n * 4));
             f->cap_scratch = n;
         }
         size_t js = 0, off = 0;
@@ -2743,8 +2754,19 @@ int qd_deflater_run(qd_deflater* f, int32_t n_pieces, const uint8_t* const* text
         f->h_first[n_pieces] = (uint32_t)js;
         if (js) DEFCHK(f, hipMemcpyAsync(f->d_sub, f->h_sub, js * sizeof(qd_lz_sub), hipMemcpyHostToDevice, f->stream));
         DEFCHK(f, hipMemcpyAsync(f->d_first, f->h_first, ((size_t)n_pieces + 1) * 4, hipMemcpyHostToDevice, f->stream));
-        DEFCHK(f, qd_launch_lz(f->d_text, f->d_pc, (uint32_t)n_pieces, f->d_sub, f->d_first, (uint32_t)js, f->d_tokens, f->d_sub_out, sub_stride,
-                               f->d_sub_bytes, f->d_out, out_stride, f->d_len, f->stream));
+        if (crc32) {
+            DEFCHK(f, qd_launch_lz(f->d_text, f->d_pc, (uint32_t)n_pieces, f->d_sub, f->d_first, (uint32_t)js, f->d_tokens, f->d_sub_out, sub_stride,
+                                   f->d_sub_bytes, f->d_out, out_stride, f->d_len, f->stream));
+        } else {  // as the pipeline (quade_pipe.cpp): the sub-blocks' CRC-32s out of the coder, combined per piece into the piece table
+            static_assert(sizeof(qd_deflate_piece) == 16 && offsetof(qd_deflate_piece, crc32) == 12, "the combined CRCs land in the piece table");
+            DEFCHK(f, grow_pair(f->h_rg, f->d_rg, f->cap_rg, js + 1));
+            for (size_t k = 0; k < js; ++k) f->h_rg[k] = qd_crc_range{f->h_sub[k].text_off, f->h_sub[k].text_len, 0};
+            if (js) DEFCHK(f, hipMemcpyAsync(f->d_rg, f->h_rg, js * sizeof(qd_crc_range), hipMemcpyHostToDevice, f->stream));
+            DEFCHK(f, qd_launch_lz_subblocks(f->d_text, f->d_sub, (uint32_t)js, f->d_tokens, f->d_sub_out, sub_stride, f->d_sub_bytes, f->d_sub_crc, f->stream));
+            DEFCHK(f, qd_text_crc32_combine(f->d_rg, f->d_sub_crc, f->d_first, (uint32_t)n_pieces, reinterpret_cast<uint32_t*>(f->d_pc) + 3, 4, f->stream));
+            DEFCHK(f, qd_launch_lz_members(f->d_pc, (uint32_t)n_pieces, f->d_sub, f->d_first, (uint32_t)js, f->d_sub_out, sub_stride, f->d_sub_bytes,
+                                           f->d_out, out_stride, f->d_len, f->stream));
+        }
     } else {
         DEFCHK(f, qd_launch_huffman(f->d_text, f->d_pc, (uint32_t)n_pieces, f->d_out, out_stride, f->d_len, f->stream));
     }
