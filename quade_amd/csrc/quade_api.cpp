@@ -53,6 +53,34 @@ struct Slot {
 
 enum { K_FAST = 1, K_GENERIC = 2 };
 
+// Per stream one device buffer that holds `units` units of a batch (pairs, here) and grows on demand: the rescue's list of a batch's
+// undetermined pairs and the two tallies' batch scratch.  Defined beside uk_malloc.
+struct StreamScratch {
+    struct Buf {
+        hipStream_t stream;
+        uint8_t* buf;
+        size_t units;  // bytes_for(units) bytes; 0 beside buf == nullptr
+    };
+    std::vector<Buf> bufs;
+    Buf* find(hipStream_t st);
+    Buf* need(qd_ctx* c, hipStream_t st, size_t units, size_t (*bytes_for)(size_t));  // nullptr: failed, qd_last_error has the text
+    void release();  // (the caller waited for the context's work)
+};
+
+// A tally of keys on the device (the unknown barcodes, the duplication report): the table (one allocation, quade_unknown.h), per
+// stream the scratch of a batch, and the event behind the last launch's count kernel that a launch on another stream waits for
+// before its claim kernel.  The tally_* functions beside uk_malloc work on it.
+struct KeyTally {
+    void* mem = nullptr;  // nullptr = off
+    int64_t slots = 0;
+    UnknownTable t{};
+    int tag_bits = 64;  // options "unknown_tag_bits" / "dup_tag_bits" (tests); outlives the table
+    hipEvent_t done = nullptr;
+    hipStream_t last = nullptr;
+    bool recorded = false;
+    StreamScratch scratch;
+};
+
 }  // namespace
 
 struct qd_ctx {
@@ -121,29 +149,11 @@ struct qd_ctx {
     MismatchParams mm{};
     QdMmBucket* d_mm_htab = nullptr;
     uint16_t* d_mm_cand = nullptr;
-    struct MmScratch {
-        hipStream_t stream;
-        uint32_t* buf;
-        size_t cap;  // uint32 entries
-    };
-    std::vector<MmScratch> mm_scratch;
+    StreamScratch mm_list;  // pairs + 4 uint32 entries
 
-    // tally of the unknown barcodes (qd_unknown_enable): the table (one allocation), per stream the scratch of a batch
-    // ([0] = count and the list of its undetermined pairs from [4], then from [4 + pairs] each listed pair's slot), and the event
-    // behind the last launch's uk_count that a launch on another stream waits for before its uk_claim
-    int64_t uk_slots = 0;  // 0 = off
-    void* d_uk = nullptr;
-    UnknownTable uk{};
-    int uk_tag_bits = 64;  // option "unknown_tag_bits" (tests)
-    hipEvent_t uk_done = nullptr;
-    hipStream_t uk_last = nullptr;
-    bool uk_recorded = false;
-    struct UkScratch {
-        hipStream_t stream;
-        uint32_t* buf;
-        size_t pairs;  // 2 * pairs + 4 uint32 entries
-    };
-    std::vector<UkScratch> uk_scratch;
+    // tally of the unknown barcodes (qd_unknown_enable); per stream the scratch of a batch: 2 * pairs + 4 uint32 entries ([0] = count
+    // and the list of its undetermined pairs from [4], then from [4 + pairs] each listed pair's slot)
+    KeyTally uk;
 
     // yield and quality counters per destination (qd_qstats_enable): uint64[(2 * S + 1)][2][6], nullptr = off
     u64* d_qs = nullptr;
@@ -174,24 +184,12 @@ struct qd_ctx {
     u64* d_filter = nullptr;
 
     // duplication tally (qd_dup_set): the parameters as given and as the kernels take them, the counters
-    // uint64[(2 * S + 1)][5] (d_dup == nullptr = off), the key table (one allocation, the unknown tally's layout), per stream the
-    // batch list (quade_dup.h), and the event behind the last launch's dup_count that a launch on another stream waits for
-    // before its dup_claim
+    // uint64[(2 * S + 1)][5] (d_dup == nullptr = off), and the key tally; per stream its scratch is the batch list,
+    // qd_dup_list_bytes(pairs) bytes (quade_dup.h)
     qd_dup_params dup{0, 0, 0};
     qd_dup_dev dup_dev{0, 0};
     u64* d_dup = nullptr;
-    void* d_dup_keys = nullptr;
-    UnknownTable dup_t{};
-    int dup_tag_bits = 64;  // option "dup_tag_bits" (tests)
-    hipEvent_t dup_done = nullptr;
-    hipStream_t dup_last = nullptr;
-    bool dup_recorded = false;
-    struct DupScratch {
-        hipStream_t stream;
-        uint8_t* buf;
-        size_t pairs;  // qd_dup_list_bytes(pairs) bytes
-    };
-    std::vector<DupScratch> dup_scratch;
+    KeyTally dup_keys;
 };
 
 namespace {
@@ -317,6 +315,140 @@ void free_table(qd_ctx* c) {
     c->have_table = false;
 }
 
+// hipMalloc; out of memory: the pool's idle buffers go back to the driver once (it can hold tens of GB) and the call is repeated
+hipError_t uk_malloc(void** p, size_t bytes) {
+    hipError_t e = hipMalloc(p, bytes);
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        (void)qd_pool_trim();
+        e = hipMalloc(p, bytes);
+    }
+    return e;
+}
+
+StreamScratch::Buf* StreamScratch::find(hipStream_t st) {
+    for (auto& b : bufs)
+        if (b.stream == st) return &b;
+    return nullptr;
+}
+
+// the stream's buffer with room for `units` units at least, grown (to twice what it held, at least) when it has not
+StreamScratch::Buf* StreamScratch::need(qd_ctx* c, hipStream_t st, size_t units, size_t (*bytes_for)(size_t)) {
+    Buf* b = find(st);
+    if (!b) {
+        bufs.push_back(Buf{st, nullptr, 0});
+        b = &bufs.back();
+    }
+    if (b->buf && b->units >= units) return b;
+    hipError_t e = hipStreamSynchronize(st);  // the old buffer may still be read by this stream's previous batch
+    if (e == hipSuccess) {
+        if (b->buf) (void)hipFree(b->buf);
+        b->buf = nullptr;
+        const size_t grown = std::max(units, b->units * 2);
+        b->units = 0;  // should the allocation fail, the next batch allocates again
+        e = uk_malloc(reinterpret_cast<void**>(&b->buf), bytes_for(grown));
+        if (e == hipSuccess) b->units = grown;
+        else b->buf = nullptr;
+    }
+    if (e == hipSuccess) return b;
+    fail(c, QD_ERR_HIP, std::string("stream scratch: ") + hipGetErrorString(e));
+    return nullptr;
+}
+
+void StreamScratch::release() {
+    for (auto& b : bufs) (void)hipFree(b.buf);
+    bufs.clear();
+}
+
+bool tally_slots_ok(int64_t slots) {  // a power of two in 2^10 .. 2^28
+    return slots >= ((int64_t)1 << QD_UK_MIN_LG) && slots <= ((int64_t)1 << QD_UK_MAX_LG) && !(slots & (slots - 1));
+}
+
+// the tally off and its memory freed (the caller waited for the context's work)
+void tally_close(KeyTally& T) {
+    if (T.mem) (void)hipFree(T.mem);
+    T.mem = nullptr;
+    T.slots = 0;
+    T.recorded = false;
+    T.scratch.release();
+    if (T.done) (void)hipEventDestroy(T.done);
+    T.done = nullptr;
+}
+
+// a closed tally on: a zeroed table of `slots` entries and its event; `what` names the table in the error text
+int tally_open(qd_ctx* c, KeyTally& T, int64_t slots, const char* what) {
+    hipError_t e = uk_malloc(&T.mem, qd_uk_bytes(slots));
+    if (e != hipSuccess) T.mem = nullptr;
+    if (e == hipSuccess) e = hipMemsetAsync(T.mem, 0, qd_uk_bytes(slots), c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&T.done, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        tally_close(T);
+        return fail(c, QD_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    }
+    qd_uk_carve(T.mem, slots, T.t);
+    T.slots = slots;
+    return QD_OK;
+}
+
+// an empty table again, on `st` (qd_reset_counts)
+hipError_t tally_zero(const KeyTally& T, hipStream_t st) { return hipMemsetAsync(T.mem, 0, qd_uk_bytes(T.slots), st); }
+
+// the table as the kernels take it
+UnknownTable tally_view(const KeyTally& T) {
+    UnknownTable t = T.t;
+    t.tag_mask = T.tag_bits >= 64 ? ~0ull : ((1ull << T.tag_bits) - 1);
+    return t;
+}
+
+// what a launch on `st` waits for before its claim kernel: the last launch's count kernel when that ran on another stream
+hipEvent_t tally_before(const KeyTally& T, hipStream_t st) { return T.recorded && T.last != st ? T.done : nullptr; }
+
+// behind a launch's count kernel on `st`
+int tally_after(qd_ctx* c, KeyTally& T, hipStream_t st) {
+    HIPCHK(c, hipEventRecord(T.done, st));
+    T.recorded = true;
+    T.last = st;
+    return QD_OK;
+}
+
+// (the caller waited for the stream: its event, should it be the last one recorded, is not waited for any more)
+void tally_retired(KeyTally& T, hipStream_t st) {
+    if (T.last == st) T.recorded = false;
+}
+
+// What qd_unknown_read and qd_dup_read share: D entries, D <= cap: their key words (QD_KEY_WORDS each) into hk and their counts
+// into counts; returns D, -D when cap is too small, or QD_UNKNOWN_READ_ERROR + QD_ERR_* with "<what> read: ..." as the text
+int64_t tally_gather(qd_ctx* c, const KeyTally& T, const char* what, int64_t cap, std::vector<u64>& hk, uint64_t* counts) {
+    auto bad = [&](const char* msg) { return QD_UNKNOWN_READ_ERROR + (int64_t)fail(c, QD_ERR_HIP, std::string(what) + " read: " + msg); };
+    uint64_t tot[4];
+    hipError_t e = hipSetDevice(c->device);
+    if (e == hipSuccess) e = wait_all(c);
+    if (e == hipSuccess) e = hipMemcpy(tot, T.t.totals, sizeof tot, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return bad(hipGetErrorString(e));
+    const int64_t D = (int64_t)tot[QD_UK_DISTINCT];
+    if (D > cap) return -D;
+    if (D == 0) return 0;
+    // the occupied entries packed on the device (uk_gather works on the table alone): only they cross the link
+    uint8_t* d_out = nullptr;
+    const size_t kbytes = (size_t)D * QD_KEY_WORDS * 8, cbytes = (size_t)D * 8;
+    if ((e = uk_malloc(reinterpret_cast<void**>(&d_out), kbytes + cbytes + 16)) != hipSuccess) return bad(hipGetErrorString(e));
+    u64* d_keys = reinterpret_cast<u64*>(d_out);
+    u64* d_counts = reinterpret_cast<u64*>(d_out + kbytes);
+    uint32_t* d_n = reinterpret_cast<uint32_t*>(d_out + kbytes + cbytes);
+    hk.resize((size_t)D * QD_KEY_WORDS);
+    uint32_t got = 0;
+    e = qd_launch_unknown_gather(T.t, d_keys, d_counts, d_n, (uint32_t)D, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(hk.data(), d_keys, kbytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, cbytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&got, d_n, 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d_out);
+    if (e != hipSuccess) return bad(hipGetErrorString(e));
+    if ((int64_t)got != D) return bad("the table's entry count and its occupied entries differ");
+    return D;
+}
+
 // budgets back to 0 and the rescue's tables freed (the caller waited for the context's work)
 void free_mismatch(qd_ctx* c, bool scratch) {
     if (c->d_mm_htab) (void)hipFree(c->d_mm_htab);
@@ -324,29 +456,14 @@ void free_mismatch(qd_ctx* c, bool scratch) {
     c->d_mm_htab = nullptr;
     c->d_mm_cand = nullptr;
     c->mm_m1 = c->mm_m2 = 0;
-    if (scratch) {
-        for (auto& m : c->mm_scratch) (void)hipFree(m.buf);
-        c->mm_scratch.clear();
-    }
+    if (scratch) c->mm_list.release();
 }
 
 // the rescue post-pass of a batch on `st` (launch(), budgets set): the stream's list holds n + 4 entries at least
 int launch_mismatch(qd_ctx* c, int64_t n, const qd_rows* rows, uint16_t* codes, hipStream_t st) {
-    qd_ctx::MmScratch* sc = nullptr;
-    for (auto& m : c->mm_scratch)
-        if (m.stream == st) sc = &m;
-    if (!sc) {
-        c->mm_scratch.push_back(qd_ctx::MmScratch{st, nullptr, 0});
-        sc = &c->mm_scratch.back();
-    }
-    if (sc->cap < (size_t)n + 4) {
-        HIPCHK(c, hipStreamSynchronize(st));  // the old list may still be read by this stream's previous batch
-        if (sc->buf) (void)hipFree(sc->buf);
-        sc->buf = nullptr;
-        const size_t cap = std::max<size_t>((size_t)n + 4, sc->cap * 2);
-        HIPCHK(c, hipMalloc(&sc->buf, cap * 4));
-        sc->cap = cap;
-    }
+    StreamScratch::Buf* sc = c->mm_list.need(c, st, (size_t)n, [](size_t pairs) { return (pairs + 4) * 4; });
+    if (!sc) return QD_ERR_HIP;
+    uint32_t* list = reinterpret_cast<uint32_t*>(sc->buf);
     MismatchParams p = c->mm;
     for (int k = 0; k < c->lay.n_streams; ++k) {
         p.seq[k] = rows->seq[k];
@@ -357,22 +474,11 @@ int launch_mismatch(qd_ctx* c, int64_t n, const qd_rows* rows, uint16_t* codes, 
     p.bk32 = c->d_bk32;
     p.htab = c->d_mm_htab;
     p.cand = c->d_mm_cand;
-    p.miss = sc->buf;
+    p.miss = list;
     p.n = n;
-    hipError_t e = qd_launch_mismatch(p, sc->buf, c->cu, st);
+    hipError_t e = qd_launch_mismatch(p, list, c->cu, st);
     if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("mismatch launch: ") + hipGetErrorString(e));
     return QD_OK;
-}
-
-// hipMalloc; out of memory: the pool's idle buffers go back to the driver once (it can hold tens of GB) and the call is repeated
-hipError_t uk_malloc(void** p, size_t bytes) {
-    hipError_t e = hipMalloc(p, bytes);
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        (void)qd_pool_trim();
-        e = hipMalloc(p, bytes);
-    }
-    return e;
 }
 
 // ---- the read stages (qstats, cstats, clip, trim, pairtrim, filter): their tables and the harness of their qd_dev_* entries ----
@@ -525,38 +631,17 @@ private:
 
 // the tally off and its memory freed (the caller waited for the context's work)
 void free_unknown(qd_ctx* c) {
-    if (c->d_uk) (void)hipFree(c->d_uk);
-    c->d_uk = nullptr;
-    c->uk_slots = 0;
-    c->uk_recorded = false;
-    for (auto& m : c->uk_scratch) (void)hipFree(m.buf);
-    c->uk_scratch.clear();
-    if (c->uk_done) (void)hipEventDestroy(c->uk_done);
-    c->uk_done = nullptr;
+    tally_close(c->uk);
 }
 
 // the tally post-pass of a batch on `st` (launch(), tally enabled), behind the rescue when one ran (`rescued`: its list is reused)
 int launch_unknown(qd_ctx* c, int64_t n, const qd_rows* rows, const uint16_t* codes, hipStream_t st, bool rescued) {
-    qd_ctx::UkScratch* sc = nullptr;
-    for (auto& m : c->uk_scratch)
-        if (m.stream == st) sc = &m;
-    if (!sc) {
-        c->uk_scratch.push_back(qd_ctx::UkScratch{st, nullptr, 0});
-        sc = &c->uk_scratch.back();
-    }
-    if (sc->pairs < (size_t)n) {
-        HIPCHK(c, hipStreamSynchronize(st));  // the old scratch may still be read by this stream's previous batch
-        if (sc->buf) (void)hipFree(sc->buf);
-        sc->buf = nullptr;
-        const size_t pairs = std::max<size_t>((size_t)n, sc->pairs * 2);
-        sc->pairs = 0;
-        HIPCHK(c, uk_malloc(reinterpret_cast<void**>(&sc->buf), (2 * pairs + 4) * 4));
-        sc->pairs = pairs;
-    }
-    uint32_t* list = sc->buf;
+    StreamScratch::Buf* sc = c->uk.scratch.need(c, st, (size_t)n, [](size_t pairs) { return (2 * pairs + 4) * 4; });
+    if (!sc) return QD_ERR_HIP;
+    uint32_t* const buf = reinterpret_cast<uint32_t*>(sc->buf);
+    uint32_t* list = buf;
     if (rescued) {
-        for (auto& m : c->mm_scratch)
-            if (m.stream == st) list = m.buf;
+        if (const StreamScratch::Buf* m = c->mm_list.find(st)) list = reinterpret_cast<uint32_t*>(m->buf);
     } else {
         hipError_t e = qd_launch_compact(codes, n, list, st);
         if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("unknown tally list: ") + hipGetErrorString(e));
@@ -575,16 +660,12 @@ int launch_unknown(qd_ctx* c, int64_t n, const qd_rows* rows, const uint16_t* co
     }
     p.codes = codes;
     p.miss = list;
-    p.where = sc->buf + 4 + sc->pairs;
-    p.t = c->uk;
-    p.t.tag_mask = c->uk_tag_bits >= 64 ? ~0ull : ((1ull << c->uk_tag_bits) - 1);
+    p.where = buf + 4 + sc->units;
+    p.t = tally_view(c->uk);
     p.n = n;
-    hipError_t e = qd_launch_unknown(p, c->cu, c->uk_recorded && c->uk_last != st ? c->uk_done : nullptr, st);
+    hipError_t e = qd_launch_unknown(p, c->cu, tally_before(c->uk, st), st);
     if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("unknown tally launch: ") + hipGetErrorString(e));
-    HIPCHK(c, hipEventRecord(c->uk_done, st));
-    c->uk_recorded = true;
-    c->uk_last = st;
-    return QD_OK;
+    return tally_after(c, c->uk, st);
 }
 
 // the quality counters off and their table freed (the caller waited for the context's work)
@@ -628,15 +709,9 @@ void free_filter(qd_ctx* c) {
 // the duplication tally off and its memory freed (the caller waited for the context's work)
 void free_dup(qd_ctx* c) {
     table_free(c->d_dup);
-    if (c->d_dup_keys) (void)hipFree(c->d_dup_keys);
-    c->d_dup_keys = nullptr;
+    tally_close(c->dup_keys);
     c->dup = qd_dup_params{0, 0, 0};
     c->dup_dev = qd_dup_dev{0, 0};
-    c->dup_recorded = false;
-    for (auto& m : c->dup_scratch) (void)hipFree(m.buf);
-    c->dup_scratch.clear();
-    if (c->dup_done) (void)hipEventDestroy(c->dup_done);
-    c->dup_done = nullptr;
 }
 
 // (re)build the device table from the host barcodes and the current plan
@@ -907,7 +982,7 @@ int launch(qd_ctx* c, int64_t n, const qd_rows* rows, uint16_t* codes, uint8_t* 
         const int r = launch_mismatch(c, n, rows, codes, st);
         if (r != QD_OK) return r;
     }
-    if (c->uk_slots) {  // opt-in tally of the pairs that stay undetermined, behind the rescue
+    if (c->uk.mem) {  // opt-in tally of the pairs that stay undetermined, behind the rescue
         const int r = launch_unknown(c, n, rows, codes, st, c->mm_m1 + c->mm_m2 > 0);
         if (r != QD_OK) return r;
     }
@@ -1018,7 +1093,7 @@ int qd_set_plan(qd_ctx* c, const qd_plan* plan) {
     if (r != QD_OK) return fail(c, r, "plan rejected: positions must satisfy 0 <= start <= end <= 255, window <= 64, "
                                        "fused barcode <= 32, 0 <= minimal_qual <= 40");
     if (!c->slots.empty()) return fail(c, QD_ERR_STATE, "destroy the slots before changing the plan");
-    if (c->mm_m1 + c->mm_m2 > 0 || c->uk_slots || c->d_qs || c->d_filter || c->d_dup) {  // a new plan resets the mismatch budgets and turns the unknown tally, the quality counters, the read filter and the duplication tally off
+    if (c->mm_m1 + c->mm_m2 > 0 || c->uk.mem || c->d_qs || c->d_filter || c->d_dup) {  // a new plan resets the mismatch budgets and turns the unknown tally, the quality counters, the read filter and the duplication tally off
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, wait_all(c));
         free_mismatch(c, false);
@@ -1060,7 +1135,7 @@ int qd_set_barcodes(qd_ctx* c, int32_t S, const uint8_t* barcodes, const int32_t
     if (!c->have_plan) return fail(c, QD_ERR_STATE, "qd_set_plan first");
     for (int i = 0; i < S; ++i)
         if (offsets[i + 1] < offsets[i]) return fail(c, QD_ERR_INVALID, "offsets must be non-decreasing");
-    if (c->mm_m1 + c->mm_m2 > 0 || c->uk_slots || c->d_qs || c->d_filter || c->d_dup) {  // new barcodes reset the mismatch budgets, as they reset the counters, and turn the unknown tally, the quality counters, the read filter and the duplication tally off
+    if (c->mm_m1 + c->mm_m2 > 0 || c->uk.mem || c->d_qs || c->d_filter || c->d_dup) {  // new barcodes reset the mismatch budgets, as they reset the counters, and turn the unknown tally, the quality counters, the read filter and the duplication tally off
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, wait_all(c));
         free_mismatch(c, false);
@@ -1134,66 +1209,32 @@ int qd_set_mismatches(qd_ctx* c, int32_t m1, int32_t m2) {
 int qd_unknown_enable(qd_ctx* c, int64_t slots) {
     if (!c) return QD_ERR_INVALID;
     if (!c->have_plan || !c->have_table) return fail(c, QD_ERR_STATE, "qd_set_plan and qd_set_barcodes first");
-    if (slots != 0 && (slots < ((int64_t)1 << QD_UK_MIN_LG) || slots > ((int64_t)1 << QD_UK_MAX_LG) || (slots & (slots - 1))))
+    if (slots != 0 && !tally_slots_ok(slots))
         return fail(c, QD_ERR_INVALID, "unknown-barcode slots must be 0 (off) or a power of two in 2^10 .. 2^28");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, wait_all(c));  // nothing of this context may still use the old table
     free_unknown(c);
     if (slots == 0) return QD_OK;
-    hipError_t e = uk_malloc(&c->d_uk, qd_uk_bytes(slots));
-    if (e != hipSuccess) {
-        c->d_uk = nullptr;
-        return fail(c, QD_ERR_HIP, std::string("unknown-barcode table: ") + hipGetErrorString(e));
-    }
-    HIPCHK(c, hipMemsetAsync(c->d_uk, 0, qd_uk_bytes(slots), c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipEventCreateWithFlags(&c->uk_done, hipEventDisableTiming));
-    qd_uk_carve(c->d_uk, slots, c->uk);
-    c->uk_slots = slots;
-    return QD_OK;
+    return tally_open(c, c->uk, slots, "unknown-barcode table");
 }
 
 int qd_unknown_stats(qd_ctx* c, uint64_t out[4]) {
     if (!c || !out) return QD_ERR_INVALID;
-    if (!c->uk_slots) return fail(c, QD_ERR_STATE, "the unknown-barcode tally is not enabled");
+    if (!c->uk.mem) return fail(c, QD_ERR_STATE, "the unknown-barcode tally is not enabled");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, wait_all(c));
-    HIPCHK(c, hipMemcpy(out, c->uk.totals, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out, c->uk.t.totals, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return QD_OK;
 }
 
 int64_t qd_unknown_read(qd_ctx* c, uint8_t* keys, uint64_t* counts, int64_t cap) {
     auto bad = [&](int code, const std::string& msg) { return QD_UNKNOWN_READ_ERROR + (int64_t)fail(c, code, msg); };
     if (!c || cap < 0 || (cap > 0 && (!keys || !counts))) return bad(QD_ERR_INVALID, "bad arguments");
-    if (!c->uk_slots) return bad(QD_ERR_STATE, "the unknown-barcode tally is not enabled");
-    uint64_t tot[4];
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = wait_all(c);
-    if (e == hipSuccess) e = hipMemcpy(tot, c->uk.totals, sizeof tot, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return bad(QD_ERR_HIP, std::string("unknown-barcode read: ") + hipGetErrorString(e));
-    const int64_t D = (int64_t)tot[QD_UK_DISTINCT];
-    if (D > cap) return -D;
-    if (D == 0) return 0;
-    // the occupied entries packed on the device: only they cross the link
-    uint8_t* d_out = nullptr;
-    const size_t kbytes = (size_t)D * QD_KEY_WORDS * 8, cbytes = (size_t)D * 8;
-    if ((e = uk_malloc(reinterpret_cast<void**>(&d_out), kbytes + cbytes + 16)) != hipSuccess)
-        return bad(QD_ERR_HIP, std::string("unknown-barcode read: ") + hipGetErrorString(e));
-    u64* d_keys = reinterpret_cast<u64*>(d_out);
-    u64* d_counts = reinterpret_cast<u64*>(d_out + kbytes);
-    uint32_t* d_n = reinterpret_cast<uint32_t*>(d_out + kbytes + cbytes);
-    std::vector<u64> hk((size_t)D * QD_KEY_WORDS);
-    uint32_t got = 0;
-    e = qd_launch_unknown_gather(c->uk, d_keys, d_counts, d_n, (uint32_t)D, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(hk.data(), d_keys, kbytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, cbytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&got, d_n, 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_out);
-    if (e != hipSuccess) return bad(QD_ERR_HIP, std::string("unknown-barcode read: ") + hipGetErrorString(e));
-    if ((int64_t)got != D) return bad(QD_ERR_HIP, "unknown-barcode read: the table's entry count and its occupied entries differ");
+    if (!c->uk.mem) return bad(QD_ERR_STATE, "the unknown-barcode tally is not enabled");
+    std::vector<u64> hk;
+    const int64_t D = tally_gather(c, c->uk, "unknown-barcode", cap, hk, counts);
     const int K = c->lay.key_width;
-    for (int64_t i = 0; i < D; ++i)
+    for (int64_t i = 0; i < D; ++i)  // (D <= 0: nothing was gathered)
         for (int b = 0; b < K; ++b) keys[i * K + b] = (uint8_t)(hk[(size_t)i * QD_KEY_WORDS + (b >> 3)] >> (8 * (b & 7)));
     return D;
 }
@@ -1638,8 +1679,7 @@ int qd_dup_set(qd_ctx* c, const qd_dup_params* params) {
         const qd_dup_params& P = *params;
         if (P.bases < 8 || P.bases > 32) return fail(c, QD_ERR_INVALID, "duplication bases: 8 to 32");
         if (P.sample < 1 || P.sample > 1024 || (P.sample & (P.sample - 1))) return fail(c, QD_ERR_INVALID, "duplication sample: a power of two, 1 to 1024");
-        if (P.slots < ((int64_t)1 << QD_UK_MIN_LG) || P.slots > ((int64_t)1 << QD_UK_MAX_LG) || (P.slots & (P.slots - 1)))
-            return fail(c, QD_ERR_INVALID, "duplication slots: a power of two in 2^10 .. 2^28");
+        if (!tally_slots_ok(P.slots)) return fail(c, QD_ERR_INVALID, "duplication slots: a power of two in 2^10 .. 2^28");
         while ((1 << sample_lg) < P.sample) ++sample_lg;
         if (!c->have_plan || !c->have_table) return fail(c, QD_ERR_STATE, "qd_set_plan and qd_set_barcodes first");
     }
@@ -1648,16 +1688,11 @@ int qd_dup_set(qd_ctx* c, const qd_dup_params* params) {
     free_dup(c);
     if (!params) return QD_OK;
     int rc = table_alloc(c, c->d_dup, qd_dup_values((uint32_t)c->S), "duplication counters");
-    if (rc != QD_OK) return rc;
-    hipError_t e = uk_malloc(&c->d_dup_keys, qd_uk_bytes(params->slots));
-    if (e == hipSuccess) e = hipMemsetAsync(c->d_dup_keys, 0, qd_uk_bytes(params->slots), c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->dup_done, hipEventDisableTiming);
-    if (e != hipSuccess) {
+    if (rc == QD_OK) rc = tally_open(c, c->dup_keys, params->slots, "duplication table");
+    if (rc != QD_OK) {
         free_dup(c);
-        return fail(c, QD_ERR_HIP, std::string("duplication table: ") + hipGetErrorString(e));
+        return rc;
     }
-    qd_uk_carve(c->d_dup_keys, params->slots, c->dup_t);
     c->dup = *params;
     c->dup_dev = qd_dup_dev{params->bases, sample_lg};
     return QD_OK;
@@ -1675,8 +1710,8 @@ int qd_stream_retired(qd_ctx* c, void* stream) {
     if (!c) return QD_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
     forget_stream(c, st);  // (the caller waited for the stream: nothing of it is outstanding)
-    if (c->uk_last == st) c->uk_recorded = false;
-    if (c->dup_last == st) c->dup_recorded = false;
+    tally_retired(c->uk, st);
+    tally_retired(c->dup_keys, st);
     return QD_OK;
 }
 
@@ -1689,33 +1724,9 @@ int64_t qd_dup_read(qd_ctx* c, uint64_t* keys, uint64_t* counts, int64_t cap) {
     auto bad = [&](int code, const std::string& msg) { return QD_DUP_READ_ERROR + (int64_t)fail(c, code, msg); };
     if (!c || cap < 0 || (cap > 0 && (!keys || !counts))) return bad(QD_ERR_INVALID, "bad arguments");
     if (!c->d_dup) return bad(QD_ERR_STATE, "the duplication tally is not on");
-    uint64_t tot[4];
-    hipError_t e = hipSetDevice(c->device);
-    if (e == hipSuccess) e = wait_all(c);
-    if (e == hipSuccess) e = hipMemcpy(tot, c->dup_t.totals, sizeof tot, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return bad(QD_ERR_HIP, std::string("duplication read: ") + hipGetErrorString(e));
-    const int64_t D = (int64_t)tot[QD_UK_DISTINCT];
-    if (D > cap) return -D;
-    if (D == 0) return 0;
-    // the occupied entries packed on the device (the unknown tally's gather: it works on the table alone): only they cross the link
-    uint8_t* d_out = nullptr;
-    const size_t kbytes = (size_t)D * QD_KEY_WORDS * 8, cbytes = (size_t)D * 8;
-    if ((e = uk_malloc(reinterpret_cast<void**>(&d_out), kbytes + cbytes + 16)) != hipSuccess)
-        return bad(QD_ERR_HIP, std::string("duplication read: ") + hipGetErrorString(e));
-    u64* d_keys = reinterpret_cast<u64*>(d_out);
-    u64* d_counts = reinterpret_cast<u64*>(d_out + kbytes);
-    uint32_t* d_n = reinterpret_cast<uint32_t*>(d_out + kbytes + cbytes);
-    std::vector<u64> hk((size_t)D * QD_KEY_WORDS);
-    uint32_t got = 0;
-    e = qd_launch_unknown_gather(c->dup_t, d_keys, d_counts, d_n, (uint32_t)D, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(hk.data(), d_keys, kbytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, cbytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&got, d_n, 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_out);
-    if (e != hipSuccess) return bad(QD_ERR_HIP, std::string("duplication read: ") + hipGetErrorString(e));
-    if ((int64_t)got != D) return bad(QD_ERR_HIP, "duplication read: the table's entry count and its occupied entries differ");
-    for (int64_t i = 0; i < D; ++i)
+    std::vector<u64> hk;
+    const int64_t D = tally_gather(c, c->dup_keys, "duplication", cap, hk, counts);
+    for (int64_t i = 0; i < D; ++i)  // (D <= 0: nothing was gathered)
         for (int q = 0; q < QD_DUP_KEY_WORDS; ++q) keys[i * QD_DUP_KEY_WORDS + q] = hk[(size_t)i * QD_KEY_WORDS + q];
     return D;
 }
@@ -1725,22 +1736,8 @@ int qd_dup_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const ui
     if (!c) return QD_ERR_INVALID;
     if (!c->d_dup || !n) return QD_OK;
     hipStream_t st = resolve_stream(c, stream);
-    qd_ctx::DupScratch* sc = nullptr;
-    for (auto& m : c->dup_scratch)
-        if (m.stream == st) sc = &m;
-    if (!sc) {
-        c->dup_scratch.push_back(qd_ctx::DupScratch{st, nullptr, 0});
-        sc = &c->dup_scratch.back();
-    }
-    if (sc->pairs < (size_t)n) {
-        HIPCHK(c, hipStreamSynchronize(st));  // the old list may still be read by this stream's previous batch
-        if (sc->buf) (void)hipFree(sc->buf);
-        sc->buf = nullptr;
-        const size_t pairs = std::max<size_t>((size_t)n, sc->pairs * 2);
-        sc->pairs = 0;
-        HIPCHK(c, uk_malloc(reinterpret_cast<void**>(&sc->buf), qd_dup_list_bytes(pairs)));
-        sc->pairs = pairs;
-    }
+    StreamScratch::Buf* sc = c->dup_keys.scratch.need(c, st, n, qd_dup_list_bytes);
+    if (!sc) return QD_ERR_HIP;
     qd_dup_args a{};
     fill_pair_args(a, text1, recs1, text2, recs2);
     a.codes = codes;
@@ -1748,14 +1745,12 @@ int qd_dup_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const ui
     a.table = c->d_dup;
     a.list_n = reinterpret_cast<uint32_t*>(sc->buf);
     a.list = reinterpret_cast<uint64_t*>(sc->buf + QD_DUP_LIST_HEAD);
-    a.where = reinterpret_cast<uint32_t*>(sc->buf + QD_DUP_LIST_HEAD + sc->pairs * QD_DUP_KEY_WORDS * 8);
-    a.t = c->dup_t;
-    a.t.tag_mask = c->dup_tag_bits >= 64 ? ~0ull : ((1ull << c->dup_tag_bits) - 1);
-    hipError_t e = qd_dup_launch(c->dup_dev, a, (uint32_t)c->S, n, c->cu, c->dup_recorded && c->dup_last != st ? c->dup_done : nullptr, st);
+    a.where = reinterpret_cast<uint32_t*>(sc->buf + QD_DUP_LIST_HEAD + sc->units * QD_DUP_KEY_WORDS * 8);
+    a.t = tally_view(c->dup_keys);
+    hipError_t e = qd_dup_launch(c->dup_dev, a, (uint32_t)c->S, n, c->cu, tally_before(c->dup_keys, st), st);
     if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("duplication tally launch: ") + hipGetErrorString(e));
-    HIPCHK(c, hipEventRecord(c->dup_done, st));
-    c->dup_recorded = true;
-    c->dup_last = st;
+    const int rc = tally_after(c, c->dup_keys, st);
+    if (rc != QD_OK) return rc;
     HIPCHK(c, track(c, st));
     return QD_OK;
 }
@@ -1813,12 +1808,12 @@ int qd_set_option(qd_ctx* c, const char* name, int64_t value) {
     }
     if (!strcmp(name, "unknown_tag_bits")) {  // test knob: the tally keeps this many low bits of a key's tag (default 64), so tag collisions can be made
         if (value < 1 || value > 64) return fail(c, QD_ERR_INVALID, "unknown_tag_bits must be 1..64");
-        c->uk_tag_bits = (int)value;
+        c->uk.tag_bits = (int)value;
         return QD_OK;
     }
     if (!strcmp(name, "dup_tag_bits")) {  // test knob: the same for the duplication tally's table
         if (value < 1 || value > 64) return fail(c, QD_ERR_INVALID, "dup_tag_bits must be 1..64");
-        c->dup_tag_bits = (int)value;
+        c->dup_keys.tag_bits = (int)value;
         return QD_OK;
     }
     return fail(c, QD_ERR_INVALID, std::string("unknown option ") + name);
@@ -1929,7 +1924,7 @@ int qd_reset_counts(qd_ctx* c) {
     HIPCHK(c, join_into_own_stream(c));
     HIPCHK(c, hipMemsetAsync(c->d_partial, 0,(size_t)c->partial_rows * c->cnt_stride * sizeof(qd_row_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_acc, 0, (size_t)c->cnt_stride * 8, c->stream));
-    if (c->uk_slots) HIPCHK(c, hipMemsetAsync(c->d_uk, 0, qd_uk_bytes(c->uk_slots), c->stream));  // sum(counts) + short + dropped == UNDETERMINED stays true
+    if (c->uk.mem) HIPCHK(c, tally_zero(c->uk, c->stream));  // sum(counts) + short + dropped == UNDETERMINED stays true
     if (c->d_qs) HIPCHK(c, hipMemsetAsync(c->d_qs, 0, qd_qstats_values((uint32_t)c->S) * 8, c->stream));  // records stay equal to the pair counters
     if (c->d_cs) HIPCHK(c, hipMemsetAsync(c->d_cs, 0, (size_t)QD_CS_VALUES * 8, c->stream));
     if (c->d_clip) HIPCHK(c, hipMemsetAsync(c->d_clip, 0, QD_CLIP_TABLE * 8, c->stream));
@@ -1938,7 +1933,7 @@ int qd_reset_counts(qd_ctx* c) {
     if (c->d_filter) HIPCHK(c, hipMemsetAsync(c->d_filter, 0, qd_filter_values((uint32_t)c->S) * 8, c->stream));
     if (c->d_dup) {  // both tables: sampled == tallied + not_tallied stays true
         HIPCHK(c, hipMemsetAsync(c->d_dup, 0, qd_dup_values((uint32_t)c->S) * 8, c->stream));
-        HIPCHK(c, hipMemsetAsync(c->d_dup_keys, 0, qd_uk_bytes(c->dup.slots), c->stream));
+        HIPCHK(c, tally_zero(c->dup_keys, c->stream));
     }
     HIPCHK(c, track(c, c->stream));  // later launches on other streams are not ordered behind this: wait here
     HIPCHK(c, hipStreamSynchronize(c->stream));

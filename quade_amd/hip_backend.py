@@ -450,6 +450,14 @@ def check_mismatch_collisions(barcodes, key_width, w1, m1, m2):
     return None
 
 
+def _merge_keyed(keys, counts):
+    """Key rows [n, w] with one count each -> (the distinct rows ascending, per row the sum of its counts as uint64)."""
+    uniq, inv = np.unique(keys, axis=0, return_inverse=True)
+    total = np.zeros(uniq.shape[0], dtype=np.uint64)
+    np.add.at(total, inv.reshape(-1), counts)
+    return uniq, total
+
+
 def merge_unknown(tables):
     """Host: unknown-barcode tables (keys uint8[n, K], counts uint64[n]) of several contexts or ranks -> one table with the counts
     of equal keys summed, in report order: count descending, then key bytes ascending.  Returns (keys, counts)."""
@@ -459,11 +467,7 @@ def merge_unknown(tables):
         return np.zeros((0, 0), dtype=np.uint8), np.zeros(0, dtype=np.uint64)
     K = tables[0][0].shape[1]
     assert all(k.shape[1] == K for k, _ in tables), "tables of different key widths"
-    keys = np.concatenate([k for k, _ in tables])
-    counts = np.concatenate([c for _, c in tables])
-    uniq, inv = np.unique(keys, axis=0, return_inverse=True)  # rows ascending by bytes
-    total = np.zeros(uniq.shape[0], dtype=np.uint64)
-    np.add.at(total, inv.reshape(-1), counts)
+    uniq, total = _merge_keyed(np.concatenate([k for k, _ in tables]), np.concatenate([c for _, c in tables]))
     order = np.argsort(-total.astype(np.int64), kind="stable")
     return np.ascontiguousarray(uniq[order]), total[order]
 
@@ -494,11 +498,7 @@ def merge_dup(tables):
         return np.zeros((0, 3), dtype=np.uint64), np.zeros(0, dtype=np.uint64)
     if len(tables) == 1:
         return tables[0]
-    keys = np.concatenate([k for k, _ in tables])
-    counts = np.concatenate([c for _, c in tables])
-    uniq, inv = np.unique(keys[:, [2, 0, 1]], axis=0, return_inverse=True)
-    total = np.zeros(uniq.shape[0], dtype=np.uint64)
-    np.add.at(total, inv.reshape(-1), counts)
+    uniq, total = _merge_keyed(np.concatenate([k for k, _ in tables])[:, [2, 0, 1]], np.concatenate([c for _, c in tables]))
     return np.ascontiguousarray(uniq[:, [1, 2, 0]]), total
 
 
@@ -613,21 +613,25 @@ class Engine(object):
         self._chk(self.lib.qd_unknown_stats(self._h, _ptr(out)))
         return out
 
-    def unknown_read(self):
-        """The table's entries in no particular order: (keys uint8[n, key_width], counts uint64[n])."""
-        K = self.layout.key_width if self.layout is not None else 0
-        n = self.lib.qd_unknown_read(self._h, None, None, 0)
+    def _tally_read(self, fn, width, dtype):
+        """A key tally's entries through its qd_*_read entry `fn` (one sizing protocol: asked for the size, then read with that
+        room until the table has not grown meanwhile): (keys dtype[n, width], counts uint64[n])."""
+        n = fn(self._h, None, None, 0)
         while True:
             if n <= QD_UNKNOWN_READ_ERROR:
                 self._chk(int(n - QD_UNKNOWN_READ_ERROR))
             if n == 0:
-                return np.zeros((0, K), dtype=np.uint8), np.zeros(0, dtype=np.uint64)
+                return np.zeros((0, width), dtype=dtype), np.zeros(0, dtype=np.uint64)
             cap = int(-n)
-            keys = np.zeros((cap, K), dtype=np.uint8)
+            keys = np.zeros((cap, width), dtype=dtype)
             counts = np.zeros(cap, dtype=np.uint64)
-            n = self.lib.qd_unknown_read(self._h, _ptr(keys), _ptr(counts), cap)
+            n = fn(self._h, _ptr(keys), _ptr(counts), cap)
             if n > 0:
                 return keys[:n], counts[:n]
+
+    def unknown_read(self):
+        """The table's entries in no particular order: (keys uint8[n, key_width], counts uint64[n])."""
+        return self._tally_read(self.lib.qd_unknown_read, self.layout.key_width if self.layout is not None else 0, np.uint8)
 
     # -- the read stages: what their dev_* and *_add methods share
     @staticmethod
@@ -887,18 +891,7 @@ class Engine(object):
 
     def dup_read(self):
         """The key table's entries in no particular order: (keys uint64[n, 3] = (w1, w2, d), counts uint64[n])."""
-        n = self.lib.qd_dup_read(self._h, None, None, 0)
-        while True:
-            if n <= QD_DUP_READ_ERROR:
-                self._chk(int(n - QD_DUP_READ_ERROR))
-            if n == 0:
-                return np.zeros((0, 3), dtype=np.uint64), np.zeros(0, dtype=np.uint64)
-            cap = int(-n)
-            keys = np.zeros((cap, 3), dtype=np.uint64)
-            counts = np.zeros(cap, dtype=np.uint64)
-            n = self.lib.qd_dup_read(self._h, _ptr(keys), _ptr(counts), cap)
-            if n > 0:
-                return keys[:n], counts[:n]
+        return self._tally_read(self.lib.qd_dup_read, 3, np.uint64)
 
     def dev_dup(self, text1, recs1, text2, recs2, codes, drop=None):
         """The duplication tally over host buffers (qd_dev_dup): texts as bytes or uint8 arrays, recs uint32[n, 6] in

@@ -194,6 +194,21 @@ def test_two_calls_equal_the_model_of_their_union_and_reset(torch_cuda):
         _check_exact(eng, *b.model(P))
 
 
+def test_a_growing_second_call_equals_the_model_of_the_union(torch_cuda):
+    """333 pairs, then 5 000: the second call's batch list is more than twice the first's, so the stream's list is freed and allocated
+    again behind the first call's kernels; the key table and the counters carry over."""
+    a, b = Stage(22, 24, 333), Stage(23, 24, 5000)
+    b.cases[:50] = a.cases[:50]  # keys of the first call come again in the second
+    b = Stage(23, 24, 5000, cases=b.cases)
+    P = DM.Params(24, 2, SLOTS)
+    with _engine(**P.keywords()) as eng:
+        a.run(eng)
+        b.run(eng)
+        model, model_stats = DM.tally(S_STAGE, a.cases + b.cases, P)
+        _check_exact(eng, model, model_stats)  # (sampled == tallied + not_tallied per destination is part of it)
+        assert any(model[k] > a.model(P)[0][k] > 0 for k in model)
+
+
 def test_state_and_errors(torch_cuda):
     st = Stage(30, 32, 64)
     P = DM.Params(32, 1, 1 << 12)

@@ -255,6 +255,45 @@ def test_rescued_pairs_are_not_tallied(torch_cuda, engine, monkeypatch):
     UM.check_exact(table, stats, model0, short0, engine.counts()[3])
 
 
+def test_growing_batches_on_two_streams_with_the_rescue(torch_cuda, engine, monkeypatch):
+    """Batches of 300, 5 000, 700 and 9 000 pairs alternate over two caller streams with budgets (1, 1): on either stream the second
+    batch is more than the first one's rescue list and tally scratch hold (700 > 300, 9 000 > 5 000), so both are freed and
+    allocated again behind that stream's work, and the tally reads the rescue's new list."""
+    torch = torch_cuda
+    from tests.mismatch_support import SHAPES, make_reads, rows_on_device, sheet
+    sizes = (300, 5000, 700, 9000)
+    n = sum(sizes)
+    bcs = sheet("dual8", 64, 1, 1)
+    streams = make_reads("dual8", bcs, n, 1, 1, seed=47, short_frac=0.05)
+    plan = SHAPES["dual8"][0]
+    reads = []
+    for s, q in streams:
+        reads += [[x.decode() for x in s], [x.decode() for x in q]]
+    monkeypatch.setattr(qo, "SampleSet", MM.tolerant_sampleset(qo, 16, 8, 1, 1))
+    codes_o, idx_o, _, counts_o = H.oracle_on_reads(bcs, plan, *reads)
+    monkeypatch.undo()
+    model, short = UM.model_from_oracle(codes_o, idx_o, 16)
+    assert sum(model.values()) > 0 and short > 0
+    engine.set_plan(plan)
+    engine.set_barcodes(bcs)
+    engine.set_mismatches(1, 1)
+    engine.unknown_enable(1 << 16)
+    seq, qual, lens, full = rows_on_device(torch, engine.layout, streams)
+    assert not full
+    cuda_streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    keep, a = [], 0
+    for i, m in enumerate(sizes):
+        cut = lambda ts: [t[a:a + m] for t in ts]  # noqa: E731
+        keep.append(launch(torch, engine, cut(seq), cut(qual), m, lens=cut(lens), stream=cuda_streams[i % 2].cuda_stream))
+        a += m
+    engine.synchronize()
+    assert (np.concatenate([np_codes(c, m) for (c, _), m in zip(keep, sizes)]) == codes_o).all()
+    counts = engine.counts()
+    assert (counts == counts_o).all()
+    table, stats = read_table(engine)
+    UM.check_exact(table, stats, model, short, counts[3])
+
+
 # ---- 4. no side effects, state ------------------------------------------------------------------------------------------------
 def test_no_side_effects_and_state(torch_cuda):
     torch = torch_cuda
