@@ -386,6 +386,52 @@ int qd_pairtrim_get(const qd_ctx* ctx, qd_pairtrim_params* out);
 int qd_pairtrim_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
 int qd_pairtrim_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
 
+/* ---- post-trimming of the insert reads: trailing N, a poly-X tail and a crop to max_length (opt-in; no reference counterpart:
+ * Quade 0.3.2 writes the insert reads as they came) -----------------------------------------------------------------------------
+ * One stage behind the clip, 3' trimming and overlap trimming stages above and in front of the read filter below, where fastp runs
+ * trim_poly_x and max_len1 / max_len2 and cutadapt --trim-n: a poly-A tail sits between the insert and the adapter and shows only
+ * once the adapter is gone.  For an insert read r (0 = R1, 1 = R2), take the record the stage receives, that is, what clip, trim and
+ * pairtrim left: sequence bytes s, length L; u(b) = b & 0xDF; P = poly_x_min_length; M_r = max_length[r].  Each of steps 1 to 3 is
+ * skipped when not configured; its output length is then its input length.
+ *   1 trailing N (tail_n = 1): Ln = L - k, where k is the number of consecutive bytes at the 3' end with u(b) == 'N'
+ *   2 poly-X (P > 0; 6..100): for each X in A, C, G, T, Lx(X) is the clip stage's step 3 exactly as stated above for poly-G, with
+ *     X in place of 'G', over s[0 .. Ln).  Lp = min over X of Lx(X).  The read's tail base is the X with Lx(X) < Ln; at most one
+ *     such X exists (a walk alive at t = P has at most P / 8 mismatches among the last P bytes, and every byte mismatches all bases
+ *     but one).  N and every other byte count as a mismatch.  One pass only: a T run behind an A run loses the T run
+ *   3 crop (M_r > 0): Lm = min(Lp, M_r)
+ *   4 floor: Lout = max(Lm, min(min_length, L)), min_length being the 3' trimming's
+ * and the read's record becomes seq_len = Lout; its other fields stay.  The stage never moves seq or qual and never drops a pair;
+ * index reads, names and the :IDX[:MOL] tag never change.  Only the sequence line is read.  With the stage on, qd_pipe_run runs it
+ * over every pair it routes (one launch per batch on its compute stream, no host sync) directly behind the overlap trimming, so that
+ * the read filter, the quality and cycle counters, the duplication tally and the output stages all see the post-trimmed reads, and
+ * adds to a device table uint64[2][16] (R1, R2), whatever the write flags say:
+ *   0 reads   1 bases_in (sum of L)   2 bases_out (sum of Lout)   3 n_tail_reads (Ln < L)   4 n_tail_bases (sum of L - Ln)
+ *   5 polya_reads (tail base A)   6 polya_bases (sum of Ln - Lp for tail base A)   7 polyc_reads   8 polyc_bases   9 polyg_reads
+ *   10 polyg_bases   11 polyt_reads   12 polyt_bases   13 cropped_reads (Lm < Lp)   14 cropped_bases (sum of Lp - Lm)
+ *   15 floored_reads (Lout > Lm)
+ * Off, nothing is allocated or launched.
+ *
+ * qd_posttrim_set: NULL, or every rule off (tail_n 0, poly_x_min_length 0, both max_length 0), turns the stage off and frees the
+ * table; otherwise the values are checked (tail_n 0 or 1, poly_x_min_length 0 = off or 6..100, max_length 0 = off or 1..65535,
+ * min_length 0..65535: QD_ERR_INVALID, the state as before) and a zeroed table allocated.  Waits for the context's outstanding
+ * work.  Independent of plan, barcodes and the other stages' setters.
+ * qd_posttrim_get: the parameters in force (all zero and QD_OK when off).
+ * qd_posttrim_read: waits for the context's work, writes n_values = 32 values (QD_ERR_INVALID on another size, QD_ERR_STATE when
+ * off).
+ * qd_posttrim_add: another context's table (qd_posttrim_read's layout) joins this one's, as qd_clip_add does.  qd_reset_counts
+ * zeroes the table. */
+#define QD_POSTTRIM_VALUES 32
+typedef struct qd_posttrim_params {
+    int32_t tail_n;            /* 1 = cut trailing N */
+    int32_t poly_x_min_length; /* 0 = off */
+    int32_t max_length[2];     /* R1, R2; 0 = off */
+    int32_t min_length;
+} qd_posttrim_params;
+int qd_posttrim_set(qd_ctx* ctx, const qd_posttrim_params* params);
+int qd_posttrim_get(const qd_ctx* ctx, qd_posttrim_params* out);
+int qd_posttrim_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
+int qd_posttrim_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
+
 /* ---- read filtering of the insert reads: length, N, quality, complexity (opt-in; no reference counterpart: Quade 0.3.2 writes
  * every pair it assigns) ----------------------------------------------------------------------------------------------------
  * The step cutadapt and fastp run directly behind trimming: discard the pairs that are not worth keeping, pair-aware, and say
@@ -964,6 +1010,13 @@ int qd_dev_trim(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t*
  * record's sequence and quality range is checked against len1 / len2 before anything is launched: QD_ERR_INVALID.  QD_ERR_STATE
  * when the stage is off.  Returns when the launch has finished. */
 int qd_dev_pairtrim(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+                    const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2);
+/* the post-trimming stage (qd_posttrim_set above; no reference counterpart) over host buffers, as qd_dev_trim: reads [0, n_pairs)
+ * of two texts with their record tables are uploaded (the texts 3 bytes off alignment) and run through the kernel qd_pipe_run
+ * launches; out_recs1 / out_recs2 receive the tables with every seq_len replaced by the length the read keeps, and the context's
+ * table grows.  Every record's sequence and quality range is checked against len1 / len2 before anything is launched:
+ * QD_ERR_INVALID.  QD_ERR_STATE when the stage is off.  Returns when the launch has finished. */
+int qd_dev_posttrim(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                     const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2);
 /* the read filter (qd_filter_set above; no reference counterpart) over host buffers, as qd_dev_qstats: pairs [0, n_pairs) of two
  * texts with their record tables and routing codes are uploaded (the texts 3 bytes off alignment) and run through the kernel

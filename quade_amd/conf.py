@@ -7,7 +7,7 @@ file written by `-i` is the reference's template byte for byte (src/Conf_file.py
 package data, quade_amd/data/Quade_conf_file.txt).  An optional [gpu] section that reference conf
 files simply do not have is read when present (defaults apply otherwise; see GPU_SECTION_HELP), and so are the optional
 mismatch budgets of the [index] section (MISMATCH_HELP), the unknown-barcode report (UNKNOWN_HELP) and the quality report
-(QUALITY_HELP), the per-cycle report (CYCLE_HELP) and the duplication report (DUPLICATION_HELP) of the [output] section, an optional [trim] section (CLIP_HELP, TRIM_HELP, PAIR_HELP) and an optional [filter] section
+(QUALITY_HELP), the per-cycle report (CYCLE_HELP) and the duplication report (DUPLICATION_HELP) of the [output] section, an optional [trim] section (CLIP_HELP, TRIM_HELP, PAIR_HELP, POSTTRIM_HELP) and an optional [filter] section
 (FILTER_HELP).
 """
 from __future__ import annotations
@@ -196,6 +196,39 @@ PAIR_OVERLAP = "Authorized values for pair_min_overlap : 8 to 1000"
 PAIR_MISMATCHES = "Authorized values for pair_max_mismatches : 0 to 64"
 PAIR_MISMATCH_PCT = "Authorized values for pair_max_mismatch_pct : 0 to 50"
 
+POSTTRIM_HELP = """\
+Optional [trim] options (not in Quade 0.3.2, whose parser ignores them; absent = as before): trailing-N, poly-X tail and
+max_length trimming of the insert reads on the GPU, behind the clipping, the 3' trimming and pair_overlap above and in front of
+[filter] (fastp's order: adapters, then trim_poly_x, then max_len1 / max_len2; cutadapt's --trim-n).  A poly-A tail sits between
+the insert and the adapter, so it shows only once the adapter is gone.  Index reads, names and the :IDX[:MOL] tag are never
+touched, no read is moved and no pair is dropped.  For an insert read r (0 = R1, 1 = R2), take the record the stage receives,
+that is, what clip, trim and pairtrim left: sequence bytes s, length L; u(b) = b & 0xDF; P = poly_x_min_length;
+M_r = max_length[r].  Each of steps 1 to 3 is skipped when not configured; its output length is then its input length.
+  tail_n : False            1 trailing N (tail_n : True): Ln = L - k, where k is the number of consecutive bytes at the 3' end
+                            with u(b) == 'N'
+  poly_x : False            2 poly-X (poly_x : True, P 6..100, default 10): for each X in A, C, G, T, Lx(X) is the clip stage's
+  poly_x_min_length : 10    step 3 exactly as include/quade_hip.h states it for poly-G, with X in place of 'G', over s[0 .. Ln)
+                            (walking from the 3' end, one base other than X per 8 is forgiven, at most 5, a run of at least P,
+                            cut at the leftmost X reached).  Lp = min over X of Lx(X).  The read's tail base is the X with
+                            Lx(X) < Ln; at most one such X exists.  N and every other byte count as a mismatch.  One pass only:
+                            a T run behind an A run loses the T run
+  max_length_R1 :           3 crop (M_r > 0, 1 to 65535; absent, empty or 0 = off): Lm = min(Lp, M_r)
+  max_length_R2 :
+                            4 floor: Lout = max(Lm, min(min_length, L)), min_length (above) being the [trim] section's
+The record becomes seq_len = Lout; its other fields stay.  The stage is on when tail_n or poly_x is True or a max_length is above
+0; poly_x_min_length alone switches nothing on.  Quade_post_trim_report.csv is then written next to the report.  These options
+turn neither the clipping nor the 3' trimming on.  [filter], quality_report, cycle_report, duplication_report and the output
+files see the reads as this stage left them.  min_length may not be above a max_length that is set.  The reads are trimmed while
+the device pipeline holds their text, so the options need the device pipeline: [gpu] device_pipeline, device_inflate and
+device_deflate True (the defaults) and gzip_level 1 or -1
+"""
+
+POSTTRIM_NEEDS = ("[trim] post-trimming (tail_n, poly_x, max_length) needs the device pipeline (device_pipeline, device_inflate, "
+                  "device_deflate : True and gzip_level 1 or -1)")
+POSTTRIM_POLY_X = "Authorized values for poly_x_min_length : 6 to 100"
+POSTTRIM_MAX_LENGTH = "Authorized values for max_length_R1 and max_length_R2 : 0 to 65535"
+POSTTRIM_FLOOR = "min_length may not be above a max_length_R1 or max_length_R2 that is set"
+
 FILTER_HELP = """\
 Optional [filter] section (not in Quade 0.3.2, whose parser ignores it; absent = every pair is written): discard pairs on the GPU,
 behind the [trim] stages and on what they left.  A pair is dropped, its R1 and its R2 record, for the first of these rules that
@@ -328,6 +361,11 @@ class QuadeConf(object):
         self.pair_min_overlap = trim("pair_min_overlap", 30)
         self.pair_max_mismatches = trim("pair_max_mismatches", 5)
         self.pair_max_mismatch_pct = trim("pair_max_mismatch_pct", 20)
+        # ... and what is trimmed behind all of that (POSTTRIM_HELP): a max_length of 0 = no crop
+        self.tail_n = trim("tail_n", False, lambda v: v.strip().lower() in ("true", "1", "yes", "on"))
+        self.poly_x = trim("poly_x", False, lambda v: v.strip().lower() in ("true", "1", "yes", "on"))
+        self.poly_x_min_length = trim("poly_x_min_length", 10)
+        self.max_length = (trim("max_length_R1", 0), trim("max_length_R2", 0))
 
         # optional per-cycle quality and base-content report (extension, CYCLE_HELP)
         self.cycle_report = False
@@ -426,6 +464,10 @@ class QuadeConf(object):
         assert 0 <= self.pair_max_mismatches <= 64, PAIR_MISMATCHES
         assert 0 <= self.pair_max_mismatch_pct <= 50, PAIR_MISMATCH_PCT
         assert not self.pair_trim or self.can_pipe, PAIR_NEEDS
+        assert 6 <= self.poly_x_min_length <= 100, POSTTRIM_POLY_X
+        assert all(0 <= m <= 65535 for m in self.max_length), POSTTRIM_MAX_LENGTH
+        assert all(self.min_length <= m for m in self.max_length if m), POSTTRIM_FLOOR
+        assert not self.posttrim or self.can_pipe, POSTTRIM_NEEDS
         for name, value in self.filter_params().items():
             assert value is None or FILTER_RANGES[name][0] <= value <= FILTER_RANGES[name][1], filter_range_message(name)
         assert not self.filter or self.can_pipe, FILTER_NEEDS
@@ -476,6 +518,16 @@ class QuadeConf(object):
         """what Engine.pairtrim_set takes"""
         return dict(min_overlap=self.pair_min_overlap, max_mismatches=self.pair_max_mismatches,
                     max_mismatch_pct=self.pair_max_mismatch_pct, min_length=self.min_length)
+
+    @property
+    def posttrim(self):
+        """trailing-N, poly-X or max_length trimming of the insert reads is on (POSTTRIM_HELP)"""
+        return bool(self.tail_n or self.poly_x or any(self.max_length))
+
+    def posttrim_params(self):
+        """what Engine.posttrim_set takes"""
+        return dict(tail_n=int(self.tail_n), poly_x_min_length=self.poly_x_min_length if self.poly_x else 0,
+                    max_length_r1=self.max_length[0], max_length_r2=self.max_length[1], min_length=self.min_length)
 
     @property
     def filter(self):

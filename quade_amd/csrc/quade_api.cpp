@@ -27,6 +27,7 @@
 #include "quade_clip.h"
 #include "quade_trim.h"
 #include "quade_pairtrim.h"
+#include "quade_posttrim.h"
 #include "quade_filter.h"
 #include "quade_dup.h"
 #include "quade_pool.h"
@@ -176,6 +177,12 @@ struct qd_ctx {
     qd_pairtrim_params pairtrim{};
     qd_pairtrim_dev pairtrim_dev{};
     u64* d_pairtrim = nullptr;
+
+    // trailing-N, poly-X and max_length trimming behind the three stages above (qd_posttrim_set): the parameters as given and as
+    // the kernel takes them, and the counters uint64[2][16]; d_posttrim == nullptr = off
+    qd_posttrim_params posttrim{};
+    qd_posttrim_dev posttrim_dev{};
+    u64* d_posttrim = nullptr;
 
     // read filtering (qd_filter_set): the parameters as given and as the kernel takes them, and the table
     // uint64[(2 * S + 1)][8]; d_filter == nullptr = off
@@ -481,7 +488,7 @@ int launch_mismatch(qd_ctx* c, int64_t n, const qd_rows* rows, uint16_t* codes, 
     return QD_OK;
 }
 
-// ---- the read stages (qstats, cstats, clip, trim, pairtrim, filter): their tables and the harness of their qd_dev_* entries ----
+// ---- the read stages (qstats, cstats, clip, trim, pairtrim, posttrim, filter): their tables and the harness of their qd_dev_* entries ----
 
 // a stage's table: n_values 64-bit counters on the device, zero
 int table_alloc(qd_ctx* c, u64*& t, size_t n_values, const char* what) {
@@ -697,6 +704,13 @@ void free_pairtrim(qd_ctx* c) {
     table_free(c->d_pairtrim);
     c->pairtrim = qd_pairtrim_params{};
     c->pairtrim_dev = qd_pairtrim_dev{};
+}
+
+// post-trimming off and its table freed (the caller waited for the context's work)
+void free_posttrim(qd_ctx* c) {
+    table_free(c->d_posttrim);
+    c->posttrim = qd_posttrim_params{};
+    c->posttrim_dev = qd_posttrim_dev{};
 }
 
 // read filtering off and its table freed (the caller waited for the context's work)
@@ -1069,6 +1083,7 @@ int qd_destroy(qd_ctx* c) {
     free_clip(c);
     free_trim(c);
     free_pairtrim(c);
+    free_posttrim(c);
     free_filter(c);
     free_dup(c);
     for (auto& t : c->tracked) (void)hipEventDestroy(t.second);
@@ -1586,6 +1601,84 @@ int qd_dev_pairtrim(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_
     return up.close(qd_pairtrim_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), up.out(0), up.out(1), QD_STREAM_CONTEXT));
 }
 
+static_assert(QD_POSTTRIM_VALUES == QD_POST_TABLE, "the public table size is the kernel's");
+
+int qd_posttrim_set(qd_ctx* c, const qd_posttrim_params* params) {
+    if (!c) return QD_ERR_INVALID;
+    qd_posttrim_params P{};
+    qd_posttrim_dev D{};
+    const bool on = params && (params->tail_n || params->poly_x_min_length || params->max_length[0] || params->max_length[1]);
+    if (on) {  // checked as the configuration file's values are, before anything changes
+        P = *params;
+        if (P.tail_n < 0 || P.tail_n > 1) return fail(c, QD_ERR_INVALID, "tail_n: 0 or 1");
+        if (P.poly_x_min_length && (P.poly_x_min_length < QD_POST_MIN_POLYX || P.poly_x_min_length > QD_POST_MAX_POLYX))
+            return fail(c, QD_ERR_INVALID, "poly_x_min_length: 0 (off) or 6 to 100");
+        for (int r = 0; r < 2; ++r) {
+            if (P.max_length[r] < 0 || P.max_length[r] > 65535) return fail(c, QD_ERR_INVALID, "max_length: 0 (off) or 1 to 65535");
+            D.max_length[r] = (uint32_t)P.max_length[r];
+        }
+        if (P.min_length < 0 || P.min_length > 65535) return fail(c, QD_ERR_INVALID, "min_length: 0 to 65535");
+        D.tail_n = (uint32_t)P.tail_n;
+        D.poly_x = (uint32_t)P.poly_x_min_length;
+        D.min_length = (uint32_t)P.min_length;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));  // nothing of this context may still read the old parameters or add to the old table
+    free_posttrim(c);
+    if (!on) return QD_OK;
+    const int rc = table_alloc(c, c->d_posttrim, QD_POST_TABLE, "post-trim counters");
+    if (rc != QD_OK) return rc;
+    c->posttrim = P;
+    c->posttrim_dev = D;
+    return QD_OK;
+}
+
+int qd_posttrim_get(const qd_ctx* c, qd_posttrim_params* out) {
+    if (!c || !out) return QD_ERR_INVALID;
+    *out = c->posttrim;
+    return QD_OK;
+}
+
+int qd_posttrim_active(const qd_ctx* c) { return c && c->d_posttrim ? 1 : 0; }
+
+int qd_posttrim_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
+    if (!c) return QD_ERR_INVALID;
+    return table_read(c, c->d_posttrim, QD_POST_TABLE, out, n_values, "post-trimming is not on", "n_values must be 32");
+}
+
+int qd_posttrim_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
+    if (!c) return QD_ERR_INVALID;
+    return table_add(c, c->d_posttrim, QD_POST_TABLE, values, n_values, "post-trimming is not on", "n_values must be 32");
+}
+
+int qd_posttrim_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
+                       qd_rec* out1, qd_rec* out2, void* stream) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_posttrim) return fail(c, QD_ERR_STATE, "post-trimming is not on");
+    if (!n) return QD_OK;
+    hipStream_t st = resolve_stream(c, stream);
+    qd_posttrim_args a{};
+    fill_pair_args(a, text1, recs1, text2, recs2);
+    a.out[0] = out1;
+    a.out[1] = out2;
+    a.table = c->d_posttrim;
+    hipError_t e = qd_posttrim_launch(c->posttrim_dev, a, n, st);
+    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("post-trim launch: ") + hipGetErrorString(e));
+    HIPCHK(c, track(c, st));
+    return QD_OK;
+}
+
+int qd_dev_posttrim(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+                    const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_posttrim) return fail(c, QD_ERR_STATE, "post-trimming is not on");
+    PairUpload up(c);
+    const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::OUT_RECS, nullptr, nullptr, out_recs1, out_recs2,
+                           nullptr);
+    if (rc != QD_OK || up.empty()) return rc;
+    return up.close(qd_posttrim_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), up.out(0), up.out(1), QD_STREAM_CONTEXT));
+}
+
 static_assert(QD_FILTER_VALUES == QD_FL_VALUES, "the public table width is the kernel's");
 
 int qd_filter_set(qd_ctx* c, const qd_filter_params* params) {
@@ -1912,12 +2005,13 @@ int qd_add_counts(qd_ctx* c, const uint64_t* counts, int32_t n_values) {
 int qd_reset_counts(qd_ctx* c) {
     if (!c) return QD_ERR_INVALID;
     if (!c->have_table) {  // no barcodes, no pair counters; the trim counters do not depend on them
-        if (!c->d_clip && !c->d_trim && !c->d_pairtrim) return QD_OK;
+        if (!c->d_clip && !c->d_trim && !c->d_pairtrim && !c->d_posttrim) return QD_OK;
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, wait_all(c));
         if (c->d_clip) HIPCHK(c, hipMemset(c->d_clip, 0, QD_CLIP_TABLE * 8));
         if (c->d_trim) HIPCHK(c, hipMemset(c->d_trim, 0, QD_TRIM_VALUES * 8));
         if (c->d_pairtrim) HIPCHK(c, hipMemset(c->d_pairtrim, 0, QD_PT_VALUES * 8));
+        if (c->d_posttrim) HIPCHK(c, hipMemset(c->d_posttrim, 0, QD_POST_TABLE * 8));
         return QD_OK;
     }
     HIPCHK(c, hipSetDevice(c->device));
@@ -1930,6 +2024,7 @@ int qd_reset_counts(qd_ctx* c) {
     if (c->d_clip) HIPCHK(c, hipMemsetAsync(c->d_clip, 0, QD_CLIP_TABLE * 8, c->stream));
     if (c->d_trim) HIPCHK(c, hipMemsetAsync(c->d_trim, 0, QD_TRIM_VALUES * 8, c->stream));
     if (c->d_pairtrim) HIPCHK(c, hipMemsetAsync(c->d_pairtrim, 0, QD_PT_VALUES * 8, c->stream));
+    if (c->d_posttrim) HIPCHK(c, hipMemsetAsync(c->d_posttrim, 0, QD_POST_TABLE * 8, c->stream));
     if (c->d_filter) HIPCHK(c, hipMemsetAsync(c->d_filter, 0, qd_filter_values((uint32_t)c->S) * 8, c->stream));
     if (c->d_dup) {  // both tables: sampled == tallied + not_tallied stays true
         HIPCHK(c, hipMemsetAsync(c->d_dup, 0, qd_dup_values((uint32_t)c->S) * 8, c->stream));

@@ -51,6 +51,7 @@
 #include "quade_clip.h"
 #include "quade_trim.h"
 #include "quade_pairtrim.h"
+#include "quade_posttrim.h"
 #include "quade_filter.h"
 
 uint32_t qd_crc32_combine_host(uint32_t crc1, uint32_t crc2, uint64_t len2);  // quade_io.cpp (zlib's)
@@ -725,6 +726,7 @@ struct qd_pipe {
     DevBuf clipped[2];  // the insert reads' record tables as the clip stage leaves them (qd_clip_set; never allocated when it is off)
     DevBuf trimmed[2];  // the insert reads' record tables with trimmed lengths (qd_trim_set; never allocated when trimming is off)
     DevBuf pairtrimmed[2];  // ... with the lengths the overlap trimming leaves (qd_pairtrim_set; never allocated when it is off)
+    DevBuf posttrimmed[2];  // ... with the lengths the post-trimming leaves (qd_posttrim_set; never allocated when it is off)
     DevBuf drop;  // the read filter's reason byte per pair (qd_filter_set; never allocated when it is off)
     PinBuf h_first;
     // tables and scratch of the format / CRC / coder launches: read by kernels on the compute stream only, so one set serves every batch
@@ -1765,6 +1767,14 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
         if (rc != QD_OK) return pfail(p, rc, std::string("overlap trim: ") + qd_last_error(p->ctx));
         for (int k = 0; k < 2; ++k) ins[k] = p->pairtrimmed[k].as<qd_rec>();
     }
+    // opt-in post-trimming (qd_posttrim_set): trailing N, a poly-X tail and the max_length crop, on what the three stages above left
+    if (qd_posttrim_active(p->ctx)) {
+        for (int k = 0; k < 2; ++k) PCHK(p, p->posttrimmed[k].need((size_t)n * sizeof(qd_rec) + 64, 0, p->cs));
+        const int rc = qd_posttrim_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p, ins[1], n,
+                                          p->posttrimmed[0].as<qd_rec>(), p->posttrimmed[1].as<qd_rec>(), p->cs);
+        if (rc != QD_OK) return pfail(p, rc, std::string("post-trim: ") + qd_last_error(p->ctx));
+        for (int k = 0; k < 2; ++k) ins[k] = p->posttrimmed[k].as<qd_rec>();
+    }
     // opt-in read filtering (qd_filter_set) of what the trimming left: a reason byte per pair; a pair with one is counted by nothing
     // behind this point, gets output lengths 0 and is not formatted -- the way a destination whose write flag is off leaves no text
     const uint8_t* drop = nullptr;
@@ -2610,7 +2620,7 @@ int qd_pipe_destroy(qd_pipe* p) {
     for (DevBuf* b : {&p->d_res, &p->rows_seq[0], &p->rows_seq[1], &p->rows_qual[0], &p->rows_qual[1], &p->rows_len[0], &p->rows_len[1], &p->codes, &p->mol,
                       &p->short_idx, &p->dest, &p->len1, &p->len2, &p->hist, &p->tmp, &p->perm, &p->sdest, &p->g1, &p->g2, &p->scan_tiles, &p->first, &p->g1_first,
                       &p->g2_first, &p->subs, &p->first_sub, &p->ranges, &p->crc, &p->tokens, &p->sub_out, &p->sub_bytes, &p->base1, &p->base2, &p->clipped[0], &p->clipped[1], &p->trimmed[0], &p->trimmed[1], &p->pairtrimmed[0],
-                      &p->pairtrimmed[1], &p->drop})
+                      &p->pairtrimmed[1], &p->posttrimmed[0], &p->posttrimmed[1], &p->drop})
         b->release();
     for (OutSet& o : p->out) {
         for (DevBuf* b : {&o.text, &o.pieces, &o.members, &o.member_len, &o.member_off, &o.packed}) b->release();

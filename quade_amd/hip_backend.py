@@ -15,8 +15,9 @@ import numpy as np
 # the read stages' table layouts, their bytes in the ranks' exchange and the stage table live in stages.py; hb.X reaches them all
 from .stages import (CLIP_COUNTERS, CSTATS_COUNTERS, CSTATS_CYCLES, CSTATS_GC_BINS, CSTATS_GR_VALUES, CSTATS_GROUPS,  # noqa: F401
                      CSTATS_LEN_BINS, CSTATS_MEANQ_BINS, CSTATS_SECTIONS, CSTATS_VALUES, FILTER_COUNTERS, FILTER_KEYS, FILTER_REASONS,
-                     PAIRTRIM_BINS, PAIRTRIM_COUNTERS, PAIRTRIM_PAIR_COUNTERS, PAIRTRIM_VALUES, QSTATS_COUNTERS, STAGE, STAGES,
-                     TRIM_COUNTERS, cstats_flat, cstats_views, pack_table, split_pairtrim, unpack_table)
+                     PAIRTRIM_BINS, PAIRTRIM_COUNTERS, PAIRTRIM_PAIR_COUNTERS, PAIRTRIM_VALUES, POSTTRIM, POSTTRIM_COUNTERS,
+                     QSTATS_COUNTERS, RUN_STAGE, RUN_STAGES, STAGE, STAGES, TRIM_COUNTERS, cstats_flat, cstats_views, pack_table,
+                     split_pairtrim, unpack_table)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libquade_hip.so")
@@ -67,6 +68,10 @@ class qd_trim_params(C.Structure):
 
 class qd_pairtrim_params(C.Structure):
     _fields_ = [("min_overlap", C.c_int32), ("max_mismatches", C.c_int32), ("max_mismatch_pct", C.c_int32), ("min_length", C.c_int32)]
+
+
+class qd_posttrim_params(C.Structure):
+    _fields_ = [("tail_n", C.c_int32), ("poly_x_min_length", C.c_int32), ("max_length", C.c_int32 * 2), ("min_length", C.c_int32)]
 
 
 class qd_filter_params(C.Structure):
@@ -150,6 +155,10 @@ SYMBOLS = [
     ("qd_pairtrim_get", C.c_int, [_P, C.POINTER(qd_pairtrim_params)]),
     ("qd_pairtrim_read", C.c_int, [_P, _P, C.c_int64]),
     ("qd_pairtrim_add", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_posttrim_set", C.c_int, [_P, C.POINTER(qd_posttrim_params)]),
+    ("qd_posttrim_get", C.c_int, [_P, C.POINTER(qd_posttrim_params)]),
+    ("qd_posttrim_read", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_posttrim_add", C.c_int, [_P, _P, C.c_int64]),
     ("qd_filter_set", C.c_int, [_P, C.POINTER(qd_filter_params)]),
     ("qd_filter_get", C.c_int, [_P, C.POINTER(qd_filter_params)]),
     ("qd_filter_read", C.c_int, [_P, _P, C.c_int64]),
@@ -245,6 +254,7 @@ SYMBOLS = [
     ("qd_dev_clip", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_trim", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_pairtrim", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
+    ("qd_dev_posttrim", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_filter", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_cstats", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_dup", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
@@ -656,7 +666,7 @@ class Engine(object):
         return t, r, codes, drop, n
 
     def _dev_recs(self, fn, text1, recs1, text2, recs2):
-        """a stage that writes new record tables (qd_dev_clip, qd_dev_trim, qd_dev_pairtrim) -> the two tables"""
+        """a stage that writes new record tables (qd_dev_clip, qd_dev_trim, qd_dev_pairtrim, qd_dev_posttrim) -> the two tables"""
         t, r, _, _, n = self._pair_inputs(text1, recs1, text2, recs2)
         out = [np.zeros_like(x) for x in r]
         self._chk(fn(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), n, _ptr(out[0]), _ptr(out[1])))
@@ -796,6 +806,43 @@ class Engine(object):
         """The overlap trimming stage over host buffers (qd_dev_pairtrim): texts as bytes or uint8 arrays, recs uint32[n, 6] in
         dev_fastq_scan's layout; -> the two tables with the lengths the reads keep; adds to the context's table."""
         return self._dev_recs(self.lib.qd_dev_pairtrim, text1, recs1, text2, recs2)
+
+    def posttrim_set(self, tail_n=0, poly_x_min_length=0, max_length_r1=0, max_length_r2=0, min_length=0):
+        """Trailing-N, poly-X and max_length trimming of the insert reads in the device pipeline, behind pairtrim_set's stage and in
+        front of filter_set's (qd_posttrim_set; conf.POSTTRIM_HELP has the rules).  Every rule off (the defaults) turns the stage
+        off and frees the counters; a value out of range is QD_ERR_INVALID and changes nothing."""
+        P = qd_posttrim_params()
+        P.tail_n, P.poly_x_min_length, P.min_length = int(tail_n), int(poly_x_min_length), int(min_length)
+        P.max_length[0], P.max_length[1] = int(max_length_r1), int(max_length_r2)
+        self._chk(self.lib.qd_posttrim_set(self._h, C.byref(P)))
+
+    def posttrim_get(self):
+        """The parameters in force, as posttrim_set's keywords (the stage off: all zero)."""
+        P = qd_posttrim_params()
+        self._chk(self.lib.qd_posttrim_get(self._h, C.byref(P)))
+        return dict(tail_n=P.tail_n, poly_x_min_length=P.poly_x_min_length, max_length_r1=P.max_length[0], max_length_r2=P.max_length[1],
+                    min_length=P.min_length)
+
+    def posttrim_active(self):
+        """whether the stage is on: what the pipeline asks before every batch (qd_posttrim_active, an internal entry of the library)"""
+        f = self.lib.qd_posttrim_active
+        f.restype, f.argtypes = C.c_int, [_P]
+        return bool(f(self._h))
+
+    def posttrim_read(self):
+        """numpy uint64[2, 16]: [R1, R2][POSTTRIM_COUNTERS]"""
+        out = np.zeros((2, len(POSTTRIM_COUNTERS)), dtype=np.uint64)
+        self._chk(self.lib.qd_posttrim_read(self._h, _ptr(out), out.size))
+        return out
+
+    def posttrim_add(self, table):
+        """Another context's counters (posttrim_read's layout) join this context's (qd_posttrim_add)."""
+        self._table_add(self.lib.qd_posttrim_add, table)
+
+    def dev_posttrim(self, text1, recs1, text2, recs2):
+        """The post-trimming stage over host buffers (qd_dev_posttrim): texts as bytes or uint8 arrays, recs uint32[n, 6] in
+        dev_fastq_scan's layout; -> the two tables with the lengths the reads keep; adds to the context's counters."""
+        return self._dev_recs(self.lib.qd_dev_posttrim, text1, recs1, text2, recs2)
 
     def filter_set(self, min_length=None, max_n=None, max_unqualified_pct=None, qualified_quality=15, min_mean_quality=None,
                    min_complexity_pct=None, on=True):

@@ -1,8 +1,8 @@
 # -*- coding: utf-8 -*-
 """
 The read stages of the device pipeline, described once: the columns of their counter tables (include/quade_hip.h, qd_qstats_*,
-qd_cstats_*, qd_clip_*, qd_trim_*, qd_pairtrim_*, qd_filter_*), the bytes a table has when the ranks exchange it, and STAGES, the
-table Quade.__call__ walks to switch the stages on, to collect their tables and to write their reports.  hip_backend and the
+qd_cstats_*, qd_clip_*, qd_trim_*, qd_pairtrim_*, qd_posttrim_*, qd_filter_*), the bytes a table has when the ranks exchange it, and
+RUN_STAGES, the table Quade.__call__ walks to switch the stages on, to collect their tables and to write their reports.  hip_backend and the
 report modules take the columns from here; nothing here touches libquade_hip.so.
 """
 from __future__ import annotations
@@ -20,6 +20,10 @@ CLIP_COUNTERS = ("reads", "bases_in", "bases_out", "front_clipped_reads", "front
 
 TRIM_COUNTERS = ("reads", "bases_in", "bases_out", "quality_trimmed_reads", "quality_trimmed_bases", "adapter_reads", "adapter_bases",
                  "floored_reads")  # per read R1 / R2 (qd_trim_*)
+
+POSTTRIM_COUNTERS = ("reads", "bases_in", "bases_out", "n_tail_reads", "n_tail_bases", "polya_reads", "polya_bases", "polyc_reads",
+                     "polyc_bases", "polyg_reads", "polyg_bases", "polyt_reads", "polyt_bases", "cropped_reads", "cropped_bases",
+                     "floored_reads")  # per read R1 / R2 (qd_posttrim_*)
 
 PAIRTRIM_COUNTERS = ("reads", "bases_in", "bases_out", "overlap_trimmed_reads", "overlap_trimmed_bases", "floored_reads")  # per read
 PAIRTRIM_PAIR_COUNTERS = ("pairs", "overlapped_pairs", "short_insert_pairs")
@@ -137,9 +141,16 @@ STAGES = (
 )
 STAGE = {s.name: s for s in STAGES}
 
+# STAGES and STAGE stay the six stages above: tests pin them, names and sizes.  The post-trimming stage (qd_posttrim_*) stands
+# in RUN_STAGES only, the tuple Quade.__call__ walks: every stage in pipeline order.
+POSTTRIM = Stage("posttrim", "posttrim", "posttrim", "posttrim_params", (2, len(POSTTRIM_COUNTERS)), None, "post-trim counters",
+                 None, None, "posttrim_report", ("params",))
+RUN_STAGES = STAGES[:5] + (POSTTRIM,) + STAGES[5:]  # quality, cycle, clip, trim, pairtrim, posttrim, filter
+RUN_STAGE = {s.name: s for s in RUN_STAGES}
+
 
 def _stage(stage):
-    return stage if isinstance(stage, Stage) else STAGE[stage]
+    return stage if isinstance(stage, Stage) else RUN_STAGE[stage]
 
 
 def pack_table(stage, table):

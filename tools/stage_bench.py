@@ -7,7 +7,7 @@ each is timed by HIP events.  "off" does what process_batch does with the stage 
 itself costs.  After the timed steps the stage's table is read back and checked against what the batch must have counted.  Prints
 one JSON line ("tool": "<stage>_bench"): per case the medians, the spread and the byte floor (the lines' bytes at 6.3 TB/s).
 
-usage: python tools/stage_bench.py --stage qstats|cycle|clip|trim|pairtrim|filter|dup [--pairs N] [--bases L] [--steps K] [--warmup W]
+usage: python tools/stage_bench.py --stage qstats|cycle|clip|trim|pairtrim|posttrim|filter|dup [--pairs N] [--bases L] [--steps K] [--warmup W]
                                    [--once CASE] [--out FILE]
   --once CASE  set up, run ONE launch and exit (for `rocprofv3 --kernel-trace --stats -- python ...`); CASE by stage:
     qstats    hot | spread | off      routing: 96 samples with 90 % of the pairs to 8 destinations (per-workgroup partials in LDS) |
@@ -18,6 +18,8 @@ usage: python tools/stage_bench.py --stage qstats|cycle|clip|trim|pairtrim|filte
                                       yardstick is the 3' trimming kernel with a cutoff only
     trim      PCT                     PCT % of the reads carry their adapter from a random position on
     pairtrim  PCT | poly              PCT % of the pairs read from an insert of 30 .. --bases - 1 bases | poly-A against poly-T
+    posttrim  CASE:PCT                clip_poly_g | polyx | crop | all, over a batch with PCT % of the reads ending in 30 A;
+                                      clip_poly_g is the clip kernel with its poly-G rule alone over the same share of G tails
     filter    drop0 | drop10 | drop100 | spread | off   the share of pairs dropped (poly-G in R1), hot or spread routing;
                                       interleaved with the quality counters' kernel over the same batch
     dup       sSAMPLE_dPCT | off      the duplication tally with duplication_sample SAMPLE (16 | 1) over a batch in which PCT (0 |
@@ -425,6 +427,65 @@ def pairtrim(B):
     return out
 
 
+def x_tails(share, base):
+    """a `share` of the reads ends in G_TAIL times `base`; plain qualities"""
+    def plant(g, n, L):
+        seq = plain_seq(g, n, L)
+        col = torch.arange(L, device="cuda").reshape(1, L)
+        has = (torch.rand(n, generator=g, device="cuda") < share).reshape(n, 1)
+        return torch.where(has & (col >= L - G_TAIL), torch.full_like(seq, ord(base)), seq), plain_qual(g, n, L)
+    return plant
+
+
+def posttrim(B):
+    """The post-trim kernel's cases over a batch with PCT % of the reads ending in 30 A, beside the clip stage's poly-G-only case
+    over the same batch with G in place of A (the two kernels stage the same line and walk the same rounds).  The byte floor: the
+    records in and out and the sequence line of every read."""
+    a, n, L = B.a, B.a.pairs, B.a.bases
+    kinds = {"clip_poly_g": lambda e: e.clip_set(poly_g_min_length=10), "polyx": lambda e: e.posttrim_set(poly_x_min_length=10),
+             "crop": lambda e: e.posttrim_set(max_length_r1=100, max_length_r2=100),
+             "all": lambda e: e.posttrim_set(tail_n=1, poly_x_min_length=10, max_length_r1=140, max_length_r2=140)}
+    launch = {k: B.entry("clip" if k == "clip_poly_g" else "posttrim") for k in kinds}
+    engines = contexts(kinds)
+    floor = 2.0 * n * (2 * 24 + L) / COPY_RATE * 1e3
+
+    def measure(pct, only=None):
+        b = Batch(n, L, plants=(x_tails(pct / 100.0, "A"),) * 2)
+        bg = Batch(n, L, plants=(x_tails(pct / 100.0, "G"),) * 2)
+        o1, o2 = b.outputs()
+        run = {k: (lambda k=k: B.launch(launch[k], engines[k], bg if k == "clip_poly_g" else b, o1, o2)) for k in engines}
+        if only is not None:
+            return B.once(run[only], {"once": only, "a_tail_percent": pct, "pairs": n, "bases": L})
+        for eng in engines.values():
+            eng.reset_counts()
+        ms = B.timed(run)
+        runs = a.steps + a.warmup
+        out = {"a_tail_percent": pct, "byte_floor_ms": floor, "cases": {}}
+        for k in engines:
+            table = engines[k].clip_read() if k == "clip_poly_g" else engines[k].posttrim_read()
+            assert int(table[0, 0]) == int(table[1, 0]) == runs * n and int(table[:, 1].sum()) == 2 * runs * n * L
+            per = lambda c: float(table[:, c].sum()) / (2 * runs * n)  # noqa: E731
+            row = {"median_ms": median(ms[k]), "min_ms": ms[k][0], "max_ms": ms[k][-1], "over_clip_poly_g": median(ms[k]) / median(ms["clip_poly_g"]),
+                   "over_floor": median(ms[k]) / floor, "mean_bases_out": per(2)}
+            if k == "clip_poly_g":
+                row.update(polyg_read_share=per(9))
+                assert abs(per(9) - pct / 100.0) < 0.01
+            else:
+                row.update(n_tail_read_share=per(3), polya_read_share=per(5), cropped_read_share=per(13))
+                assert k == "crop" or abs(per(5) - pct / 100.0) < 0.01  # a planted tail is always found, a random one next to never
+            out["cases"][k] = row
+        return out
+
+    if a.once is not None:
+        case, pct = a.once.split(":")
+        assert case in engines, "--once clip_poly_g|polyx|crop|all:PCT"
+        return measure(int(pct), only=case)
+    out = B.head("posttrim_bench", line_bytes=2 * n * L, steps=a.steps, yardstick="clip_reads, poly_g_min_length 10, the same share of G tails",
+                 params={k: engines[k].posttrim_get() for k in list(engines)[1:]}, batches=[measure(pct) for pct in (0, 10, 100)])
+    close(engines)
+    return out
+
+
 def filter_(B):
     a, n, L = B.a, B.a.pairs, B.a.bases
     cases = {"drop0": (0.0, "hot"), "drop10": (0.1, "hot"), "drop100": (1.0, "hot"), "spread": (0.1, "spread")}
@@ -551,7 +612,7 @@ def dup(B):
     return out
 
 
-STAGES = {"dup": dup, "qstats": qstats, "cycle": cycle, "clip": clip, "trim": trim, "pairtrim": pairtrim, "filter": filter_}
+STAGES = {"dup": dup, "qstats": qstats, "cycle": cycle, "clip": clip, "trim": trim, "pairtrim": pairtrim, "posttrim": posttrim, "filter": filter_}
 
 
 def main():
