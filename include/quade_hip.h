@@ -486,6 +486,63 @@ int qd_filter_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
 int qd_filter_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
 int qd_filter_kind(const qd_ctx* ctx);
 
+/* ---- k-mer screen of the insert reads against a reference: PhiX, a spike-in, a vector, a contaminant (opt-in;
+ * no reference counterpart: Quade 0.3.2 knows no reference sequence) --------------------------------------------------------------
+ * What bbduk does with ref=phix.fa k=31 in a pass of its own over every output file, done while the device pipeline holds the
+ * reads' text.  The definition:
+ *   u(b) = b & 0xDF.  A base is valid when u(b) is one of A, C, G, T.  Its code is c(b) = (u(b) >> 1) & 3, which gives A 0, C 1,
+ *   T 2, G 3 (the duplication key's code); the complement is c ^ 2.  k = kmer, 15 to 32.
+ *   The k-mer at position p of a sequence s exists when s[p .. p + k) are all valid.  Its forward word is
+ *   w = sum c(s[p + i]) << 2 (k - 1 - i), its reverse-complement word rc = sum (c(s[p + k - 1 - i]) ^ 2) << 2 (k - 1 - i), its
+ *   canonical word min(w, rc).
+ *   The reference set R holds the distinct canonical words of every k-mer of every record of the reference FASTA.  Records are
+ *   linear; a line starting with '>' separates records, so k-mers never span two records; lower case counts; any other letter
+ *   breaks k-mers.
+ *   hits(read) is the number of positions p in [0, L - k] whose k-mer exists and whose canonical word is in R.  A read shorter
+ *   than k has 0 hits and 0 k-mers.  A pair is matched when hits(R1) + hits(R2) >= min_hits (1 to 65535).
+ * The stage sees the pairs the output stages see: behind clip, trim, pairtrim, posttrim and the read filter, only pairs the filter
+ * kept, the reads as those stages left them (seq, seq_len of the last table), every destination whatever its write flag.  With
+ * action QD_SCREEN_REPORT nothing else changes.  With QD_SCREEN_DROP a matched pair leaves the run the way a filtered pair does:
+ * output lengths 0, in no file, counted neither by the quality and cycle counters nor by the duplication tally; qd_get_counts
+ * and the filter's table are exactly as without the stage.  With the stage on, qd_pipe_run runs it over every batch (one launch
+ * on its compute stream, no host sync) between the read filter and the quality counters and adds to a device table
+ * uint64[2 * S + 1][8], destination-major in routing code order as qd_qstats_read's:
+ *   0 pairs   1 matched_pairs   2 r1_hit_reads (pairs whose R1 has at least one hit)   3 r2_hit_reads   4 kmers (k-mers that exist,
+ *   over both reads)   5 hit_kmers   6 bases_in (sum of L over both reads)   7 bases_matched (... of the matched pairs)
+ * Off, nothing is allocated or launched.
+ *
+ * qd_screen_set: params NULL or n_kmers 0 turns the stage off and frees everything.  Otherwise kmer (15 .. 32), min_hits
+ * (1 .. 65535) and action (0, 1) are checked, and the list of R's words: strictly ascending, every word below 4^kmer, every word
+ * canonical, n_kmers <= QD_SCREEN_MAX_KMERS; a bad value is QD_ERR_INVALID and leaves the state as before.  The library builds an
+ * open-addressing table of 64-bit words on the host (linear probing, at most half full, the empty slot all ones, which no
+ * canonical word equals) and uploads it: up to QD_SCREEN_LDS_MAX_KMERS words the kernel keeps the table in the workgroup's LDS
+ * (16384 slots, 128 KiB, at most three eighths full), beyond that it probes it in global memory.  Compares are exact, so no result depends on the hash
+ * function.  Needs qd_set_plan and qd_set_barcodes (QD_ERR_STATE), which turn the stage off, as they do the read filter.  Waits
+ * for the context's outstanding work.
+ * qd_screen_get: the parameters in force (all zero, *n_kmers 0 and QD_OK when off); n_kmers may be NULL.
+ * qd_screen_kind: 1 = the table in LDS, 2 = in global memory; QD_ERR_STATE when off.
+ * qd_screen_first_slot: the slot at which the probe for `word` starts in the table built for n_kmers words (for tests that build
+ * long probe chains); QD_ERR_INVALID for an n_kmers outside 1 .. QD_SCREEN_MAX_KMERS.
+ * qd_screen_read: waits for the context's work, writes n_values = (2 * S + 1) * 8 values (QD_ERR_INVALID on another size,
+ * QD_ERR_STATE when off).  qd_screen_add: another context's table joins this one's.  qd_reset_counts zeroes the table. */
+#define QD_SCREEN_VALUES 8
+#define QD_SCREEN_MAX_KMERS (1u << 22)
+#define QD_SCREEN_LDS_MAX_KMERS 6144u
+#define QD_SCREEN_REPORT 0
+#define QD_SCREEN_DROP 1
+#define QD_SCREEN_DROPPED 0x80u /* the flag byte of a pair the screen drops */
+typedef struct qd_screen_params {
+    int32_t kmer;
+    int32_t min_hits;
+    int32_t action; /* QD_SCREEN_REPORT | QD_SCREEN_DROP */
+} qd_screen_params;
+int qd_screen_set(qd_ctx* ctx, const qd_screen_params* params, const uint64_t* kmers, int64_t n_kmers);
+int qd_screen_get(const qd_ctx* ctx, qd_screen_params* out, int64_t* n_kmers);
+int qd_screen_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
+int qd_screen_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
+int qd_screen_kind(const qd_ctx* ctx);
+int64_t qd_screen_first_slot(uint64_t word, int64_t n_kmers);
+
 /* ---- per-cycle quality and base content, per-read distributions (opt-in; no reference counterpart) -----------------------------
  * What the first plots of a read QC tool show: quality and base composition by cycle, and the distributions of read length,
  * per-read mean quality and GC content.  A device-resident table of exact uint64 counters over the insert reads as the output
@@ -1025,6 +1082,16 @@ int qd_dev_posttrim(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint3
  * launched: QD_ERR_INVALID.  QD_ERR_STATE when the stage is off.  Returns when the launch has finished. */
 int qd_dev_filter(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                   const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes, uint8_t* reasons);
+/* the k-mer screen (qd_screen_set above; no reference counterpart) over host buffers, as qd_dev_filter: pairs [0, n_pairs) of two
+ * texts with their record tables and routing codes are uploaded (the texts 3 bytes off alignment) and run through the kernel
+ * qd_pipe_run launches.  drop_in: NULL or a byte per pair; hits_out: uint32[n_pairs][2], hits(R1) and hits(R2); flag_out: a byte
+ * per pair.  flag_out[j] is drop_in[j] when that is non-zero: the pair is then skipped and counted nowhere, with hits 0, 0.  Else
+ * it is QD_SCREEN_DROPPED when the pair is matched and the action is QD_SCREEN_DROP, else 0.  The context's table grows.  Every
+ * record's sequence and quality range is checked against len1 / len2 and every code against 2 * S before anything is launched:
+ * QD_ERR_INVALID.  QD_ERR_STATE when the stage is off.  Returns when the launch has finished. */
+int qd_dev_screen(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+                  const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes, const uint8_t* drop_in, uint32_t* hits_out,
+                  uint8_t* flag_out);
 /* the per-cycle counters' stage (qd_cstats_enable above; no reference counterpart) over host buffers, as qd_dev_qstats: pairs
  * [0, n_pairs) of two texts with their record tables and routing codes are uploaded (the texts 3 bytes off alignment), counted by
  * the kernel qd_pipe_run launches, and added to the context's table.  drop may be NULL; otherwise pair j is skipped where

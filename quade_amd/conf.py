@@ -7,13 +7,14 @@ file written by `-i` is the reference's template byte for byte (src/Conf_file.py
 package data, quade_amd/data/Quade_conf_file.txt).  An optional [gpu] section that reference conf
 files simply do not have is read when present (defaults apply otherwise; see GPU_SECTION_HELP), and so are the optional
 mismatch budgets of the [index] section (MISMATCH_HELP), the unknown-barcode report (UNKNOWN_HELP) and the quality report
-(QUALITY_HELP), the per-cycle report (CYCLE_HELP) and the duplication report (DUPLICATION_HELP) of the [output] section, an optional [trim] section (CLIP_HELP, TRIM_HELP, PAIR_HELP, POSTTRIM_HELP) and an optional [filter] section
-(FILTER_HELP).
+(QUALITY_HELP), the per-cycle report (CYCLE_HELP) and the duplication report (DUPLICATION_HELP) of the [output] section, an optional [trim] section (CLIP_HELP, TRIM_HELP, PAIR_HELP, POSTTRIM_HELP), an optional [filter] section
+(FILTER_HELP) and an optional [screen] section (SCREEN_HELP).
 """
 from __future__ import annotations
 
 import configparser
 import os
+import zlib
 
 CONF_NAME = "Quade_conf_file.txt"
 
@@ -253,6 +254,42 @@ FILTER_RANGES = {"min_length": (1, 100000), "max_n": (0, 100000), "max_unqualifi
 FILTER_RULES = ("min_length", "max_n", "max_unqualified_pct", "min_mean_quality", "min_complexity_pct")  # in the rule's order
 
 
+SCREEN_HELP = """\
+Optional [screen] section (not in Quade 0.3.2, whose parser ignores it; absent = as before): a k-mer screen of the insert reads
+against a reference on the GPU -- PhiX, a spike-in, an rRNA set, a vector, a contaminant -- what bbduk does with ref=phix.fa k=31
+in a pass of its own over every output file.  The user supplies the FASTA; no genome is shipped.
+  reference :               a FASTA path, plain or .gz; an empty value turns the stage off
+  kmer : 31                 15 to 32
+  min_hits : 1              1 to 65535
+  action : report           report or drop
+u(b) = b & 0xDF.  A base is valid when u(b) is one of A, C, G, T.  Its code is c(b) = (u(b) >> 1) & 3, which gives A 0, C 1, T 2,
+G 3 (the duplication key's code); the complement is c ^ 2.  The k-mer at position p of a sequence s exists when s[p .. p + k) are
+all valid.  Its forward word is w = sum c(s[p + i]) << 2 (k - 1 - i), its reverse-complement word
+rc = sum (c(s[p + k - 1 - i]) ^ 2) << 2 (k - 1 - i), its canonical word min(w, rc).  The reference set R holds the distinct
+canonical words of every k-mer of every record of the reference FASTA.  Records are linear; a line starting with '>' separates
+records, so k-mers never span two records; lower case counts; any other letter breaks k-mers.  hits(read) is the number of
+positions p in [0, L - k] whose k-mer exists and whose canonical word is in R.  A read shorter than k has 0 hits and 0 k-mers.  A
+pair is matched when hits(R1) + hits(R2) >= min_hits.
+The stage sees the pairs the output stages see: behind clip, [trim], pair_overlap, post-trim and [filter], only pairs the filter
+kept, the reads as those stages left them, every destination whatever its write flag.  With action : report nothing else
+changes.  With action : drop a matched pair leaves the run the way a filtered pair does: it is in no file, and quality_report,
+cycle_report and duplication_report do not count it; Quade_report.csv and Quade_filter_report.csv are exactly as without the
+stage.  Quade_screen_report.csv is written next to the report: per destination pairs, matched pairs, reads with a hit, k-mers,
+hit k-mers, bases in and bases of the matched pairs.  A reference of up to 6144 distinct k-mers (PhiX has about 5400) is looked up
+in the compute unit's LDS, a larger one, up to 4194304, in global memory.  The reads are screened while the device pipeline
+holds their text, so the section needs the device pipeline: [gpu] device_pipeline, device_inflate and device_deflate True (the
+defaults) and gzip_level 1 or -1
+"""
+
+SCREEN_NEEDS = "[screen] needs the device pipeline (device_pipeline, device_inflate, device_deflate : True and gzip_level 1 or -1)"
+SCREEN_REFERENCE = "[screen] reference is missing or cannot be read as a FASTA file, plain or gzip"
+SCREEN_NO_KMER = "[screen] reference holds no k-mer: no record has kmer valid bases in a row"
+SCREEN_TOO_MANY = "[screen] reference holds more than 4194304 distinct k-mers"
+SCREEN_KMER = "Authorized values for [screen] kmer : 15 to 32"
+SCREEN_MIN_HITS = "Authorized values for [screen] min_hits : 1 to 65535"
+SCREEN_ACTION = "Authorized values for [screen] action : report or drop"
+
+
 def filter_range_message(name):
     return "Authorized values for [filter] %s : %d to %d" % ((name,) + FILTER_RANGES[name])
 
@@ -384,6 +421,18 @@ class QuadeConf(object):
         self.filter_min_mean_quality = flt("min_mean_quality")
         self.filter_min_complexity_pct = flt("min_complexity_pct")
 
+        # optional [screen] section (extension, SCREEN_HELP): an empty reference = off
+        def scr(name, default, conv=int):
+            if cp.has_section("screen") and cp.has_option("screen", name) and cp.get("screen", name) not in (None, ""):
+                return conv(cp.get("screen", name))
+            return default
+
+        self.screen_reference = scr("reference", "", str).strip()
+        self.screen_kmer = scr("kmer", 31)
+        self.screen_min_hits = scr("min_hits", 1)
+        self.screen_action = scr("action", "report", str).strip().lower()
+        self._screen_ref = None  # screen.Reference, read by _test_values when the stage is on
+
         # (name, fused barcode) per [sample*] section, in file order (src/Quade.py:133-139)
         self.samples = []
         for section in [i for i in cp.sections() if i.startswith("sample")]:
@@ -471,6 +520,19 @@ class QuadeConf(object):
         for name, value in self.filter_params().items():
             assert value is None or FILTER_RANGES[name][0] <= value <= FILTER_RANGES[name][1], filter_range_message(name)
         assert not self.filter or self.can_pipe, FILTER_NEEDS
+        if self.screen:  # the reference is read here, before any read is processed
+            from . import screen
+            assert screen.MIN_KMER <= self.screen_kmer <= screen.MAX_KMER, SCREEN_KMER
+            assert 1 <= self.screen_min_hits <= 65535, SCREEN_MIN_HITS
+            assert self.screen_action in ("report", "drop"), SCREEN_ACTION
+            assert self.can_pipe, SCREEN_NEEDS
+            try:
+                data = screen.read_fasta(self.screen_reference)
+            except (OSError, EOFError, zlib.error):
+                raise AssertionError(SCREEN_REFERENCE)
+            self._screen_ref = screen.reference_kmers(data, self.screen_kmer)
+            assert self._screen_ref.kmers.size > 0, SCREEN_NO_KMER
+            assert self._screen_ref.kmers.size <= screen.MAX_KMERS, SCREEN_TOO_MANY
         for pos in [self.idx1_pos, self.idx2_pos, self.mol1_pos, self.mol2_pos]:
             assert pos["start"] >= 0
             assert pos["end"] >= pos["start"]
@@ -540,6 +602,18 @@ class QuadeConf(object):
         return dict(min_length=self.filter_min_length, max_n=self.filter_max_n, max_unqualified_pct=self.filter_max_unqualified_pct,
                     qualified_quality=self.filter_qualified_quality, min_mean_quality=self.filter_min_mean_quality,
                     min_complexity_pct=self.filter_min_complexity_pct)
+
+    @property
+    def screen(self):
+        """the k-mer screen is on: the [screen] section names a reference (SCREEN_HELP)"""
+        return bool(self.screen_reference)
+
+    def screen_params(self):
+        """what Engine.screen_set takes: the parameters, the reference set's words and, for the report, what the FASTA held"""
+        ref = self._screen_ref
+        return dict(kmer=self.screen_kmer, min_hits=self.screen_min_hits, action=self.screen_action, kmers=ref.kmers,
+                    reference=dict(name=os.path.basename(self.screen_reference), records=ref.records, bases=ref.bases,
+                                   kmers=int(ref.kmers.size)))
 
     def plan(self):
         """The qd_plan the HIP library takes (include/quade_hip.h)."""

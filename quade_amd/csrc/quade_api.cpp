@@ -29,6 +29,7 @@
 #include "quade_pairtrim.h"
 #include "quade_posttrim.h"
 #include "quade_filter.h"
+#include "quade_screen.h"
 #include "quade_dup.h"
 #include "quade_pool.h"
 
@@ -189,6 +190,14 @@ struct qd_ctx {
     qd_filter_params filter{-1, -1, -1, 15, -1, -1};
     qd_filter_dev filter_dev{-1, -1, -1, 33 + 15, -1, -1};
     u64* d_filter = nullptr;
+
+    // k-mer screen against a reference (qd_screen_set): the parameters as given and as the kernel takes them, the reference's
+    // hash table (1 << screen_dev.slots_lg words) and the counters uint64[(2 * S + 1)][8]; d_screen == nullptr = off
+    qd_screen_params screen{};
+    qd_screen_dev screen_dev{};
+    int64_t screen_kmers = 0;
+    u64* d_screen_slots = nullptr;
+    u64* d_screen = nullptr;
 
     // duplication tally (qd_dup_set): the parameters as given and as the kernels take them, the counters
     // uint64[(2 * S + 1)][5] (d_dup == nullptr = off), and the key tally; per stream its scratch is the batch list,
@@ -549,14 +558,15 @@ void fill_pair_args(ARGS& a, const uint8_t* text1, const qd_rec* recs1, const ui
 //     return up.close(qd_<stage>_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), ..., QD_STREAM_CONTEXT));
 class PairUpload {
 public:
-    enum { CODES = 1, OUT_RECS = 2, REASONS = 4 };  // what the stage needs besides the texts and record tables
+    enum { CODES = 1, OUT_RECS = 2, REASONS = 4, HITS = 8 };  // what the stage needs besides the texts and record tables
 
     explicit PairUpload(qd_ctx* ctx) : c(ctx) {}
 
     // Every size, range and code is checked here, before anything is allocated: a bad table cannot become a bad address.  want:
     // which of codes, out_recs1 / out_recs2 and reasons must be given; drop is uploaded when it is.
     int open(const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2, const uint32_t* recs2,
-             int64_t n_pairs, int want, const uint16_t* codes, const uint8_t* drop, uint32_t* out_recs1, uint32_t* out_recs2, uint8_t* reasons) {
+             int64_t n_pairs, int want, const uint16_t* codes, const uint8_t* drop, uint32_t* out_recs1, uint32_t* out_recs2, uint8_t* reasons,
+             uint32_t* hits = nullptr) {
         const int64_t len[2] = {len1, len2};
         const uint8_t* text[2] = {text1, text2};
         const uint32_t* recs[2] = {recs1, recs2};
@@ -564,6 +574,7 @@ public:
             return fail(c, QD_ERR_INVALID, "bad sizes");
         if (n_pairs == 0) return QD_OK;
         if (!recs1 || !recs2 || ((want & CODES) && !codes) || ((want & OUT_RECS) && (!out_recs1 || !out_recs2)) || ((want & REASONS) && !reasons) ||
+            ((want & HITS) && !hits) ||
             (!text1 && len1) || (!text2 && len2))
             return fail(c, QD_ERR_INVALID, "null argument");
         static_assert(sizeof(qd_rec) == 6 * sizeof(uint32_t), "qd_dev_fastq_scan's record layout");
@@ -595,10 +606,12 @@ public:
             HIPCHK(c, hipMemcpyAsync(d_drop.p, drop, (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
         }
         if (want & REASONS) HIPCHK(c, uk_malloc(&d_reason.p, (size_t)n_pairs));
+        if (want & HITS) HIPCHK(c, uk_malloc(&d_hits.p, (size_t)n_pairs * 8));
         pairs = n_pairs;
         h_out[0] = out_recs1;
         h_out[1] = out_recs2;
         h_reason = reasons;
+        h_hits = hits;
         return QD_OK;
     }
     bool empty() const { return pairs == 0; }  // open() found no pairs: nothing was uploaded, there is nothing to launch
@@ -610,6 +623,7 @@ public:
     const uint8_t* drop() const { return static_cast<const uint8_t*>(d_drop.p); }  // nullptr when none was given
     qd_rec* out(int r) const { return static_cast<qd_rec*>(d_out[r].p); }
     uint8_t* reason() const { return static_cast<uint8_t*>(d_reason.p); }
+    uint32_t* hits() const { return static_cast<uint32_t*>(d_hits.p); }  // uint32[n][2]
 
     // behind the stage, which returned rc: what it wrote goes to the host when it succeeded, and the stream is waited for
     int close(int rc) {
@@ -617,6 +631,7 @@ public:
             for (int r = 0; r < 2; ++r)
                 if (d_out[r].p) HIPCHK(c, hipMemcpyAsync(h_out[r], d_out[r].p, (size_t)pairs * sizeof(qd_rec), hipMemcpyDeviceToHost, c->stream));
             if (d_reason.p) HIPCHK(c, hipMemcpyAsync(h_reason, d_reason.p, (size_t)pairs, hipMemcpyDeviceToHost, c->stream));
+            if (d_hits.p) HIPCHK(c, hipMemcpyAsync(h_hits, d_hits.p, (size_t)pairs * 8, hipMemcpyDeviceToHost, c->stream));
         }
         HIPCHK(c, hipStreamSynchronize(c->stream));  // the scratch is freed on return
         return rc;
@@ -631,9 +646,10 @@ private:
     };
     qd_ctx* c;
     int64_t pairs = 0;
-    Dev d_text[2], d_recs[2], d_codes, d_drop, d_out[2], d_reason;
+    Dev d_text[2], d_recs[2], d_codes, d_drop, d_out[2], d_reason, d_hits;
     uint32_t* h_out[2] = {nullptr, nullptr};
     uint8_t* h_reason = nullptr;
+    uint32_t* h_hits = nullptr;
 };
 
 // the tally off and its memory freed (the caller waited for the context's work)
@@ -718,6 +734,15 @@ void free_filter(qd_ctx* c) {
     table_free(c->d_filter);
     c->filter = qd_filter_params{-1, -1, -1, 15, -1, -1};
     c->filter_dev = qd_filter_dev{-1, -1, -1, 33 + 15, -1, -1};
+}
+
+// the k-mer screen off, its hash table and its counters freed (the caller waited for the context's work)
+void free_screen(qd_ctx* c) {
+    table_free(c->d_screen);
+    table_free(c->d_screen_slots);
+    c->screen = qd_screen_params{};
+    c->screen_dev = qd_screen_dev{};
+    c->screen_kmers = 0;
 }
 
 // the duplication tally off and its memory freed (the caller waited for the context's work)
@@ -1085,6 +1110,7 @@ int qd_destroy(qd_ctx* c) {
     free_pairtrim(c);
     free_posttrim(c);
     free_filter(c);
+    free_screen(c);
     free_dup(c);
     for (auto& t : c->tracked) (void)hipEventDestroy(t.second);
     c->tracked.clear();
@@ -1108,13 +1134,14 @@ int qd_set_plan(qd_ctx* c, const qd_plan* plan) {
     if (r != QD_OK) return fail(c, r, "plan rejected: positions must satisfy 0 <= start <= end <= 255, window <= 64, "
                                        "fused barcode <= 32, 0 <= minimal_qual <= 40");
     if (!c->slots.empty()) return fail(c, QD_ERR_STATE, "destroy the slots before changing the plan");
-    if (c->mm_m1 + c->mm_m2 > 0 || c->uk.mem || c->d_qs || c->d_filter || c->d_dup) {  // a new plan resets the mismatch budgets and turns the unknown tally, the quality counters, the read filter and the duplication tally off
+    if (c->mm_m1 + c->mm_m2 > 0 || c->uk.mem || c->d_qs || c->d_filter || c->d_screen || c->d_dup) {  // a new plan resets the mismatch budgets and turns the unknown tally, the quality counters, the read filter, the k-mer screen and the duplication tally off
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, wait_all(c));
         free_mismatch(c, false);
         free_unknown(c);
         free_qstats(c);
         free_filter(c);
+        free_screen(c);
         free_dup(c);
     }
     c->plan = *plan;
@@ -1150,13 +1177,14 @@ int qd_set_barcodes(qd_ctx* c, int32_t S, const uint8_t* barcodes, const int32_t
     if (!c->have_plan) return fail(c, QD_ERR_STATE, "qd_set_plan first");
     for (int i = 0; i < S; ++i)
         if (offsets[i + 1] < offsets[i]) return fail(c, QD_ERR_INVALID, "offsets must be non-decreasing");
-    if (c->mm_m1 + c->mm_m2 > 0 || c->uk.mem || c->d_qs || c->d_filter || c->d_dup) {  // new barcodes reset the mismatch budgets, as they reset the counters, and turn the unknown tally, the quality counters, the read filter and the duplication tally off
+    if (c->mm_m1 + c->mm_m2 > 0 || c->uk.mem || c->d_qs || c->d_filter || c->d_screen || c->d_dup) {  // new barcodes reset the mismatch budgets, as they reset the counters, and turn the unknown tally, the quality counters, the read filter, the k-mer screen and the duplication tally off
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, wait_all(c));
         free_mismatch(c, false);
         free_unknown(c);
         free_qstats(c);
         free_filter(c);
+        free_screen(c);
         free_dup(c);
     }
     c->S = S;
@@ -1762,6 +1790,126 @@ int qd_dev_filter(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t*
     return up.close(qd_filter_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), up.codes(), up.reason(), QD_STREAM_CONTEXT));
 }
 
+static_assert(QD_SCREEN_VALUES == QD_SC_VALUES, "the public table width is the kernel's");
+static_assert(QD_SCREEN_MAX_KMERS == QD_SC_MAX_KMERS && QD_SCREEN_LDS_MAX_KMERS == QD_SC_LDS_MAX_KMERS, "the public caps are the kernel's");
+static_assert(QD_SCREEN_DROPPED == QD_SC_DROPPED, "the public flag byte is the kernel's");
+
+namespace {
+// the reverse-complement word of a k-mer's forward word, base by base (the kernel reverses bit pairs)
+uint64_t screen_revcomp(uint64_t w, int k) {
+    uint64_t rc = 0;
+    for (int i = 0; i < k; ++i) rc = (rc << 2) | (((w >> (2 * i)) & 3u) ^ 2u);
+    return rc;
+}
+}  // namespace
+
+int qd_screen_set(qd_ctx* c, const qd_screen_params* params, const uint64_t* kmers, int64_t n_kmers) {
+    if (!c) return QD_ERR_INVALID;
+    const bool on = params && n_kmers != 0;
+    qd_screen_params P{};
+    std::vector<u64> slots;
+    uint32_t lg = 0;
+    if (on) {  // checked as the configuration file's values are, before anything changes
+        P = *params;
+        if (P.kmer < QD_SC_MIN_K || P.kmer > QD_SC_MAX_K) return fail(c, QD_ERR_INVALID, "screen kmer: 15 to 32");
+        if (P.min_hits < 1 || P.min_hits > 65535) return fail(c, QD_ERR_INVALID, "screen min_hits: 1 to 65535");
+        if (P.action != QD_SC_REPORT && P.action != QD_SC_DROP) return fail(c, QD_ERR_INVALID, "screen action: 0 (report) or 1 (drop)");
+        if (!kmers || n_kmers < 0 || n_kmers > (int64_t)QD_SC_MAX_KMERS) return fail(c, QD_ERR_INVALID, "screen k-mers: 1 to 4194304 words");
+        for (int64_t i = 0; i < n_kmers; ++i) {
+            const uint64_t w = kmers[i];
+            if (i && kmers[i - 1] >= w) return fail(c, QD_ERR_INVALID, "screen k-mers: the words must ascend strictly");
+            if (P.kmer < 32 && (w >> (2 * P.kmer))) return fail(c, QD_ERR_INVALID, "screen k-mers: a word is not below 4^kmer");
+            if (screen_revcomp(w, P.kmer) < w) return fail(c, QD_ERR_INVALID, "screen k-mers: a word is not canonical");
+        }
+        if (!c->have_plan || !c->have_table) return fail(c, QD_ERR_STATE, "qd_set_plan and qd_set_barcodes first");
+        lg = qd_screen_slots_lg((uint64_t)n_kmers);
+        slots.assign((size_t)1 << lg, QD_SC_EMPTY);
+        const uint32_t mask = (1u << lg) - 1u;
+        for (int64_t i = 0; i < n_kmers; ++i) {  // at most half full: a free slot is never far
+            uint32_t s = qd_screen_slot(kmers[i], lg);
+            while (slots[s] != QD_SC_EMPTY) s = (s + 1) & mask;
+            slots[s] = kmers[i];
+        }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));  // nothing of this context may still read the old table or add to the old counters
+    free_screen(c);
+    if (!on) return QD_OK;
+    int rc = table_alloc(c, c->d_screen, qd_screen_values((uint32_t)c->S), "screen counters");
+    if (rc == QD_OK) rc = table_alloc(c, c->d_screen_slots, slots.size(), "screen hash table");
+    if (rc != QD_OK) {
+        free_screen(c);
+        return rc;
+    }
+    HIPCHK(c, hipMemcpy(c->d_screen_slots, slots.data(), slots.size() * 8, hipMemcpyHostToDevice));
+    c->screen = P;
+    c->screen_dev = qd_screen_dev{(uint32_t)P.kmer, (uint32_t)P.min_hits, (uint32_t)P.action, lg};
+    c->screen_kmers = n_kmers;
+    return QD_OK;
+}
+
+int qd_screen_get(const qd_ctx* c, qd_screen_params* out, int64_t* n_kmers) {
+    if (!c || !out) return QD_ERR_INVALID;
+    *out = c->screen;
+    if (n_kmers) *n_kmers = c->screen_kmers;
+    return QD_OK;
+}
+
+int qd_screen_active(const qd_ctx* c) { return c && c->d_screen ? (c->screen.action == QD_SC_DROP ? 2 : 1) : 0; }
+
+int qd_screen_kind(const qd_ctx* c) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_screen) return fail(c, QD_ERR_STATE, "the k-mer screen is not on");
+    return qd_screen_path((uint64_t)c->screen_kmers);
+}
+
+int64_t qd_screen_first_slot(uint64_t word, int64_t n_kmers) {
+    if (n_kmers < 1 || n_kmers > (int64_t)QD_SC_MAX_KMERS) return QD_ERR_INVALID;
+    return qd_screen_slot(word, qd_screen_slots_lg((uint64_t)n_kmers));
+}
+
+int qd_screen_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
+    if (!c) return QD_ERR_INVALID;
+    return table_read(c, c->d_screen, qd_screen_values((uint32_t)c->S), out, n_values, "the k-mer screen is not on", "n_values must be (2*S+1)*8");
+}
+
+int qd_screen_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
+    if (!c) return QD_ERR_INVALID;
+    return table_add(c, c->d_screen, qd_screen_values((uint32_t)c->S), values, n_values, "the k-mer screen is not on", "n_values must be (2*S+1)*8");
+}
+
+int qd_screen_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
+                     const uint16_t* codes, const uint8_t* drop_in, uint32_t* hits, uint8_t* flag, void* stream) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_screen) return fail(c, QD_ERR_STATE, "the k-mer screen is not on");
+    if (!n) return QD_OK;
+    hipStream_t st = resolve_stream(c, stream);
+    qd_screen_args a{};
+    fill_pair_args(a, text1, recs1, text2, recs2);
+    a.codes = codes;
+    a.drop_in = drop_in;
+    a.hits = hits;
+    a.flag = flag;
+    a.slots = c->d_screen_slots;
+    a.table = c->d_screen;
+    hipError_t e = qd_screen_launch(c->screen_dev, a, (uint32_t)c->S, n, qd_screen_path((uint64_t)c->screen_kmers), (uint32_t)c->cu, st);
+    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("screen launch: ") + hipGetErrorString(e));
+    HIPCHK(c, track(c, st));
+    return QD_OK;
+}
+
+int qd_dev_screen(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+                  const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes, const uint8_t* drop_in, uint32_t* hits_out, uint8_t* flag_out) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->d_screen) return fail(c, QD_ERR_STATE, "the k-mer screen is not on");
+    PairUpload up(c);
+    const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::CODES | PairUpload::REASONS | PairUpload::HITS, codes,
+                           drop_in, nullptr, nullptr, flag_out, hits_out);
+    if (rc != QD_OK || up.empty()) return rc;
+    return up.close(qd_screen_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), up.codes(), up.drop(), up.hits(), up.reason(),
+                                     QD_STREAM_CONTEXT));
+}
+
 static_assert(QD_DUP_VALUES == QD_DP_VALUES, "the public row size is the kernels'");
 static_assert(QD_DUP_READ_ERROR == QD_UNKNOWN_READ_ERROR, "one sizing protocol");
 
@@ -2026,6 +2174,7 @@ int qd_reset_counts(qd_ctx* c) {
     if (c->d_pairtrim) HIPCHK(c, hipMemsetAsync(c->d_pairtrim, 0, QD_PT_VALUES * 8, c->stream));
     if (c->d_posttrim) HIPCHK(c, hipMemsetAsync(c->d_posttrim, 0, QD_POST_TABLE * 8, c->stream));
     if (c->d_filter) HIPCHK(c, hipMemsetAsync(c->d_filter, 0, qd_filter_values((uint32_t)c->S) * 8, c->stream));
+    if (c->d_screen) HIPCHK(c, hipMemsetAsync(c->d_screen, 0, qd_screen_values((uint32_t)c->S) * 8, c->stream));
     if (c->d_dup) {  // both tables: sampled == tallied + not_tallied stays true
         HIPCHK(c, hipMemsetAsync(c->d_dup, 0, qd_dup_values((uint32_t)c->S) * 8, c->stream));
         HIPCHK(c, tally_zero(c->dup_keys, c->stream));

@@ -53,6 +53,7 @@
 #include "quade_pairtrim.h"
 #include "quade_posttrim.h"
 #include "quade_filter.h"
+#include "quade_screen.h"
 
 uint32_t qd_crc32_combine_host(uint32_t crc1, uint32_t crc2, uint64_t len2);  // quade_io.cpp (zlib's)
 
@@ -727,7 +728,7 @@ struct qd_pipe {
     DevBuf trimmed[2];  // the insert reads' record tables with trimmed lengths (qd_trim_set; never allocated when trimming is off)
     DevBuf pairtrimmed[2];  // ... with the lengths the overlap trimming leaves (qd_pairtrim_set; never allocated when it is off)
     DevBuf posttrimmed[2];  // ... with the lengths the post-trimming leaves (qd_posttrim_set; never allocated when it is off)
-    DevBuf drop;  // the read filter's reason byte per pair (qd_filter_set; never allocated when it is off)
+    DevBuf drop;  // the read filter's reason byte per pair, 0x80 for a pair the k-mer screen drops (qd_filter_set, qd_screen_set with action drop; never allocated when both are off)
     PinBuf h_first;
     // tables and scratch of the format / CRC / coder launches: read by kernels on the compute stream only, so one set serves every batch
     DevBuf subs, first_sub, ranges, crc, tokens, sub_out, sub_bytes, base1, base2;
@@ -1784,6 +1785,20 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
                                         p->codes.as<uint16_t>(), p->drop.p, p->cs);
         if (rc != QD_OK) return pfail(p, rc, std::string("filter: ") + qd_last_error(p->ctx));
         drop = p->drop.p;
+    }
+    // opt-in k-mer screen against a reference (qd_screen_set) of the pairs the filter kept.  Action report only reads the drop bytes;
+    // action drop writes QD_SC_DROPPED over the 0 of a matched pair, in the filter's buffer or, the filter off, in a buffer of its
+    // own that the kernel fills whole -- everything behind tests the byte for non-zero
+    if (const int screen = qd_screen_active(p->ctx)) {
+        uint8_t* flag = nullptr;
+        if (screen == 2) {
+            PCHK(p, p->drop.need((size_t)n + 64, 0, p->cs));
+            flag = p->drop.p;
+        }
+        const int rc = qd_screen_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p, ins[1], n,
+                                        p->codes.as<uint16_t>(), drop, nullptr, flag, p->cs);
+        if (rc != QD_OK) return pfail(p, rc, std::string("screen: ") + qd_last_error(p->ctx));
+        if (flag) drop = flag;
     }
     {  // opt-in yield and quality counters of the insert reads (qd_qstats_enable): the codes are final, the windows still hold the pairs
         const int rc = qd_qstats_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p,

@@ -1,5 +1,6 @@
 // Device-only helpers of the stages that walk a batch's insert reads with 16 lanes (one DPP row) per read or pair:
-// quade_trim.hip, quade_clip.hip, quade_pairtrim.hip, quade_qstats.hip, quade_filter.hip and quade_cstats.hip.
+// quade_trim.hip, quade_clip.hip, quade_pairtrim.hip, quade_posttrim.hip, quade_qstats.hip, quade_filter.hip, quade_cstats.hip and
+// quade_screen.hip (which packs the line to two bits a base on its way into the slab).
 //
 // The shared shape.  A record's line lies anywhere in the batch's text; a Line is the 16-byte aligned words that hold it, so that
 // every load is a whole uint4 whatever the line's offset.  Two ways to take the words:

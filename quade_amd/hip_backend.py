@@ -16,8 +16,8 @@ import numpy as np
 from .stages import (CLIP_COUNTERS, CSTATS_COUNTERS, CSTATS_CYCLES, CSTATS_GC_BINS, CSTATS_GR_VALUES, CSTATS_GROUPS,  # noqa: F401
                      CSTATS_LEN_BINS, CSTATS_MEANQ_BINS, CSTATS_SECTIONS, CSTATS_VALUES, FILTER_COUNTERS, FILTER_KEYS, FILTER_REASONS,
                      PAIRTRIM_BINS, PAIRTRIM_COUNTERS, PAIRTRIM_PAIR_COUNTERS, PAIRTRIM_VALUES, POSTTRIM, POSTTRIM_COUNTERS,
-                     QSTATS_COUNTERS, RUN_STAGE, RUN_STAGES, STAGE, STAGES, TRIM_COUNTERS, cstats_flat, cstats_views, pack_table,
-                     split_pairtrim, unpack_table)
+                     PIPE_STAGE, PIPE_STAGES, QSTATS_COUNTERS, RUN_STAGE, RUN_STAGES, SCREEN, SCREEN_ACTIONS, SCREEN_COUNTERS, STAGE,
+                     STAGES, TRIM_COUNTERS, cstats_flat, cstats_views, pack_table, split_pairtrim, unpack_table)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libquade_hip.so")
@@ -72,6 +72,10 @@ class qd_pairtrim_params(C.Structure):
 
 class qd_posttrim_params(C.Structure):
     _fields_ = [("tail_n", C.c_int32), ("poly_x_min_length", C.c_int32), ("max_length", C.c_int32 * 2), ("min_length", C.c_int32)]
+
+
+class qd_screen_params(C.Structure):
+    _fields_ = [("kmer", C.c_int32), ("min_hits", C.c_int32), ("action", C.c_int32)]
 
 
 class qd_filter_params(C.Structure):
@@ -159,6 +163,12 @@ SYMBOLS = [
     ("qd_posttrim_get", C.c_int, [_P, C.POINTER(qd_posttrim_params)]),
     ("qd_posttrim_read", C.c_int, [_P, _P, C.c_int64]),
     ("qd_posttrim_add", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_screen_set", C.c_int, [_P, C.POINTER(qd_screen_params), _P, C.c_int64]),
+    ("qd_screen_get", C.c_int, [_P, C.POINTER(qd_screen_params), C.POINTER(C.c_int64)]),
+    ("qd_screen_read", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_screen_add", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_screen_kind", C.c_int, [_P]),
+    ("qd_screen_first_slot", C.c_int64, [C.c_uint64, C.c_int64]),
     ("qd_filter_set", C.c_int, [_P, C.POINTER(qd_filter_params)]),
     ("qd_filter_get", C.c_int, [_P, C.POINTER(qd_filter_params)]),
     ("qd_filter_read", C.c_int, [_P, _P, C.c_int64]),
@@ -256,6 +266,7 @@ SYMBOLS = [
     ("qd_dev_pairtrim", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_posttrim", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_filter", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
+    ("qd_dev_screen", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P]),
     ("qd_dev_cstats", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_dup", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_pack_rows", C.c_int, [C.c_int, C.POINTER(qd_layout), _P * 2, C.c_int64 * 2, _P * 2, C.c_int64, C.c_int64, _P * 2, _P * 2, _P * 2,
@@ -888,6 +899,66 @@ class Engine(object):
         out = np.zeros(n, dtype=np.uint8)
         self._chk(self.lib.qd_dev_filter(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), n, _ptr(codes), _ptr(out)))
         return out
+
+    def screen_set(self, kmer=31, min_hits=1, action="report", kmers=None, reference=None, on=True):
+        """The k-mer screen against a reference in the device pipeline, behind filter_set's stage (qd_screen_set; conf.SCREEN_HELP
+        has the definition).  kmers: the reference set's distinct canonical words, uint64, ascending (screen.reference_kmers makes
+        them); action "report" or "drop" (or 0, 1); reference: what the report says about the FASTA, not looked at here.
+        on=False, or no k-mers, turns the stage off and frees the hash table and the counters; a bad value is QD_ERR_INVALID and
+        changes nothing.  Needs the plan and the barcodes."""
+        if not on or kmers is None or len(kmers) == 0:
+            self._chk(self.lib.qd_screen_set(self._h, None, None, 0))
+            return
+        kmers = np.ascontiguousarray(kmers, dtype=np.uint64).reshape(-1)
+        P = qd_screen_params(int(kmer), int(min_hits), SCREEN_ACTIONS.index(action) if action in SCREEN_ACTIONS else int(action))
+        self._chk(self.lib.qd_screen_set(self._h, C.byref(P), _ptr(kmers), kmers.size))
+
+    def screen_get(self):
+        """The parameters in force, as screen_set's keywords with n_kmers in place of the words; None when the stage is off."""
+        P, n = qd_screen_params(), C.c_int64(0)
+        self._chk(self.lib.qd_screen_get(self._h, C.byref(P), C.byref(n)))
+        return dict(kmer=int(P.kmer), min_hits=int(P.min_hits), action=SCREEN_ACTIONS[P.action], n_kmers=int(n.value)) if n.value else None
+
+    def screen_active(self):
+        """whether the stage is on: what the pipeline asks before every batch (qd_screen_active, an internal entry of the library)"""
+        f = self.lib.qd_screen_active
+        f.restype, f.argtypes = C.c_int, [_P]
+        return bool(f(self._h))
+
+    def screen_kind(self):
+        """Where the kernel keeps the reference's hash table: "lds" or "global"."""
+        kind = self.lib.qd_screen_kind(self._h)
+        if kind < 0:
+            self._chk(kind)
+        return {1: "lds", 2: "global"}[kind]
+
+    def screen_first_slot(self, word, n_kmers):
+        """the slot at which the probe for a canonical word starts in the table built for n_kmers words (qd_screen_first_slot)"""
+        slot = self.lib.qd_screen_first_slot(int(word), int(n_kmers))
+        if slot < 0:
+            self._chk(int(slot))
+        return int(slot)
+
+    def screen_read(self):
+        """numpy uint64[2S+1, 8]: [destination (code; Undetermined last)][SCREEN_COUNTERS]"""
+        out = np.zeros((2 * self.n_samples + 1, len(SCREEN_COUNTERS)), dtype=np.uint64)
+        self._chk(self.lib.qd_screen_read(self._h, _ptr(out), out.size))
+        return out
+
+    def screen_add(self, table):
+        """Another context's table (screen_read's layout) joins this context's (qd_screen_add)."""
+        self._table_add(self.lib.qd_screen_add, table)
+
+    def dev_screen(self, text1, recs1, text2, recs2, codes, drop=None):
+        """The screen stage over host buffers (qd_dev_screen): texts as bytes or uint8 arrays, recs uint32[n, 6] in
+        dev_fastq_scan's layout, codes uint16[n], drop None or uint8[n] (non-zero = the pair is skipped); -> (hits uint32[n, 2],
+        flags uint8[n]: the drop byte of a skipped pair, 0x80 for a matched pair under action drop, else 0); adds to the context's
+        table."""
+        t, r, codes, drop, n = self._pair_inputs(text1, recs1, text2, recs2, codes, drop)
+        hits, flags = np.zeros((n, 2), dtype=np.uint32), np.zeros(n, dtype=np.uint8)
+        self._chk(self.lib.qd_dev_screen(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), n, _ptr(codes),
+                                         _ptr(drop) if drop is not None else None, _ptr(hits), _ptr(flags)))
+        return hits, flags
 
     def cstats_enable(self, on=True):
         """Per-cycle quality and base content and the per-read distributions (qd_cstats_enable): every pair the device pipeline

@@ -1,8 +1,8 @@
 # -*- coding: utf-8 -*-
 """
 The read stages of the device pipeline, described once: the columns of their counter tables (include/quade_hip.h, qd_qstats_*,
-qd_cstats_*, qd_clip_*, qd_trim_*, qd_pairtrim_*, qd_posttrim_*, qd_filter_*), the bytes a table has when the ranks exchange it, and
-RUN_STAGES, the table Quade.__call__ walks to switch the stages on, to collect their tables and to write their reports.  hip_backend and the
+qd_cstats_*, qd_clip_*, qd_trim_*, qd_pairtrim_*, qd_posttrim_*, qd_filter_*, qd_screen_*), the bytes a table has when the ranks exchange it, and
+PIPE_STAGES, the table Quade.__call__ walks to switch the stages on, to collect their tables and to write their reports.  hip_backend and the
 report modules take the columns from here; nothing here touches libquade_hip.so.
 """
 from __future__ import annotations
@@ -42,6 +42,10 @@ def split_pairtrim(table):
 FILTER_REASONS = ("too_short", "too_many_n", "low_quality", "low_mean_quality", "low_complexity")
 FILTER_COUNTERS = ("pairs",) + FILTER_REASONS + ("bases_in", "bases_dropped")  # per destination
 FILTER_KEYS = ("min_length", "max_n", "max_unqualified_pct", "qualified_quality", "min_mean_quality", "min_complexity_pct")
+
+# qd_screen_*: the table's columns per destination, and the actions in the order of their numbers
+SCREEN_COUNTERS = ("pairs", "matched_pairs", "r1_hit_reads", "r2_hit_reads", "kmers", "hit_kmers", "bases_in", "bases_matched")
+SCREEN_ACTIONS = ("report", "drop")
 
 # the per-cycle table (qd_cstats_*): uint64, group-major (pass, fail, Undetermined), then read; per (group, read) the sections
 CSTATS_GROUPS = ("pass", "fail", "Undetermined")
@@ -142,15 +146,23 @@ STAGES = (
 STAGE = {s.name: s for s in STAGES}
 
 # STAGES and STAGE stay the six stages above: tests pin them, names and sizes.  The post-trimming stage (qd_posttrim_*) stands
-# in RUN_STAGES only, the tuple Quade.__call__ walks: every stage in pipeline order.
+# in RUN_STAGES, the seven stages up to the filter in pipeline order.
 POSTTRIM = Stage("posttrim", "posttrim", "posttrim", "posttrim_params", (2, len(POSTTRIM_COUNTERS)), None, "post-trim counters",
                  None, None, "posttrim_report", ("params",))
 RUN_STAGES = STAGES[:5] + (POSTTRIM,) + STAGES[5:]  # quality, cycle, clip, trim, pairtrim, posttrim, filter
 RUN_STAGE = {s.name: s for s in RUN_STAGES}
 
 
+# RUN_STAGES is pinned at those seven in turn.  The k-mer screen (qd_screen_*) runs behind the filter: PIPE_STAGES is every stage
+# in pipeline order, and what Quade.__call__, pack_table and unpack_table walk.
+SCREEN = Stage("screen", "screen", "screen", "screen_params", (-1, len(SCREEN_COUNTERS)), "rows", "screen table",
+               None, None, "screen_report", ("samples", "params"))
+PIPE_STAGES = RUN_STAGES + (SCREEN,)  # quality, cycle, clip, trim, pairtrim, posttrim, filter, screen
+PIPE_STAGE = {s.name: s for s in PIPE_STAGES}
+
+
 def _stage(stage):
-    return stage if isinstance(stage, Stage) else RUN_STAGE[stage]
+    return stage if isinstance(stage, Stage) else PIPE_STAGE[stage]
 
 
 def pack_table(stage, table):

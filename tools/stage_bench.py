@@ -7,7 +7,7 @@ each is timed by HIP events.  "off" does what process_batch does with the stage 
 itself costs.  After the timed steps the stage's table is read back and checked against what the batch must have counted.  Prints
 one JSON line ("tool": "<stage>_bench"): per case the medians, the spread and the byte floor (the lines' bytes at 6.3 TB/s).
 
-usage: python tools/stage_bench.py --stage qstats|cycle|clip|trim|pairtrim|posttrim|filter|dup [--pairs N] [--bases L] [--steps K] [--warmup W]
+usage: python tools/stage_bench.py --stage qstats|cycle|clip|trim|pairtrim|posttrim|filter|screen|dup [--pairs N] [--bases L] [--steps K] [--warmup W]
                                    [--once CASE] [--out FILE]
   --once CASE  set up, run ONE launch and exit (for `rocprofv3 --kernel-trace --stats -- python ...`); CASE by stage:
     qstats    hot | spread | off      routing: 96 samples with 90 % of the pairs to 8 destinations (per-workgroup partials in LDS) |
@@ -22,6 +22,10 @@ usage: python tools/stage_bench.py --stage qstats|cycle|clip|trim|pairtrim|postt
                                       clip_poly_g is the clip kernel with its poly-G rule alone over the same share of G tails
     filter    drop0 | drop10 | drop100 | spread | off   the share of pairs dropped (poly-G in R1), hot or spread routing;
                                       interleaved with the quality counters' kernel over the same batch
+    screen    lds_PCT | ldscap_PCT | globaledge_PCT | global_PCT | off   the k-mer screen against a PhiX-sized random reference
+                                      (5 386 bases, the hash table in LDS), one of 6 144 k-mers (the fullest LDS table), of 6 145 (the
+                                      smallest table in global memory) or of 200 000, PCT (0 | 10 | 100) % of the pairs drawn from
+                                      the reference; interleaved with the quality counters' and the pairtrim kernel
     dup       sSAMPLE_dPCT | off      the duplication tally with duplication_sample SAMPLE (16 | 1) over a batch in which PCT (0 |
                                       30 | 100) % of the pairs repeat another pair's reads and destination, 8 hot destinations;
                                       interleaved with the quality counters' kernel over the same batch
@@ -542,6 +546,92 @@ def filter_(B):
     return out
 
 
+def screen(B):
+    """The k-mer screen's kernel with the reference's hash table in LDS (a PhiX-sized random reference) and in global memory (a
+    reference of 200 000 k-mers), 0, 10 and 100 % of the pairs drawn from the reference, beside the quality counters' kernel and the
+    pairtrim kernel over the same batch.  The byte floor: the two records, the code and the hit words of every pair and the sequence
+    line of every read."""
+    from quade_amd import screen as qscreen
+    a, n, L, k = B.a, B.a.pairs, B.a.bases, 31
+    # bases of the random reference: PhiX's size; the fullest LDS table (6 144 k-mers) and the smallest global one (6 145), the two
+    # sides of the threshold; 200 000 k-mers
+    refs = {"lds": 5386, "ldscap": qscreen.LDS_MAX_KMERS + k - 1, "globaledge": qscreen.LDS_MAX_KMERS + k, "global": 200000 + k - 1}
+    cases = {"%s_%d" % (place, pct): (place, pct) for place in refs for pct in (0, 10, 100)}
+    B.once_in([None, "off"] + sorted(cases))
+    g = generator(7)
+    f = B.lib.qd_screen_device
+    f.restype, f.argtypes = C.c_int, [C.c_void_p] * 5 + [C.c_uint32] + [C.c_void_p] * 5
+    q_launch, p_launch, active = B.entry("qstats"), B.entry("pairtrim"), B.asker("screen")
+    hits = torch.zeros((n + 64, 2), dtype=torch.int32, device="cuda")
+    flag = torch.zeros(n + 64, dtype=torch.uint8, device="cuda")
+    floor = n * (2 * 24 + 2 + 8 + 1 + 2 * L) / COPY_RATE * 1e3
+    bases = torch.tensor(list(b"ACGT"), dtype=torch.uint8, device="cuda")
+
+    def reference(place):
+        seq = bases[torch.randint(0, 4, (refs[place],), generator=g, device="cuda")]
+        ref = qscreen.reference_kmers(b">random\n" + bytes(seq.cpu().numpy()) + b"\n", k)
+        return seq, ref.kmers
+
+    def texts(seq, pct):
+        """the batch (bases from ACGT) with pct % of its pairs off the reference: R1 and R2 two stretches of it"""
+        b = Batch(n, L)
+        take = torch.rand(n, generator=g, device="cuda") < pct / 100.0 if 0 < pct < 100 else torch.full((n,), pct >= 100, device="cuda")
+        col = torch.arange(L, device="cuda").reshape(1, L)
+        for t in (b.t1, b.t2):
+            v = t.view(n, b.rec)
+            v[:, 22:22 + L] = bases[torch.randint(0, 4, (n, L), generator=g, device="cuda")]
+            at = torch.randint(0, seq.numel() - L, (n, 1), generator=g, device="cuda")
+            v[:, 22:22 + L] = torch.where(take.reshape(n, 1), seq[at + col], v[:, 22:22 + L])
+        return b, int(take.sum())
+
+    def measure(case):
+        place, pct = cases[case]
+        seq, kmers = reference(place)
+        b, n_ref = texts(seq, pct)
+        S, codes = routed_codes(g, n, "hot")
+        kinds = {"off": None, "screen": lambda e: e.screen_set(kmer=k, min_hits=1, action="drop", kmers=kmers),
+                 "qstats": lambda e: e.qstats_enable(True), "pairtrim": lambda e: e.pairtrim_set()}
+        engines = contexts({name: kinds[name] for name in (("off",) if a.once == "off" else ("screen",) if a.once else kinds)}, S)
+        o1, o2 = b.outputs()
+
+        def off():  # what process_batch does with the stage off: it asks, and launches nothing
+            assert active(engines["off"]._h) == 0
+
+        def on():
+            rc = f(engines["screen"]._h, b.t1.data_ptr(), b.r1.data_ptr(), b.t2.data_ptr(), b.r2.data_ptr(), n, codes.data_ptr(), None,
+                   hits.data_ptr(), flag.data_ptr(), B.st.cuda_stream)
+            assert rc == 0, rc
+        run = {"off": off, "screen": on, "qstats": lambda: B.launch(q_launch, engines["qstats"], b, codes.data_ptr(), None),
+               "pairtrim": lambda: B.launch(p_launch, engines["pairtrim"], b, o1, o2)}
+        run = {name: run[name] for name in engines}
+        if a.once:
+            out = B.once(run["off" if a.once == "off" else "screen"],
+                         {"once": a.once, "pairs": n, "bases": L, "path": engines["screen"].screen_kind() if "screen" in engines else None})
+            close(engines)
+            return out
+        ms = B.timed(run)
+        table, launches = engines["screen"].screen_read(), a.steps + a.warmup
+        tot = [int(x) for x in table.sum(axis=0)]
+        # every read is bases alone: all its k-mers exist; a pair off the reference hits with all of them, another pair with none
+        assert tot[0] == launches * n and tot[6] == 2 * launches * n * L and tot[4] == 2 * launches * n * (L - k + 1)
+        assert tot[1] == tot[2] == tot[3] == launches * n_ref and tot[5] == 2 * launches * n_ref * (L - k + 1)
+        assert int(flag[:n].count_nonzero()) == n_ref and int(hits[:n].sum()) == 2 * n_ref * (L - k + 1)
+        out = {"case": case, "table": engines["screen"].screen_kind(), "reference_kmers": int(kmers.size), "kmer": k, "samples": S,
+               "matched_share": n_ref / n, "byte_floor_ms": floor, "screen_over_qstats": median(ms["screen"]) / median(ms["qstats"]),
+               "screen_over_pairtrim": median(ms["screen"]) / median(ms["pairtrim"]), "screen_over_floor": median(ms["screen"]) / floor,
+               **by_name(ms)}
+        close(engines)
+        return out
+
+    if a.once:
+        return measure("lds_10" if a.once == "off" else a.once)
+    out = B.head("screen_bench", line_bytes=2 * n * L, steps=a.steps, lds_max_kmers=qscreen.LDS_MAX_KMERS,
+                 lds_bytes_per_workgroup=(8 << 14) + 24576, workgroup_lanes=1024)
+    for case in cases:
+        out[case] = measure(case)
+    return out
+
+
 def dup(B):
     """The duplication tally's three launches (dup_keys, dup_claim, dup_count) against the quality counters' kernel.  The byte floor:
     the two records, the code and the reason byte of every pair, the aligned 16-byte words that hold the first 32 bases of both
@@ -612,7 +702,7 @@ def dup(B):
     return out
 
 
-STAGES = {"dup": dup, "qstats": qstats, "cycle": cycle, "clip": clip, "trim": trim, "pairtrim": pairtrim, "posttrim": posttrim, "filter": filter_}
+STAGES = {"dup": dup, "qstats": qstats, "cycle": cycle, "clip": clip, "trim": trim, "pairtrim": pairtrim, "posttrim": posttrim, "filter": filter_, "screen": screen}
 
 
 def main():
