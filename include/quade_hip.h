@@ -220,6 +220,44 @@ int qd_unknown_enable(qd_ctx* ctx, int64_t slots);
 int qd_unknown_stats(qd_ctx* ctx, uint64_t out[4]);
 int64_t qd_unknown_read(qd_ctx* ctx, uint8_t* keys, uint64_t* counts, int64_t cap);
 
+/* ---- index-hopping matrix (opt-in, additive: QD_ABI_VERSION stays 6; no reference counterpart) -------------------------
+ * For a dual plan (qd_plan.dual == 1) with K = key_width, w1 = idx1_end - idx1_start and w2 = K - w1, both > 0.
+ * Part lists: take the samples whose registered barcode is K bytes long, in ordinal order (a barcode of another length is
+ * "off the matrix" and takes no part).  P1 = the distinct values of bc[0:w1] in order of first appearance, P2 = the same for
+ * bc[w1:K]; n1 = |P1|, n2 = |P2|; sample s has part1[s] and part2[s], both -1 when it is off the matrix.  A cell (a, b) is
+ * "on the sheet" when some sample has exactly that pair.
+ * Table: uint64[(n1+1) * (n2+1) + 1], row-major; row n1 = "index 1 matches no part", column n2 = "index 2 matches no part";
+ * the last value is `short`.
+ * Counted is every pair whose FINAL routing code is 0xFFFF (after the exact kernels, the ragged fix-up and the mismatch
+ * rescue): the pairs the unknown tally counts.  A pair with a read that ends inside its index window (the row is zero padded
+ * there) adds 1 to `short`.  Otherwise a = the index in P1 of the pair's index-1 slice after the case fold, or n1 when it
+ * equals none, b the same for index 2 (N and any other byte are ordinary symbols), and cell (a, b) += 1.
+ * Matching per part is exact whatever the mismatch budgets are: a tolerant match per part is not unique (the collision rule
+ * holds for whole barcodes only), so with budgets above 0 the rates derived from the table are lower bounds.
+ * For all work launched since the matrix was enabled or zeroed: sum(table) == qd_get_counts()[3], and every on-sheet cell is 0
+ * (such a pair would have matched exactly).  Limit: (n1+1) * (n2+1) <= 2^24 (128 MiB per context).
+ * The matrix is one more post-pass of every launch (qd_demux_device, _ragged, qd_submit, qd_submit_ragged, qd_pipe_run) on the
+ * launch's stream; it is updated with atomics only, so launches on different streams need no order among themselves.
+ * Disabled, nothing is launched or allocated.
+ *
+ * qd_hop_index: host only, never touches the GPU -- the one definition of the part lists.  Writes part1[n_samples],
+ * part2[n_samples], *n1, *n2.  QD_ERR_INVALID on bad arguments (1 <= w1 < key_width <= QD_MAX_KEY), QD_ERR_UNSUPPORTED when
+ * the sheet is over the limit (the outputs are written all the same).
+ * qd_hop_enable: on != 0 builds the part tables, allocates and zeroes the table; 0 frees everything.  Needs qd_set_plan and
+ * qd_set_barcodes first (QD_ERR_STATE), a dual plan with w1, w2 > 0 (QD_ERR_INVALID) and a sheet within the limit
+ * (QD_ERR_UNSUPPORTED); waits for the context's outstanding work.  qd_set_plan and qd_set_barcodes turn the matrix off;
+ * qd_reset_counts zeroes it.
+ * qd_hop_shape: n1 and n2; QD_ERR_STATE when off.
+ * qd_hop_read: waits for the context's work, writes n_values = (n1+1)*(n2+1)+1 values (QD_ERR_INVALID on another size,
+ * QD_ERR_STATE when off).
+ * qd_hop_add: another context's table (qd_hop_read's layout) joins this one's, as qd_qstats_add does. */
+int qd_hop_index(int32_t n_samples, const uint8_t* barcodes, const int32_t* offsets, int32_t key_width, int32_t w1, int32_t* part1,
+                 int32_t* part2, int32_t* n1, int32_t* n2);
+int qd_hop_enable(qd_ctx* ctx, int32_t on);
+int qd_hop_shape(const qd_ctx* ctx, int32_t* n1, int32_t* n2);
+int qd_hop_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
+int qd_hop_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
+
 /* ---- yield and quality per destination (opt-in; no reference counterpart: Quade 0.3.2 reports pair counts only) ------
  * A device-resident table of exact uint64 counters, [(2*S+1)][2][6], destination-major: destination d = routing code,
  * 0xFFFF -> 2*S (even = <sample>_pass, odd = <sample>_fail, as the files); read 0 = R1, 1 = R2; counters

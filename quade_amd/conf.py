@@ -6,7 +6,7 @@ sections, option names, 1-based -> 0-based start conversion, assertion messages)
 file written by `-i` is the reference's template byte for byte (src/Conf_file.py:18-104; shipped as
 package data, quade_amd/data/Quade_conf_file.txt).  An optional [gpu] section that reference conf
 files simply do not have is read when present (defaults apply otherwise; see GPU_SECTION_HELP), and so are the optional
-mismatch budgets of the [index] section (MISMATCH_HELP), the unknown-barcode report (UNKNOWN_HELP) and the quality report
+mismatch budgets of the [index] section (MISMATCH_HELP), the unknown-barcode report (UNKNOWN_HELP), the index-hopping report (HOPPING_HELP) and the quality report
 (QUALITY_HELP), the per-cycle report (CYCLE_HELP) and the duplication report (DUPLICATION_HELP) of the [output] section, an optional [trim] section (CLIP_HELP, TRIM_HELP, PAIR_HELP, POSTTRIM_HELP), an optional [filter] section
 (FILTER_HELP) and an optional [screen] section (SCREEN_HELP).
 """
@@ -70,6 +70,30 @@ Optional [gpu] option:
   unknown_slots : 16777216  entries of that table per context: a power of two, 1024 to 268435456 (48 bytes each).  Barcodes that
                             find no room are counted as "Not tallied" in the report's head
 """
+
+HOPPING_HELP = """\
+Optional [output] option (not in Quade 0.3.2, whose parser ignores it; absent, empty or False = no report):
+  index_hopping_report : False  True: write Quade_index_hopping_report.csv next to the report.  Needs index2 : True.  With K the
+                            width of the fused barcode, w1 the width of index 1's window and w2 = K - w1: take the samples whose
+                            barcode is K long, in sheet order (the others are "off the matrix"); the distinct values of their
+                            first w1 bases, in order of first appearance, are the n1 index-1 values, the distinct values of
+                            their last w2 bases the n2 index-2 values.  Every pair that ends Undetermined (after the exact match
+                            and the mismatch rescue) is counted on the GPU in the cell (a, b) of a table of (n1+1) x (n2+1)
+                            cells: a = the index-1 value its index 1 slice equals after upper-casing, or "none", b the same for
+                            index 2 (N and any other byte are ordinary symbols); a pair with a read that ends inside its index
+                            window counts as "short index slice" instead.  A cell with both parts known is an unexpected
+                            combination -- index hopping, or a combination missing from the sheet -- and
+                            unexpected_per_100000 = both known * 100000 // (assigned + both known).  Matching per part is
+                            exact whatever the mismatch budgets are (a tolerant match per part is not unique): with a budget
+                            above 0 the rates are lower bounds, and the report says so.  The per-sample rows give the pairs that
+                            carry the sample's index 1 with another known index 2, its index 2 with another known index 1, and
+                            either with an unknown partner; in a combinatorial sheet the samples that share an index value
+                            share that sum.  At most 10000 combinations are listed.  (n1+1) x (n2+1) may not exceed 16777216
+                            (4095 distinct values per index read); the report works on every path and [gpu] configuration
+"""
+
+HOPPING_NEEDS = "index_hopping_report needs a dual index (index2 : True)"
+HOPPING_TOO_MANY = "index_hopping_report : (distinct index1 + 1) x (distinct index2 + 1) may not exceed 16777216"
 
 QUALITY_HELP = """\
 Optional [output] option (not in Quade 0.3.2, whose parser ignores it; absent, empty or False = no report):
@@ -357,6 +381,10 @@ class QuadeConf(object):
         self.top_unknown_barcodes = 0
         if cp.has_option("output", "top_unknown_barcodes") and cp.get("output", "top_unknown_barcodes") not in (None, ""):
             self.top_unknown_barcodes = cp.getint("output", "top_unknown_barcodes")
+        # optional index-hopping report (extension, HOPPING_HELP)
+        self.index_hopping_report = False
+        if cp.has_option("output", "index_hopping_report") and cp.get("output", "index_hopping_report") not in (None, ""):
+            self.index_hopping_report = cp.get("output", "index_hopping_report").strip().lower() in ("true", "1", "yes", "on")
         # optional yield and quality report per destination (extension, QUALITY_HELP)
         self.quality_report = False
         if cp.has_option("output", "quality_report") and cp.get("output", "quality_report") not in (None, ""):
@@ -489,6 +517,7 @@ class QuadeConf(object):
         assert 0 <= self.top_unknown_barcodes <= 1000, "Authorized values for top_unknown_barcodes : 0 to 1000"
         assert 1 << 10 <= self.unknown_slots <= 1 << 28 and self.unknown_slots & (self.unknown_slots - 1) == 0, \
             "[gpu] unknown_slots : a power of two, 1024 to 268435456"
+        assert not self.index_hopping_report or self.idx2, HOPPING_NEEDS
         assert not self.quality_report or self.can_pipe, QUALITY_NEEDS
         assert not self.cycle_report or self.can_pipe, CYCLE_NEEDS
         assert 8 <= self.duplication_bases <= 32, DUPLICATION_BASES

@@ -22,6 +22,7 @@
 #include "quade_text.h"
 #include "quade_mismatch.h"
 #include "quade_unknown.h"
+#include "quade_hop.h"
 #include "quade_qstats.h"
 #include "quade_cstats.h"
 #include "quade_clip.h"
@@ -206,6 +207,15 @@ struct qd_ctx {
     qd_dup_dev dup_dev{0, 0};
     u64* d_dup = nullptr;
     KeyTally dup_keys;
+
+    // index-hopping matrix (qd_hop_enable): the table uint64[(hop_n1 + 1) * (hop_n2 + 1) + 1] (d_hop == nullptr = off), the two
+    // part lookup tables in one allocation (slots of part 1, slots of part 2, then their key words), and per stream a list of
+    // a batch's undetermined pairs (pairs + 4 uint32 entries) for the launches that neither rescue nor tally
+    u64* d_hop = nullptr;
+    void* d_hop_parts = nullptr;
+    HopPart hop_part[2]{};
+    int32_t hop_n1 = 0, hop_n2 = 0;
+    StreamScratch hop_list;
 };
 
 namespace {
@@ -691,6 +701,87 @@ int launch_unknown(qd_ctx* c, int64_t n, const qd_rows* rows, const uint16_t* co
     return tally_after(c, c->uk, st);
 }
 
+// Host: the part lists of a sheet, the one definition (include/quade_hip.h qd_hop_index).  part1 / part2: per sample the
+// ordinal of its index-1 / index-2 value among the distinct values in order of first appearance, -1 for a barcode whose length is
+// not K; key1 / key2 (may be NULL): per distinct value its canonical key words.
+void hop_parts(int32_t S, const uint8_t* bc, const int32_t* off, int32_t K, int32_t w1, int32_t* part1, int32_t* part2, int32_t& n1,
+               int32_t& n2, std::vector<u64>* key1, std::vector<u64>* key2) {
+    std::map<std::string, int32_t> seen[2];
+    int32_t* part[2] = {part1, part2};
+    std::vector<u64>* key[2] = {key1, key2};
+    const int from[2] = {0, w1}, width[2] = {w1, K - w1};
+    for (int32_t i = 0; i < S; ++i) {
+        const uint8_t* b = bc + off[i];
+        const bool on = off[i + 1] - off[i] == K;
+        for (int h = 0; h < 2; ++h) {
+            if (!on) {
+                part[h][i] = -1;
+                continue;
+            }
+            const std::string v((const char*)b + from[h], (size_t)width[h]);
+            auto it = seen[h].find(v);
+            if (it == seen[h].end()) {
+                it = seen[h].emplace(v, (int32_t)seen[h].size()).first;
+                if (key[h]) {
+                    u64 w[QD_KEY_WORDS];
+                    canon(b + from[h], width[h], w);
+                    key[h]->insert(key[h]->end(), w, w + QD_KEY_WORDS);
+                }
+            }
+            part[h][i] = it->second;
+        }
+    }
+    n1 = (int32_t)seen[0].size();
+    n2 = (int32_t)seen[1].size();
+}
+
+size_t hop_values(const qd_ctx* c) { return (size_t)(c->hop_n1 + 1) * (size_t)(c->hop_n2 + 1) + 1; }
+
+// the matrix off and its memory freed (the caller waited for the context's work)
+void free_hop(qd_ctx* c) {
+    table_free(c->d_hop);
+    if (c->d_hop_parts) (void)hipFree(c->d_hop_parts);
+    c->d_hop_parts = nullptr;
+    c->hop_n1 = c->hop_n2 = 0;
+    c->hop_list.release();
+}
+
+// the matrix post-pass of a batch on `st` (launch(), matrix enabled), behind the rescue and the tally: the rescue's list when one ran
+// (`rescued`), else the tally's (`tallied`: launch_unknown has listed the batch on this stream), else a compaction of its own
+int launch_hop(qd_ctx* c, int64_t n, const qd_rows* rows, const uint16_t* codes, hipStream_t st, bool rescued, bool tallied) {
+    const StreamScratch::Buf* have = rescued ? c->mm_list.find(st) : (tallied ? c->uk.scratch.find(st) : nullptr);
+    const uint32_t* list = have ? reinterpret_cast<const uint32_t*>(have->buf) : nullptr;
+    if (!list) {
+        StreamScratch::Buf* sc = c->hop_list.need(c, st, (size_t)n, [](size_t pairs) { return (pairs + 4) * 4; });
+        if (!sc) return QD_ERR_HIP;
+        uint32_t* own = reinterpret_cast<uint32_t*>(sc->buf);
+        hipError_t e = qd_launch_compact(codes, n, own, st);
+        if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("index-hopping list: ") + hipGetErrorString(e));
+        list = own;
+    }
+    HopParams p{};
+    const qd_layout& L = c->lay;
+    const qd_plan& P = c->plan;
+    const int is[2] = {P.idx1_start, P.idx2_start}, ie[2] = {P.idx1_end, P.idx2_end};
+    for (int k = 0; k < 2; ++k) {  // (a dual plan: two streams, both windows non-empty)
+        p.seq[k] = rows->seq[k];
+        p.seq_stride[k] = L.seq_stride[k];
+        p.idx_w[k] = ie[k] - is[k];
+        p.idx_off[k] = is[k] - L.seq_off[k];
+        p.part[k] = c->hop_part[k];
+    }
+    p.codes = codes;
+    p.miss = list;
+    p.table = c->d_hop;
+    p.n = n;
+    p.K = L.key_width;
+    p.n1 = (uint32_t)c->hop_n1;
+    p.n2 = (uint32_t)c->hop_n2;
+    hipError_t e = qd_launch_hop(p, c->cu, st);
+    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("index-hopping launch: ") + hipGetErrorString(e));
+    return QD_OK;
+}
+
 // the quality counters off and their table freed (the caller waited for the context's work)
 void free_qstats(qd_ctx* c) {
     table_free(c->d_qs);
@@ -1025,6 +1116,10 @@ int launch(qd_ctx* c, int64_t n, const qd_rows* rows, uint16_t* codes, uint8_t* 
         const int r = launch_unknown(c, n, rows, codes, st, c->mm_m1 + c->mm_m2 > 0);
         if (r != QD_OK) return r;
     }
+    if (c->d_hop) {  // opt-in index-hopping matrix over the same pairs, behind both
+        const int r = launch_hop(c, n, rows, codes, st, c->mm_m1 + c->mm_m2 > 0, c->uk.mem != nullptr);
+        if (r != QD_OK) return r;
+    }
     c->total_pairs += (uint64_t)n;
     c->pairs_in_rows += (uint64_t)n;
     e = track(c, st);
@@ -1103,6 +1198,7 @@ int qd_destroy(qd_ctx* c) {
     free_table(c);
     free_mismatch(c, true);
     free_unknown(c);
+    free_hop(c);
     free_qstats(c);
     free_cstats(c);
     free_clip(c);
@@ -1134,11 +1230,12 @@ int qd_set_plan(qd_ctx* c, const qd_plan* plan) {
     if (r != QD_OK) return fail(c, r, "plan rejected: positions must satisfy 0 <= start <= end <= 255, window <= 64, "
                                        "fused barcode <= 32, 0 <= minimal_qual <= 40");
     if (!c->slots.empty()) return fail(c, QD_ERR_STATE, "destroy the slots before changing the plan");
-    if (c->mm_m1 + c->mm_m2 > 0 || c->uk.mem || c->d_qs || c->d_filter || c->d_screen || c->d_dup) {  // a new plan resets the mismatch budgets and turns the unknown tally, the quality counters, the read filter, the k-mer screen and the duplication tally off
+    if (c->mm_m1 + c->mm_m2 > 0 || c->uk.mem || c->d_hop || c->d_qs || c->d_filter || c->d_screen || c->d_dup) {  // a new plan resets the mismatch budgets and turns the unknown tally, the index-hopping matrix, the quality counters, the read filter, the k-mer screen and the duplication tally off
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, wait_all(c));
         free_mismatch(c, false);
         free_unknown(c);
+        free_hop(c);
         free_qstats(c);
         free_filter(c);
         free_screen(c);
@@ -1177,11 +1274,12 @@ int qd_set_barcodes(qd_ctx* c, int32_t S, const uint8_t* barcodes, const int32_t
     if (!c->have_plan) return fail(c, QD_ERR_STATE, "qd_set_plan first");
     for (int i = 0; i < S; ++i)
         if (offsets[i + 1] < offsets[i]) return fail(c, QD_ERR_INVALID, "offsets must be non-decreasing");
-    if (c->mm_m1 + c->mm_m2 > 0 || c->uk.mem || c->d_qs || c->d_filter || c->d_screen || c->d_dup) {  // new barcodes reset the mismatch budgets, as they reset the counters, and turn the unknown tally, the quality counters, the read filter, the k-mer screen and the duplication tally off
+    if (c->mm_m1 + c->mm_m2 > 0 || c->uk.mem || c->d_hop || c->d_qs || c->d_filter || c->d_screen || c->d_dup) {  // new barcodes reset the mismatch budgets, as they reset the counters, and turn the unknown tally, the index-hopping matrix, the quality counters, the read filter, the k-mer screen and the duplication tally off
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, wait_all(c));
         free_mismatch(c, false);
         free_unknown(c);
+        free_hop(c);
         free_qstats(c);
         free_filter(c);
         free_screen(c);
@@ -1280,6 +1378,83 @@ int64_t qd_unknown_read(qd_ctx* c, uint8_t* keys, uint64_t* counts, int64_t cap)
     for (int64_t i = 0; i < D; ++i)  // (D <= 0: nothing was gathered)
         for (int b = 0; b < K; ++b) keys[i * K + b] = (uint8_t)(hk[(size_t)i * QD_KEY_WORDS + (b >> 3)] >> (8 * (b & 7)));
     return D;
+}
+
+int qd_hop_index(int32_t S, const uint8_t* barcodes, const int32_t* offsets, int32_t K, int32_t w1, int32_t* part1, int32_t* part2,
+                 int32_t* n1, int32_t* n2) {
+    if (S < 0 || S > QD_MAX_SAMPLES || (S > 0 && (!barcodes || !offsets || !part1 || !part2)) || !n1 || !n2 || K < 2 || K > QD_MAX_KEY ||
+        w1 < 1 || w1 >= K)
+        return QD_ERR_INVALID;
+    for (int i = 0; i < S; ++i)
+        if (offsets[i + 1] < offsets[i]) return QD_ERR_INVALID;
+    hop_parts(S, barcodes, offsets, K, w1, part1, part2, *n1, *n2, nullptr, nullptr);
+    return (int64_t)(*n1 + 1) * (int64_t)(*n2 + 1) > QD_HOP_MAX_CELLS ? QD_ERR_UNSUPPORTED : QD_OK;
+}
+
+int qd_hop_enable(qd_ctx* c, int32_t on) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->have_plan || !c->have_table) return fail(c, QD_ERR_STATE, "qd_set_plan and qd_set_barcodes first");
+    const int K = c->lay.key_width, w1 = c->plan.idx1_end - c->plan.idx1_start;
+    if (on && (!c->plan.dual || w1 < 1 || w1 >= K))
+        return fail(c, QD_ERR_INVALID, "the index-hopping matrix needs a dual-index plan with both index windows non-empty");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));  // nothing of this context may still add to the old table
+    free_hop(c);
+    if (!on) return QD_OK;
+    std::vector<int32_t> part1((size_t)std::max(c->S, 1)), part2((size_t)std::max(c->S, 1));
+    std::vector<u64> key[2];
+    int32_t n[2] = {0, 0};
+    hop_parts(c->S, c->bc.data(), c->bc_off.data(), K, w1, part1.data(), part2.data(), n[0], n[1], &key[0], &key[1]);
+    if ((int64_t)(n[0] + 1) * (int64_t)(n[1] + 1) > QD_HOP_MAX_CELLS) {
+        char m[160];
+        snprintf(m, sizeof m, "index-hopping matrix: %d x %d distinct index values are more than (n1+1)*(n2+1) <= 2^24 admits", n[0], n[1]);
+        return fail(c, QD_ERR_UNSUPPORTED, m);
+    }
+    // one allocation: [slots of part 1][slots of part 2][keys of part 1][keys of part 2] (entries of 16 bytes first: aligned)
+    std::vector<HopSlot> slots[2];
+    for (int h = 0; h < 2; ++h) {
+        qd_hop_build(key[h], n[h], slots[h], c->hop_part[h].mask, c->hop_part[h].lg);
+        if (key[h].empty()) key[h].assign(QD_KEY_WORDS, 0);  // never read (no entry names it), keeps the device array non-empty
+    }
+    const size_t sb[2] = {slots[0].size() * sizeof(HopSlot), slots[1].size() * sizeof(HopSlot)};
+    const size_t kb[2] = {key[0].size() * 8, key[1].size() * 8};
+    hipError_t e = uk_malloc(&c->d_hop_parts, sb[0] + sb[1] + kb[0] + kb[1]);
+    if (e != hipSuccess) {
+        c->d_hop_parts = nullptr;
+        return fail(c, QD_ERR_HIP, std::string("index-hopping part tables: ") + hipGetErrorString(e));
+    }
+    uint8_t* base = static_cast<uint8_t*>(c->d_hop_parts);
+    const size_t so[2] = {0, sb[0]}, ko[2] = {sb[0] + sb[1], sb[0] + sb[1] + kb[0]};
+    for (int h = 0; h < 2 && e == hipSuccess; ++h) {
+        c->hop_part[h].slots = reinterpret_cast<const HopSlot*>(base + so[h]);
+        c->hop_part[h].keys = reinterpret_cast<const u64*>(base + ko[h]);
+        e = hipMemcpy(base + so[h], slots[h].data(), sb[h], hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(base + ko[h], key[h].data(), kb[h], hipMemcpyHostToDevice);
+    }
+    c->hop_n1 = n[0];
+    c->hop_n2 = n[1];
+    int rc = e == hipSuccess ? table_alloc(c, c->d_hop, hop_values(c), "index-hopping matrix")
+                             : fail(c, QD_ERR_HIP, std::string("index-hopping part tables: ") + hipGetErrorString(e));
+    if (rc != QD_OK) free_hop(c);
+    return rc;
+}
+
+int qd_hop_shape(const qd_ctx* c, int32_t* n1, int32_t* n2) {
+    if (!c || !n1 || !n2) return QD_ERR_INVALID;
+    if (!c->d_hop) return fail(c, QD_ERR_STATE, "the index-hopping matrix is not enabled");
+    *n1 = c->hop_n1;
+    *n2 = c->hop_n2;
+    return QD_OK;
+}
+
+int qd_hop_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
+    if (!c) return QD_ERR_INVALID;
+    return table_read(c, c->d_hop, hop_values(c), out, n_values, "the index-hopping matrix is not enabled", "n_values must be (n1+1)*(n2+1)+1");
+}
+
+int qd_hop_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
+    if (!c) return QD_ERR_INVALID;
+    return table_add(c, c->d_hop, hop_values(c), values, n_values, "the index-hopping matrix is not enabled", "n_values must be (n1+1)*(n2+1)+1");
 }
 
 int qd_qstats_enable(qd_ctx* c, int32_t on) {
@@ -2167,6 +2342,7 @@ int qd_reset_counts(qd_ctx* c) {
     HIPCHK(c, hipMemsetAsync(c->d_partial, 0,(size_t)c->partial_rows * c->cnt_stride * sizeof(qd_row_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_acc, 0, (size_t)c->cnt_stride * 8, c->stream));
     if (c->uk.mem) HIPCHK(c, tally_zero(c->uk, c->stream));  // sum(counts) + short + dropped == UNDETERMINED stays true
+    if (c->d_hop) HIPCHK(c, hipMemsetAsync(c->d_hop, 0, hop_values(c) * 8, c->stream));  // sum(table) == UNDETERMINED stays true
     if (c->d_qs) HIPCHK(c, hipMemsetAsync(c->d_qs, 0, qd_qstats_values((uint32_t)c->S) * 8, c->stream));  // records stay equal to the pair counters
     if (c->d_cs) HIPCHK(c, hipMemsetAsync(c->d_cs, 0, (size_t)QD_CS_VALUES * 8, c->stream));
     if (c->d_clip) HIPCHK(c, hipMemsetAsync(c->d_clip, 0, QD_CLIP_TABLE * 8, c->stream));

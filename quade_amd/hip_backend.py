@@ -143,6 +143,11 @@ SYMBOLS = [
     ("qd_unknown_enable", C.c_int, [_P, C.c_int64]),
     ("qd_unknown_stats", C.c_int, [_P, _P]),
     ("qd_unknown_read", C.c_int64, [_P, _P, _P, C.c_int64]),
+    ("qd_hop_index", C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("qd_hop_enable", C.c_int, [_P, C.c_int32]),
+    ("qd_hop_shape", C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("qd_hop_read", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_hop_add", C.c_int, [_P, _P, C.c_int64]),
     ("qd_qstats_enable", C.c_int, [_P, C.c_int32]),
     ("qd_qstats_read", C.c_int, [_P, _P, C.c_int64]),
     ("qd_qstats_add", C.c_int, [_P, _P, C.c_int64]),
@@ -471,6 +476,47 @@ def check_mismatch_collisions(barcodes, key_width, w1, m1, m2):
     return None
 
 
+HOP_MAX_CELLS = 1 << 24  # (n1 + 1) * (n2 + 1) at most (include/quade_hip.h)
+
+
+def hop_index(barcodes, key_width, w1):
+    """Host only (no GPU): the part lists of the index-hopping matrix, as qd_hop_index defines them -- (part1 int32[S], part2
+    int32[S], n1, n2): per sample the ordinal of its index-1 / index-2 value among the sheet's distinct values in order of first
+    appearance, -1 for a barcode that is not key_width long.  A sheet over the limit raises QuadeHipError(QD_ERR_UNSUPPORTED)."""
+    lib = load_library()
+    blob, offs, n = _barcode_blob(barcodes)
+    part1, part2 = np.full(max(n, 1), -1, dtype=np.int32), np.full(max(n, 1), -1, dtype=np.int32)
+    n1, n2 = C.c_int32(0), C.c_int32(0)
+    r = lib.qd_hop_index(n, _ptr(blob), _ptr(offs), int(key_width), int(w1), _ptr(part1), _ptr(part2), C.byref(n1), C.byref(n2))
+    if r == QD_ERR_UNSUPPORTED:
+        raise QuadeHipError(r, "%d x %d distinct index values: (n1+1)*(n2+1) may not exceed %d" % (n1.value, n2.value, HOP_MAX_CELLS))
+    if r != QD_OK:
+        raise QuadeHipError(r, lib.qd_strerror(r).decode())
+    return part1[:n], part2[:n], n1.value, n2.value
+
+
+def hop_values(n1, n2):
+    """values of an index-hopping table: the (n1 + 1) x (n2 + 1) cells and `short`"""
+    return (n1 + 1) * (n2 + 1) + 1
+
+
+def pack_hop(n1, n2, table):
+    """One context's or rank's index-hopping table as bytes (the ranks' exchange through the rendezvous directory): n1 and n2 in
+    front of the values; unpack_hop reverses it."""
+    table = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1)
+    assert table.size == hop_values(n1, n2), "an index-hopping table of %d values for %d x %d parts" % (table.size, n1, n2)
+    return np.array([n1, n2], dtype=np.uint64).tobytes() + table.tobytes()
+
+
+def unpack_hop(blob):
+    """-> (n1, n2, table uint64[(n1+1)*(n2+1)+1]); asserts that the blob holds exactly what its head names"""
+    assert len(blob) >= 16, "an index-hopping table of %d bytes has no head" % len(blob)
+    n1, n2 = (int(x) for x in np.frombuffer(blob, dtype=np.uint64, count=2))
+    assert len(blob) == 16 + 8 * hop_values(n1, n2), \
+        "an index-hopping table of %d bytes does not hold the %d x %d parts its head names" % (len(blob), n1, n2)
+    return n1, n2, np.frombuffer(blob, dtype=np.uint64, count=hop_values(n1, n2), offset=16)
+
+
 def _merge_keyed(keys, counts):
     """Key rows [n, w] with one count each -> (the distinct rows ascending, per row the sum of its counts as uint64)."""
     uniq, inv = np.unique(keys, axis=0, return_inverse=True)
@@ -653,6 +699,30 @@ class Engine(object):
     def unknown_read(self):
         """The table's entries in no particular order: (keys uint8[n, key_width], counts uint64[n])."""
         return self._tally_read(self.lib.qd_unknown_read, self.layout.key_width if self.layout is not None else 0, np.uint8)
+
+    def hop_enable(self, on=True):
+        """Index-hopping matrix (qd_hop_enable; conf.HOPPING_HELP has the definition): every pair that stays Undetermined is
+        counted in the cell (its index 1 among the sheet's distinct index-1 values, its index 2 among the distinct index-2
+        values), on every launch path.  A dual plan only.  After set_barcodes (and set_mismatches): set_plan and set_barcodes turn
+        it off, reset_counts zeroes it."""
+        self._chk(self.lib.qd_hop_enable(self._h, int(bool(on))))
+
+    def hop_shape(self):
+        """(n1, n2): the sheet's distinct index-1 and index-2 values"""
+        n1, n2 = C.c_int32(0), C.c_int32(0)
+        self._chk(self.lib.qd_hop_shape(self._h, C.byref(n1), C.byref(n2)))
+        return n1.value, n2.value
+
+    def hop_read(self):
+        """numpy uint64[(n1+1)*(n2+1)+1]: the cells row-major (row n1 / column n2 = no part), then `short`"""
+        n1, n2 = self.hop_shape()
+        out = np.zeros(hop_values(n1, n2), dtype=np.uint64)
+        self._chk(self.lib.qd_hop_read(self._h, _ptr(out), out.size))
+        return out
+
+    def hop_add(self, table):
+        """Another context's table (hop_read's layout) joins this context's (qd_hop_add)."""
+        self._table_add(self.lib.qd_hop_add, table)
 
     # -- the read stages: what their dev_* and *_add methods share
     @staticmethod

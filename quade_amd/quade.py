@@ -85,6 +85,7 @@ class Quade(object):
             for name, index in self.cf.samples:
                 Sample(name=name, index=index)
             self._check_mismatch_collisions()
+            self._check_hopping_limit()
         # same three families of errors, same messages, exit status 1 (src/Quade.py:145-153)
         except (configparser.NoOptionError, configparser.NoSectionError) as E:
             print("Option or section missing. Report to the template configuration file\n" + E.message)
@@ -111,6 +112,25 @@ class Quade(object):
         if hit is not None:
             a, b = Sample.SAMPLE_LIST[hit[0]].name, Sample.SAMPLE_LIST[hit[1]].name
             raise AssertionError("{} and {} : Index collision with index1_mismatches={} index2_mismatches={}".format(a, b, m1, m2))
+
+    def _check_hopping_limit(self):
+        """[output] index_hopping_report: a sheet whose matrix would pass the limit is a configuration error, found on the host
+        before any GPU work (the part lists are qd_hop_index's: hip_backend.hop_index)."""
+        cf = self.cf
+        self.hop_index = None
+        if not cf.index_hopping_report:
+            return
+        from .conf import HOPPING_TOO_MANY
+        w1 = cf.idx1_pos["end"] - cf.idx1_pos["start"]
+        w2 = cf.idx2_pos["end"] - cf.idx2_pos["start"]
+        if w1 < 1 or w2 < 1 or w1 + w2 > 32:
+            return  # (an empty window or a barcode beyond 32 bases: qd_set_plan / qd_hop_enable say so before a read is processed)
+        try:
+            self.hop_index = hb.hop_index(Sample.BARCODES(), w1 + w2, w1)
+        except hb.QuadeHipError as E:
+            if E.code != hb.QD_ERR_UNSUPPORTED:
+                raise
+            raise AssertionError(HOPPING_TOO_MANY)
 
     def __repr__(self):
         return "<Instance of {} from {} >\n".format(self.__class__.__name__, self.__module__)
@@ -167,6 +187,8 @@ class Quade(object):
                     eng.set_mismatches(cf.idx1_mismatches, cf.idx2_mismatches)
                 if cf.top_unknown_barcodes > 0:  # the barcodes of the Undetermined pairs are counted on the device
                     eng.unknown_enable(cf.unknown_slots)
+                if cf.index_hopping_report:  # ... and their index pairs in the matrix of the sheet's index values
+                    eng.hop_enable(True)
                 if cf.duplication_report:  # the read-pair keys are tallied on the device, beside the quality counters
                     eng.dup_set(**cf.duplication_params())
                 for stage in hb.PIPE_STAGES:  # what the pipeline does to the insert reads while it holds their text, in its order
@@ -198,6 +220,7 @@ class Quade(object):
         counts = self._reduce_counts(devices)
         # (the unknown-barcode tally is no entry of the stage table: its tables merge by key, they are not added)
         unknown = self._collect_unknown() if cf.top_unknown_barcodes > 0 else None
+        hopping = self._collect_hopping() if cf.index_hopping_report else None  # (nor is the matrix: its shape depends on the sheet)
         with _timed("duplication gather + merge"):  # (nor is the duplication tally a stage of the table: it merges by key too)
             dup = self._collect_dup() if cf.duplication_report else None
         tables = [(stage, self._collect(stage)) for stage in hb.PIPE_STAGES if stage.on(cf)]
@@ -238,6 +261,13 @@ class Quade(object):
             w1 = cf.idx1_pos["end"] - cf.idx1_pos["start"]
             write_report(os.path.join(self.outdir, REPORT_NAME), keys, ucounts, short, dropped, int(counts[3]),
                          cf.top_unknown_barcodes, w1, bool(cf.idx2), [(s.name, s.index) for s in Sample.SAMPLE_LIST])
+        if hopping is not None:
+            from .hopping_report import REPORT_NAME, write_report
+            part1, part2, n1, n2 = self.hop_index
+            write_report(os.path.join(self.outdir, REPORT_NAME), hopping, n1, n2, part1, part2,
+                         [(s.name, s.index) for s in Sample.SAMPLE_LIST], cf.idx1_pos["end"] - cf.idx1_pos["start"],
+                         (cf.idx1_mismatches, cf.idx2_mismatches), int(counts[0]),
+                         [int(counts[4 + 2 * i]) + int(counts[5 + 2 * i]) for i in range(len(Sample.SAMPLE_LIST))])
         if dup is not None:
             from .duplication_report import REPORT_NAME, write_report
             keys, dcounts, stats = dup
@@ -312,6 +342,26 @@ class Quade(object):
             keys, ucounts = hb.merge_unknown([(k, c) for k, c, _, _ in parts])
             short, dropped = sum(p[2] for p in parts), sum(p[3] for p in parts)
         return keys, ucounts, short, dropped
+
+    def _collect_hopping(self):
+        """[output] index_hopping_report: the tables of every context of this process added element by element (chunk workers,
+        devices); with several ranks every rank publishes its sum in the rendezvous directory and adds all of them (rank 0 writes
+        the file).  Returns uint64[(n1+1)*(n2+1)+1]."""
+        from . import dist
+        n1, n2 = self.hop_index[2], self.hop_index[3]
+        table = None
+        for eng in self.engines:
+            assert eng.hop_shape() == (n1, n2), "the context's part lists are not the sheet's"
+            t = eng.hop_read()
+            table = t if table is None else table + t
+        if self.world > 1:
+            got = dist.allgather_bytes(self.outdir, self.token, self.rank, self.world, "hopping", hb.pack_hop(n1, n2, table))
+            table = None
+            for b in got:
+                r1, r2, t = hb.unpack_hop(b)
+                assert (r1, r2) == (n1, n2), "a rank's index-hopping table has another shape"
+                table = t.copy() if table is None else table + t
+        return table
 
     def _collect_dup(self):
         """[output] duplication_report: the key tables of every context of this process merged (equal keys summed) and their
