@@ -84,6 +84,27 @@ struct KeyTally {
     StreamScratch scratch;
 };
 
+// A table of 64-bit counters on the device with what its messages call it: a read stage's (qd_ctx::stage) or the index-hopping
+// matrix'.  The table_*, stage_* and stages_* functions work on it.
+struct StageTable {
+    const char* what;       // in an allocation's error
+    const char* launch;     // in a launch's error (the matrix has none of its own)
+    const char* off_text;   // the error text while the table is off
+    const char* size_text;  // the error text for a caller's table of another size
+    bool per_destination;   // a row per destination: a new plan and new barcodes switch it off
+    u64* d = nullptr;       // nullptr = off
+    size_t n_values = 0;    // as allocated
+};
+
+// the read stages, in the pipeline's order
+enum StageId { ST_CLIP, ST_TRIM, ST_PAIRTRIM, ST_POSTTRIM, ST_FILTER, ST_SCREEN, ST_QSTATS, ST_CSTATS, ST_DUP, ST_COUNT };
+
+// a stage's parameters while it is off: all zero, but for the filter's, whose rules are off at -1 (and qualified_quality is 15)
+constexpr qd_filter_params FILTER_OFF{-1, -1, -1, 15, -1, -1};
+constexpr qd_filter_dev filter_dev_of(const qd_filter_params& P) {
+    return qd_filter_dev{P.min_length, P.max_n, P.max_unqualified_pct, 33 + P.qualified_quality, P.min_mean_quality, P.min_complexity_pct};
+}
+
 }  // namespace
 
 struct qd_ctx {
@@ -158,60 +179,47 @@ struct qd_ctx {
     // and the list of its undetermined pairs from [4], then from [4 + pairs] each listed pair's slot)
     KeyTally uk;
 
-    // yield and quality counters per destination (qd_qstats_enable): uint64[(2 * S + 1)][2][6], nullptr = off
-    u64* d_qs = nullptr;
-    // per-cycle counters and per-read distributions (qd_cstats_enable): uint64[QD_CS_VALUES], nullptr = off
-    u64* d_cs = nullptr;
-
-    // end clipping, window and poly-G trimming of the insert reads (qd_clip_set): the parameters as given and as the kernel takes
-    // them, and the counters uint64[2][12]; d_clip == nullptr = off
-    qd_clip_params clip{};
+    // The read stages' tables, by StageId: what each is called, whether it has a row per destination, and, while the stage is on,
+    // its counters.  clip uint64[2][12], trim [2][8], pairtrim [1040], posttrim [2][16], filter [(2 * S + 1)][8], screen
+    // [(2 * S + 1)][8], qstats [(2 * S + 1)][2][6], cstats [QD_CS_VALUES], dup [(2 * S + 1)][5].  Everything that switches stages off,
+    // zeroes, reads or adds to a table goes through this array; a new stage adds its row here.
+    StageTable stage[ST_COUNT] = {
+        {"clip counters", "clip", "clipping is not on", "n_values must be 24", false},
+        {"trim counters", "trim", "trimming is not on", "n_values must be 16", false},
+        {"overlap trimming table", "overlap trimming", "overlap trimming is not on", "n_values must be 1040", false},
+        {"post-trim counters", "post-trim", "post-trimming is not on", "n_values must be 32", false},
+        {"filter table", "filter", "the read filter is not on", "n_values must be (2*S+1)*8", true},
+        {"screen counters", "screen", "the k-mer screen is not on", "n_values must be (2*S+1)*8", true},
+        {"quality counters", "quality counters", "the quality counters are not enabled", "n_values must be (2*S+1)*12", true},
+        {"cycle counters", "cycle counters", "the cycle counters are not enabled", "n_values must be QD_CS_VALUES", false},
+        {"duplication counters", "duplication tally", "the duplication tally is not on", "n_values must be (2*S+1)*5", true},
+    };
+    // The stages' parameters as given (qd_*_set) and as the kernels take them; a stage that is off holds the off values (stage_off).
+    qd_clip_params clip{};  // end clipping, window and poly-G trimming of the insert reads
     qd_clip_dev clip_dev{};
-    u64* d_clip = nullptr;
-    // 3' trimming of the insert reads (qd_trim_set): the parameters as given and as the kernel takes them, and the counters
-    // uint64[2][8]; d_trim == nullptr = off
-    qd_trim_params trim{};
+    qd_trim_params trim{};  // 3' trimming of the insert reads
     qd_trim_dev trim_dev{};
-    u64* d_trim = nullptr;
-
-    // paired-end overlap trimming with insert sizes (qd_pairtrim_set): the parameters as given and as the kernel takes them, and
-    // the table uint64[1040]; d_pairtrim == nullptr = off
-    qd_pairtrim_params pairtrim{};
+    qd_pairtrim_params pairtrim{};  // paired-end overlap trimming with insert sizes
     qd_pairtrim_dev pairtrim_dev{};
-    u64* d_pairtrim = nullptr;
-
-    // trailing-N, poly-X and max_length trimming behind the three stages above (qd_posttrim_set): the parameters as given and as
-    // the kernel takes them, and the counters uint64[2][16]; d_posttrim == nullptr = off
-    qd_posttrim_params posttrim{};
+    qd_posttrim_params posttrim{};  // trailing-N, poly-X and max_length trimming behind the three stages above
     qd_posttrim_dev posttrim_dev{};
-    u64* d_posttrim = nullptr;
-
-    // read filtering (qd_filter_set): the parameters as given and as the kernel takes them, and the table
-    // uint64[(2 * S + 1)][8]; d_filter == nullptr = off
-    qd_filter_params filter{-1, -1, -1, 15, -1, -1};
-    qd_filter_dev filter_dev{-1, -1, -1, 33 + 15, -1, -1};
-    u64* d_filter = nullptr;
-
-    // k-mer screen against a reference (qd_screen_set): the parameters as given and as the kernel takes them, the reference's
-    // hash table (1 << screen_dev.slots_lg words) and the counters uint64[(2 * S + 1)][8]; d_screen == nullptr = off
+    qd_filter_params filter = FILTER_OFF;  // read filtering
+    qd_filter_dev filter_dev = filter_dev_of(FILTER_OFF);
+    // k-mer screen against a reference: besides the parameters the reference's hash table (1 << screen_dev.slots_lg words)
     qd_screen_params screen{};
     qd_screen_dev screen_dev{};
     int64_t screen_kmers = 0;
     u64* d_screen_slots = nullptr;
-    u64* d_screen = nullptr;
-
-    // duplication tally (qd_dup_set): the parameters as given and as the kernels take them, the counters
-    // uint64[(2 * S + 1)][5] (d_dup == nullptr = off), and the key tally; per stream its scratch is the batch list,
-    // qd_dup_list_bytes(pairs) bytes (quade_dup.h)
-    qd_dup_params dup{0, 0, 0};
-    qd_dup_dev dup_dev{0, 0};
-    u64* d_dup = nullptr;
+    // duplication tally: besides the parameters the key tally; per stream its scratch is the batch list, qd_dup_list_bytes(pairs)
+    // bytes (quade_dup.h)
+    qd_dup_params dup{};
+    qd_dup_dev dup_dev{};
     KeyTally dup_keys;
 
-    // index-hopping matrix (qd_hop_enable): the table uint64[(hop_n1 + 1) * (hop_n2 + 1) + 1] (d_hop == nullptr = off), the two
+    // index-hopping matrix (qd_hop_enable): the table uint64[(hop_n1 + 1) * (hop_n2 + 1) + 1] (hop.d == nullptr = off), the two
     // part lookup tables in one allocation (slots of part 1, slots of part 2, then their key words), and per stream a list of
     // a batch's undetermined pairs (pairs + 4 uint32 entries) for the launches that neither rescue nor tally
-    u64* d_hop = nullptr;
+    StageTable hop{"index-hopping matrix", nullptr, "the index-hopping matrix is not enabled", "n_values must be (n1+1)*(n2+1)+1", true};
     void* d_hop_parts = nullptr;
     HopPart hop_part[2]{};
     int32_t hop_n1 = 0, hop_n2 = 0;
@@ -507,48 +515,111 @@ int launch_mismatch(qd_ctx* c, int64_t n, const qd_rows* rows, uint16_t* codes, 
     return QD_OK;
 }
 
-// ---- the read stages (qstats, cstats, clip, trim, pairtrim, posttrim, filter): their tables and the harness of their qd_dev_* entries ----
+// ---- the read stages (StageId): their tables' lifecycle, the harness of their qd_*_device launches and of their qd_dev_* entries ----
 
-// a stage's table: n_values 64-bit counters on the device, zero
-int table_alloc(qd_ctx* c, u64*& t, size_t n_values, const char* what) {
-    hipError_t e = uk_malloc(reinterpret_cast<void**>(&t), n_values * 8);
+// T on: n_values 64-bit counters on the device, zero
+int table_alloc(qd_ctx* c, StageTable& T, size_t n_values) {
+    hipError_t e = uk_malloc(reinterpret_cast<void**>(&T.d), n_values * 8);
     if (e != hipSuccess) {
-        t = nullptr;
-        return fail(c, QD_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+        T.d = nullptr;
+        return fail(c, QD_ERR_HIP, std::string(T.what) + ": " + hipGetErrorString(e));
     }
-    HIPCHK(c, hipMemsetAsync(t, 0, n_values * 8, c->stream));
+    T.n_values = n_values;
+    HIPCHK(c, hipMemsetAsync(T.d, 0, n_values * 8, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return QD_OK;
 }
 
 // (the caller waited for the context's work)
-void table_free(u64*& t) {
-    if (t) (void)hipFree(t);
-    t = nullptr;
+void table_free(StageTable& T) {
+    if (T.d) (void)hipFree(T.d);
+    T.d = nullptr;
+    T.n_values = 0;
 }
 
-// qd_*_read: off_text when the stage is off (t == nullptr), size_text when n_values is not the table's n_expected
-int table_read(qd_ctx* c, const u64* t, size_t n_expected, uint64_t* out, int64_t n_values, const char* off_text, const char* size_text) {
+// qd_*_read
+int table_read(qd_ctx* c, const StageTable& T, uint64_t* out, int64_t n_values) {
     if (!out) return QD_ERR_INVALID;
-    if (!t) return fail(c, QD_ERR_STATE, off_text);
-    if (n_values != (int64_t)n_expected) return fail(c, QD_ERR_INVALID, size_text);
+    if (!T.d) return fail(c, QD_ERR_STATE, T.off_text);
+    if (n_values != (int64_t)T.n_values) return fail(c, QD_ERR_INVALID, T.size_text);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, wait_all(c));
-    HIPCHK(c, hipMemcpy(out, t, n_expected * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out, T.d, T.n_values * 8, hipMemcpyDeviceToHost));
     return QD_OK;
 }
 
 // qd_*_add: another context's table joins this one
-int table_add(qd_ctx* c, u64* t, size_t n_expected, const uint64_t* values, int64_t n_values, const char* off_text, const char* size_text) {
+int table_add(qd_ctx* c, const StageTable& T, const uint64_t* values, int64_t n_values) {
     if (!values) return QD_ERR_INVALID;
-    if (!t) return fail(c, QD_ERR_STATE, off_text);
-    if (n_values != (int64_t)n_expected) return fail(c, QD_ERR_INVALID, size_text);
+    if (!T.d) return fail(c, QD_ERR_STATE, T.off_text);
+    if (n_values != (int64_t)T.n_values) return fail(c, QD_ERR_INVALID, T.size_text);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, wait_all(c));  // the kernels add to the table: nothing of this context may be in flight
-    std::vector<u64> h(n_expected);
-    HIPCHK(c, hipMemcpy(h.data(), t, h.size() * 8, hipMemcpyDeviceToHost));
+    std::vector<u64> h(T.n_values);
+    HIPCHK(c, hipMemcpy(h.data(), T.d, h.size() * 8, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < h.size(); ++i) h[i] += values[i];
-    HIPCHK(c, hipMemcpy(t, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(T.d, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+    return QD_OK;
+}
+
+// a stage off: its table freed, its parameters at their off values, and what screen and dup hold besides (the caller waited for
+// the context's work)
+void stage_off(qd_ctx* c, int id) {
+    table_free(c->stage[id]);
+    switch (id) {
+        case ST_CLIP: c->clip = {}; c->clip_dev = {}; break;
+        case ST_TRIM: c->trim = {}; c->trim_dev = {}; break;
+        case ST_PAIRTRIM: c->pairtrim = {}; c->pairtrim_dev = {}; break;
+        case ST_POSTTRIM: c->posttrim = {}; c->posttrim_dev = {}; break;
+        case ST_FILTER: c->filter = FILTER_OFF; c->filter_dev = filter_dev_of(FILTER_OFF); break;
+        case ST_SCREEN:
+            c->screen = {}; c->screen_dev = {};
+            if (c->d_screen_slots) (void)hipFree(c->d_screen_slots);
+            c->d_screen_slots = nullptr;
+            c->screen_kmers = 0;
+            break;
+        case ST_DUP:
+            c->dup = {}; c->dup_dev = {};
+            tally_close(c->dup_keys);
+            break;
+        default: break;  // qstats, cstats: a table and nothing else
+    }
+}
+
+// whether any stage is on, or any of those whose tables have a row per destination
+bool stages_on(const qd_ctx* c, bool per_destination_only) {
+    for (const StageTable& T : c->stage)
+        if (T.d && (T.per_destination || !per_destination_only)) return true;
+    return false;
+}
+
+// every stage off, or those only whose tables have a row per destination (the caller waited for the context's work)
+void stages_off(qd_ctx* c, bool per_destination_only) {
+    for (int id = 0; id < ST_COUNT; ++id)
+        if (c->stage[id].per_destination || !per_destination_only) stage_off(c, id);
+}
+
+// What every qd_*_enable and qd_*_set does behind its own checks: the stage goes off, and when it is to be on its table of n_values
+// is allocated.  The caller stores the parameters behind QD_OK with `on`.
+int stage_install(qd_ctx* c, int id, bool on, size_t n_values) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));  // nothing of this context may still read the old parameters or add to the old table
+    stage_off(c, id);
+    return on ? table_alloc(c, c->stage[id], n_values) : QD_OK;
+}
+
+// What every qd_*_device does around its launch: launch(table, stream) fills the stage's qd_*_args and launches.  A stage that is off
+// is an error with its off text (off_is_error) or has nothing to do.
+template <typename LAUNCH>
+int stage_launch(qd_ctx* c, int id, bool off_is_error, uint32_t n, void* stream, LAUNCH launch) {
+    if (!c) return QD_ERR_INVALID;
+    const StageTable& T = c->stage[id];
+    if (!T.d) return off_is_error ? fail(c, QD_ERR_STATE, T.off_text) : QD_OK;
+    if (!n) return QD_OK;
+    hipStream_t st = resolve_stream(c, stream);
+    hipError_t e = launch(T.d, st);
+    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string(T.launch) + " launch: " + hipGetErrorString(e));
+    HIPCHK(c, track(c, st));
     return QD_OK;
 }
 
@@ -662,6 +733,20 @@ private:
     uint32_t* h_hits = nullptr;
 };
 
+// qd_dev_clip, qd_dev_trim, qd_dev_pairtrim, qd_dev_posttrim: the stages that write new record tables, whose qd_*_device have one
+// signature
+typedef int (*rewrite_device_fn)(qd_ctx*, const uint8_t*, const qd_rec*, const uint8_t*, const qd_rec*, uint32_t, qd_rec*, qd_rec*, void*);
+int dev_rewrite(qd_ctx* c, int id, rewrite_device_fn device, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2,
+                int64_t len2, const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->stage[id].d) return fail(c, QD_ERR_STATE, c->stage[id].off_text);
+    PairUpload up(c);
+    const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::OUT_RECS, nullptr, nullptr, out_recs1, out_recs2,
+                           nullptr);
+    if (rc != QD_OK || up.empty()) return rc;
+    return up.close(device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), up.out(0), up.out(1), QD_STREAM_CONTEXT));
+}
+
 // the tally off and its memory freed (the caller waited for the context's work)
 void free_unknown(qd_ctx* c) {
     tally_close(c->uk);
@@ -739,7 +824,7 @@ size_t hop_values(const qd_ctx* c) { return (size_t)(c->hop_n1 + 1) * (size_t)(c
 
 // the matrix off and its memory freed (the caller waited for the context's work)
 void free_hop(qd_ctx* c) {
-    table_free(c->d_hop);
+    table_free(c->hop);
     if (c->d_hop_parts) (void)hipFree(c->d_hop_parts);
     c->d_hop_parts = nullptr;
     c->hop_n1 = c->hop_n2 = 0;
@@ -772,7 +857,7 @@ int launch_hop(qd_ctx* c, int64_t n, const qd_rows* rows, const uint16_t* codes,
     }
     p.codes = codes;
     p.miss = list;
-    p.table = c->d_hop;
+    p.table = c->hop.d;
     p.n = n;
     p.K = L.key_width;
     p.n1 = (uint32_t)c->hop_n1;
@@ -782,66 +867,17 @@ int launch_hop(qd_ctx* c, int64_t n, const qd_rows* rows, const uint16_t* codes,
     return QD_OK;
 }
 
-// the quality counters off and their table freed (the caller waited for the context's work)
-void free_qstats(qd_ctx* c) {
-    table_free(c->d_qs);
-}
-
-// the per-cycle counters off and their table freed (the caller waited for the context's work)
-void free_cstats(qd_ctx* c) {
-    table_free(c->d_cs);
-}
-
-// clipping off and its table freed (the caller waited for the context's work)
-void free_clip(qd_ctx* c) {
-    table_free(c->d_clip);
-    c->clip = qd_clip_params{};
-    c->clip_dev = qd_clip_dev{};
-}
-
-// trimming off and its table freed (the caller waited for the context's work)
-void free_trim(qd_ctx* c) {
-    table_free(c->d_trim);
-    c->trim = qd_trim_params{};
-    c->trim_dev = qd_trim_dev{};
-}
-
-// overlap trimming off and its table freed (the caller waited for the context's work)
-void free_pairtrim(qd_ctx* c) {
-    table_free(c->d_pairtrim);
-    c->pairtrim = qd_pairtrim_params{};
-    c->pairtrim_dev = qd_pairtrim_dev{};
-}
-
-// post-trimming off and its table freed (the caller waited for the context's work)
-void free_posttrim(qd_ctx* c) {
-    table_free(c->d_posttrim);
-    c->posttrim = qd_posttrim_params{};
-    c->posttrim_dev = qd_posttrim_dev{};
-}
-
-// read filtering off and its table freed (the caller waited for the context's work)
-void free_filter(qd_ctx* c) {
-    table_free(c->d_filter);
-    c->filter = qd_filter_params{-1, -1, -1, 15, -1, -1};
-    c->filter_dev = qd_filter_dev{-1, -1, -1, 33 + 15, -1, -1};
-}
-
-// the k-mer screen off, its hash table and its counters freed (the caller waited for the context's work)
-void free_screen(qd_ctx* c) {
-    table_free(c->d_screen);
-    table_free(c->d_screen_slots);
-    c->screen = qd_screen_params{};
-    c->screen_dev = qd_screen_dev{};
-    c->screen_kmers = 0;
-}
-
-// the duplication tally off and its memory freed (the caller waited for the context's work)
-void free_dup(qd_ctx* c) {
-    table_free(c->d_dup);
-    tally_close(c->dup_keys);
-    c->dup = qd_dup_params{0, 0, 0};
-    c->dup_dev = qd_dup_dev{0, 0};
+// What a new plan and new barcodes do first: the mismatch budgets are reset, as the counters are, and everything with a row or a key
+// per destination goes off -- the unknown tally, the index-hopping matrix and the read stages whose tables say so
+int destinations_change(qd_ctx* c) {
+    if (!(c->mm_m1 + c->mm_m2 > 0 || c->uk.mem || c->hop.d || stages_on(c, true))) return QD_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, wait_all(c));
+    free_mismatch(c, false);
+    free_unknown(c);
+    free_hop(c);
+    stages_off(c, true);
+    return QD_OK;
 }
 
 // (re)build the device table from the host barcodes and the current plan
@@ -1116,7 +1152,7 @@ int launch(qd_ctx* c, int64_t n, const qd_rows* rows, uint16_t* codes, uint8_t* 
         const int r = launch_unknown(c, n, rows, codes, st, c->mm_m1 + c->mm_m2 > 0);
         if (r != QD_OK) return r;
     }
-    if (c->d_hop) {  // opt-in index-hopping matrix over the same pairs, behind both
+    if (c->hop.d) {  // opt-in index-hopping matrix over the same pairs, behind both
         const int r = launch_hop(c, n, rows, codes, st, c->mm_m1 + c->mm_m2 > 0, c->uk.mem != nullptr);
         if (r != QD_OK) return r;
     }
@@ -1199,15 +1235,7 @@ int qd_destroy(qd_ctx* c) {
     free_mismatch(c, true);
     free_unknown(c);
     free_hop(c);
-    free_qstats(c);
-    free_cstats(c);
-    free_clip(c);
-    free_trim(c);
-    free_pairtrim(c);
-    free_posttrim(c);
-    free_filter(c);
-    free_screen(c);
-    free_dup(c);
+    stages_off(c, false);
     for (auto& t : c->tracked) (void)hipEventDestroy(t.second);
     c->tracked.clear();
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1230,17 +1258,8 @@ int qd_set_plan(qd_ctx* c, const qd_plan* plan) {
     if (r != QD_OK) return fail(c, r, "plan rejected: positions must satisfy 0 <= start <= end <= 255, window <= 64, "
                                        "fused barcode <= 32, 0 <= minimal_qual <= 40");
     if (!c->slots.empty()) return fail(c, QD_ERR_STATE, "destroy the slots before changing the plan");
-    if (c->mm_m1 + c->mm_m2 > 0 || c->uk.mem || c->d_hop || c->d_qs || c->d_filter || c->d_screen || c->d_dup) {  // a new plan resets the mismatch budgets and turns the unknown tally, the index-hopping matrix, the quality counters, the read filter, the k-mer screen and the duplication tally off
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, wait_all(c));
-        free_mismatch(c, false);
-        free_unknown(c);
-        free_hop(c);
-        free_qstats(c);
-        free_filter(c);
-        free_screen(c);
-        free_dup(c);
-    }
+    const int rc = destinations_change(c);
+    if (rc != QD_OK) return rc;
     c->plan = *plan;
     c->lay = L;
     c->have_plan = true;
@@ -1274,17 +1293,8 @@ int qd_set_barcodes(qd_ctx* c, int32_t S, const uint8_t* barcodes, const int32_t
     if (!c->have_plan) return fail(c, QD_ERR_STATE, "qd_set_plan first");
     for (int i = 0; i < S; ++i)
         if (offsets[i + 1] < offsets[i]) return fail(c, QD_ERR_INVALID, "offsets must be non-decreasing");
-    if (c->mm_m1 + c->mm_m2 > 0 || c->uk.mem || c->d_hop || c->d_qs || c->d_filter || c->d_screen || c->d_dup) {  // new barcodes reset the mismatch budgets, as they reset the counters, and turn the unknown tally, the index-hopping matrix, the quality counters, the read filter, the k-mer screen and the duplication tally off
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, wait_all(c));
-        free_mismatch(c, false);
-        free_unknown(c);
-        free_hop(c);
-        free_qstats(c);
-        free_filter(c);
-        free_screen(c);
-        free_dup(c);
-    }
+    const int rc = destinations_change(c);
+    if (rc != QD_OK) return rc;
     c->S = S;
     c->bc.assign(barcodes, barcodes + (S ? offsets[S] : 0));
     c->bc_off.assign(offsets, offsets + (S ? S + 1 : 0));
@@ -1433,7 +1443,7 @@ int qd_hop_enable(qd_ctx* c, int32_t on) {
     }
     c->hop_n1 = n[0];
     c->hop_n2 = n[1];
-    int rc = e == hipSuccess ? table_alloc(c, c->d_hop, hop_values(c), "index-hopping matrix")
+    int rc = e == hipSuccess ? table_alloc(c, c->hop, hop_values(c))
                              : fail(c, QD_ERR_HIP, std::string("index-hopping part tables: ") + hipGetErrorString(e));
     if (rc != QD_OK) free_hop(c);
     return rc;
@@ -1441,7 +1451,7 @@ int qd_hop_enable(qd_ctx* c, int32_t on) {
 
 int qd_hop_shape(const qd_ctx* c, int32_t* n1, int32_t* n2) {
     if (!c || !n1 || !n2) return QD_ERR_INVALID;
-    if (!c->d_hop) return fail(c, QD_ERR_STATE, "the index-hopping matrix is not enabled");
+    if (!c->hop.d) return fail(c, QD_ERR_STATE, c->hop.off_text);
     *n1 = c->hop_n1;
     *n2 = c->hop_n2;
     return QD_OK;
@@ -1449,60 +1459,46 @@ int qd_hop_shape(const qd_ctx* c, int32_t* n1, int32_t* n2) {
 
 int qd_hop_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
     if (!c) return QD_ERR_INVALID;
-    return table_read(c, c->d_hop, hop_values(c), out, n_values, "the index-hopping matrix is not enabled", "n_values must be (n1+1)*(n2+1)+1");
+    return table_read(c, c->hop, out, n_values);
 }
 
 int qd_hop_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
     if (!c) return QD_ERR_INVALID;
-    return table_add(c, c->d_hop, hop_values(c), values, n_values, "the index-hopping matrix is not enabled", "n_values must be (n1+1)*(n2+1)+1");
+    return table_add(c, c->hop, values, n_values);
 }
 
 int qd_qstats_enable(qd_ctx* c, int32_t on) {
     if (!c) return QD_ERR_INVALID;
     if (!c->have_plan || !c->have_table) return fail(c, QD_ERR_STATE, "qd_set_plan and qd_set_barcodes first");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));  // nothing of this context may still add to the old table
-    free_qstats(c);
-    if (!on) return QD_OK;
-    return table_alloc(c, c->d_qs, qd_qstats_values((uint32_t)c->S), "quality counters");
+    return stage_install(c, ST_QSTATS, on != 0, qd_qstats_values((uint32_t)c->S));
 }
 
 int qd_qstats_kind(const qd_ctx* c) {
     if (!c) return QD_ERR_INVALID;
-    if (!c->d_qs) return fail(c, QD_ERR_STATE, "the quality counters are not enabled");
+    if (!c->stage[ST_QSTATS].d) return fail(c, QD_ERR_STATE, c->stage[ST_QSTATS].off_text);
     return qd_qstats_path((uint32_t)c->S);
 }
 
-int qd_qstats_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
-    if (!c) return QD_ERR_INVALID;
-    return table_read(c, c->d_qs, qd_qstats_values((uint32_t)c->S), out, n_values, "the quality counters are not enabled", "n_values must be (2*S+1)*12");
-}
+int qd_qstats_read(qd_ctx* c, uint64_t* out, int64_t n_values) { return c ? table_read(c, c->stage[ST_QSTATS], out, n_values) : QD_ERR_INVALID; }
 
-int qd_qstats_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
-    if (!c) return QD_ERR_INVALID;
-    return table_add(c, c->d_qs, qd_qstats_values((uint32_t)c->S), values, n_values, "the quality counters are not enabled", "n_values must be (2*S+1)*12");
-}
+int qd_qstats_add(qd_ctx* c, const uint64_t* values, int64_t n_values) { return c ? table_add(c, c->stage[ST_QSTATS], values, n_values) : QD_ERR_INVALID; }
 
 int qd_qstats_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
                      const uint16_t* codes, const uint8_t* drop, void* stream) {
-    if (!c) return QD_ERR_INVALID;
-    if (!c->d_qs || !n) return QD_OK;
-    hipStream_t st = resolve_stream(c, stream);
-    qd_qstats_args a{};
-    fill_pair_args(a, text1, recs1, text2, recs2);
-    a.codes = codes;
-    a.drop = drop;
-    a.table = c->d_qs;
-    hipError_t e = qd_qstats_launch(a, (uint32_t)c->S, n, st);
-    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("quality counters launch: ") + hipGetErrorString(e));
-    HIPCHK(c, track(c, st));
-    return QD_OK;
+    return stage_launch(c, ST_QSTATS, false, n, stream, [&](u64* table, hipStream_t st) {
+        qd_qstats_args a{};
+        fill_pair_args(a, text1, recs1, text2, recs2);
+        a.codes = codes;
+        a.drop = drop;
+        a.table = table;
+        return qd_qstats_launch(a, (uint32_t)c->S, n, st);
+    });
 }
 
 int qd_dev_qstats(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                   const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes) {
     if (!c) return QD_ERR_INVALID;
-    if (!c->d_qs) return fail(c, QD_ERR_STATE, "the quality counters are not enabled");
+    if (!c->stage[ST_QSTATS].d) return fail(c, QD_ERR_STATE, c->stage[ST_QSTATS].off_text);
     PairUpload up(c);
     const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::CODES, codes, nullptr, nullptr, nullptr, nullptr);
     if (rc != QD_OK || up.empty()) return rc;
@@ -1511,45 +1507,31 @@ int qd_dev_qstats(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t*
 
 int qd_cstats_enable(qd_ctx* c, int32_t on) {
     if (!c) return QD_ERR_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));  // nothing of this context may still add to the old table
-    free_cstats(c);
-    if (!on) return QD_OK;
-    return table_alloc(c, c->d_cs, QD_CS_VALUES, "cycle counters");
+    return stage_install(c, ST_CSTATS, on != 0, QD_CS_VALUES);
 }
 
 int qd_cstats_lds_cycles(void) { return (int)QD_CS_LDS_CYCLES; }
 
-int qd_cstats_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
-    if (!c) return QD_ERR_INVALID;
-    return table_read(c, c->d_cs, QD_CS_VALUES, out, n_values, "the cycle counters are not enabled", "n_values must be QD_CS_VALUES");
-}
+int qd_cstats_read(qd_ctx* c, uint64_t* out, int64_t n_values) { return c ? table_read(c, c->stage[ST_CSTATS], out, n_values) : QD_ERR_INVALID; }
 
-int qd_cstats_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
-    if (!c) return QD_ERR_INVALID;
-    return table_add(c, c->d_cs, QD_CS_VALUES, values, n_values, "the cycle counters are not enabled", "n_values must be QD_CS_VALUES");
-}
+int qd_cstats_add(qd_ctx* c, const uint64_t* values, int64_t n_values) { return c ? table_add(c, c->stage[ST_CSTATS], values, n_values) : QD_ERR_INVALID; }
 
 int qd_cstats_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
                      const uint16_t* codes, const uint8_t* drop, void* stream) {
-    if (!c) return QD_ERR_INVALID;
-    if (!c->d_cs || !n) return QD_OK;
-    hipStream_t st = resolve_stream(c, stream);
-    qd_cstats_args a{};
-    fill_pair_args(a, text1, recs1, text2, recs2);
-    a.codes = codes;
-    a.drop = drop;
-    a.table = c->d_cs;
-    hipError_t e = qd_cstats_launch(a, n, st);
-    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("cycle counters launch: ") + hipGetErrorString(e));
-    HIPCHK(c, track(c, st));
-    return QD_OK;
+    return stage_launch(c, ST_CSTATS, false, n, stream, [&](u64* table, hipStream_t st) {
+        qd_cstats_args a{};
+        fill_pair_args(a, text1, recs1, text2, recs2);
+        a.codes = codes;
+        a.drop = drop;
+        a.table = table;
+        return qd_cstats_launch(a, n, st);
+    });
 }
 
 int qd_dev_cstats(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                   const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes, const uint8_t* drop) {
     if (!c) return QD_ERR_INVALID;
-    if (!c->d_cs) return fail(c, QD_ERR_STATE, "the cycle counters are not enabled");
+    if (!c->stage[ST_CSTATS].d) return fail(c, QD_ERR_STATE, c->stage[ST_CSTATS].off_text);
     PairUpload up(c);
     const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::CODES, codes, drop, nullptr, nullptr, nullptr);
     if (rc != QD_OK || up.empty()) return rc;
@@ -1583,12 +1565,8 @@ int qd_clip_set(qd_ctx* c, const qd_clip_params* params) {
         D.poly_g = (uint32_t)P.poly_g_min_length;
         D.min_length = (uint32_t)P.min_length;
     }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));  // nothing of this context may still read the old parameters or add to the old table
-    free_clip(c);
-    if (!on) return QD_OK;
-    const int rc = table_alloc(c, c->d_clip, QD_CLIP_TABLE, "clip counters");
-    if (rc != QD_OK) return rc;
+    const int rc = stage_install(c, ST_CLIP, on, QD_CLIP_TABLE);
+    if (rc != QD_OK || !on) return rc;
     c->clip = P;
     c->clip_dev = D;
     return QD_OK;
@@ -1600,44 +1578,27 @@ int qd_clip_get(const qd_ctx* c, qd_clip_params* out) {
     return QD_OK;
 }
 
-int qd_clip_active(const qd_ctx* c) { return c && c->d_clip ? 1 : 0; }
+int qd_clip_active(const qd_ctx* c) { return c && c->stage[ST_CLIP].d ? 1 : 0; }
 
-int qd_clip_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
-    if (!c) return QD_ERR_INVALID;
-    return table_read(c, c->d_clip, QD_CLIP_TABLE, out, n_values, "clipping is not on", "n_values must be 24");
-}
+int qd_clip_read(qd_ctx* c, uint64_t* out, int64_t n_values) { return c ? table_read(c, c->stage[ST_CLIP], out, n_values) : QD_ERR_INVALID; }
 
-int qd_clip_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
-    if (!c) return QD_ERR_INVALID;
-    return table_add(c, c->d_clip, QD_CLIP_TABLE, values, n_values, "clipping is not on", "n_values must be 24");
-}
+int qd_clip_add(qd_ctx* c, const uint64_t* values, int64_t n_values) { return c ? table_add(c, c->stage[ST_CLIP], values, n_values) : QD_ERR_INVALID; }
 
 int qd_clip_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
                    qd_rec* out1, qd_rec* out2, void* stream) {
-    if (!c) return QD_ERR_INVALID;
-    if (!c->d_clip) return fail(c, QD_ERR_STATE, "clipping is not on");
-    if (!n) return QD_OK;
-    hipStream_t st = resolve_stream(c, stream);
-    qd_clip_args a{};
-    fill_pair_args(a, text1, recs1, text2, recs2);
-    a.out[0] = out1;
-    a.out[1] = out2;
-    a.table = c->d_clip;
-    hipError_t e = qd_clip_launch(c->clip_dev, a, n, st);
-    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("clip launch: ") + hipGetErrorString(e));
-    HIPCHK(c, track(c, st));
-    return QD_OK;
+    return stage_launch(c, ST_CLIP, true, n, stream, [&](u64* table, hipStream_t st) {
+        qd_clip_args a{};
+        fill_pair_args(a, text1, recs1, text2, recs2);
+        a.out[0] = out1;
+        a.out[1] = out2;
+        a.table = table;
+        return qd_clip_launch(c->clip_dev, a, n, st);
+    });
 }
 
 int qd_dev_clip(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                 const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2) {
-    if (!c) return QD_ERR_INVALID;
-    if (!c->d_clip) return fail(c, QD_ERR_STATE, "clipping is not on");
-    PairUpload up(c);
-    const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::OUT_RECS, nullptr, nullptr, out_recs1, out_recs2,
-                           nullptr);
-    if (rc != QD_OK || up.empty()) return rc;
-    return up.close(qd_clip_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), up.out(0), up.out(1), QD_STREAM_CONTEXT));
+    return dev_rewrite(c, ST_CLIP, qd_clip_device, text1, len1, recs1, text2, len2, recs2, n_pairs, out_recs1, out_recs2);
 }
 
 int qd_trim_set(qd_ctx* c, const qd_trim_params* params) {
@@ -1673,12 +1634,8 @@ int qd_trim_set(qd_ctx* c, const qd_trim_params* params) {
         D.mismatch_pct = (uint32_t)P.max_mismatch_pct;
         D.min_length = (uint32_t)P.min_length;
     }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));  // nothing of this context may still read the old parameters or add to the old table
-    free_trim(c);
-    if (!on) return QD_OK;
-    const int rc = table_alloc(c, c->d_trim, QD_TRIM_VALUES, "trim counters");
-    if (rc != QD_OK) return rc;
+    const int rc = stage_install(c, ST_TRIM, on, QD_TRIM_VALUES);
+    if (rc != QD_OK || !on) return rc;
     c->trim = P;
     c->trim_dev = D;
     return QD_OK;
@@ -1690,44 +1647,27 @@ int qd_trim_get(const qd_ctx* c, qd_trim_params* out) {
     return QD_OK;
 }
 
-int qd_trim_active(const qd_ctx* c) { return c && c->d_trim ? 1 : 0; }
+int qd_trim_active(const qd_ctx* c) { return c && c->stage[ST_TRIM].d ? 1 : 0; }
 
-int qd_trim_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
-    if (!c) return QD_ERR_INVALID;
-    return table_read(c, c->d_trim, QD_TRIM_VALUES, out, n_values, "trimming is not on", "n_values must be 16");
-}
+int qd_trim_read(qd_ctx* c, uint64_t* out, int64_t n_values) { return c ? table_read(c, c->stage[ST_TRIM], out, n_values) : QD_ERR_INVALID; }
 
-int qd_trim_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
-    if (!c) return QD_ERR_INVALID;
-    return table_add(c, c->d_trim, QD_TRIM_VALUES, values, n_values, "trimming is not on", "n_values must be 16");
-}
+int qd_trim_add(qd_ctx* c, const uint64_t* values, int64_t n_values) { return c ? table_add(c, c->stage[ST_TRIM], values, n_values) : QD_ERR_INVALID; }
 
 int qd_trim_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
                    qd_rec* out1, qd_rec* out2, void* stream) {
-    if (!c) return QD_ERR_INVALID;
-    if (!c->d_trim) return fail(c, QD_ERR_STATE, "trimming is not on");
-    if (!n) return QD_OK;
-    hipStream_t st = resolve_stream(c, stream);
-    qd_trim_args a{};
-    fill_pair_args(a, text1, recs1, text2, recs2);
-    a.out[0] = out1;
-    a.out[1] = out2;
-    a.table = c->d_trim;
-    hipError_t e = qd_trim_launch(c->trim_dev, a, n, st);
-    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("trim launch: ") + hipGetErrorString(e));
-    HIPCHK(c, track(c, st));
-    return QD_OK;
+    return stage_launch(c, ST_TRIM, true, n, stream, [&](u64* table, hipStream_t st) {
+        qd_trim_args a{};
+        fill_pair_args(a, text1, recs1, text2, recs2);
+        a.out[0] = out1;
+        a.out[1] = out2;
+        a.table = table;
+        return qd_trim_launch(c->trim_dev, a, n, st);
+    });
 }
 
 int qd_dev_trim(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                 const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2) {
-    if (!c) return QD_ERR_INVALID;
-    if (!c->d_trim) return fail(c, QD_ERR_STATE, "trimming is not on");
-    PairUpload up(c);
-    const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::OUT_RECS, nullptr, nullptr, out_recs1, out_recs2,
-                           nullptr);
-    if (rc != QD_OK || up.empty()) return rc;
-    return up.close(qd_trim_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), up.out(0), up.out(1), QD_STREAM_CONTEXT));
+    return dev_rewrite(c, ST_TRIM, qd_trim_device, text1, len1, recs1, text2, len2, recs2, n_pairs, out_recs1, out_recs2);
 }
 
 static_assert(QD_PAIRTRIM_VALUES == QD_PT_VALUES, "the public table size is the kernel's");
@@ -1747,12 +1687,8 @@ int qd_pairtrim_set(qd_ctx* c, const qd_pairtrim_params* params) {
         D.mismatch_pct = (uint32_t)P.max_mismatch_pct;
         D.min_length = (uint32_t)P.min_length;
     }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));  // nothing of this context may still read the old parameters or add to the old table
-    free_pairtrim(c);
-    if (!params) return QD_OK;
-    const int rc = table_alloc(c, c->d_pairtrim, QD_PT_VALUES, "overlap trimming table");
-    if (rc != QD_OK) return rc;
+    const int rc = stage_install(c, ST_PAIRTRIM, params, QD_PT_VALUES);
+    if (rc != QD_OK || !params) return rc;
     c->pairtrim = P;
     c->pairtrim_dev = D;
     return QD_OK;
@@ -1764,44 +1700,27 @@ int qd_pairtrim_get(const qd_ctx* c, qd_pairtrim_params* out) {
     return QD_OK;
 }
 
-int qd_pairtrim_active(const qd_ctx* c) { return c && c->d_pairtrim ? 1 : 0; }
+int qd_pairtrim_active(const qd_ctx* c) { return c && c->stage[ST_PAIRTRIM].d ? 1 : 0; }
 
-int qd_pairtrim_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
-    if (!c) return QD_ERR_INVALID;
-    return table_read(c, c->d_pairtrim, QD_PT_VALUES, out, n_values, "overlap trimming is not on", "n_values must be 1040");
-}
+int qd_pairtrim_read(qd_ctx* c, uint64_t* out, int64_t n_values) { return c ? table_read(c, c->stage[ST_PAIRTRIM], out, n_values) : QD_ERR_INVALID; }
 
-int qd_pairtrim_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
-    if (!c) return QD_ERR_INVALID;
-    return table_add(c, c->d_pairtrim, QD_PT_VALUES, values, n_values, "overlap trimming is not on", "n_values must be 1040");
-}
+int qd_pairtrim_add(qd_ctx* c, const uint64_t* values, int64_t n_values) { return c ? table_add(c, c->stage[ST_PAIRTRIM], values, n_values) : QD_ERR_INVALID; }
 
 int qd_pairtrim_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
                        qd_rec* out1, qd_rec* out2, void* stream) {
-    if (!c) return QD_ERR_INVALID;
-    if (!c->d_pairtrim) return fail(c, QD_ERR_STATE, "overlap trimming is not on");
-    if (!n) return QD_OK;
-    hipStream_t st = resolve_stream(c, stream);
-    qd_pairtrim_args a{};
-    fill_pair_args(a, text1, recs1, text2, recs2);
-    a.out[0] = out1;
-    a.out[1] = out2;
-    a.table = c->d_pairtrim;
-    hipError_t e = qd_pairtrim_launch(c->pairtrim_dev, a, n, st);
-    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("overlap trimming launch: ") + hipGetErrorString(e));
-    HIPCHK(c, track(c, st));
-    return QD_OK;
+    return stage_launch(c, ST_PAIRTRIM, true, n, stream, [&](u64* table, hipStream_t st) {
+        qd_pairtrim_args a{};
+        fill_pair_args(a, text1, recs1, text2, recs2);
+        a.out[0] = out1;
+        a.out[1] = out2;
+        a.table = table;
+        return qd_pairtrim_launch(c->pairtrim_dev, a, n, st);
+    });
 }
 
 int qd_dev_pairtrim(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                     const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2) {
-    if (!c) return QD_ERR_INVALID;
-    if (!c->d_pairtrim) return fail(c, QD_ERR_STATE, "overlap trimming is not on");
-    PairUpload up(c);
-    const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::OUT_RECS, nullptr, nullptr, out_recs1, out_recs2,
-                           nullptr);
-    if (rc != QD_OK || up.empty()) return rc;
-    return up.close(qd_pairtrim_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), up.out(0), up.out(1), QD_STREAM_CONTEXT));
+    return dev_rewrite(c, ST_PAIRTRIM, qd_pairtrim_device, text1, len1, recs1, text2, len2, recs2, n_pairs, out_recs1, out_recs2);
 }
 
 static_assert(QD_POSTTRIM_VALUES == QD_POST_TABLE, "the public table size is the kernel's");
@@ -1825,12 +1744,8 @@ int qd_posttrim_set(qd_ctx* c, const qd_posttrim_params* params) {
         D.poly_x = (uint32_t)P.poly_x_min_length;
         D.min_length = (uint32_t)P.min_length;
     }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));  // nothing of this context may still read the old parameters or add to the old table
-    free_posttrim(c);
-    if (!on) return QD_OK;
-    const int rc = table_alloc(c, c->d_posttrim, QD_POST_TABLE, "post-trim counters");
-    if (rc != QD_OK) return rc;
+    const int rc = stage_install(c, ST_POSTTRIM, on, QD_POST_TABLE);
+    if (rc != QD_OK || !on) return rc;
     c->posttrim = P;
     c->posttrim_dev = D;
     return QD_OK;
@@ -1842,55 +1757,38 @@ int qd_posttrim_get(const qd_ctx* c, qd_posttrim_params* out) {
     return QD_OK;
 }
 
-int qd_posttrim_active(const qd_ctx* c) { return c && c->d_posttrim ? 1 : 0; }
+int qd_posttrim_active(const qd_ctx* c) { return c && c->stage[ST_POSTTRIM].d ? 1 : 0; }
 
-int qd_posttrim_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
-    if (!c) return QD_ERR_INVALID;
-    return table_read(c, c->d_posttrim, QD_POST_TABLE, out, n_values, "post-trimming is not on", "n_values must be 32");
-}
+int qd_posttrim_read(qd_ctx* c, uint64_t* out, int64_t n_values) { return c ? table_read(c, c->stage[ST_POSTTRIM], out, n_values) : QD_ERR_INVALID; }
 
-int qd_posttrim_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
-    if (!c) return QD_ERR_INVALID;
-    return table_add(c, c->d_posttrim, QD_POST_TABLE, values, n_values, "post-trimming is not on", "n_values must be 32");
-}
+int qd_posttrim_add(qd_ctx* c, const uint64_t* values, int64_t n_values) { return c ? table_add(c, c->stage[ST_POSTTRIM], values, n_values) : QD_ERR_INVALID; }
 
 int qd_posttrim_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
                        qd_rec* out1, qd_rec* out2, void* stream) {
-    if (!c) return QD_ERR_INVALID;
-    if (!c->d_posttrim) return fail(c, QD_ERR_STATE, "post-trimming is not on");
-    if (!n) return QD_OK;
-    hipStream_t st = resolve_stream(c, stream);
-    qd_posttrim_args a{};
-    fill_pair_args(a, text1, recs1, text2, recs2);
-    a.out[0] = out1;
-    a.out[1] = out2;
-    a.table = c->d_posttrim;
-    hipError_t e = qd_posttrim_launch(c->posttrim_dev, a, n, st);
-    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("post-trim launch: ") + hipGetErrorString(e));
-    HIPCHK(c, track(c, st));
-    return QD_OK;
+    return stage_launch(c, ST_POSTTRIM, true, n, stream, [&](u64* table, hipStream_t st) {
+        qd_posttrim_args a{};
+        fill_pair_args(a, text1, recs1, text2, recs2);
+        a.out[0] = out1;
+        a.out[1] = out2;
+        a.table = table;
+        return qd_posttrim_launch(c->posttrim_dev, a, n, st);
+    });
 }
 
 int qd_dev_posttrim(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                     const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2) {
-    if (!c) return QD_ERR_INVALID;
-    if (!c->d_posttrim) return fail(c, QD_ERR_STATE, "post-trimming is not on");
-    PairUpload up(c);
-    const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::OUT_RECS, nullptr, nullptr, out_recs1, out_recs2,
-                           nullptr);
-    if (rc != QD_OK || up.empty()) return rc;
-    return up.close(qd_posttrim_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), up.out(0), up.out(1), QD_STREAM_CONTEXT));
+    return dev_rewrite(c, ST_POSTTRIM, qd_posttrim_device, text1, len1, recs1, text2, len2, recs2, n_pairs, out_recs1, out_recs2);
 }
 
 static_assert(QD_FILTER_VALUES == QD_FL_VALUES, "the public table width is the kernel's");
 
 int qd_filter_set(qd_ctx* c, const qd_filter_params* params) {
     if (!c) return QD_ERR_INVALID;
-    qd_filter_params P{-1, -1, -1, 15, -1, -1};
+    qd_filter_params P = FILTER_OFF;
     bool on = false;
     if (params) {  // checked as the configuration file's values are, before anything changes
         P = *params;
-        if (P.qualified_quality == -1) P.qualified_quality = 15;
+        if (P.qualified_quality == -1) P.qualified_quality = FILTER_OFF.qualified_quality;
         if (P.min_length != -1 && (P.min_length < 1 || P.min_length > 100000)) return fail(c, QD_ERR_INVALID, "filter min_length: 1 to 100000 (-1: off)");
         if (P.max_n != -1 && (P.max_n < 0 || P.max_n > 100000)) return fail(c, QD_ERR_INVALID, "filter max_n: 0 to 100000 (-1: off)");
         if (P.max_unqualified_pct != -1 && (P.max_unqualified_pct < 0 || P.max_unqualified_pct > 100))
@@ -1902,14 +1800,10 @@ int qd_filter_set(qd_ctx* c, const qd_filter_params* params) {
         on = P.min_length >= 0 || P.max_n >= 0 || P.max_unqualified_pct >= 0 || P.min_mean_quality >= 0 || P.min_complexity_pct >= 0;
     }
     if (on && (!c->have_plan || !c->have_table)) return fail(c, QD_ERR_STATE, "qd_set_plan and qd_set_barcodes first");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));  // nothing of this context may still read the old parameters or add to the old table
-    free_filter(c);
-    if (!on) return QD_OK;
-    const int rc = table_alloc(c, c->d_filter, qd_filter_values((uint32_t)c->S), "filter table");
-    if (rc != QD_OK) return rc;
+    const int rc = stage_install(c, ST_FILTER, on, qd_filter_values((uint32_t)c->S));
+    if (rc != QD_OK || !on) return rc;
     c->filter = P;
-    c->filter_dev = qd_filter_dev{P.min_length, P.max_n, P.max_unqualified_pct, 33 + P.qualified_quality, P.min_mean_quality, P.min_complexity_pct};
+    c->filter_dev = filter_dev_of(P);
     return QD_OK;
 }
 
@@ -1919,45 +1813,34 @@ int qd_filter_get(const qd_ctx* c, qd_filter_params* out) {
     return QD_OK;
 }
 
-int qd_filter_active(const qd_ctx* c) { return c && c->d_filter ? 1 : 0; }
+int qd_filter_active(const qd_ctx* c) { return c && c->stage[ST_FILTER].d ? 1 : 0; }
 
 int qd_filter_kind(const qd_ctx* c) {
     if (!c) return QD_ERR_INVALID;
-    if (!c->d_filter) return fail(c, QD_ERR_STATE, "the read filter is not on");
+    if (!c->stage[ST_FILTER].d) return fail(c, QD_ERR_STATE, c->stage[ST_FILTER].off_text);
     return qd_filter_path((uint32_t)c->S);
 }
 
-int qd_filter_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
-    if (!c) return QD_ERR_INVALID;
-    return table_read(c, c->d_filter, qd_filter_values((uint32_t)c->S), out, n_values, "the read filter is not on", "n_values must be (2*S+1)*8");
-}
+int qd_filter_read(qd_ctx* c, uint64_t* out, int64_t n_values) { return c ? table_read(c, c->stage[ST_FILTER], out, n_values) : QD_ERR_INVALID; }
 
-int qd_filter_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
-    if (!c) return QD_ERR_INVALID;
-    return table_add(c, c->d_filter, qd_filter_values((uint32_t)c->S), values, n_values, "the read filter is not on", "n_values must be (2*S+1)*8");
-}
+int qd_filter_add(qd_ctx* c, const uint64_t* values, int64_t n_values) { return c ? table_add(c, c->stage[ST_FILTER], values, n_values) : QD_ERR_INVALID; }
 
 int qd_filter_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
                      const uint16_t* codes, uint8_t* reason, void* stream) {
-    if (!c) return QD_ERR_INVALID;
-    if (!c->d_filter) return fail(c, QD_ERR_STATE, "the read filter is not on");
-    if (!n) return QD_OK;
-    hipStream_t st = resolve_stream(c, stream);
-    qd_filter_args a{};
-    fill_pair_args(a, text1, recs1, text2, recs2);
-    a.codes = codes;
-    a.reason = reason;
-    a.table = c->d_filter;
-    hipError_t e = qd_filter_launch(c->filter_dev, a, (uint32_t)c->S, n, st);
-    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("filter launch: ") + hipGetErrorString(e));
-    HIPCHK(c, track(c, st));
-    return QD_OK;
+    return stage_launch(c, ST_FILTER, true, n, stream, [&](u64* table, hipStream_t st) {
+        qd_filter_args a{};
+        fill_pair_args(a, text1, recs1, text2, recs2);
+        a.codes = codes;
+        a.reason = reason;
+        a.table = table;
+        return qd_filter_launch(c->filter_dev, a, (uint32_t)c->S, n, st);
+    });
 }
 
 int qd_dev_filter(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                   const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes, uint8_t* reasons) {
     if (!c) return QD_ERR_INVALID;
-    if (!c->d_filter) return fail(c, QD_ERR_STATE, "the read filter is not on");
+    if (!c->stage[ST_FILTER].d) return fail(c, QD_ERR_STATE, c->stage[ST_FILTER].off_text);
     PairUpload up(c);
     const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::CODES | PairUpload::REASONS, codes, nullptr,
                            nullptr, nullptr, reasons);
@@ -2006,15 +1889,13 @@ int qd_screen_set(qd_ctx* c, const qd_screen_params* params, const uint64_t* kme
             slots[s] = kmers[i];
         }
     }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));  // nothing of this context may still read the old table or add to the old counters
-    free_screen(c);
-    if (!on) return QD_OK;
-    int rc = table_alloc(c, c->d_screen, qd_screen_values((uint32_t)c->S), "screen counters");
-    if (rc == QD_OK) rc = table_alloc(c, c->d_screen_slots, slots.size(), "screen hash table");
-    if (rc != QD_OK) {
-        free_screen(c);
-        return rc;
+    const int rc = stage_install(c, ST_SCREEN, on, qd_screen_values((uint32_t)c->S));
+    if (rc != QD_OK || !on) return rc;
+    hipError_t e = uk_malloc(reinterpret_cast<void**>(&c->d_screen_slots), slots.size() * 8);
+    if (e != hipSuccess) {
+        c->d_screen_slots = nullptr;
+        stage_off(c, ST_SCREEN);
+        return fail(c, QD_ERR_HIP, std::string("screen hash table: ") + hipGetErrorString(e));
     }
     HIPCHK(c, hipMemcpy(c->d_screen_slots, slots.data(), slots.size() * 8, hipMemcpyHostToDevice));
     c->screen = P;
@@ -2030,11 +1911,11 @@ int qd_screen_get(const qd_ctx* c, qd_screen_params* out, int64_t* n_kmers) {
     return QD_OK;
 }
 
-int qd_screen_active(const qd_ctx* c) { return c && c->d_screen ? (c->screen.action == QD_SC_DROP ? 2 : 1) : 0; }
+int qd_screen_active(const qd_ctx* c) { return c && c->stage[ST_SCREEN].d ? (c->screen.action == QD_SC_DROP ? 2 : 1) : 0; }
 
 int qd_screen_kind(const qd_ctx* c) {
     if (!c) return QD_ERR_INVALID;
-    if (!c->d_screen) return fail(c, QD_ERR_STATE, "the k-mer screen is not on");
+    if (!c->stage[ST_SCREEN].d) return fail(c, QD_ERR_STATE, c->stage[ST_SCREEN].off_text);
     return qd_screen_path((uint64_t)c->screen_kmers);
 }
 
@@ -2043,40 +1924,29 @@ int64_t qd_screen_first_slot(uint64_t word, int64_t n_kmers) {
     return qd_screen_slot(word, qd_screen_slots_lg((uint64_t)n_kmers));
 }
 
-int qd_screen_read(qd_ctx* c, uint64_t* out, int64_t n_values) {
-    if (!c) return QD_ERR_INVALID;
-    return table_read(c, c->d_screen, qd_screen_values((uint32_t)c->S), out, n_values, "the k-mer screen is not on", "n_values must be (2*S+1)*8");
-}
+int qd_screen_read(qd_ctx* c, uint64_t* out, int64_t n_values) { return c ? table_read(c, c->stage[ST_SCREEN], out, n_values) : QD_ERR_INVALID; }
 
-int qd_screen_add(qd_ctx* c, const uint64_t* values, int64_t n_values) {
-    if (!c) return QD_ERR_INVALID;
-    return table_add(c, c->d_screen, qd_screen_values((uint32_t)c->S), values, n_values, "the k-mer screen is not on", "n_values must be (2*S+1)*8");
-}
+int qd_screen_add(qd_ctx* c, const uint64_t* values, int64_t n_values) { return c ? table_add(c, c->stage[ST_SCREEN], values, n_values) : QD_ERR_INVALID; }
 
 int qd_screen_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
                      const uint16_t* codes, const uint8_t* drop_in, uint32_t* hits, uint8_t* flag, void* stream) {
-    if (!c) return QD_ERR_INVALID;
-    if (!c->d_screen) return fail(c, QD_ERR_STATE, "the k-mer screen is not on");
-    if (!n) return QD_OK;
-    hipStream_t st = resolve_stream(c, stream);
-    qd_screen_args a{};
-    fill_pair_args(a, text1, recs1, text2, recs2);
-    a.codes = codes;
-    a.drop_in = drop_in;
-    a.hits = hits;
-    a.flag = flag;
-    a.slots = c->d_screen_slots;
-    a.table = c->d_screen;
-    hipError_t e = qd_screen_launch(c->screen_dev, a, (uint32_t)c->S, n, qd_screen_path((uint64_t)c->screen_kmers), (uint32_t)c->cu, st);
-    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("screen launch: ") + hipGetErrorString(e));
-    HIPCHK(c, track(c, st));
-    return QD_OK;
+    return stage_launch(c, ST_SCREEN, true, n, stream, [&](u64* table, hipStream_t st) {
+        qd_screen_args a{};
+        fill_pair_args(a, text1, recs1, text2, recs2);
+        a.codes = codes;
+        a.drop_in = drop_in;
+        a.hits = hits;
+        a.flag = flag;
+        a.slots = c->d_screen_slots;
+        a.table = table;
+        return qd_screen_launch(c->screen_dev, a, (uint32_t)c->S, n, qd_screen_path((uint64_t)c->screen_kmers), (uint32_t)c->cu, st);
+    });
 }
 
 int qd_dev_screen(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                   const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes, const uint8_t* drop_in, uint32_t* hits_out, uint8_t* flag_out) {
     if (!c) return QD_ERR_INVALID;
-    if (!c->d_screen) return fail(c, QD_ERR_STATE, "the k-mer screen is not on");
+    if (!c->stage[ST_SCREEN].d) return fail(c, QD_ERR_STATE, c->stage[ST_SCREEN].off_text);
     PairUpload up(c);
     const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::CODES | PairUpload::REASONS | PairUpload::HITS, codes,
                            drop_in, nullptr, nullptr, flag_out, hits_out);
@@ -2099,14 +1969,11 @@ int qd_dup_set(qd_ctx* c, const qd_dup_params* params) {
         while ((1 << sample_lg) < P.sample) ++sample_lg;
         if (!c->have_plan || !c->have_table) return fail(c, QD_ERR_STATE, "qd_set_plan and qd_set_barcodes first");
     }
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, wait_all(c));  // nothing of this context may still use the old tables
-    free_dup(c);
-    if (!params) return QD_OK;
-    int rc = table_alloc(c, c->d_dup, qd_dup_values((uint32_t)c->S), "duplication counters");
-    if (rc == QD_OK) rc = tally_open(c, c->dup_keys, params->slots, "duplication table");
+    int rc = stage_install(c, ST_DUP, params != nullptr, qd_dup_values((uint32_t)c->S));
+    if (rc != QD_OK || !params) return rc;
+    rc = tally_open(c, c->dup_keys, params->slots, "duplication table");
     if (rc != QD_OK) {
-        free_dup(c);
+        stage_off(c, ST_DUP);
         return rc;
     }
     c->dup = *params;
@@ -2120,7 +1987,7 @@ int qd_dup_get(const qd_ctx* c, qd_dup_params* out) {
     return QD_OK;
 }
 
-int qd_dup_active(const qd_ctx* c) { return c && c->d_dup ? 1 : 0; }
+int qd_dup_active(const qd_ctx* c) { return c && c->stage[ST_DUP].d ? 1 : 0; }
 
 int qd_stream_retired(qd_ctx* c, void* stream) {
     if (!c) return QD_ERR_INVALID;
@@ -2131,15 +1998,12 @@ int qd_stream_retired(qd_ctx* c, void* stream) {
     return QD_OK;
 }
 
-int qd_dup_stats(qd_ctx* c, uint64_t* out, int64_t n_values) {
-    if (!c) return QD_ERR_INVALID;
-    return table_read(c, c->d_dup, qd_dup_values((uint32_t)c->S), out, n_values, "the duplication tally is not on", "n_values must be (2*S+1)*5");
-}
+int qd_dup_stats(qd_ctx* c, uint64_t* out, int64_t n_values) { return c ? table_read(c, c->stage[ST_DUP], out, n_values) : QD_ERR_INVALID; }
 
 int64_t qd_dup_read(qd_ctx* c, uint64_t* keys, uint64_t* counts, int64_t cap) {
     auto bad = [&](int code, const std::string& msg) { return QD_DUP_READ_ERROR + (int64_t)fail(c, code, msg); };
     if (!c || cap < 0 || (cap > 0 && (!keys || !counts))) return bad(QD_ERR_INVALID, "bad arguments");
-    if (!c->d_dup) return bad(QD_ERR_STATE, "the duplication tally is not on");
+    if (!c->stage[ST_DUP].d) return bad(QD_ERR_STATE, c->stage[ST_DUP].off_text);
     std::vector<u64> hk;
     const int64_t D = tally_gather(c, c->dup_keys, "duplication", cap, hk, counts);
     for (int64_t i = 0; i < D; ++i)  // (D <= 0: nothing was gathered)
@@ -2149,32 +2013,33 @@ int64_t qd_dup_read(qd_ctx* c, uint64_t* keys, uint64_t* counts, int64_t cap) {
 
 int qd_dup_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
                   const uint16_t* codes, const uint8_t* drop, void* stream) {
-    if (!c) return QD_ERR_INVALID;
-    if (!c->d_dup || !n) return QD_OK;
-    hipStream_t st = resolve_stream(c, stream);
-    StreamScratch::Buf* sc = c->dup_keys.scratch.need(c, st, n, qd_dup_list_bytes);
-    if (!sc) return QD_ERR_HIP;
-    qd_dup_args a{};
-    fill_pair_args(a, text1, recs1, text2, recs2);
-    a.codes = codes;
-    a.drop = drop;
-    a.table = c->d_dup;
-    a.list_n = reinterpret_cast<uint32_t*>(sc->buf);
-    a.list = reinterpret_cast<uint64_t*>(sc->buf + QD_DUP_LIST_HEAD);
-    a.where = reinterpret_cast<uint32_t*>(sc->buf + QD_DUP_LIST_HEAD + sc->units * QD_DUP_KEY_WORDS * 8);
-    a.t = tally_view(c->dup_keys);
-    hipError_t e = qd_dup_launch(c->dup_dev, a, (uint32_t)c->S, n, c->cu, tally_before(c->dup_keys, st), st);
-    if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("duplication tally launch: ") + hipGetErrorString(e));
-    const int rc = tally_after(c, c->dup_keys, st);
-    if (rc != QD_OK) return rc;
-    HIPCHK(c, track(c, st));
-    return QD_OK;
+    int own = QD_OK;  // what the scratch or the handshake refused: qd_last_error has their text
+    const int rc = stage_launch(c, ST_DUP, false, n, stream, [&](u64* table, hipStream_t st) {
+        StreamScratch::Buf* sc = c->dup_keys.scratch.need(c, st, n, qd_dup_list_bytes);
+        if (!sc) {
+            own = QD_ERR_HIP;
+            return hipSuccess;
+        }
+        qd_dup_args a{};
+        fill_pair_args(a, text1, recs1, text2, recs2);
+        a.codes = codes;
+        a.drop = drop;
+        a.table = table;
+        a.list_n = reinterpret_cast<uint32_t*>(sc->buf);
+        a.list = reinterpret_cast<uint64_t*>(sc->buf + QD_DUP_LIST_HEAD);
+        a.where = reinterpret_cast<uint32_t*>(sc->buf + QD_DUP_LIST_HEAD + sc->units * QD_DUP_KEY_WORDS * 8);
+        a.t = tally_view(c->dup_keys);
+        hipError_t e = qd_dup_launch(c->dup_dev, a, (uint32_t)c->S, n, c->cu, tally_before(c->dup_keys, st), st);
+        if (e == hipSuccess) own = tally_after(c, c->dup_keys, st);
+        return e;
+    });
+    return own != QD_OK ? own : rc;
 }
 
 int qd_dev_dup(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes, const uint8_t* drop) {
     if (!c) return QD_ERR_INVALID;
-    if (!c->d_dup) return fail(c, QD_ERR_STATE, "the duplication tally is not on");
+    if (!c->stage[ST_DUP].d) return fail(c, QD_ERR_STATE, c->stage[ST_DUP].off_text);
     PairUpload up(c);
     const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::CODES, codes, drop, nullptr, nullptr, nullptr);
     if (rc != QD_OK || up.empty()) return rc;
@@ -2327,14 +2192,12 @@ int qd_add_counts(qd_ctx* c, const uint64_t* counts, int32_t n_values) {
 
 int qd_reset_counts(qd_ctx* c) {
     if (!c) return QD_ERR_INVALID;
-    if (!c->have_table) {  // no barcodes, no pair counters; the trim counters do not depend on them
-        if (!c->d_clip && !c->d_trim && !c->d_pairtrim && !c->d_posttrim) return QD_OK;
+    if (!c->have_table) {  // no barcodes, no pair counters; the stages that need none (clip, trim, pairtrim, posttrim, cstats) may be on
+        if (!stages_on(c, false)) return QD_OK;
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, wait_all(c));
-        if (c->d_clip) HIPCHK(c, hipMemset(c->d_clip, 0, QD_CLIP_TABLE * 8));
-        if (c->d_trim) HIPCHK(c, hipMemset(c->d_trim, 0, QD_TRIM_VALUES * 8));
-        if (c->d_pairtrim) HIPCHK(c, hipMemset(c->d_pairtrim, 0, QD_PT_VALUES * 8));
-        if (c->d_posttrim) HIPCHK(c, hipMemset(c->d_posttrim, 0, QD_POST_TABLE * 8));
+        for (const StageTable& T : c->stage)
+            if (T.d) HIPCHK(c, hipMemset(T.d, 0, T.n_values * 8));
         return QD_OK;
     }
     HIPCHK(c, hipSetDevice(c->device));
@@ -2342,19 +2205,10 @@ int qd_reset_counts(qd_ctx* c) {
     HIPCHK(c, hipMemsetAsync(c->d_partial, 0,(size_t)c->partial_rows * c->cnt_stride * sizeof(qd_row_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_acc, 0, (size_t)c->cnt_stride * 8, c->stream));
     if (c->uk.mem) HIPCHK(c, tally_zero(c->uk, c->stream));  // sum(counts) + short + dropped == UNDETERMINED stays true
-    if (c->d_hop) HIPCHK(c, hipMemsetAsync(c->d_hop, 0, hop_values(c) * 8, c->stream));  // sum(table) == UNDETERMINED stays true
-    if (c->d_qs) HIPCHK(c, hipMemsetAsync(c->d_qs, 0, qd_qstats_values((uint32_t)c->S) * 8, c->stream));  // records stay equal to the pair counters
-    if (c->d_cs) HIPCHK(c, hipMemsetAsync(c->d_cs, 0, (size_t)QD_CS_VALUES * 8, c->stream));
-    if (c->d_clip) HIPCHK(c, hipMemsetAsync(c->d_clip, 0, QD_CLIP_TABLE * 8, c->stream));
-    if (c->d_trim) HIPCHK(c, hipMemsetAsync(c->d_trim, 0, QD_TRIM_VALUES * 8, c->stream));
-    if (c->d_pairtrim) HIPCHK(c, hipMemsetAsync(c->d_pairtrim, 0, QD_PT_VALUES * 8, c->stream));
-    if (c->d_posttrim) HIPCHK(c, hipMemsetAsync(c->d_posttrim, 0, QD_POST_TABLE * 8, c->stream));
-    if (c->d_filter) HIPCHK(c, hipMemsetAsync(c->d_filter, 0, qd_filter_values((uint32_t)c->S) * 8, c->stream));
-    if (c->d_screen) HIPCHK(c, hipMemsetAsync(c->d_screen, 0, qd_screen_values((uint32_t)c->S) * 8, c->stream));
-    if (c->d_dup) {  // both tables: sampled == tallied + not_tallied stays true
-        HIPCHK(c, hipMemsetAsync(c->d_dup, 0, qd_dup_values((uint32_t)c->S) * 8, c->stream));
-        HIPCHK(c, tally_zero(c->dup_keys, c->stream));
-    }
+    if (c->hop.d) HIPCHK(c, hipMemsetAsync(c->hop.d, 0, c->hop.n_values * 8, c->stream));  // sum(table) == UNDETERMINED stays true
+    for (const StageTable& T : c->stage)  // (the quality counters: records stay equal to the pair counters)
+        if (T.d) HIPCHK(c, hipMemsetAsync(T.d, 0, T.n_values * 8, c->stream));
+    if (c->dup_keys.mem) HIPCHK(c, tally_zero(c->dup_keys, c->stream));  // both of dup's tables: sampled == tallied + not_tallied stays true
     HIPCHK(c, track(c, c->stream));  // later launches on other streams are not ordered behind this: wait here
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->total_pairs = 0;

@@ -724,10 +724,7 @@ struct qd_pipe {
     // index rows, codes, routing scratch (sized for batch_pairs)
     DevBuf rows_seq[2], rows_qual[2], rows_len[2], codes, mol, short_idx, dest, len1, len2, hist, tmp, perm, sdest, g1, g2, scan_tiles, first, g1_first,
         g2_first;
-    DevBuf clipped[2];  // the insert reads' record tables as the clip stage leaves them (qd_clip_set; never allocated when it is off)
-    DevBuf trimmed[2];  // the insert reads' record tables with trimmed lengths (qd_trim_set; never allocated when trimming is off)
-    DevBuf pairtrimmed[2];  // ... with the lengths the overlap trimming leaves (qd_pairtrim_set; never allocated when it is off)
-    DevBuf posttrimmed[2];  // ... with the lengths the post-trimming leaves (qd_posttrim_set; never allocated when it is off)
+    DevBuf recs_out[4][2];  // the insert reads' record tables as clip, trim, pairtrim and posttrim leave them (a stage's are never allocated when it is off)
     DevBuf drop;  // the read filter's reason byte per pair, 0x80 for a pair the k-mer screen drops (qd_filter_set, qd_screen_set with action drop; never allocated when both are off)
     PinBuf h_first;
     // tables and scratch of the format / CRC / coder launches: read by kernels on the compute stream only, so one set serves every batch
@@ -1743,46 +1740,34 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
     // The insert reads' tables: the opt-in stages below write copies of their own, which everything behind them reads sequence and
     // quality through.  The scan's tables stay as they are: the carry and the next batch use them
     const qd_rec* ins[2] = {p->win[0].recs.as<qd_rec>(), p->win[1].recs.as<qd_rec>()};
-    // opt-in end clipping, window and poly-G trimming (qd_clip_set), in front of the 3' trimming: copies with seq, qual and seq_len
-    // of their own, so that a 5' clip reaches every stage behind it through the tables alone
-    if (qd_clip_active(p->ctx)) {
-        for (int k = 0; k < 2; ++k) PCHK(p, p->clipped[k].need((size_t)n * sizeof(qd_rec) + 64, 0, p->cs));
-        const int rc = qd_clip_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p, ins[1], n,
-                                      p->clipped[0].as<qd_rec>(), p->clipped[1].as<qd_rec>(), p->cs);
-        if (rc != QD_OK) return pfail(p, rc, std::string("clip: ") + qd_last_error(p->ctx));
-        for (int k = 0; k < 2; ++k) ins[k] = p->clipped[k].as<qd_rec>();
-    }
-    // opt-in 3' trimming of the insert reads (qd_trim_set): trimmed copies of the two tables
-    if (qd_trim_active(p->ctx)) {
-        for (int k = 0; k < 2; ++k) PCHK(p, p->trimmed[k].need((size_t)n * sizeof(qd_rec) + 64, 0, p->cs));
-        const int rc = qd_trim_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p, ins[1], n,
-                                      p->trimmed[0].as<qd_rec>(), p->trimmed[1].as<qd_rec>(), p->cs);
-        if (rc != QD_OK) return pfail(p, rc, std::string("trim: ") + qd_last_error(p->ctx));
-        for (int k = 0; k < 2; ++k) ins[k] = p->trimmed[k].as<qd_rec>();
-    }
-    // opt-in paired-end overlap trimming (qd_pairtrim_set): R1 and R2 of a pair together, on the lengths the stage above left
-    if (qd_pairtrim_active(p->ctx)) {
-        for (int k = 0; k < 2; ++k) PCHK(p, p->pairtrimmed[k].need((size_t)n * sizeof(qd_rec) + 64, 0, p->cs));
-        const int rc = qd_pairtrim_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p, ins[1], n,
-                                          p->pairtrimmed[0].as<qd_rec>(), p->pairtrimmed[1].as<qd_rec>(), p->cs);
-        if (rc != QD_OK) return pfail(p, rc, std::string("overlap trim: ") + qd_last_error(p->ctx));
-        for (int k = 0; k < 2; ++k) ins[k] = p->pairtrimmed[k].as<qd_rec>();
-    }
-    // opt-in post-trimming (qd_posttrim_set): trailing N, a poly-X tail and the max_length crop, on what the three stages above left
-    if (qd_posttrim_active(p->ctx)) {
-        for (int k = 0; k < 2; ++k) PCHK(p, p->posttrimmed[k].need((size_t)n * sizeof(qd_rec) + 64, 0, p->cs));
-        const int rc = qd_posttrim_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p, ins[1], n,
-                                          p->posttrimmed[0].as<qd_rec>(), p->posttrimmed[1].as<qd_rec>(), p->cs);
-        if (rc != QD_OK) return pfail(p, rc, std::string("post-trim: ") + qd_last_error(p->ctx));
-        for (int k = 0; k < 2; ++k) ins[k] = p->posttrimmed[k].as<qd_rec>();
+    const uint8_t* const text1 = p->win[0].buf[p->win[0].cur].p;
+    const uint8_t* const text2 = p->win[1].buf[p->win[1].cur].p;
+    // The opt-in stages that rewrite the tables, each on what the one before left: end clipping, window and poly-G trimming
+    // (qd_clip_set; copies with seq, qual and seq_len of their own, so that a 5' clip reaches every stage behind it through the tables
+    // alone), 3' trimming (qd_trim_set), paired-end overlap trimming of R1 and R2 together (qd_pairtrim_set), then trailing N, a poly-X
+    // tail and the max_length crop (qd_posttrim_set)
+    static const struct {
+        int (*active)(const qd_ctx*);
+        int (*device)(qd_ctx*, const uint8_t*, const qd_rec*, const uint8_t*, const qd_rec*, uint32_t, qd_rec*, qd_rec*, void*);
+        const char* label;
+    } rewriting[4] = {{qd_clip_active, qd_clip_device, "clip: "},
+                      {qd_trim_active, qd_trim_device, "trim: "},
+                      {qd_pairtrim_active, qd_pairtrim_device, "overlap trim: "},
+                      {qd_posttrim_active, qd_posttrim_device, "post-trim: "}};
+    for (int s = 0; s < 4; ++s) {
+        if (!rewriting[s].active(p->ctx)) continue;
+        DevBuf* out = p->recs_out[s];
+        for (int k = 0; k < 2; ++k) PCHK(p, out[k].need((size_t)n * sizeof(qd_rec) + 64, 0, p->cs));
+        const int rc = rewriting[s].device(p->ctx, text1, ins[0], text2, ins[1], n, out[0].as<qd_rec>(), out[1].as<qd_rec>(), p->cs);
+        if (rc != QD_OK) return pfail(p, rc, std::string(rewriting[s].label) + qd_last_error(p->ctx));
+        for (int k = 0; k < 2; ++k) ins[k] = out[k].as<qd_rec>();
     }
     // opt-in read filtering (qd_filter_set) of what the trimming left: a reason byte per pair; a pair with one is counted by nothing
     // behind this point, gets output lengths 0 and is not formatted -- the way a destination whose write flag is off leaves no text
     const uint8_t* drop = nullptr;
     if (qd_filter_active(p->ctx)) {
         PCHK(p, p->drop.need((size_t)n + 64, 0, p->cs));
-        const int rc = qd_filter_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p, ins[1], n,
-                                        p->codes.as<uint16_t>(), p->drop.p, p->cs);
+        const int rc = qd_filter_device(p->ctx, text1, ins[0], text2, ins[1], n, p->codes.as<uint16_t>(), p->drop.p, p->cs);
         if (rc != QD_OK) return pfail(p, rc, std::string("filter: ") + qd_last_error(p->ctx));
         drop = p->drop.p;
     }
@@ -1795,25 +1780,21 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
             PCHK(p, p->drop.need((size_t)n + 64, 0, p->cs));
             flag = p->drop.p;
         }
-        const int rc = qd_screen_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p, ins[1], n,
-                                        p->codes.as<uint16_t>(), drop, nullptr, flag, p->cs);
+        const int rc = qd_screen_device(p->ctx, text1, ins[0], text2, ins[1], n, p->codes.as<uint16_t>(), drop, nullptr, flag, p->cs);
         if (rc != QD_OK) return pfail(p, rc, std::string("screen: ") + qd_last_error(p->ctx));
         if (flag) drop = flag;
     }
     {  // opt-in yield and quality counters of the insert reads (qd_qstats_enable): the codes are final, the windows still hold the pairs
-        const int rc = qd_qstats_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p,
-                                        ins[1], n, p->codes.as<uint16_t>(), drop, p->cs);
+        const int rc = qd_qstats_device(p->ctx, text1, ins[0], text2, ins[1], n, p->codes.as<uint16_t>(), drop, p->cs);
         if (rc != QD_OK) return pfail(p, rc, std::string("quality counters: ") + qd_last_error(p->ctx));
     }
     {  // opt-in per-cycle counters and per-read distributions (qd_cstats_enable): the same reads, by pass / fail / Undetermined
-        const int rc = qd_cstats_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p,
-                                        ins[1], n, p->codes.as<uint16_t>(), drop, p->cs);
+        const int rc = qd_cstats_device(p->ctx, text1, ins[0], text2, ins[1], n, p->codes.as<uint16_t>(), drop, p->cs);
         if (rc != QD_OK) return pfail(p, rc, std::string("cycle counters: ") + qd_last_error(p->ctx));
     }
     // opt-in duplication tally (qd_dup_set): the same pairs keyed by their first bases and counted in the context's hash table
     if (qd_dup_active(p->ctx)) {
-        const int rc = qd_dup_device(p->ctx, p->win[0].buf[p->win[0].cur].p, ins[0], p->win[1].buf[p->win[1].cur].p, ins[1], n,
-                                     p->codes.as<uint16_t>(), drop, p->cs);
+        const int rc = qd_dup_device(p->ctx, text1, ins[0], text2, ins[1], n, p->codes.as<uint16_t>(), drop, p->cs);
         if (rc != QD_OK) return pfail(p, rc, std::string("duplication tally: ") + qd_last_error(p->ctx));
     }
     // 3. destinations, output lengths, stable sort by destination, output offsets
@@ -1943,8 +1924,8 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
     fa.g2 = p->g2.as<uint32_t>();
     fa.base1 = p->base1.as<int64_t>();
     fa.base2 = p->base2.as<int64_t>();
-    fa.text1 = p->win[0].buf[p->win[0].cur].p;
-    fa.text2 = p->win[1].buf[p->win[1].cur].p;
+    fa.text1 = text1;
+    fa.text2 = text2;
     fa.r1 = ra.r1;
     fa.r2 = ra.r2;
     for (int k = 0; k < ni; ++k) {
@@ -2634,9 +2615,10 @@ int qd_pipe_destroy(qd_pipe* p) {
     p->gz = nullptr;
     for (DevBuf* b : {&p->d_res, &p->rows_seq[0], &p->rows_seq[1], &p->rows_qual[0], &p->rows_qual[1], &p->rows_len[0], &p->rows_len[1], &p->codes, &p->mol,
                       &p->short_idx, &p->dest, &p->len1, &p->len2, &p->hist, &p->tmp, &p->perm, &p->sdest, &p->g1, &p->g2, &p->scan_tiles, &p->first, &p->g1_first,
-                      &p->g2_first, &p->subs, &p->first_sub, &p->ranges, &p->crc, &p->tokens, &p->sub_out, &p->sub_bytes, &p->base1, &p->base2, &p->clipped[0], &p->clipped[1], &p->trimmed[0], &p->trimmed[1], &p->pairtrimmed[0],
-                      &p->pairtrimmed[1], &p->posttrimmed[0], &p->posttrimmed[1], &p->drop})
+                      &p->g2_first, &p->subs, &p->first_sub, &p->ranges, &p->crc, &p->tokens, &p->sub_out, &p->sub_bytes, &p->base1, &p->base2, &p->drop})
         b->release();
+    for (auto& stage : p->recs_out)
+        for (DevBuf& b : stage) b.release();
     for (OutSet& o : p->out) {
         for (DevBuf* b : {&o.text, &o.pieces, &o.members, &o.member_len, &o.member_off, &o.packed}) b->release();
         o.h_len.release();

@@ -716,9 +716,7 @@ class Engine(object):
     def hop_read(self):
         """numpy uint64[(n1+1)*(n2+1)+1]: the cells row-major (row n1 / column n2 = no part), then `short`"""
         n1, n2 = self.hop_shape()
-        out = np.zeros(hop_values(n1, n2), dtype=np.uint64)
-        self._chk(self.lib.qd_hop_read(self._h, _ptr(out), out.size))
-        return out
+        return self._table_read(self.lib.qd_hop_read, hop_values(n1, n2))
 
     def hop_add(self, table):
         """Another context's table (hop_read's layout) joins this context's (qd_hop_add)."""
@@ -753,6 +751,12 @@ class Engine(object):
         self._chk(fn(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), n, _ptr(out[0]), _ptr(out[1])))
         return out[0], out[1]
 
+    def _table_read(self, fn, shape):
+        """a table through its qd_*_read entry `fn` -> uint64 of `shape`"""
+        out = np.zeros(shape, dtype=np.uint64)
+        self._chk(fn(self._h, _ptr(out), out.size))
+        return out
+
     def _table_add(self, fn, table):
         table = np.ascontiguousarray(table, dtype=np.uint64)
         self._chk(fn(self._h, _ptr(table), table.size))
@@ -764,9 +768,7 @@ class Engine(object):
 
     def qstats_read(self):
         """numpy uint64[2S+1, 2, 6]: [destination (code; Undetermined last)][R1, R2][QSTATS_COUNTERS]"""
-        out = np.zeros((2 * self.n_samples + 1, 2, len(QSTATS_COUNTERS)), dtype=np.uint64)
-        self._chk(self.lib.qd_qstats_read(self._h, _ptr(out), out.size))
-        return out
+        return self._table_read(self.lib.qd_qstats_read, (2 * self.n_samples + 1, 2, len(QSTATS_COUNTERS)))
 
     def qstats_add(self, table):
         """Another context's table (qstats_read's layout) joins this context's (qd_qstats_add)."""
@@ -810,9 +812,7 @@ class Engine(object):
 
     def clip_read(self):
         """numpy uint64[2, 12]: [R1, R2][CLIP_COUNTERS]"""
-        out = np.zeros((2, len(CLIP_COUNTERS)), dtype=np.uint64)
-        self._chk(self.lib.qd_clip_read(self._h, _ptr(out), out.size))
-        return out
+        return self._table_read(self.lib.qd_clip_read, (2, len(CLIP_COUNTERS)))
 
     def clip_add(self, table):
         """Another context's counters (clip_read's layout) join this context's (qd_clip_add)."""
@@ -845,9 +845,7 @@ class Engine(object):
 
     def trim_read(self):
         """numpy uint64[2, 8]: [R1, R2][TRIM_COUNTERS]"""
-        out = np.zeros((2, len(TRIM_COUNTERS)), dtype=np.uint64)
-        self._chk(self.lib.qd_trim_read(self._h, _ptr(out), out.size))
-        return out
+        return self._table_read(self.lib.qd_trim_read, (2, len(TRIM_COUNTERS)))
 
     def trim_add(self, table):
         """Another context's counters (trim_read's layout) join this context's (qd_trim_add)."""
@@ -875,9 +873,7 @@ class Engine(object):
 
     def pairtrim_read(self):
         """numpy uint64[1040]: [R1, R2][PAIRTRIM_COUNTERS], PAIRTRIM_PAIR_COUNTERS, the insert size bins (split_pairtrim)"""
-        out = np.zeros(PAIRTRIM_VALUES, dtype=np.uint64)
-        self._chk(self.lib.qd_pairtrim_read(self._h, _ptr(out), out.size))
-        return out
+        return self._table_read(self.lib.qd_pairtrim_read, PAIRTRIM_VALUES)
 
     def pairtrim_add(self, table):
         """Another context's table (pairtrim_read's layout) joins this context's (qd_pairtrim_add)."""
@@ -912,9 +908,7 @@ class Engine(object):
 
     def posttrim_read(self):
         """numpy uint64[2, 16]: [R1, R2][POSTTRIM_COUNTERS]"""
-        out = np.zeros((2, len(POSTTRIM_COUNTERS)), dtype=np.uint64)
-        self._chk(self.lib.qd_posttrim_read(self._h, _ptr(out), out.size))
-        return out
+        return self._table_read(self.lib.qd_posttrim_read, (2, len(POSTTRIM_COUNTERS)))
 
     def posttrim_add(self, table):
         """Another context's counters (posttrim_read's layout) join this context's (qd_posttrim_add)."""
@@ -946,9 +940,7 @@ class Engine(object):
 
     def filter_read(self):
         """numpy uint64[2S+1, 8]: [destination (code; Undetermined last)][FILTER_COUNTERS]"""
-        out = np.zeros((2 * self.n_samples + 1, len(FILTER_COUNTERS)), dtype=np.uint64)
-        self._chk(self.lib.qd_filter_read(self._h, _ptr(out), out.size))
-        return out
+        return self._table_read(self.lib.qd_filter_read, (2 * self.n_samples + 1, len(FILTER_COUNTERS)))
 
     def filter_add(self, table):
         """Another context's table (filter_read's layout) joins this context's (qd_filter_add)."""
@@ -1011,9 +1003,7 @@ class Engine(object):
 
     def screen_read(self):
         """numpy uint64[2S+1, 8]: [destination (code; Undetermined last)][SCREEN_COUNTERS]"""
-        out = np.zeros((2 * self.n_samples + 1, len(SCREEN_COUNTERS)), dtype=np.uint64)
-        self._chk(self.lib.qd_screen_read(self._h, _ptr(out), out.size))
-        return out
+        return self._table_read(self.lib.qd_screen_read, (2 * self.n_samples + 1, len(SCREEN_COUNTERS)))
 
     def screen_add(self, table):
         """Another context's table (screen_read's layout) joins this context's (qd_screen_add)."""
@@ -1038,9 +1028,7 @@ class Engine(object):
     def cstats_read(self):
         """dict of uint64 views into one flat table: cycle[3, 2, 1024, 8], len[3, 2, 1025], meanq[3, 2, 94], gc[3, 2, 101] --
         [CSTATS_GROUPS][R1, R2][...] (cstats_flat gives the flat table back)"""
-        out = np.zeros(CSTATS_VALUES, dtype=np.uint64)
-        self._chk(self.lib.qd_cstats_read(self._h, _ptr(out), out.size))
-        return cstats_views(out)
+        return cstats_views(self._table_read(self.lib.qd_cstats_read, CSTATS_VALUES))
 
     def cstats_add(self, table):
         """Another context's table (cstats_read's dict or flat) joins this context's (qd_cstats_add)."""
@@ -1073,9 +1061,7 @@ class Engine(object):
 
     def dup_stats(self):
         """numpy uint64[2S+1, 5]: [destination (code; Undetermined last)][DUP_COUNTERS]"""
-        out = np.zeros((2 * self.n_samples + 1, len(DUP_COUNTERS)), dtype=np.uint64)
-        self._chk(self.lib.qd_dup_stats(self._h, _ptr(out), out.size))
-        return out
+        return self._table_read(self.lib.qd_dup_stats, (2 * self.n_samples + 1, len(DUP_COUNTERS)))
 
     def dup_read(self):
         """The key table's entries in no particular order: (keys uint64[n, 3] = (w1, w2, d), counts uint64[n])."""
