@@ -529,7 +529,10 @@ class Feeder {
                 const size_t avail = fill - pos;
                 const size_t bs = qdio::bgzf_block_size(b, avail);
                 if (!bs) {
-                    if (avail >= 18 || eof) switch_at = file_pos + (int64_t)pos;  // (fewer bytes than a header: the next read completes it)
+                    // fewer bytes than a header, or than a header with its extra field ('BC' may stand anywhere in it): the next
+                    // read completes it
+                    const bool cut_short = avail < 18 || (b[0] == 0x1f && b[1] == 0x8b && b[2] == 8 && (b[3] & 4) && avail < 12 + (b[10] | ((size_t)b[11] << 8)));
+                    if (!cut_short || eof) switch_at = file_pos + (int64_t)pos;
                     break;
                 }
                 if (bs > avail) {
