@@ -15,6 +15,7 @@
 
 #include "../../include/quade_hip.h"
 #include "quade_common.h"
+#include "gz_framing.h"
 #include "quade_kernels.h"
 #include "quade_inflate.h"
 #include "quade_inflate3.h"
@@ -2543,7 +2544,6 @@ int qd_comm_destroy(qd_comm* cm) {
 
 // ---- BGZF inflate on the device (include/quade_hip.h; kernel: quade_inflate.hip) ------------------------------
 uint32_t qd_io_crc32(const uint8_t* p, size_t n);  // quade_io.cpp: libdeflate's when loaded, else zlib's
-uint32_t qd_crc32_combine_host(uint32_t crc1, uint32_t crc2, uint64_t len2);  // quade_io.cpp (zlib's)
 
 struct qd_inflater {
     int device = -1;
@@ -2738,31 +2738,13 @@ static int inflater_run(qd_inflater* f, const uint8_t* comp, int64_t comp_len, u
     f->crc.clear();
     size_t pos = 0, opos = 0;
     while (pos < (size_t)comp_len) {
-        const uint8_t* p = comp + pos;
-        const size_t avail = (size_t)comp_len - pos;
-        size_t bsize = 0, xlen = 0;
-        if (avail >= 18 && p[0] == 0x1f && p[1] == 0x8b && p[2] == 8 && (p[3] & 4)) {
-            xlen = p[10] | ((size_t)p[11] << 8);
-            if (avail >= 12 + xlen)
-                for (size_t o = 12; o + 4 <= 12 + xlen;) {
-                    const size_t slen = p[o + 2] | ((size_t)p[o + 3] << 8);
-                    if (p[o] == 'B' && p[o + 1] == 'C' && slen == 2 && o + 6 <= 12 + xlen) {
-                        bsize = (size_t)(p[o + 4] | (p[o + 5] << 8)) + 1;
-                        break;
-                    }
-                    o += 4 + slen;
-                }
-        }
-        if (!bsize || bsize > avail || bsize < 12 + xlen + 8 || (p[3] & ~4))  // other gzip flags (name, comment, hcrc): not bgzip's
-            return inf_fail(f, QD_ERR_FORMAT, "not a run of whole BGZF blocks");
-        const uint8_t* tr = p + bsize - 8;
-        const uint32_t crc = tr[0] | ((uint32_t)tr[1] << 8) | ((uint32_t)tr[2] << 16) | ((uint32_t)tr[3] << 24);
-        const uint32_t isize = tr[4] | ((uint32_t)tr[5] << 8) | ((uint32_t)tr[6] << 16) | ((uint32_t)tr[7] << 24);
-        if (isize > (64u << 10) || opos + isize > (size_t)out_len) return inf_fail(f, QD_ERR_FORMAT, "BGZF block sizes do not add up");
-        blk.push_back(qd_inflate_block{(uint32_t)(pos + 12 + xlen), (uint32_t)(bsize - 12 - xlen - 8), (uint32_t)opos, isize});
-        f->crc.push_back(crc);
-        pos += bsize;
-        opos += isize;
+        const gzf::BgzfBlock b = gzf::bgzf_block(comp + pos, (size_t)comp_len - pos);
+        if (!b.framed()) return inf_fail(f, QD_ERR_FORMAT, "not a run of whole BGZF blocks");  // (other gzip flags -- name, comment, hcrc: not bgzip's)
+        if (!b.is_bgzip_layout() || opos + b.isize > (size_t)out_len) return inf_fail(f, QD_ERR_FORMAT, "BGZF block sizes do not add up");
+        blk.push_back(qd_inflate_block{(uint32_t)(pos + b.payload_off), (uint32_t)b.payload_len, (uint32_t)opos, b.isize});
+        f->crc.push_back(b.crc);
+        pos += b.bsize;
+        opos += b.isize;
     }
     if (opos != (size_t)out_len) return inf_fail(f, QD_ERR_FORMAT, "BGZF block sizes do not add up");
     if (blk.empty()) return QD_OK;
@@ -3060,26 +3042,6 @@ int qd_deflater_run(qd_deflater* f, int32_t n_pieces, const uint8_t* const* text
 }  // extern "C"
 
 // ---- a whole gzip file image through the device's gzip inflater (include/quade_hip.h: qd_dev_gunzip) -----------------------------------
-namespace {
-// bytes of a gzip member's header at p[0 .. n) (RFC 1952), 0 when it is none or does not end inside n
-size_t gzip_header_bytes(const uint8_t* p, size_t n) {
-    if (n < 10 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || (p[3] & 0xe0)) return 0;
-    const int flg = p[3];
-    size_t at = 10;
-    if (flg & 4) {
-        if (at + 2 > n) return 0;
-        at += 2 + (p[at] | ((size_t)p[at + 1] << 8));
-    }
-    for (int bit : {8, 16})
-        if (flg & bit) {
-            while (at < n && p[at]) ++at;
-            ++at;
-        }
-    if (flg & 2) at += 2;
-    return at <= n ? at : 0;
-}
-}  // namespace
-
 extern "C" int qd_dev_gunzip(int device_id, const uint8_t* gz, int64_t gz_len, uint8_t* out, int64_t out_cap, int64_t* out_len, int64_t step_bytes,
                              int64_t stretch_bytes, int64_t unit_text, int64_t* stats) {
     if (!gz || gz_len < 0 || !out_len || (out_cap > 0 && !out) || step_bytes < 4096) return QD_ERR_INVALID;
@@ -3118,34 +3080,34 @@ extern "C" int qd_dev_gunzip(int device_id, const uint8_t* gz, int64_t gz_len, u
     if (hipMemset(d_gz + gz_len, 0, 4096) != hipSuccess || (gz_len && hipMemcpy(d_gz, gz, (size_t)gz_len, hipMemcpyHostToDevice) != hipSuccess) ||
         hipMemset(d_win, 0, 32768) != hipSuccess)
         return done(QD_ERR_HIP);
-    int64_t pos = 0, opos = 0;  // next member's header; text so far
-    while (pos < gz_len && rc == QD_OK) {
-        const size_t hb = gzip_header_bytes(gz + pos, (size_t)(gz_len - pos));
-        if (!hb) {
+    gzf::MemberWalk walk;  // the whole image is on hand: comp_off 0, comp_len gz_len
+    int64_t opos = 0;      // text so far
+    while ((int64_t)walk.hdr_off < gz_len && rc == QD_OK) {
+        // (zero padding behind the last member is refused here, unlike the readers: DESIGN.md 7.1)
+        const int64_t hb = gzf::gzip_header_len(gz + walk.hdr_off, (size_t)gz_len - walk.hdr_off);
+        if (hb <= 0) {
             rc = QD_ERR_FORMAT;
             break;
         }
-        uint64_t bit = 8 * (uint64_t)(pos + (int64_t)hb);  // absolute bit position of the next block header
-        uint32_t crc = 0;
-        uint64_t member_text = 0;
+        walk.begin((uint64_t)hb);
         qd_gz_step s{};
         s.carried = d_win;
         s.carried_valid = 0;
         int64_t step = step_bytes;
         bool ended = false;
         while (!ended) {
-            const uint64_t byte0 = (bit >> 3) & ~(uint64_t)15;
-            s.comp = d_gz + byte0;
-            s.comp_bytes = (uint64_t)std::min<int64_t>(step, gz_len - (int64_t)byte0);
-            s.bit_start = bit - 8 * byte0;
-            s.at_end = (int64_t)byte0 + (int64_t)s.comp_bytes >= gz_len;
+            const gzf::MemberWalk::Window win = walk.window(0, (uint64_t)gz_len, (uint64_t)step);
+            s.comp = d_gz + win.byte0;
+            s.comp_bytes = win.comp_bytes;
+            s.bit_start = win.bit_start;
+            s.at_end = win.byte0 + win.comp_bytes >= (uint64_t)gz_len;
             if (G.decode(&s, 1, st) != hipSuccess) return done(QD_ERR_HIP);
             ++steps_run;
             if (s.failed) {
                 rc = QD_ERR_FORMAT;
                 break;
             }
-            if (s.bit_next == s.bit_start && !s.member_end && !s.starved) {  // a block longer than the step: more input, if there is any
+            if (walk.stalled(s)) {  // a block longer than the step: more input, if there is any
                 if (s.at_end) {
                     rc = QD_ERR_FORMAT;
                     break;
@@ -3163,28 +3125,23 @@ extern "C" int qd_dev_gunzip(int device_id, const uint8_t* gz, int64_t gz_len, u
                 rc = QD_ERR_FORMAT;
                 break;
             }
-            crc = member_text ? qd_crc32_combine_host(crc, s.crc32, s.text_len) : s.crc32;
-            if (s.text_len == 0 && member_text == 0) crc = 0;
-            member_text += s.text_len;
+            walk.account(s, win);
             opos += (int64_t)s.text_len;
-            bit = 8 * byte0 + s.bit_next;
             ended = s.member_end != 0;
         }
         if (rc != QD_OK) break;
-        const int64_t tr = (int64_t)((bit + 7) >> 3);  // the trailer: CRC-32 and ISIZE of the member's text
-        if (tr + 8 > gz_len) {
+        if (!walk.trailer_inside((uint64_t)gz_len)) {
             rc = QD_ERR_FORMAT;
             break;
         }
-        const uint32_t want_crc = gz[tr] | ((uint32_t)gz[tr + 1] << 8) | ((uint32_t)gz[tr + 2] << 16) | ((uint32_t)gz[tr + 3] << 24);
-        const uint32_t want_len = gz[tr + 4] | ((uint32_t)gz[tr + 5] << 8) | ((uint32_t)gz[tr + 6] << 16) | ((uint32_t)gz[tr + 7] << 24);
-        if (want_crc != crc || want_len != (uint32_t)member_text) {
-            if (getenv("QUADE_GZ_DEBUG")) fprintf(stderr, "[qd_dev_gunzip] trailer at %lld: crc %08x (text's %08x), isize %u (text %llu)\n", (long long)tr, want_crc, crc, want_len, (unsigned long long)member_text);
+        const uint64_t tr = walk.trailer_off();
+        const gzf::MemberWalk::Trailer t = walk.end_member(gz + tr);  // CRC-32 and ISIZE of the member's text
+        if (!t.ok) {
+            if (getenv("QUADE_GZ_DEBUG")) fprintf(stderr, "[qd_dev_gunzip] trailer at %lld: crc %08x (text's %08x), isize %u (text %llu)\n", (long long)tr, t.crc, walk.crc, t.isize, (unsigned long long)walk.text);
             rc = QD_ERR_FORMAT;
             break;
         }
         ++members;
-        pos = tr + 8;
     }
     if (rc == QD_OK && opos && hipMemcpy(out, d_out, (size_t)opos, hipMemcpyDeviceToHost) != hipSuccess) rc = QD_ERR_HIP;
     if (rc == QD_OK) *out_len = opos;

@@ -43,6 +43,7 @@
 
 #include "../../include/quade_hip.h"
 #include "fastq_scan.h"
+#include "gz_framing.h"
 #include "quade_pgz.h"
 
 namespace {
@@ -1449,22 +1450,7 @@ bool hand_over(qd_reader* r, int i, size_t len, const uint8_t* ptr = nullptr) {
     return !r->stop;
 }
 
-// BGZF (bgzip, htslib): gzip members of <= 64 KiB whose header carries their own size in an extra
-// subfield 'B','C' -- so the file can be cut into blocks WITHOUT inflating it, and the blocks inflated
-// in parallel.  Returns the block's total size (header .. ISIZE), 0 when [p, p+avail) does not start with
-// a complete BGZF block header.
-size_t bgzf_block_size(const uint8_t* p, size_t avail) {
-    if (avail < 18 || p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) return 0;
-    const size_t xlen = p[10] | ((size_t)p[11] << 8);
-    if (avail < 12 + xlen) return 0;
-    for (size_t o = 12; o + 4 <= 12 + xlen;) {
-        const size_t slen = p[o + 2] | ((size_t)p[o + 3] << 8);
-        if (p[o] == 'B' && p[o + 1] == 'C' && slen == 2 && o + 6 <= 12 + xlen) return (size_t)(p[o + 4] | (p[o + 5] << 8)) + 1;
-        o += 4 + slen;
-    }
-    return 0;
-}
-
+// BGZF blocks (gz_framing.h) are cut without inflating the file, and inflated in parallel.
 constexpr size_t PIN_BYTES = 48u << 20;  // text of one device run (16 MB of blocks inflate to ~30 MB of fastq text)
 
 struct BgzfRun {  // consecutive blocks inflated by one pool job
@@ -1646,20 +1632,20 @@ bool inflate_bgzf(qd_reader* r, Input& in, int& cur, bool& ok) {
                 more = false;
                 break;
             }
-            const size_t bs = bgzf_block_size(in.buf.data() + in.pos, in.avail());
-            if (!bs || bs > in.avail() || bs < 26) {
+            const uint8_t* b = in.buf.data() + in.pos;
+            const gzf::BgzfBlock blk = gzf::bgzf_block(b, in.avail());
+            // (the host's inflater reads a member's whole header: other FLG bits and a long extra field are fine here)
+            if (!blk.whole || blk.bsize < gzf::BGZF_MIN_BLOCK) {
                 still_bgzf = more = false;  // not (or no longer) BGZF here: the member loop takes over
                 break;
             }
-            const uint8_t* b = in.buf.data() + in.pos;
-            const size_t isize = (size_t)b[bs - 4] | ((size_t)b[bs - 3] << 8) | ((size_t)b[bs - 2] << 16) | ((size_t)b[bs - 1] << 24);
-            if (isize > 65536) {  // a BGZF block holds at most 64 KiB of text: whatever this is, its trailer does not size a buffer
+            if (blk.isize > 65536) {  // a BGZF block holds at most 64 KiB of text: whatever this is, its trailer does not size a buffer
                 still_bgzf = more = false;
                 break;
             }
-            out_bytes += isize;
-            run->in.insert(run->in.end(), b, b + bs);
-            in.pos += bs;
+            out_bytes += blk.isize;
+            run->in.insert(run->in.end(), b, b + blk.bsize);
+            in.pos += blk.bsize;
         }
         if (!ok) break;
         if (!run->in.empty()) {
@@ -1797,7 +1783,7 @@ void inflate_thread(qd_reader* r) {
         }
     } else {
         LibDeflate& L = deflate_lib();
-        if (L.ok && in.refill(1u << 17) && bgzf_block_size(in.buf.data() + in.pos, in.avail())) {
+        if (L.ok && in.refill(1u << 17) && gzf::bgzf_block(in.buf.data() + in.pos, in.avail()).is == gzf::BGZF_BLOCK) {
             // bgzip'd input: blocks are indexed by their headers and inflated in parallel; if the file turns
             // into ordinary gzip members further on, the loop below continues from there
             const bool to_the_end = inflate_bgzf(r, in, cur, ok);
@@ -1822,9 +1808,8 @@ void inflate_thread(qd_reader* r) {
                 break;
             }
             if (!in.avail()) break;  // clean end: the last member ended where the file ends
-            bool all_zero = in.eof;  // zero padding behind the last member is tolerated
-            for (size_t i = in.pos; all_zero && i < in.fill; ++i) all_zero = in.buf.data()[i] == 0;
-            if (all_zero) break;
+            // zero padding behind the last member is tolerated (anything else: the inflaters below say what is wrong with it)
+            if (gzf::member_start(in.buf.data() + in.pos, in.avail(), in.eof) == gzf::START_PADDING) break;
             if (whole_members) {
                 if (r->scratch[cur].size() < MEMBER_OUT) r->scratch[cur].resize(MEMBER_OUT);
                 size_t ain = 0, aout = 0;
@@ -2160,8 +2145,6 @@ int raw_next(qd_reader* r, const uint8_t** ptr, size_t* len, std::string* err) {
 }
 
 void raw_close(qd_reader* r) { qd_reader_close(r); }
-
-size_t bgzf_block_size(const uint8_t* p, size_t avail) { return ::bgzf_block_size(p, avail); }
 
 bool host_inflate_members(const uint8_t* comp, size_t comp_len, uint8_t* out, size_t out_len) {
     LibDeflate& L = deflate_lib();

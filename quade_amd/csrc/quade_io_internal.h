@@ -7,6 +7,8 @@
 #include <string>
 #include <vector>
 
+#include "gz_framing.h"
+
 struct qd_sink;
 struct qd_reader;
 
@@ -21,7 +23,7 @@ int raw_next(qd_reader* r, const uint8_t** ptr, size_t* len, std::string* err);
 void raw_close(qd_reader* r);
 
 // total size of the BGZF block that starts at p (header .. ISIZE), 0 when p does not start with a complete BGZF header
-size_t bgzf_block_size(const uint8_t* p, size_t avail);
+inline size_t bgzf_block_size(const uint8_t* p, size_t avail) { return gzf::bgzf_block(p, avail).size(); }
 // whole BGZF blocks (or any gzip members) back to back -> exactly out_len bytes of text; false: damaged
 bool host_inflate_members(const uint8_t* comp, size_t comp_len, uint8_t* out, size_t out_len);
 // one gzip member of `level` (-1 = Huffman only) from n bytes of text, by the host's coder

@@ -3,6 +3,8 @@
 // offset, stop at a chosen block boundary, and write 16-bit symbols over a window of markers.
 #include "quade_pgz.h"
 
+#include "gz_framing.h"
+
 #include <zlib.h>  // crc32_combine
 
 #include <algorithm>
@@ -423,27 +425,6 @@ Rc read_dynamic(Bits& b, Tables& t) {
     return RC_BLOCK_END;
 }
 
-// gzip member header at p (RFC 1952) -> its length; 0 = not a header, -1 = cut off by the end of the input
-int64_t gzip_header_len(const uint8_t* p, size_t n) {
-    if (n < 10) return (n >= 1 && p[0] != 0x1f) || (n >= 2 && p[1] != 0x8b) ? 0 : -1;
-    if (!looks_like_gzip(p, n)) return 0;
-    const uint8_t flg = p[3];
-    size_t o = 10;
-    if (flg & 4) {
-        if (o + 2 > n) return -1;
-        o += 2 + ((size_t)p[o] | ((size_t)p[o + 1] << 8));
-        if (o > n) return -1;
-    }
-    for (int f = 8; f <= 16; f <<= 1)  // FNAME, FCOMMENT: zero-terminated
-        if (flg & f) {
-            while (o < n && p[o]) ++o;
-            if (o >= n) return -1;
-            ++o;
-        }
-    if (flg & 2) o += 2;
-    return o > n ? -1 : (int64_t)o;
-}
-
 // ---- buffers: kept between uses (a fresh 30 MB buffer per chunk is thousands of page faults) ------------------
 struct BufPool {
     std::mutex m;
@@ -547,7 +528,7 @@ void inflate_run(const uint8_t* data, size_t size, int64_t start_bit, bool heade
     size_t lowest = WIN - valid;  // index into r.buf
     if (header_first) {
         const size_t at = (size_t)(start_bit >> 3);
-        const int64_t h = gzip_header_len(data + at, size - at);
+        const int64_t h = gzf::gzip_header_len(data + at, size - at);
         if (h <= 0) {
             r.err = h < 0 ? ERR_TRUNC : "not a valid gzip stream (no gzip header where a member should begin)";
             return;
@@ -639,20 +620,19 @@ void inflate_run(const uint8_t* data, size_t size, int64_t start_bit, bool heade
             }
             MemberEnd me;
             me.out_pos = r.n;
-            me.crc = b.p[0] | ((uint32_t)b.p[1] << 8) | ((uint32_t)b.p[2] << 16) | ((uint32_t)b.p[3] << 24);
-            me.isize = b.p[4] | ((uint32_t)b.p[5] << 8) | ((uint32_t)b.p[6] << 16) | ((uint32_t)b.p[7] << 24);
+            me.crc = gzf::le32(b.p);
+            me.isize = gzf::le32(b.p + 4);
             r.ends.push_back(me);
             b.p += 8;
-            bool zeros = true;  // zero padding behind the last member is tolerated (as by gzip itself)
-            for (const uint8_t* q = b.p; zeros && q < b.end; ++q) zeros = *q == 0;
-            if (zeros) {
+            int64_t hl = 0;
+            const gzf::MemberStart next = gzf::member_start(b.p, (size_t)(b.end - b.p), true, &hl);
+            if (next == gzf::START_PADDING) {  // (zero padding included)
                 r.end_bit = (int64_t)size * 8;
                 r.stop = STOP_EOF;
                 return;
             }
-            const int64_t hl = gzip_header_len(b.p, (size_t)(b.end - b.p));
-            if (hl <= 0) {
-                r.err = hl < 0 ? ERR_TRUNC : "not a valid gzip stream (garbage behind a gzip member)";
+            if (next != gzf::START_HEADER) {
+                r.err = next == gzf::START_CUT ? ERR_TRUNC : "not a valid gzip stream (garbage behind a gzip member)";
                 return;
             }
             b.p += hl;

@@ -70,7 +70,4 @@ class Gunzip {
     std::shared_ptr<State> s_;
 };
 
-// first bytes of a gzip member (RFC 1952): magic, CM = 8, no reserved flag bits
-inline bool looks_like_gzip(const uint8_t* p, size_t n) { return n >= 10 && p[0] == 0x1f && p[1] == 0x8b && p[2] == 8 && !(p[3] & 0xe0); }
-
 }  // namespace qdpgz

@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "../../include/quade_hip.h"
+#include "gz_framing.h"
 #include "quade_deflate.h"
 #include "quade_inflate.h"
 #include "quade_inflate3.h"
@@ -55,7 +56,6 @@
 #include "quade_filter.h"
 #include "quade_screen.h"
 
-uint32_t qd_crc32_combine_host(uint32_t crc1, uint32_t crc2, uint64_t len2);  // quade_io.cpp (zlib's)
 
 namespace {
 
@@ -472,13 +472,13 @@ class Feeder {
                 }
                 if (range_end >= 0 && read_pos >= range_end) eof = true;
             }
-            if (first && !qdio::bgzf_block_size(pin, fill)) {  // ordinary gzip
+            if (first && gzf::bgzf_block(pin, fill).is != gzf::BGZF_BLOCK) {  // ordinary gzip
                 if (ranged) {
                     fail(c, path + ": no BGZF block at the start of the byte range");
                     close(fd);
                     return;
                 }
-                if (device_gunzip_ && fill >= 18 && pin[0] == 0x1f && pin[1] == 0x8b && pin[2] == 8) {
+                if (device_gunzip_ && fill >= 18 && gzf::has_magic_cm(pin, fill)) {
                     // the device inflates it (quade_inflate3.hip): the file's bytes go up as they are, upload after upload
                     int64_t at = 0;
                     for (;;) {
@@ -525,28 +525,23 @@ class Feeder {
             size_t pos = 0, seg_start = 0;  // seg holds the blocks of pin[seg_start, pos)
             bool upload_failed = false;
             while (pos < fill) {
-                const uint8_t* b = pin + pos;
-                const size_t avail = fill - pos;
-                const size_t bs = qdio::bgzf_block_size(b, avail);
-                if (!bs) {
-                    // fewer bytes than a header, or than a header with its extra field ('BC' may stand anywhere in it): the next
-                    // read completes it
-                    const bool cut_short = avail < 18 || (b[0] == 0x1f && b[1] == 0x8b && b[2] == 8 && (b[3] & 4) && avail < 12 + (b[10] | ((size_t)b[11] << 8)));
-                    if (!cut_short || eof) switch_at = file_pos + (int64_t)pos;
+                const gzf::BgzfBlock b = gzf::bgzf_block(pin + pos, fill - pos);
+                if (b.is != gzf::BGZF_BLOCK) {
+                    // short: fewer bytes than a header, or than a header with its extra field ('BC' may stand anywhere in it): the
+                    // next read completes it
+                    if (b.is != gzf::BGZF_SHORT || eof) switch_at = file_pos + (int64_t)pos;
                     break;
                 }
-                if (bs > avail) {
+                if (!b.whole) {
                     if (eof) switch_at = file_pos + (int64_t)pos;  // a truncated block: the member loop reports it
                     break;
                 }
-                const size_t xlen = b[10] | ((size_t)b[11] << 8);
-                const uint32_t isize = (uint32_t)b[bs - 4] | ((uint32_t)b[bs - 3] << 8) | ((uint32_t)b[bs - 2] << 16) | ((uint32_t)b[bs - 1] << 24);
-                if (bs < 12 + xlen + 8 || (b[3] & ~4) || isize > 65536) {  // not bgzip's layout
+                if (!b.is_bgzip_layout()) {
                     switch_at = file_pos + (int64_t)pos;
                     break;
                 }
-                const uint32_t crc = (uint32_t)b[bs - 8] | ((uint32_t)b[bs - 7] << 8) | ((uint32_t)b[bs - 6] << 16) | ((uint32_t)b[bs - 5] << 24);
-                const uint32_t in_len = (uint32_t)(bs - 12 - xlen - 8);
+                const size_t bs = b.bsize;
+                const uint32_t isize = b.isize, crc = b.crc, in_len = (uint32_t)b.payload_len;
                 if (seg.text_bytes + isize > SEG_TEXT_MAX && !seg.blocks.empty()) {
                     // text that compresses far better than fastq does: the upload goes out in several segments, so that no window
                     // has to take more than SEG_TEXT_MAX bytes of text in one step (its offsets are 32 bit)
@@ -560,7 +555,7 @@ class Feeder {
                     seg.file_off = file_pos + (int64_t)pos;
                     seg_start = pos;
                 }
-                seg.blocks.push_back(qd_inflate_block{(uint32_t)(pos - seg_start + 12 + xlen), in_len, (uint32_t)seg.text_bytes, isize});
+                seg.blocks.push_back(qd_inflate_block{(uint32_t)(pos - seg_start + b.payload_off), in_len, (uint32_t)seg.text_bytes, isize});
                 seg.crcs.push_back(crc);
                 seg.starts.push_back((uint32_t)(pos - seg_start));
                 seg.text_bytes += isize;
@@ -698,20 +693,16 @@ struct qd_pipe {
         std::string path;
         qd_scan_result res{};
         // an ordinary gzip file on its way through the device's gzip kernels: the file's bytes [comp_off, comp_off + comp_len) lie in
-        // comp[ccur]; the next block header (or, need_header: the next member's header) is known exactly
+        // comp[ccur]; the next block header (or, walk.need_header: the next member's header) is known exactly
         struct Gz {
             bool active = false;
             DevBuf comp[2];
             int ccur = 0;
             uint64_t comp_off = 0, comp_len = 0;
             bool file_done = false;   // the feeder has delivered the file's last byte
-            bool need_header = true;
-            uint64_t hdr_off = 0;     // file offset of the next member's header
-            uint64_t bit = 0;         // file position (bits) of the next block header
-            DevBuf carried;           // the 32 KiB of text in front of it
+            gzf::MemberWalk walk;     // where the stream stands: member, next block header, the member's text and CRC so far
+            DevBuf carried;           // the 32 KiB of text in front of the next block header
             uint32_t carried_valid = 0;
-            uint32_t member_crc = 0;
-            uint64_t member_text = 0, member_off = 0;
             double ratio = 3.5;       // text per compressed byte, learned
             int fd = -1;
             int64_t file_size = 0;
@@ -1092,31 +1083,11 @@ void gz_close(Window& w) {
     g.active = false;
     g.comp_off = g.comp_len = 0;
     g.file_done = false;
-    g.need_header = true;
-    g.hdr_off = g.bit = 0;
+    g.walk = gzf::MemberWalk();
     g.carried_valid = 0;
-    g.member_crc = 0;
-    g.member_text = g.member_off = g.host_skip = 0;
+    g.host_skip = 0;
     g.stepped_end = ~0ull;
     g.stepped_done = false;
-}
-
-// bytes of a gzip member's header at p[0 .. n) (RFC 1952); 0: none, or it does not end inside n
-size_t gz_header_bytes(const uint8_t* h, size_t n) {
-    if (n < 10 || h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || (h[3] & 0xe0)) return 0;
-    const int flg = h[3];
-    size_t at = 10;
-    if (flg & 4) {
-        if (at + 2 > n) return 0;
-        at += 2 + (h[at] | ((size_t)h[at + 1] << 8));
-    }
-    for (int bit : {8, 16})
-        if (flg & bit) {
-            while (at < n && h[at]) ++at;
-            ++at;
-        }
-    if (flg & 2) at += 2;
-    return at <= n ? at : 0;
 }
 
 // the window's file is an ordinary gzip file that the device inflates: its state (idempotent)
@@ -1171,9 +1142,9 @@ int gz_fallback(qd_pipe* p, Feeder& f, Window& w, int chunk) {
         PCHK(p, f.consumed(s.slot, p->cs));
     }
     std::string err;
-    g.host = qdio::raw_open(w.path.c_str(), (int64_t)g.member_off, &err);
+    g.host = qdio::raw_open(w.path.c_str(), (int64_t)g.walk.member_off, &err);
     if (!g.host) return pfail(p, QD_ERR_FORMAT, err);
-    g.host_skip = g.member_text;
+    g.host_skip = g.walk.text;
     g.comp_len = 0;
     return QD_OK;
 }
@@ -1219,13 +1190,13 @@ int gz_host_fill(qd_pipe* p, Window& w, size_t want) {
 int gz_steps(qd_pipe* p, std::vector<std::unique_ptr<Feeder>>& feeders, int chunk) {
     std::vector<qd_gz_step> steps;
     std::vector<int> who;
-    std::vector<uint64_t> byte0s;
+    std::vector<gzf::MemberWalk::Window> wins;
     for (int s = 0; s < p->n_streams; ++s) {
         Window& w = p->win[s];
         Window::Gz& g = w.gz;
         if (!g.active || g.host || w.eof) continue;
-        if (g.need_header) {  // the next member's header (from the file: the compressed bytes live on the device)
-            if ((int64_t)g.hdr_off >= g.file_size) {
+        if (g.walk.need_header) {  // the next member's header (from the file: the compressed bytes live on the device)
+            if ((int64_t)g.walk.hdr_off >= g.file_size) {
                 if (g.file_done) {
                     w.eof = true;
                     w.dirty = true;
@@ -1233,44 +1204,39 @@ int gz_steps(qd_pipe* p, std::vector<std::unique_ptr<Feeder>>& feeders, int chun
                 continue;
             }
             uint8_t h[65536];
-            const ssize_t got = pread(g.fd, h, sizeof h, (off_t)g.hdr_off);
-            const size_t hb = got > 0 ? gz_header_bytes(h, (size_t)got) : 0;
-            if (!hb) {
-                bool zeros = got > 0;
-                for (ssize_t k = 0; k < got && zeros; ++k) zeros = h[k] == 0;
-                if (zeros && (int64_t)g.hdr_off + got >= g.file_size) {  // (padding behind the last member)
-                    g.hdr_off = (uint64_t)g.file_size;
-                    w.eof = g.file_done;
-                    w.dirty = true;
-                    continue;
-                }
-                g.member_off = g.hdr_off;
-                g.member_text = 0;
+            const ssize_t got = pread(g.fd, h, sizeof h, (off_t)g.walk.hdr_off);
+            int64_t hb = 0;
+            const gzf::MemberStart what =
+                got > 0 ? gzf::member_start(h, (size_t)got, (int64_t)g.walk.hdr_off + got >= g.file_size, &hb) : gzf::START_GARBAGE;
+            if (what == gzf::START_PADDING) {  // (behind the last member)
+                g.walk.hdr_off = (uint64_t)g.file_size;
+                w.eof = g.file_done;
+                w.dirty = true;
+                continue;
+            }
+            if (what != gzf::START_HEADER) {
+                g.walk.begin(0);
                 const int rc = gz_fallback(p, *feeders[(size_t)s], w, chunk);  // (the host's reader says what is wrong with it)
                 if (rc != QD_OK) return rc;
                 continue;
             }
-            g.member_off = g.hdr_off;
-            g.member_text = 0;
-            g.member_crc = 0;
+            g.walk.begin((uint64_t)hb);
             g.carried_valid = 0;
-            g.bit = 8 * (g.hdr_off + hb);
-            g.need_header = false;
         }
-        if (g.bit >= 8 * (g.comp_off + g.comp_len)) continue;  // nothing of it on the device yet
+        if (g.walk.bit >= 8 * (g.comp_off + g.comp_len)) continue;  // nothing of it on the device yet
         // (a step that made no progress -- the bytes on the device end inside a block -- is not tried again until more have arrived)
         if (g.stepped_end == g.comp_off + g.comp_len && g.stepped_done == g.file_done) continue;
         qd_gz_step st{};
-        const uint64_t byte0 = ((g.bit >> 3) - g.comp_off) & ~(uint64_t)15;
-        st.comp = g.comp[g.ccur].p + byte0;
-        st.comp_bytes = g.comp_len - byte0;
-        st.bit_start = g.bit - 8 * (g.comp_off + byte0);
+        const gzf::MemberWalk::Window win = g.walk.window(g.comp_off, g.comp_len);
+        st.comp = g.comp[g.ccur].p + win.byte0;
+        st.comp_bytes = win.comp_bytes;
+        st.bit_start = win.bit_start;
         st.at_end = g.file_done ? 1 : 0;
         st.carried = g.carried.p;
         st.carried_valid = g.carried_valid;
         steps.push_back(st);
         who.push_back(s);
-        byte0s.push_back(byte0);
+        wins.push_back(win);
     }
     if (steps.empty()) return QD_OK;
     const int n = (int)steps.size();
@@ -1326,9 +1292,8 @@ int gz_steps(qd_pipe* p, std::vector<std::unique_ptr<Feeder>>& feeders, int chun
             if (rc != QD_OK) return rc;
             continue;
         }
+        const bool progress = g.walk.account(st, wins[(size_t)i]);
         if (st.text_len) {
-            g.member_crc = g.member_text ? qd_crc32_combine_host(g.member_crc, st.crc32, st.text_len) : st.crc32;
-            g.member_text += st.text_len;
             w.len += (uint32_t)st.text_len;
             w.dirty = true;
             p->st.text_in_bytes += (int64_t)st.text_len;
@@ -1336,35 +1301,26 @@ int gz_steps(qd_pipe* p, std::vector<std::unique_ptr<Feeder>>& feeders, int chun
             if (used) g.ratio = 0.5 * g.ratio + 0.5 * std::min(64.0, std::max(1.0, (double)st.text_len / (double)used));
         }
         g.carried_valid = st.carried_valid;
-        const bool progress = st.bit_next != st.bit_start || st.member_end;
-        if (!progress && !st.starved) {
+        if (!progress) {
             g.stepped_end = g.comp_off + g.comp_len;
             g.stepped_done = g.file_done;
         }
-        g.bit = 8 * (g.comp_off + byte0s[(size_t)i]) + st.bit_next;
         if (st.member_end) {  // the trailer: CRC-32 and ISIZE of the member's text
-            const uint64_t tr = (g.bit + 7) >> 3;
             uint8_t t[8];
-            if (pread(g.fd, t, 8, (off_t)tr) != 8) {
+            if (pread(g.fd, t, 8, (off_t)g.walk.trailer_off()) != 8) {
                 const int rc = gz_fallback(p, *feeders[(size_t)s], w, chunk);  // (truncated: the host's reader reports it)
                 if (rc != QD_OK) return rc;
                 continue;
             }
-            const uint32_t want_crc = t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-            const uint32_t want_len = t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
-            if (want_crc != (g.member_text ? g.member_crc : 0u) || want_len != (uint32_t)g.member_text)
-                return pfail(p, QD_ERR_FORMAT, w.path + ": CRC-32 or length of a gzip member does not match its text");
+            if (!g.walk.end_member(t).ok) return pfail(p, QD_ERR_FORMAT, w.path + ": CRC-32 or length of a gzip member does not match its text");
             ++p->st.gzip_members;
-            g.need_header = true;
-            g.hdr_off = tr + 8;
-            g.bit = 8 * g.hdr_off;
-        } else if (!progress && g.file_done && !st.starved) {
+        } else if (!progress && g.file_done) {
             const int rc = gz_fallback(p, *feeders[(size_t)s], w, chunk);  // the stream ends inside a block: the host's reader reports it
             if (rc != QD_OK) return rc;
             continue;
         }
         // what lies in front of the next block header has been used: the rest moves to the front of the other buffer
-        const uint64_t keep_from = std::min<uint64_t>(((g.bit >> 3) - g.comp_off) & ~(uint64_t)15, g.comp_len);
+        const uint64_t keep_from = std::min<uint64_t>(g.walk.window(g.comp_off, g.comp_len).byte0, g.comp_len);
         if (keep_from) {
             const uint64_t left = g.comp_len - keep_from;
             const int nx = g.ccur ^ 1;
@@ -1374,7 +1330,7 @@ int gz_steps(qd_pipe* p, std::vector<std::unique_ptr<Feeder>>& feeders, int chun
             g.comp_off += keep_from;
             g.comp_len = left;
         }
-        if (g.file_done && g.need_header && (int64_t)g.hdr_off >= g.file_size) {
+        if (g.file_done && g.walk.need_header && (int64_t)g.walk.hdr_off >= g.file_size) {
             w.eof = true;
             w.dirty = true;
         }
@@ -1388,7 +1344,7 @@ int top_up(qd_pipe* p, Feeder& f, Window& w, int stream_index, int chunk, size_t
     while (!w.eof && (size_t)w.len + w.pending_text < want) {
         if (w.gz.active) {
             // (an estimate of the text the compressed bytes on the device stand for: gz_steps will tell)
-            const uint64_t held = 8 * (w.gz.comp_off + w.gz.comp_len) > w.gz.bit ? w.gz.comp_off + w.gz.comp_len - (w.gz.bit >> 3) : 0;
+            const uint64_t held = 8 * (w.gz.comp_off + w.gz.comp_len) > w.gz.walk.bit ? w.gz.comp_off + w.gz.comp_len - (w.gz.walk.bit >> 3) : 0;
             const bool stuck = w.gz.stepped_end == w.gz.comp_off + w.gz.comp_len;  // (the last step could use none of what is held: more must come)
             if (w.gz.file_done || (!stuck && (double)w.len + (double)held * w.gz.ratio >= (double)want)) break;
         }
@@ -2000,8 +1956,8 @@ Peek peek_record_bytes(const char* path, int64_t start) {
     if (got < 32) return pk;
     const uint8_t* text = in.data();
     size_t n_text = (size_t)got;
-    if (in[0] == 0x1f && in[1] == 0x8b) {
-        pk.plain_gzip = in[2] == 8 && !qdio::bgzf_block_size(in.data(), (size_t)got);  // (the feeder's test: Feeder::one_file)
+    if (gzf::has_magic(in.data(), (size_t)got)) {
+        pk.plain_gzip = gzf::has_magic_cm(in.data(), (size_t)got) && gzf::bgzf_block(in.data(), (size_t)got).is != gzf::BGZF_BLOCK;  // (the feeder's test: Feeder::one_file)
         z_stream z;
         memset(&z, 0, sizeof z);
         if (inflateInit2(&z, 15 + 32) != Z_OK) return pk;
@@ -2094,7 +2050,7 @@ int run_chunk(qd_pipe* p, std::vector<std::unique_ptr<Feeder>>& feeders, int chu
                 fprintf(stderr, " [%d len %u want %zu kept %u eof %d%s", s, w.len, want[s], w.res.n_kept, (int)w.eof, w.gz.active ? " gz" : "");
                 if (w.gz.active)
                     fprintf(stderr, " comp %llu+%llu bit %llu hdr %d done %d host %d", (unsigned long long)w.gz.comp_off, (unsigned long long)w.gz.comp_len,
-                            (unsigned long long)w.gz.bit, (int)w.gz.need_header, (int)w.gz.file_done, w.gz.host ? 1 : 0);
+                            (unsigned long long)w.gz.walk.bit, (int)w.gz.walk.need_header, (int)w.gz.file_done, w.gz.host ? 1 : 0);
                 fprintf(stderr, "]");
             }
             fprintf(stderr, "\n");
@@ -2283,8 +2239,9 @@ int walk_bgzf(qd_pipe* p, const char* path, std::vector<int64_t>* off) {
     int rc = QD_OK;
     while (at < (int64_t)sb.st_size) {
         const ssize_t g = pread(fd, h, sizeof h, (off_t)at);
-        const size_t bs = g > 0 ? qdio::bgzf_block_size(h, (size_t)g) : 0;
-        if (bs < 26 || at + (int64_t)bs > (int64_t)sb.st_size) {
+        // (64 bytes a block: a 'BC' behind more than 52 bytes of extra field reads as "short", and counts as not BGZF -- DESIGN.md 9)
+        const size_t bs = g > 0 ? gzf::bgzf_block(h, (size_t)g).size() : 0;
+        if (bs < gzf::BGZF_MIN_BLOCK || at + (int64_t)bs > (int64_t)sb.st_size) {
             rc = pfail(p, QD_ERR_UNSUPPORTED, std::string(path) + ": not BGZF blocks throughout (a shared chunk needs bgzip files)");
             break;
         }

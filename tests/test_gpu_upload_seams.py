@@ -4,18 +4,18 @@ and its counters -- and, from the run's statistics, that the run went where the 
 
 What each framing reaches in quade_amd/csrc/quade_pipe.cpp (Feeder::one_file, gz_append / gz_steps / top_up, drain_chunk):
 
-  gz               SEG_GZIP uploads two to four of a file; gz_append joins them at comp_off + comp_len; steps that resume at g.bit
+  gz               SEG_GZIP uploads two to four of a file; gz_append joins them at comp_off + comp_len; steps that resume at walk.bit
                    behind bytes that keep_from has moved; the 32 KiB carried window; stepped_end / stuck (an upload ends inside a
                    block); the member's CRC combined over its steps; the fourth upload reuses a page-locked buffer (take_pin)
   bgzf             the partial block behind a buffer's last whole one carried in `tail`; file_pos / seg.file_off above 0
   gz_members       headers and trailers read with pread at file offsets while the payload is on the device: a trailer that ends at a
-                   seam, one across a seam, a header across a seam; g.bit >= 8 * (comp_off + comp_len) (the next member has nothing
+                   seam, one across a seam, a header across a seam; walk.bit >= 8 * (comp_off + comp_len) (the next member has nothing
                    on the device yet); an empty member; the zero-padding rule
   bgzf_seams       an empty `tail` (a block ends at a buffer's end); fewer than 18 bytes of a header at a buffer's end; 18 or more
                    bytes but not the whole extra field (the feeder took that for "no longer BGZF" and sent the rest of the file down
                    the host's text path: text_segments == 0 is the assertion that caught it)
   bgzf_then_gz     switch_at > 0: text_from(c, path, switch_at) behind blocks that the device inflated
-  gz_refused_late  gz_fallback with host_skip = member_text > 0: the host inflates the member again from its start and the text that
+  gz_refused_late  gz_fallback with host_skip = walk.text > 0: the host inflates the member again from its start and the text that
                    was delivered is dropped -- text_in_bytes says that no byte came twice or not at all
   *_damaged_late   a decoder status or a CRC of the second upload fails the run with the file's name; the next run is clean
   ends_early_*     a chunk that ends with index_R2 while the insert streams' uploads are in flight: skip_below, drain_chunk,
