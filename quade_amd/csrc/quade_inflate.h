@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "quade_inflate_block.h"
+
 // status codes of one block (0 = inflated to exactly out_len bytes)
 #define QD_INFLATE_TRUNCATED 1     /* the compressed payload ended inside a code                      */
 #define QD_INFLATE_BAD_TYPE 2      /* reserved block type, or no final block                          */
@@ -16,11 +18,6 @@
 #define QD_INFLATE_TABLE_SPACE 10  /* third form: more symbols with long codes than a lane's table holds -- another form takes the block */
 #define QD_INFLATE_TOKEN_SPACE 11  /* third form: more tokens than the unit's slot region holds                                          */
 #define QD_INFLATE_CHAIN 12        /* third form, a stretch of a gzip member: the decode passed its stop position, no block starts there   */
-
-struct qd_inflate_block {
-    uint32_t in_off, in_len;    // raw deflate payload of the block inside the compressed buffer
-    uint32_t out_off, out_len;  // where its text goes, and how much there must be (ISIZE)
-};
 
 hipError_t qd_launch_inflate(const uint8_t* comp, const qd_inflate_block* blocks, uint32_t n_blocks, uint8_t* out,
                              int32_t* status, hipStream_t st);

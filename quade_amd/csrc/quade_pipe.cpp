@@ -26,6 +26,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cassert>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -55,6 +56,9 @@
 #include "quade_posttrim.h"
 #include "quade_filter.h"
 #include "quade_screen.h"
+#pragma GCC visibility push(hidden)  // (header-only and used here alone: the library exports nothing of it)
+#include "feed_cut.h"
+#pragma GCC visibility pop
 
 
 namespace {
@@ -185,17 +189,13 @@ class StagePool {
 };
 
 // ---- feeders: file -> page-locked buffer -> device ring ----------------------------------------------------------------------
-enum { SEG_BGZF, SEG_TEXT, SEG_END, SEG_ERROR, SEG_GZIP };
-struct Segment {
-    int kind = SEG_END;
-    int chunk = 0;
+using feed::SEG_BGZF, feed::SEG_TEXT, feed::SEG_END, feed::SEG_ERROR, feed::SEG_GZIP;
+static_assert(SEG_BYTES >= 2 * feed::BGZF_LARGEST, "feed::Cutter: a buffer holds a largest block behind a carried tail");
+struct Segment : feed::Cut {  // kind, chunk, and a BGZF segment's blocks (offsets inside the slot) and file offset: feed_cut.h
+    Segment() = default;
+    explicit Segment(feed::Cut&& c) : feed::Cut(std::move(c)) {}
     int slot = -1;          // ring slot that holds `bytes` bytes
     size_t bytes = 0;
-    size_t text_bytes = 0;  // BGZF: what the blocks inflate to
-    std::vector<qd_inflate_block> blocks;  // in_off inside the slot, out_off inside the segment's text
-    std::vector<uint32_t> crcs;
-    std::vector<uint32_t> starts;  // where every block starts in the slot (its file offset = file_off + that)
-    int64_t file_off = 0;   // BGZF: where the blocks start in the file (a run the device refuses is read again by the host)
     std::string err;
 };
 
@@ -389,184 +389,162 @@ class Feeder {
         qdio::raw_close(r);
     }
 
-    void one_file(int c) {
-        const std::string& path = files_[c].path;
-        const int64_t range_start = files_[c].start, range_end = files_[c].end;
-        const bool ranged = range_start > 0 || range_end >= 0;
-        if (!ends_gz(path)) {
-            if (ranged) return fail(c, path + ": a byte range needs a BGZF file");
-            return text_from(c, path, 0);
+    struct Fd {  // the one owner of a file descriptor
+        const int fd;
+        explicit Fd(int f) : fd(f) {}
+        ~Fd() {
+            if (fd >= 0) close(fd);
         }
-        const int fd = open(path.c_str(), O_RDONLY | O_CLOEXEC);
-        if (fd < 0) return fail(c, path + ": " + strerror(errno));
-        std::vector<uint8_t> tail;  // the partial block behind the last whole one of the previous buffer
-        int64_t file_pos = range_start;  // file offset of the buffer's first byte
-        int64_t read_pos = range_start;  // file offset of the next byte to read
+        Fd(const Fd&) = delete;
+        Fd& operator=(const Fd&) = delete;
+    };
+    struct Filled {
+        size_t bytes = 0;    // read in front of the first part that came short
+        bool eof = false;    // the file ends inside them
+        bool error = false;
+    };
+    // dst[0 .. want) <- the file from offset `from` on.  One thread copies ~2.5 GB/s out of the page cache, less than the device
+    // inflates: the parts of `part` bytes are read side by side on the library's pool (pread at known offsets), the last on this thread
+    static Filled fill_from(int fd, uint8_t* dst, size_t want, int64_t from, size_t part) {
+        const int parts = (int)((want + part - 1) / part);
+        std::vector<ssize_t> got((size_t)parts, 0);
+        struct {
+            std::mutex m;
+            std::condition_variable cv;
+            int left;
+        } latch;
+        latch.left = parts;
+        for (int q = 0; q < parts; ++q) {
+            uint8_t* to = dst + (size_t)q * part;
+            const size_t len = std::min(part, want - (size_t)q * part);
+            const int64_t at = from + (int64_t)q * (int64_t)part;
+            auto job = [fd, to, len, at, q, &got, &latch] {
+                size_t n = 0;
+                ssize_t r = 0;
+                while (n < len && (r = pread(fd, to + n, len - n, (off_t)(at + (int64_t)n))) != 0) {
+                    if (r < 0) {
+                        if (errno == EINTR) continue;
+                        break;
+                    }
+                    n += (size_t)r;
+                }
+                got[(size_t)q] = r < 0 ? -1 : (ssize_t)n;
+                std::lock_guard<std::mutex> g(latch.m);
+                if (--latch.left == 0) latch.cv.notify_all();
+            };
+            if (q + 1 < parts) qdio::pool_submit(job, true);
+            else job();
+        }
+        {
+            std::unique_lock<std::mutex> g(latch.m);
+            latch.cv.wait(g, [&] { return latch.left == 0; });
+        }
+        Filled f;
+        for (int q = 0; q < parts && !f.eof; ++q) {
+            if (got[(size_t)q] < 0) {
+                f.error = true;
+                break;
+            }
+            f.bytes += (size_t)got[(size_t)q];
+            f.eof = (size_t)got[(size_t)q] < std::min(part, want - (size_t)q * part);
+        }
+        return f;
+    }
+
+    // an ordinary gzip file that the device inflates (quade_inflate3.hip): its bytes go up as they are, upload after upload, one
+    // serial read each.  pin[0 .. fill): the file's first buffer
+    void feed_gzip(int c, int fd, uint8_t* pin, size_t fill, bool eof) {
+        int64_t at = 0;
+        for (;;) {
+            Segment seg;
+            seg.kind = SEG_GZIP;
+            seg.chunk = c;
+            seg.file_off = at;
+            if (!upload(seg, pin, fill)) break;
+            at += (int64_t)fill;
+            if (eof || skip_.load() > c || stopping()) break;
+            pin = take_pin();
+            if (!pin) {
+                fail(c, "page-locked memory: allocation or upload failed");
+                break;
+            }
+            const Filled got = fill_from(fd, pin, SEG_BYTES, at, SEG_BYTES);
+            if (got.error) {
+                fail(c, files_[c].path + ": read error");
+                break;
+            }
+            fill = got.bytes;
+            eof = got.eof;
+            if (fill == 0) break;
+        }
+    }
+
+    // the blocks of a .gz file, buffer after buffer, as feed::Cutter cuts them into segments (a file that is ordinary gzip at its
+    // start: feed_gzip, or the host's readers).  -> the file offset from which the host's text path takes over, -1: nothing is left to it
+    int64_t feed_bgzf(int c, int fd) {
+        const std::string& path = files_[c].path;
+        const int64_t range_end = files_[c].end;
+        const bool ranged = files_[c].start > 0 || range_end >= 0;
+        feed::Cutter cutter(SEG_BYTES, SEG_TEXT_MAX, files_[c].start, c);
         bool eof = false, first = true;
-        int64_t switch_at = -1;     // >= 0: not (or no longer) BGZF from this file offset on
-        while (!eof && switch_at < 0) {
+        while (!eof) {
             if (skip_.load() > c || stopping()) break;
             uint8_t* pin = take_pin();
             if (!pin) {
                 fail(c, "page-locked memory: allocation or upload failed");
                 break;
             }
-            size_t fill = tail.size();
-            if (fill) memcpy(pin, tail.data(), fill);
-            tail.clear();
-            {
-                // one thread copies ~2.5 GB/s out of the page cache, less than the device inflates: the buffer's parts are
-                // read side by side on the library's pool (pread at known offsets; the blocks are cut afterwards)
-                size_t want = SEG_BYTES - fill;
-                if (range_end >= 0) {
-                    want = (size_t)std::min<int64_t>((int64_t)want, std::max<int64_t>(range_end - read_pos, 0));
-                    if (want == 0) eof = true;
-                }
-                const int64_t from = read_pos;
-                const int parts = (int)((want + READ_PART - 1) / READ_PART);
-                std::vector<ssize_t> got((size_t)parts, 0);
-                struct {
-                    std::mutex m;
-                    std::condition_variable cv;
-                    int left;
-                } latch;
-                latch.left = parts;
-                for (int q = 0; q < parts; ++q) {
-                    uint8_t* dst = pin + fill + (size_t)q * READ_PART;
-                    const size_t len = std::min(READ_PART, want - (size_t)q * READ_PART);
-                    const int64_t at = from + (int64_t)q * (int64_t)READ_PART;
-                    auto job = [fd, dst, len, at, q, &got, &latch] {
-                        size_t n = 0;
-                        ssize_t r = 0;
-                        while (n < len && (r = pread(fd, dst + n, len - n, (off_t)(at + (int64_t)n))) != 0) {
-                            if (r < 0) {
-                                if (errno == EINTR) continue;
-                                break;
-                            }
-                            n += (size_t)r;
-                        }
-                        got[(size_t)q] = r < 0 ? -1 : (ssize_t)n;
-                        std::lock_guard<std::mutex> g(latch.m);
-                        if (--latch.left == 0) latch.cv.notify_all();
-                    };
-                    if (q + 1 < parts) qdio::pool_submit(job, true);
-                    else job();  // (the last part on this thread)
-                }
-                {
-                    std::unique_lock<std::mutex> g(latch.m);
-                    latch.cv.wait(g, [&] { return latch.left == 0; });
-                }
-                for (int q = 0; q < parts; ++q) {
-                    if (got[(size_t)q] < 0) {
-                        fail(c, path + ": read error");
-                        close(fd);
-                        return;
-                    }
-                    fill += (size_t)got[(size_t)q];
-                    read_pos += got[(size_t)q];
-                    const size_t len = std::min(READ_PART, want - (size_t)q * READ_PART);
-                    if ((size_t)got[(size_t)q] < len) {  // the file ends inside this part
-                        eof = true;
-                        break;
-                    }
-                }
-                if (range_end >= 0 && read_pos >= range_end) eof = true;
+            size_t fill = cutter.carry_into(pin);
+            const int64_t from = cutter.read_from();
+            size_t want = SEG_BYTES - fill;
+            if (range_end >= 0) {
+                want = (size_t)std::min<int64_t>((int64_t)want, std::max<int64_t>(range_end - from, 0));
+                if (want == 0) eof = true;
             }
-            if (first && gzf::bgzf_block(pin, fill).is != gzf::BGZF_BLOCK) {  // ordinary gzip
-                if (ranged) {
+            const Filled got = fill_from(fd, pin + fill, want, from, READ_PART);
+            if (got.error) {
+                fail(c, path + ": read error");
+                return -1;
+            }
+            fill += got.bytes;
+            if (got.eof || (range_end >= 0 && from + (int64_t)got.bytes >= range_end)) eof = true;
+            if (first) {
+                const feed::FirstBuffer is = feed::classify_first(pin, fill);
+                if (is != feed::FIRST_BGZF && ranged) {
                     fail(c, path + ": no BGZF block at the start of the byte range");
-                    close(fd);
-                    return;
+                    return -1;
                 }
-                if (device_gunzip_ && fill >= 18 && gzf::has_magic_cm(pin, fill)) {
-                    // the device inflates it (quade_inflate3.hip): the file's bytes go up as they are, upload after upload
-                    int64_t at = 0;
-                    for (;;) {
-                        Segment seg;
-                        seg.kind = SEG_GZIP;
-                        seg.chunk = c;
-                        seg.file_off = at;
-                        if (!upload(seg, pin, fill)) break;
-                        at += (int64_t)fill;
-                        if (eof || skip_.load() > c || stopping()) break;
-                        pin = take_pin();
-                        if (!pin) {
-                            fail(c, "page-locked memory: allocation or upload failed");
-                            break;
-                        }
-                        fill = 0;
-                        while (fill < SEG_BYTES) {
-                            const ssize_t r = pread(fd, pin + fill, SEG_BYTES - fill, (off_t)(at + (int64_t)fill));
-                            if (r < 0 && errno == EINTR) continue;
-                            if (r < 0) {
-                                fail(c, path + ": read error");
-                                close(fd);
-                                return;
-                            }
-                            if (r == 0) {
-                                eof = true;
-                                break;
-                            }
-                            fill += (size_t)r;
-                        }
-                        if (fill == 0) break;
-                    }
-                    close(fd);
-                    return;
+                if (is == feed::FIRST_GZIP && device_gunzip_) {
+                    feed_gzip(c, fd, pin, fill, eof);
+                    return -1;
                 }
-                switch_at = 0;  // ... or the host's parallel inflater takes the file
-                break;
+                if (is != feed::FIRST_BGZF) return 0;  // the host's parallel inflater takes the file
+                first = false;
             }
-            first = false;
-            Segment seg;
-            seg.kind = SEG_BGZF;
-            seg.chunk = c;
-            seg.file_off = file_pos;
-            size_t pos = 0, seg_start = 0;  // seg holds the blocks of pin[seg_start, pos)
-            bool upload_failed = false;
-            while (pos < fill) {
-                const gzf::BgzfBlock b = gzf::bgzf_block(pin + pos, fill - pos);
-                if (b.is != gzf::BGZF_BLOCK) {
-                    // short: fewer bytes than a header, or than a header with its extra field ('BC' may stand anywhere in it): the
-                    // next read completes it
-                    if (b.is != gzf::BGZF_SHORT || eof) switch_at = file_pos + (int64_t)pos;
-                    break;
-                }
-                if (!b.whole) {
-                    if (eof) switch_at = file_pos + (int64_t)pos;  // a truncated block: the member loop reports it
-                    break;
-                }
-                if (!b.is_bgzip_layout()) {
-                    switch_at = file_pos + (int64_t)pos;
-                    break;
-                }
-                const size_t bs = b.bsize;
-                const uint32_t isize = b.isize, crc = b.crc, in_len = (uint32_t)b.payload_len;
-                if (seg.text_bytes + isize > SEG_TEXT_MAX && !seg.blocks.empty()) {
-                    // text that compresses far better than fastq does: the upload goes out in several segments, so that no window
-                    // has to take more than SEG_TEXT_MAX bytes of text in one step (its offsets are 32 bit)
-                    if (!upload(seg, pin + seg_start, pos - seg_start)) {
-                        upload_failed = true;
-                        break;
-                    }
-                    seg = Segment();
-                    seg.kind = SEG_BGZF;
-                    seg.chunk = c;
-                    seg.file_off = file_pos + (int64_t)pos;
-                    seg_start = pos;
-                }
-                seg.blocks.push_back(qd_inflate_block{(uint32_t)(pos - seg_start + b.payload_off), in_len, (uint32_t)seg.text_bytes, isize});
-                seg.crcs.push_back(crc);
-                seg.starts.push_back((uint32_t)(pos - seg_start));
-                seg.text_bytes += isize;
-                pos += bs;
-            }
-            if (upload_failed) break;
-            if (switch_at < 0 && pos < fill) tail.assign(pin + pos, pin + fill);
-            file_pos += (int64_t)pos;
-            if (!seg.blocks.empty() && !upload(seg, pin + seg_start, pos - seg_start)) break;
+            const feed::Outcome o = cutter.cut(pin, fill, eof, [this](feed::Cut&& cut, const uint8_t* at, size_t n) {
+                Segment seg(std::move(cut));
+                return upload(seg, at, n);
+            });
+            if (o != feed::CUT_GO_ON) break;
         }
-        close(fd);
+        // (also behind an upload that failed after the switch was found: the text path's segments then follow the SEG_ERROR, which
+        // the driver's top_up stops at and its drain_chunk skips)
+        return cutter.switch_at();
+    }
+
+    void one_file(int c) {
+        const std::string& path = files_[c].path;
+        const bool ranged = files_[c].start > 0 || files_[c].end >= 0;
+        if (!ends_gz(path)) {
+            if (ranged) return fail(c, path + ": a byte range needs a BGZF file");
+            return text_from(c, path, 0);
+        }
+        int64_t switch_at;  // >= 0: not (or no longer) BGZF from this file offset on
+        {
+            const Fd file(open(path.c_str(), O_RDONLY | O_CLOEXEC));
+            if (file.fd < 0) return fail(c, path + ": " + strerror(errno));
+            switch_at = feed_bgzf(c, file.fd);
+        }
         if (switch_at >= 0 && ranged) return fail(c, path + ": the byte range is not BGZF blocks throughout");
         if (switch_at >= 0 && skip_.load() <= c && !stopping()) text_from(c, path, switch_at);
     }
@@ -1957,7 +1935,7 @@ Peek peek_record_bytes(const char* path, int64_t start) {
     const uint8_t* text = in.data();
     size_t n_text = (size_t)got;
     if (gzf::has_magic(in.data(), (size_t)got)) {
-        pk.plain_gzip = gzf::has_magic_cm(in.data(), (size_t)got) && gzf::bgzf_block(in.data(), (size_t)got).is != gzf::BGZF_BLOCK;  // (the feeder's test: Feeder::one_file)
+        pk.plain_gzip = feed::classify_first(in.data(), (size_t)got) == feed::FIRST_GZIP;
         z_stream z;
         memset(&z, 0, sizeof z);
         if (inflateInit2(&z, 15 + 32) != Z_OK) return pk;

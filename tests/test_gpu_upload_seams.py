@@ -2,7 +2,7 @@
 tests/test_host_upload_seams.py), each through one CLI run with batch_pairs 97, against oracle.run_quade's directory byte for byte
 and its counters -- and, from the run's statistics, that the run went where the framing aims.  One oracle run per text set.
 
-What each framing reaches in quade_amd/csrc/quade_pipe.cpp (Feeder::one_file, gz_append / gz_steps / top_up, drain_chunk):
+What each framing reaches in quade_amd/csrc/quade_pipe.cpp (Feeder::feed_bgzf / feed_gzip with feed_cut.h's cutter, gz_append / gz_steps / top_up, drain_chunk):
 
   gz               SEG_GZIP uploads two to four of a file; gz_append joins them at comp_off + comp_len; steps that resume at walk.bit
                    behind bytes that keep_from has moved; the 32 KiB carried window; stepped_end / stuck (an upload ends inside a

@@ -341,7 +341,7 @@ def bgzf_layout(path, upto=None):
 
 
 def bgzf_cuts(path):
-    """A model of the feeder's cuts (Feeder::one_file): buffer k covers the file's bytes [pos_k, pos_k + S), and pos_k+1 is the start
+    """A model of the feeder's cuts (feed::Cutter, quade_amd/csrc/feed_cut.h): buffer k covers the file's bytes [pos_k, pos_k + S), and pos_k+1 is the start
     of the first block that is not wholly inside it.  [(pos_k, [blocks wholly inside buffer k])] up to the end of the file's blocks"""
     blocks = bgzf_layout(path)
     out, i = [], 0
