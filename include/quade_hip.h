@@ -636,6 +636,47 @@ int qd_cstats_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
 int qd_cstats_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
 int qd_cstats_lds_cycles(void);
 
+/* ---- adapter content of the raw insert reads (opt-in; no reference counterpart) ------------------------------------------------
+ * Which known adapter is in the library, in what share of the reads, from which cycle on and in which samples: what a user needs
+ * before choosing adapter_R1 / adapter_R2 for the trimming stage.  A device-resident table of exact uint64 counters.
+ *
+ * Probes.  A probe is QD_ADAPTERS_K = 12 bytes, each one of A, C, G, T (upper case).  Up to QD_ADAPTERS_PROBES = 16 are in force;
+ *   slot a is the a-th probe given to qd_adapters_set.  No two are equal.
+ * Reads.  The insert reads AS THE SCAN LEFT THEM, R1 and R2 (r = 0 / 1): in front of clipping, trimming, overlap trimming,
+ *   post-trimming, the read filter and the screen.  It is the only stage that counts raw reads: the table describes the library, not
+ *   what the trimmers left.  Every pair the pipeline routes is counted, whatever the write flags say and whatever the filter or
+ *   the screen do to it later.
+ * Per read.  With u[i] = s[i] & 0xDF and L the sequence length, first(a) is the smallest p in [0, L - 12] with u[p .. p + 12)
+ *   equal to probe a; otherwise it is none.  A byte that is not A, C, G or T after folding never matches, so an N inside the 12
+ *   bases means no match at that p.  first(any) is the minimum over the probes in force.
+ * Table.  uint64, two parts, QD_ADAPTERS_HIST_VALUES + (2 * S + 1) * QD_ADAPTERS_DEST_VALUES values:
+ *   hist[r][a][bin]   a is one of 17 columns, the 16 slots then any; a read with first(a) adds one to bin = min(first(a), 1024);
+ *                     2 x 17 x 1025 = 34 850 values; unused slots stay 0
+ *   dest[d][r][c]     d the destination in routing code order, 0xFFFF -> 2 * S, as qd_qstats_read's; c = 0 the reads, c = 1 + a
+ *                     the reads with first(a) not none: 18 columns, 36 values per destination
+ * Cross-checks.  The sum over bins of hist[r][a] equals the sum over d of dest[d][r][1 + a]; the sum of dest[d][r][0] equals the
+ *   pairs routed.
+ *
+ * With the stage on, qd_pipe_run adds every pair it routes: one launch per batch on its compute stream, no host sync, on the
+ * scan's record tables and the final routing codes, in front of the stages that rewrite the tables; a chunk part (skip_kept,
+ * max_pairs) counts exactly its pairs.  Off, nothing is allocated or launched.
+ * qd_adapters_set: probes = n_probes x 12 bytes; NULL or n_probes 0 turns the stage off and frees the table.  A byte outside ACGT,
+ *   two equal probes or n_probes outside 0 .. 16 is QD_ERR_INVALID and leaves the state as before.  Needs qd_set_plan and
+ *   qd_set_barcodes (QD_ERR_STATE), which turn the stage off as they do the quality counters: the table has a row per destination.
+ *   Waits for the context's outstanding work.
+ * qd_adapters_get: the probes in force (*n_probes 0 and QD_OK when off); probes (room for 16 x 12 bytes) may be NULL.
+ * qd_adapters_read: waits for the context's work, writes n_values = 34850 + (2 * S + 1) * 36 values (QD_ERR_INVALID on another size,
+ * QD_ERR_STATE when off).  qd_adapters_add: another context's table joins this one's.  qd_reset_counts zeroes the table. */
+#define QD_ADAPTERS_K 12
+#define QD_ADAPTERS_PROBES 16
+#define QD_ADAPTERS_BINS 1025
+#define QD_ADAPTERS_HIST_VALUES 34850
+#define QD_ADAPTERS_DEST_VALUES 36
+int qd_adapters_set(qd_ctx* ctx, const uint8_t* probes, int32_t n_probes);
+int qd_adapters_get(const qd_ctx* ctx, uint8_t* probes, int32_t* n_probes);
+int qd_adapters_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
+int qd_adapters_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
+
 /* ---- duplication report: read-pair keys tallied on the device (opt-in; no reference counterpart) -------------------------------
  * The library duplication rate: how many of a destination's pairs repeat an earlier pair's first bases.  It is no sum of per-read
  * counters: a device-resident hash table, fed by every batch, counts the pairs per key.  The pairs are those the output stages
@@ -1146,6 +1187,13 @@ int qd_dev_cstats(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_
  * Returns when the launches have finished. */
 int qd_dev_dup(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes, const uint8_t* drop);
+/* the adapter content stage (qd_adapters_set above; no reference counterpart) over host buffers, as qd_dev_qstats: pairs
+ * [0, n_pairs) of two texts with their record tables and routing codes are uploaded (the texts 3 bytes off alignment), searched by
+ * the kernel qd_pipe_run launches, and added to the context's table.  Every record's sequence and quality range is checked against
+ * len1 / len2 and every code against 2 * S (0xFFFF apart) before anything is launched: QD_ERR_INVALID.  QD_ERR_STATE when the stage
+ * is off.  Returns when the launch has finished. */
+int qd_dev_adapters(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+                    const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes);
 /* ---- the routing and format stages of qd_pipe_run one at a time (additive: QD_ABI_VERSION stays 6) ----------------------------
  * These three run the kernels between the record tables and the packed members on host buffers, for tests that compare every stage
  * with a plain model (tests/route_model.py).  They are stage harnesses: no reference counterpart (what the stages themselves

@@ -7,7 +7,7 @@ file written by `-i` is the reference's template byte for byte (src/Conf_file.py
 package data, quade_amd/data/Quade_conf_file.txt).  An optional [gpu] section that reference conf
 files simply do not have is read when present (defaults apply otherwise; see GPU_SECTION_HELP), and so are the optional
 mismatch budgets of the [index] section (MISMATCH_HELP), the unknown-barcode report (UNKNOWN_HELP), the index-hopping report (HOPPING_HELP) and the quality report
-(QUALITY_HELP), the per-cycle report (CYCLE_HELP) and the duplication report (DUPLICATION_HELP) of the [output] section, an optional [trim] section (CLIP_HELP, TRIM_HELP, PAIR_HELP, POSTTRIM_HELP), an optional [filter] section
+(QUALITY_HELP), the per-cycle report (CYCLE_HELP), the adapter content report (ADAPTER_HELP) and the duplication report (DUPLICATION_HELP) of the [output] section, an optional [trim] section (CLIP_HELP, TRIM_HELP, PAIR_HELP, POSTTRIM_HELP), an optional [filter] section
 (FILTER_HELP) and an optional [screen] section (SCREEN_HELP).
 """
 from __future__ import annotations
@@ -120,6 +120,35 @@ Optional [output] option (not in Quade 0.3.2, whose parser ignores it; absent, e
 """
 
 CYCLE_NEEDS = "cycle_report needs the device pipeline (device_pipeline, device_inflate, device_deflate : True and gzip_level 1 or -1)"
+
+ADAPTER_HELP = """\
+Optional [output] options (not in Quade 0.3.2, whose parser ignores them; absent, empty or False = no report):
+  adapter_report : False    True: write Quade_adapter_report.csv next to the report -- which known adapters start where in R1 and
+                            R2: for every probe and for any of them the reads that hold it and their share per 100000, the most
+                            frequent one (top_adapter_R1, top_adapter_R2), the cumulative content by position (the curve FastQC
+                            draws) and the counts per destination (<sample>_pass, <sample>_fail, Undetermined, Total).  A probe is
+                            the first 12 bases of an adapter; a read holds it where 12 consecutive bases equal it, either case,
+                            and an N matches nothing.  The built-in probes are illumina_universal AGATCGGAAGAG,
+                            illumina_small_rna_3p TGGAATTCTCGG, illumina_small_rna_5p GATCGTCGGACT, nextera_transposase
+                            CTGTCTCTTATA, poly_a and poly_g; [trim] adapter_R1 and adapter_R2 join them under those names when
+                            set.  The report describes the library, not what the trimmers left: it is the only stage that counts
+                            the RAW insert reads, as they are in the input files -- in front of the clipping, [trim],
+                            pair_overlap, the post-trimming, [filter] and [screen] -- and every pair the run routes, whatever the
+                            write flags say and whatever the filter or the screen drop later.  Read it before choosing
+                            adapter_R1, poly_g or poly_x.  The reads are searched on the GPU while the device pipeline holds
+                            their text, so the option needs the device pipeline: [gpu] device_pipeline, device_inflate and
+                            device_deflate True (the defaults) and gzip_level 1 or -1
+  adapter_report_extra :    NAME=SEQ;NAME=SEQ... further probes: a name is letters, digits and _ and differs from every other
+                            name, the probe is the first 12 bases of SEQ.  A sequence shorter than 12 bases or whose first 12
+                            are not all A, C, G or T is left off, one whose probe equals an earlier probe is an alias of it: the
+                            report lists both.  At most 16 distinct probes in all.  Without adapter_report the option does nothing
+"""
+
+ADAPTER_NEEDS = "adapter_report needs the device pipeline (device_pipeline, device_inflate, device_deflate : True and gzip_level 1 or -1)"
+ADAPTER_EXTRA = "adapter_report_extra : NAME=SEQ;NAME=SEQ... with names of letters, digits and _ that differ from every other probe's name"
+ADAPTER_TOO_MANY = "adapter_report : more than 16 distinct probes (6 built in, adapter_R1, adapter_R2 and adapter_report_extra)"
+ADAPTER_SHORT = "shorter than 12 bases"
+ADAPTER_NOT_ACGT = "the first 12 bases are not all A, C, G or T"
 
 DUPLICATION_HELP = """\
 Optional [output] options (not in Quade 0.3.2, whose parser ignores them; absent, empty or False = no report):
@@ -436,6 +465,14 @@ class QuadeConf(object):
         self.cycle_report = False
         if cp.has_option("output", "cycle_report") and cp.get("output", "cycle_report") not in (None, ""):
             self.cycle_report = cp.get("output", "cycle_report").strip().lower() in ("true", "1", "yes", "on")
+        # optional adapter content report of the raw insert reads (extension, ADAPTER_HELP); the extra probes count only with it
+        self.adapter_report = False
+        if cp.has_option("output", "adapter_report") and cp.get("output", "adapter_report") not in (None, ""):
+            self.adapter_report = cp.get("output", "adapter_report").strip().lower() in ("true", "1", "yes", "on")
+        self.adapter_report_extra = ""
+        if cp.has_option("output", "adapter_report_extra") and cp.get("output", "adapter_report_extra") not in (None, ""):
+            self.adapter_report_extra = cp.get("output", "adapter_report_extra").strip()
+        self._adapters = None  # adapter_params' dict, made by _test_values when the report is on
         # optional [filter] section (extension, FILTER_HELP): None = the rule is off
         def flt(name, default=None):
             if cp.has_section("filter") and cp.has_option("filter", name) and cp.get("filter", name) not in (None, ""):
@@ -520,6 +557,9 @@ class QuadeConf(object):
         assert not self.index_hopping_report or self.idx2, HOPPING_NEEDS
         assert not self.quality_report or self.can_pipe, QUALITY_NEEDS
         assert not self.cycle_report or self.can_pipe, CYCLE_NEEDS
+        if self.adapter_report:  # the probes are settled here, before any read is processed
+            assert self.can_pipe, ADAPTER_NEEDS
+            self._adapters = self._adapter_probes()
         assert 8 <= self.duplication_bases <= 32, DUPLICATION_BASES
         assert 1 <= self.duplication_sample <= 1024 and self.duplication_sample & (self.duplication_sample - 1) == 0, DUPLICATION_SAMPLE
         assert 1 << 10 <= self.duplicate_slots <= 1 << 28 and self.duplicate_slots & (self.duplicate_slots - 1) == 0, DUPLICATION_SLOTS
@@ -574,6 +614,36 @@ class QuadeConf(object):
         """the device pipeline can run: every device stage is on and the gzip level is one the device codes; what the read
         stages need (the *_NEEDS messages) and what Quade takes the pipeline for"""
         return bool(self.device_pipeline and self.device_inflate and self.device_deflate and self.gzip_level in (1, -1))
+
+    def _adapter_probes(self):
+        """The probes of the adapter content report (ADAPTER_HELP): the built-in list, adapter_R1 and adapter_R2 when set, then
+        adapter_report_extra -> dict(probes=[(name, probe)] in slot order, aliases=[(name, the name of the earlier equal probe)],
+        left_off=[(name, reason)])"""
+        import re
+        from .stages import ADAPTER_BUILTIN, ADAPTER_K, ADAPTER_PROBES
+        given = list(ADAPTER_BUILTIN) + [(name, seq) for name, seq in (("adapter_R1", self.adapter_R1), ("adapter_R2", self.adapter_R2)) if seq]
+        for item in (self.adapter_report_extra.split(";") if self.adapter_report_extra else []):
+            m = re.match(r"^\s*([A-Za-z0-9_]+)\s*=\s*([A-Za-z]+)\s*$", item)
+            assert m, ADAPTER_EXTRA
+            given.append((m.group(1), m.group(2)))
+        assert len(set(name for name, _ in given)) == len(given), ADAPTER_EXTRA
+        probes, aliases, left_off = [], [], []
+        for name, seq in given:
+            probe = seq[:ADAPTER_K].upper()
+            if len(probe) < ADAPTER_K:
+                left_off.append((name, ADAPTER_SHORT))
+            elif probe.strip("ACGT"):
+                left_off.append((name, ADAPTER_NOT_ACGT))
+            elif probe in [p for _, p in probes]:
+                aliases.append((name, [n for n, p in probes if p == probe][0]))
+            else:
+                probes.append((name, probe))
+        assert len(probes) <= ADAPTER_PROBES, ADAPTER_TOO_MANY
+        return dict(probes=probes, aliases=aliases, left_off=left_off)
+
+    def adapter_params(self):
+        """what Engine.adapters_set takes, and the report: the probes in force, the aliases and the sequences left off"""
+        return self._adapters
 
     def duplication_params(self):
         """what Engine.dup_set takes"""

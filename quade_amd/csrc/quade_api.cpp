@@ -26,6 +26,7 @@
 #include "quade_hop.h"
 #include "quade_qstats.h"
 #include "quade_cstats.h"
+#include "quade_adapters.h"
 #include "quade_clip.h"
 #include "quade_trim.h"
 #include "quade_pairtrim.h"
@@ -98,7 +99,7 @@ struct StageTable {
 };
 
 // the read stages, in the pipeline's order
-enum StageId { ST_CLIP, ST_TRIM, ST_PAIRTRIM, ST_POSTTRIM, ST_FILTER, ST_SCREEN, ST_QSTATS, ST_CSTATS, ST_DUP, ST_COUNT };
+enum StageId { ST_ADAPTERS, ST_CLIP, ST_TRIM, ST_PAIRTRIM, ST_POSTTRIM, ST_FILTER, ST_SCREEN, ST_QSTATS, ST_CSTATS, ST_DUP, ST_COUNT };
 
 // a stage's parameters while it is off: all zero, but for the filter's, whose rules are off at -1 (and qualified_quality is 15)
 constexpr qd_filter_params FILTER_OFF{-1, -1, -1, 15, -1, -1};
@@ -181,10 +182,11 @@ struct qd_ctx {
     KeyTally uk;
 
     // The read stages' tables, by StageId: what each is called, whether it has a row per destination, and, while the stage is on,
-    // its counters.  clip uint64[2][12], trim [2][8], pairtrim [1040], posttrim [2][16], filter [(2 * S + 1)][8], screen
+    // its counters.  adapters uint64[34850 + (2 * S + 1) * 36], clip uint64[2][12], trim [2][8], pairtrim [1040], posttrim [2][16], filter [(2 * S + 1)][8], screen
     // [(2 * S + 1)][8], qstats [(2 * S + 1)][2][6], cstats [QD_CS_VALUES], dup [(2 * S + 1)][5].  Everything that switches stages off,
     // zeroes, reads or adds to a table goes through this array; a new stage adds its row here.
     StageTable stage[ST_COUNT] = {
+        {"adapter counters", "adapter content", "the adapter content is not on", "n_values must be 34850+(2*S+1)*36", true},
         {"clip counters", "clip", "clipping is not on", "n_values must be 24", false},
         {"trim counters", "trim", "trimming is not on", "n_values must be 16", false},
         {"overlap trimming table", "overlap trimming", "overlap trimming is not on", "n_values must be 1040", false},
@@ -196,6 +198,8 @@ struct qd_ctx {
         {"duplication counters", "duplication tally", "the duplication tally is not on", "n_values must be (2*S+1)*5", true},
     };
     // The stages' parameters as given (qd_*_set) and as the kernels take them; a stage that is off holds the off values (stage_off).
+    uint8_t adapters[QD_AD_PROBES * QD_AD_K] = {0};  // adapter content of the raw insert reads: the probes as given, and their words
+    qd_adapters_dev adapters_dev{};
     qd_clip_params clip{};  // end clipping, window and poly-G trimming of the insert reads
     qd_clip_dev clip_dev{};
     qd_trim_params trim{};  // 3' trimming of the insert reads
@@ -568,6 +572,7 @@ int table_add(qd_ctx* c, const StageTable& T, const uint64_t* values, int64_t n_
 void stage_off(qd_ctx* c, int id) {
     table_free(c->stage[id]);
     switch (id) {
+        case ST_ADAPTERS: std::memset(c->adapters, 0, sizeof c->adapters); c->adapters_dev = {}; break;
         case ST_CLIP: c->clip = {}; c->clip_dev = {}; break;
         case ST_TRIM: c->trim = {}; c->trim_dev = {}; break;
         case ST_PAIRTRIM: c->pairtrim = {}; c->pairtrim_dev = {}; break;
@@ -1537,6 +1542,74 @@ int qd_dev_cstats(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t*
     const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::CODES, codes, drop, nullptr, nullptr, nullptr);
     if (rc != QD_OK || up.empty()) return rc;
     return up.close(qd_cstats_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), up.codes(), up.drop(), QD_STREAM_CONTEXT));
+}
+
+static_assert(QD_ADAPTERS_PROBES == QD_AD_PROBES && QD_ADAPTERS_K == QD_AD_K && QD_ADAPTERS_HIST_VALUES == QD_AD_HIST_VALUES &&
+                  QD_ADAPTERS_DEST_VALUES == QD_AD_DEST_VALUES,
+              "the public table sizes are the kernel's");
+
+int qd_adapters_set(qd_ctx* c, const uint8_t* probes, int32_t n_probes) {
+    if (!c) return QD_ERR_INVALID;
+    const bool on = probes && n_probes != 0;
+    qd_adapters_dev D{};
+    if (on) {
+        if (n_probes < 0 || n_probes > (int32_t)QD_AD_PROBES) return fail(c, QD_ERR_INVALID, "n_probes must be 0 to 16");
+        if (!c->have_plan || !c->have_table) return fail(c, QD_ERR_STATE, "qd_set_plan and qd_set_barcodes first");
+        for (uint32_t a = 0; a < QD_AD_PROBES; ++a) D.word[a] = QD_AD_NO_PROBE;
+        for (int32_t a = 0; a < n_probes; ++a) {
+            uint32_t w = 0;
+            for (uint32_t i = 0; i < QD_AD_K; ++i) {
+                const uint8_t b = probes[a * QD_AD_K + i];
+                if (b != 'A' && b != 'C' && b != 'G' && b != 'T') return fail(c, QD_ERR_INVALID, "a probe holds a byte that is not A, C, G or T");
+                w = (w << 2) | ((b >> 1) & 3u);
+            }
+            for (int32_t e = 0; e < a; ++e)
+                if (D.word[e] == w) return fail(c, QD_ERR_INVALID, "two probes are equal");
+            D.word[a] = w;
+        }
+        D.n_probes = (uint32_t)n_probes;
+    }
+    uint8_t given[sizeof c->adapters] = {0};  // (probes may be the context's own copy)
+    if (on) std::memcpy(given, probes, (size_t)n_probes * QD_AD_K);
+    const int rc = stage_install(c, ST_ADAPTERS, on, qd_adapters_values((uint32_t)c->S));
+    if (rc != QD_OK || !on) return rc;
+    std::memcpy(c->adapters, given, sizeof given);
+    c->adapters_dev = D;
+    return QD_OK;
+}
+
+int qd_adapters_get(const qd_ctx* c, uint8_t* probes, int32_t* n_probes) {
+    if (!c || !n_probes) return QD_ERR_INVALID;
+    *n_probes = (int32_t)c->adapters_dev.n_probes;
+    if (probes) std::memcpy(probes, c->adapters, (size_t)c->adapters_dev.n_probes * QD_AD_K);
+    return QD_OK;
+}
+
+int qd_adapters_active(const qd_ctx* c) { return c && c->stage[ST_ADAPTERS].d ? 1 : 0; }
+
+int qd_adapters_read(qd_ctx* c, uint64_t* out, int64_t n_values) { return c ? table_read(c, c->stage[ST_ADAPTERS], out, n_values) : QD_ERR_INVALID; }
+
+int qd_adapters_add(qd_ctx* c, const uint64_t* values, int64_t n_values) { return c ? table_add(c, c->stage[ST_ADAPTERS], values, n_values) : QD_ERR_INVALID; }
+
+int qd_adapters_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
+                       const uint16_t* codes, void* stream) {
+    return stage_launch(c, ST_ADAPTERS, false, n, stream, [&](u64* table, hipStream_t st) {
+        qd_adapters_args a{};
+        fill_pair_args(a, text1, recs1, text2, recs2);
+        a.codes = codes;
+        a.table = table;
+        return qd_adapters_launch(c->adapters_dev, a, (uint32_t)c->S, n, st);
+    });
+}
+
+int qd_dev_adapters(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+                    const uint32_t* recs2, int64_t n_pairs, const uint16_t* codes) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->stage[ST_ADAPTERS].d) return fail(c, QD_ERR_STATE, c->stage[ST_ADAPTERS].off_text);
+    PairUpload up(c);
+    const int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, PairUpload::CODES, codes, nullptr, nullptr, nullptr, nullptr);
+    if (rc != QD_OK || up.empty()) return rc;
+    return up.close(qd_adapters_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), up.codes(), QD_STREAM_CONTEXT));
 }
 
 static_assert(QD_CLIP_VALUES == QD_CLIP_TABLE, "the public table size is the kernel's");

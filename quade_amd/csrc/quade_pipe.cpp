@@ -48,6 +48,7 @@
 #include "quade_pool.h"
 #include "quade_qstats.h"
 #include "quade_cstats.h"
+#include "quade_adapters.h"
 #include "quade_dup.h"
 #include "quade_text.h"
 #include "quade_clip.h"
@@ -1679,6 +1680,10 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
     const qd_rec* ins[2] = {p->win[0].recs.as<qd_rec>(), p->win[1].recs.as<qd_rec>()};
     const uint8_t* const text1 = p->win[0].buf[p->win[0].cur].p;
     const uint8_t* const text2 = p->win[1].buf[p->win[1].cur].p;
+    {  // opt-in adapter content (qd_adapters_set): the one stage that counts the reads as the scan left them, by the final codes
+        const int rc = qd_adapters_device(p->ctx, text1, ins[0], text2, ins[1], n, p->codes.as<uint16_t>(), p->cs);
+        if (rc != QD_OK) return pfail(p, rc, std::string("adapter content: ") + qd_last_error(p->ctx));
+    }
     // The opt-in stages that rewrite the tables, each on what the one before left: end clipping, window and poly-G trimming
     // (qd_clip_set; copies with seq, qual and seq_len of their own, so that a 5' clip reaches every stage behind it through the tables
     // alone), 3' trimming (qd_trim_set), paired-end overlap trimming of R1 and R2 together (qd_pairtrim_set), then trailing N, a poly-X

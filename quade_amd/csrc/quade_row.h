@@ -1,6 +1,6 @@
 // Device-only helpers of the stages that walk a batch's insert reads with 16 lanes (one DPP row) per read or pair:
-// quade_trim.hip, quade_clip.hip, quade_pairtrim.hip, quade_posttrim.hip, quade_qstats.hip, quade_filter.hip, quade_cstats.hip and
-// quade_screen.hip (which packs the line to two bits a base on its way into the slab).
+// quade_trim.hip, quade_clip.hip, quade_pairtrim.hip, quade_posttrim.hip, quade_qstats.hip, quade_filter.hip, quade_cstats.hip,
+// quade_screen.hip and quade_adapters.hip (which two pack the line to two bits a base on its way into the slab).
 //
 // The shared shape.  A record's line lies anywhere in the batch's text; a Line is the 16-byte aligned words that hold it, so that
 // every load is a whole uint4 whatever the line's offset.  Two ways to take the words:
@@ -122,6 +122,15 @@ __device__ __forceinline__ uint4 fold_case(uint4 v) {
     v.z &= 0xDFDFDFDFu;
     v.w &= 0xDFDFDFDFu;
     return v;
+}
+// Two bits a base (screen, adapters): the code of a base is (u >> 1) & 3 of u = b & 0xDF -- A 0, C 1, T 2, G 3.
+// four bytes -> their four codes, the first byte's in bits 7 .. 6 (the products' bit fields do not meet: no carries)
+__device__ __forceinline__ uint32_t base_codes4(uint32_t x) { return (((x >> 1) & 0x03030303u) * 0x40100401u) >> 24; }
+// four bytes -> four bits, the first byte's in bit 3: 1 = A, C, G or T in either case
+__device__ __forceinline__ uint32_t base_valid4(uint32_t x) {
+    const uint32_t u = x & 0xDFDFDFDFu;
+    const uint32_t m = (bytes_eq(u, 'A') | bytes_eq(u, 'C') | bytes_eq(u, 'G') | bytes_eq(u, 'T')) & 0x01010101u;
+    return (m * 0x08040201u) >> 24;
 }
 
 // ---- the aligned line ------------------------------------------------------------------------------------------------------------

@@ -31,22 +31,13 @@ static_assert(FAST_WORDS + 2 <= SC_WORDS && SC_WORDS <= 2 * ROW, "a window of th
 static_assert(SC_GROUPS * 2 * 2 * SC_WORDS * 4 + SC_LDS_TABLE_BYTES <= 160 * 1024, "slabs and hash table exceed the CU's LDS");
 static_assert(QD_SC_VALUES <= ROW, "one lane per value");
 
-// four bytes -> their four codes, the first byte's in bits 7 .. 6 (the products' bit fields do not meet: no carries)
-__device__ __forceinline__ uint32_t codes4(uint32_t x) { return (((x >> 1) & 0x03030303u) * 0x40100401u) >> 24; }
-// four bytes -> four bits, the first byte's in bit 3: 1 = A, C, G or T in either case
-__device__ __forceinline__ uint32_t valid4(uint32_t x) {
-    const uint32_t u = x & 0xDFDFDFDFu;
-    const uint32_t m = (bytes_eq(u, 'A') | bytes_eq(u, 'C') | bytes_eq(u, 'G') | bytes_eq(u, 'T')) & 0x01010101u;
-    return (m * 0x08040201u) >> 24;
-}
-
-// the row packs the line into its slab: codes[k] and valid[k] for every word k < SC_WORDS, zeros beyond the line
+// the row packs the line (base_codes4 and base_valid4: quade_row.h) into its slab: codes[k] and valid[k] for every word k < SC_WORDS, zeros beyond the line
 __device__ __forceinline__ void stage_packed(uint32_t* codes, uint32_t* valid, const Line& L, uint32_t sub) {
     for (uint32_t k = sub; k < SC_WORDS; k += ROW) {
         uint4 v = make_uint4(0, 0, 0, 0);
         if (k < L.n_words) v = mask_word(L, k, L.w0[k]);
-        codes[k] = (codes4(v.x) << 24) | (codes4(v.y) << 16) | (codes4(v.z) << 8) | codes4(v.w);
-        valid[k] = (valid4(v.x) << 12) | (valid4(v.y) << 8) | (valid4(v.z) << 4) | valid4(v.w);
+        codes[k] = (base_codes4(v.x) << 24) | (base_codes4(v.y) << 16) | (base_codes4(v.z) << 8) | base_codes4(v.w);
+        valid[k] = (base_valid4(v.x) << 12) | (base_valid4(v.y) << 8) | (base_valid4(v.z) << 4) | base_valid4(v.w);
     }
 }
 

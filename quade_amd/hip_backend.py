@@ -13,7 +13,9 @@ import os
 import numpy as np
 
 # the read stages' table layouts, their bytes in the ranks' exchange and the stage table live in stages.py; hb.X reaches them all
-from .stages import (CLIP_COUNTERS, CSTATS_COUNTERS, CSTATS_CYCLES, CSTATS_GC_BINS, CSTATS_GR_VALUES, CSTATS_GROUPS,  # noqa: F401
+from .stages import (ADAPTER_BINS, ADAPTER_BUILTIN, ADAPTER_COLUMNS, ADAPTER_DEST_VALUES, ADAPTER_HIST_VALUES, ADAPTER_K,  # noqa: F401
+                     ADAPTER_PROBES, ADAPTERS, READ_STAGE, READ_STAGES, adapters_flat, adapters_values, adapters_views,
+                     CLIP_COUNTERS, CSTATS_COUNTERS, CSTATS_CYCLES, CSTATS_GC_BINS, CSTATS_GR_VALUES, CSTATS_GROUPS,  # noqa: F401
                      CSTATS_LEN_BINS, CSTATS_MEANQ_BINS, CSTATS_SECTIONS, CSTATS_VALUES, FILTER_COUNTERS, FILTER_KEYS, FILTER_REASONS,
                      PAIRTRIM_BINS, PAIRTRIM_COUNTERS, PAIRTRIM_PAIR_COUNTERS, PAIRTRIM_VALUES, POSTTRIM, POSTTRIM_COUNTERS,
                      PIPE_STAGE, PIPE_STAGES, QSTATS_COUNTERS, RUN_STAGE, RUN_STAGES, SCREEN, SCREEN_ACTIONS, SCREEN_COUNTERS, STAGE,
@@ -183,6 +185,10 @@ SYMBOLS = [
     ("qd_cstats_read", C.c_int, [_P, _P, C.c_int64]),
     ("qd_cstats_add", C.c_int, [_P, _P, C.c_int64]),
     ("qd_cstats_lds_cycles", C.c_int, []),
+    ("qd_adapters_set", C.c_int, [_P, _P, C.c_int32]),
+    ("qd_adapters_get", C.c_int, [_P, _P, C.POINTER(C.c_int32)]),
+    ("qd_adapters_read", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_adapters_add", C.c_int, [_P, _P, C.c_int64]),
     ("qd_dup_set", C.c_int, [_P, C.POINTER(qd_dup_params)]),
     ("qd_dup_get", C.c_int, [_P, C.POINTER(qd_dup_params)]),
     ("qd_dup_stats", C.c_int, [_P, _P, C.c_int64]),
@@ -274,6 +280,7 @@ SYMBOLS = [
     ("qd_dev_screen", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P]),
     ("qd_dev_cstats", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_dup", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
+    ("qd_dev_adapters", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P]),
     ("qd_dev_pack_rows", C.c_int, [C.c_int, C.POINTER(qd_layout), _P * 2, C.c_int64 * 2, _P * 2, C.c_int64, C.c_int64, _P * 2, _P * 2, _P * 2,
                                    _P, C.c_int64, C.POINTER(C.c_uint32)]),
     ("qd_dev_route_format", C.c_int, [C.c_int, C.POINTER(qd_plan), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P * 4, C.c_int64 * 4, _P * 4, _P, _P,
@@ -1041,6 +1048,50 @@ class Engine(object):
         t, r, codes, drop, n = self._pair_inputs(text1, recs1, text2, recs2, codes, drop)
         self._chk(self.lib.qd_dev_cstats(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), n, _ptr(codes),
                                          _ptr(drop) if drop is not None else None))
+
+    def adapters_set(self, probes=(), aliases=None, left_off=None, on=True):
+        """The adapter content of the raw insert reads in the device pipeline, in front of every trimming stage (qd_adapters_set;
+        conf.ADAPTER_HELP has the definition).  probes: up to 16 (name, probe) or plain probes of 12 bases of ACGT, no two equal;
+        their order is the table's slot order.  aliases and left_off are the report's (conf.adapter_params).  No probe or
+        on=False turns the stage off and frees the table; a bad probe is QD_ERR_INVALID and changes nothing.  Needs the plan
+        and the barcodes, which turn it off; reset_counts zeroes the table."""
+        seqs = [p if isinstance(p, (str, bytes)) else p[1] for p in probes] if on else []
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        if not seqs:
+            self._chk(self.lib.qd_adapters_set(self._h, None, 0))
+            return
+        if any(len(s) != ADAPTER_K for s in seqs):
+            raise ValueError("a probe is %d bases" % ADAPTER_K)
+        flat = np.frombuffer(b"".join(seqs), dtype=np.uint8)
+        self._chk(self.lib.qd_adapters_set(self._h, _ptr(flat), len(seqs)))
+
+    def adapters_get(self):
+        """the probes in force, in slot order, as strings; [] when the stage is off (qd_adapters_get)"""
+        buf, n = np.zeros(ADAPTER_PROBES * ADAPTER_K, dtype=np.uint8), C.c_int32(0)
+        self._chk(self.lib.qd_adapters_get(self._h, _ptr(buf), C.byref(n)))
+        return [buf[a * ADAPTER_K:(a + 1) * ADAPTER_K].tobytes().decode() for a in range(n.value)]
+
+    def adapters_active(self):
+        """whether the stage is on (qd_adapters_active, an internal entry of the library)"""
+        f = self.lib.qd_adapters_active
+        f.restype, f.argtypes = C.c_int, [_P]
+        return bool(f(self._h))
+
+    def adapters_read(self):
+        """dict of uint64 views into one flat table: hist[2, 17, 1025] -- [R1, R2][16 probe slots, any][min(first, 1024)] -- and
+        dest[2S+1, 2, 18] -- [destination (code; Undetermined last)][R1, R2][reads, 16 probe slots, any] (adapters_flat gives the
+        flat table back)"""
+        return adapters_views(self._table_read(self.lib.qd_adapters_read, adapters_values(self.n_samples)))
+
+    def adapters_add(self, table):
+        """Another context's table (adapters_read's dict or flat) joins this context's (qd_adapters_add)."""
+        self._table_add(self.lib.qd_adapters_add, adapters_flat(table) if isinstance(table, dict) else np.reshape(table, -1))
+
+    def dev_adapters(self, text1, recs1, text2, recs2, codes):
+        """The adapter content stage over host buffers (qd_dev_adapters): texts as bytes or uint8 arrays, recs uint32[n, 6] in
+        dev_fastq_scan's layout, codes uint16[n]; adds to the context's table."""
+        t, r, codes, _, n = self._pair_inputs(text1, recs1, text2, recs2, codes)
+        self._chk(self.lib.qd_dev_adapters(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), n, _ptr(codes)))
 
     def dup_set(self, bases=32, sample=16, slots=1 << 24, on=True):
         """The duplication tally in the device pipeline (qd_dup_set; conf.DUPLICATION_HELP has the definition): `bases` 8 .. 32

@@ -191,7 +191,7 @@ class Quade(object):
                     eng.hop_enable(True)
                 if cf.duplication_report:  # the read-pair keys are tallied on the device, beside the quality counters
                     eng.dup_set(**cf.duplication_params())
-                for stage in hb.PIPE_STAGES:  # what the pipeline does to the insert reads while it holds their text, in its order
+                for stage in hb.READ_STAGES:  # what the pipeline does to the insert reads while it holds their text, in its order
                     if stage.on(cf):
                         stage.enable(eng, cf)
                 if not self.use_pipe:
@@ -223,7 +223,7 @@ class Quade(object):
         hopping = self._collect_hopping() if cf.index_hopping_report else None  # (nor is the matrix: its shape depends on the sheet)
         with _timed("duplication gather + merge"):  # (nor is the duplication tally a stage of the table: it merges by key too)
             dup = self._collect_dup() if cf.duplication_report else None
-        tables = [(stage, self._collect(stage)) for stage in hb.PIPE_STAGES if stage.on(cf)]
+        tables = [(stage, self._collect(stage)) for stage in hb.READ_STAGES if stage.on(cf)]
         for eng in self.engines:
             eng.close()
         self.engines = []
@@ -384,7 +384,7 @@ class Quade(object):
         return keys, dcounts, stats
 
     def _collect(self, stage):
-        """A read stage's tables (hip_backend.PIPE_STAGES) of every context of this process summed (chunk workers, devices); with
+        """A read stage's tables (hip_backend.READ_STAGES) of every context of this process summed (chunk workers, devices); with
         several ranks every rank publishes its sum in the rendezvous directory under the stage's name and adds all of them (rank
         0 writes the file)."""
         from . import dist

@@ -1,8 +1,8 @@
 # -*- coding: utf-8 -*-
 """
 The read stages of the device pipeline, described once: the columns of their counter tables (include/quade_hip.h, qd_qstats_*,
-qd_cstats_*, qd_clip_*, qd_trim_*, qd_pairtrim_*, qd_posttrim_*, qd_filter_*, qd_screen_*), the bytes a table has when the ranks exchange it, and
-PIPE_STAGES, the table Quade.__call__ walks to switch the stages on, to collect their tables and to write their reports.  hip_backend and the
+qd_cstats_*, qd_clip_*, qd_trim_*, qd_pairtrim_*, qd_posttrim_*, qd_filter_*, qd_screen_*, qd_adapters_*), the bytes a table has when the ranks
+exchange it, and READ_STAGES, the table Quade.__call__ walks to switch the stages on, to collect their tables and to write their reports.  hip_backend and the
 report modules take the columns from here; nothing here touches libquade_hip.so.
 """
 from __future__ import annotations
@@ -89,7 +89,8 @@ class Stage(namedtuple("Stage", "name engine conf params shape count what flat v
     engine       the prefix of its Engine methods: <engine>_read, and <engine>_set(**params) or <engine>_enable(True)
     conf         the QuadeConf attribute that says the stage is on
     params       the QuadeConf method that gives its keyword parameters, or None: the stage has none
-    shape        its table, uint64; a leading -1 = one row per destination (2 * samples + 1)
+    shape        its table, uint64; a leading -1 = one row per destination (2 * samples + 1); (-1,) = a flat table whose size depends
+                 on the samples (count "values")
     count        the uint64 in front of the packed table: "rows" (the destinations), "values" (all of them) or None
     what         the table's name in the message of a blob of the wrong size
     flat, view   None, or table -> flat array and flat array -> table for a stage whose table is not one array (cycle: a dict)
@@ -161,8 +162,52 @@ PIPE_STAGES = RUN_STAGES + (SCREEN,)  # quality, cycle, clip, trim, pairtrim, po
 PIPE_STAGE = {s.name: s for s in PIPE_STAGES}
 
 
+# the adapter content table (qd_adapters_*): uint64, hist[R1, R2][16 probe slots, any][1025 bins] and then, per destination,
+# dest[R1, R2][reads, 16 probe slots, any].  The probes are the first 12 bases of an adapter; the built-in ones are FastQC's
+# adapter_list, in its order
+ADAPTER_K, ADAPTER_PROBES, ADAPTER_BINS = 12, 16, 1025
+ADAPTER_COLUMNS = ADAPTER_PROBES + 1  # the slots, then any
+ADAPTER_HIST_VALUES = 2 * ADAPTER_COLUMNS * ADAPTER_BINS  # 34850
+ADAPTER_DEST_VALUES = 2 * (ADAPTER_COLUMNS + 1)  # per destination: 36
+ADAPTER_BUILTIN = (("illumina_universal", "AGATCGGAAGAG"), ("illumina_small_rna_3p", "TGGAATTCTCGG"),
+                   ("illumina_small_rna_5p", "GATCGTCGGACT"), ("nextera_transposase", "CTGTCTCTTATA"),
+                   ("poly_a", "AAAAAAAAAAAA"), ("poly_g", "GGGGGGGGGGGG"))
+
+
+def adapters_values(n_samples):
+    return ADAPTER_HIST_VALUES + (2 * n_samples + 1) * ADAPTER_DEST_VALUES
+
+
+def adapters_views(flat):
+    """The flat table (uint64[34850 + (2S+1) * 36]) as a dict of views into it: hist[2, 17, 1025] and dest[2S+1, 2, 18]"""
+    flat = np.asarray(flat)
+    rest = flat.size - ADAPTER_HIST_VALUES
+    assert flat.ndim == 1 and flat.dtype == np.uint64 and rest >= ADAPTER_DEST_VALUES and rest % (2 * ADAPTER_DEST_VALUES) == ADAPTER_DEST_VALUES, \
+        "adapter table of the wrong size"
+    return {"hist": flat[:ADAPTER_HIST_VALUES].reshape(2, ADAPTER_COLUMNS, ADAPTER_BINS),
+            "dest": flat[ADAPTER_HIST_VALUES:].reshape(-1, 2, ADAPTER_COLUMNS + 1)}
+
+
+def adapters_flat(table):
+    """adapters_views' dict (or a flat table) -> the flat layout of qd_adapters_read"""
+    if isinstance(table, dict):
+        table = np.concatenate([np.asarray(table[k], dtype=np.uint64).reshape(-1) for k in ("hist", "dest")])
+    flat = np.ascontiguousarray(table, dtype=np.uint64).reshape(-1)
+    adapters_views(flat)  # (the size)
+    return flat
+
+
+# PIPE_STAGES is pinned at those eight in turn.  The adapter content (qd_adapters_*) is counted in front of all of them, on the
+# reads as the scan left them: READ_STAGES is every stage in pipeline order, and what Quade.__call__, pack_table and unpack_table
+# walk.  Its table's size depends on the sheet in one part only: shape (-1,), its value count in front of the packed table.
+ADAPTERS = Stage("adapters", "adapters", "adapter_report", "adapter_params", (-1,), "values", "adapter table",
+                 adapters_flat, adapters_views, "adapter_report", ("samples", "params"))
+READ_STAGES = (ADAPTERS,) + PIPE_STAGES  # adapters, quality, cycle, clip, trim, pairtrim, posttrim, filter, screen
+READ_STAGE = {s.name: s for s in READ_STAGES}
+
+
 def _stage(stage):
-    return stage if isinstance(stage, Stage) else PIPE_STAGE[stage]
+    return stage if isinstance(stage, Stage) else READ_STAGE[stage]
 
 
 def pack_table(stage, table):
@@ -179,7 +224,8 @@ def unpack_table(stage, blob):
     stage = _stage(stage)
     at = 8 if stage.count else 0
     n = int(np.frombuffer(blob, dtype=np.uint64, count=1)[0]) if stage.count else 0
-    values = n * int(np.prod(stage.shape[1:])) if stage.count == "rows" else int(np.prod(stage.shape))
+    counted = stage.count == "rows" or stage.shape[0] == -1  # the count in front says how long the table is (adapters: its view checks it)
+    values = n * int(np.prod(stage.shape[1:])) if counted else int(np.prod(stage.shape))
     assert len(blob) == at + values * 8 and (stage.count != "values" or n == values), stage.what + " of the wrong size"
-    table = np.frombuffer(blob, dtype=np.uint64, offset=at).reshape((n,) + stage.shape[1:] if stage.count == "rows" else stage.shape).copy()
+    table = np.frombuffer(blob, dtype=np.uint64, offset=at).reshape((n,) + stage.shape[1:] if counted else stage.shape).copy()
     return stage.view(table) if stage.view else table

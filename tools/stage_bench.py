@@ -7,7 +7,7 @@ each is timed by HIP events.  "off" does what process_batch does with the stage 
 itself costs.  After the timed steps the stage's table is read back and checked against what the batch must have counted.  Prints
 one JSON line ("tool": "<stage>_bench"): per case the medians, the spread and the byte floor (the lines' bytes at 6.3 TB/s).
 
-usage: python tools/stage_bench.py --stage qstats|cycle|clip|trim|pairtrim|posttrim|filter|screen|dup [--pairs N] [--bases L] [--steps K] [--warmup W]
+usage: python tools/stage_bench.py --stage qstats|cycle|clip|trim|pairtrim|posttrim|filter|screen|dup|adapters [--pairs N] [--bases L] [--steps K] [--warmup W]
                                    [--once CASE] [--out FILE]
   --once CASE  set up, run ONE launch and exit (for `rocprofv3 --kernel-trace --stats -- python ...`); CASE by stage:
     qstats    hot | spread | off      routing: 96 samples with 90 % of the pairs to 8 destinations (per-workgroup partials in LDS) |
@@ -29,6 +29,9 @@ usage: python tools/stage_bench.py --stage qstats|cycle|clip|trim|pairtrim|postt
     dup       sSAMPLE_dPCT | off      the duplication tally with duplication_sample SAMPLE (16 | 1) over a batch in which PCT (0 |
                                       30 | 100) % of the pairs repeat another pair's reads and destination, 8 hot destinations;
                                       interleaved with the quality counters' kernel over the same batch
+    adapters  pN_PCT | off            the adapter content with N (6 | 16) probes in force over a batch in which PCT (0 | 10 | 100) % of the
+                                      reads carry the Illumina universal adapter from a random position on; interleaved with the
+                                      quality counters' kernel over the same batch
 The end-to-end rates come from tools/e2e_bench.py with the stage's E2E_* switch against none."""
 import argparse
 import ctypes as C
@@ -328,10 +331,11 @@ def clip(B):
     return out
 
 
-def adapters(adapter, share):
-    """a `share` of the reads holds the adapter (cut at the read's end) from a random position on"""
+def adapters(adapter, share, whole=None):
+    """a `share` of the reads holds the adapter (cut at the read's end) from a random position on; whole: a list that receives, per
+    text made, the reads that hold the adapter's first 12 bases whole"""
     def plant(g, n, L):
-        seq = plain_seq(g, n, L)
+        seq, held = plain_seq(g, n, L), 0
         if share > 0:
             ad = torch.tensor(list(adapter.encode()), dtype=torch.uint8, device="cuda")
             has = torch.rand(n, generator=g, device="cuda") < share
@@ -339,6 +343,9 @@ def adapters(adapter, share):
             col = torch.arange(L, device="cuda").reshape(1, L)
             inside = has.reshape(n, 1) & (col >= p) & (col < p + len(ad))
             seq = torch.where(inside, ad[(col - p).clamp(0, len(ad) - 1)], seq)
+            held = int((has & (p[:, 0] <= L - 12)).sum())
+        if whole is not None:
+            whole.append(held)
         return seq, plain_qual(g, n, L)
     return plant
 
@@ -702,7 +709,61 @@ def dup(B):
     return out
 
 
-STAGES = {"dup": dup, "qstats": qstats, "cycle": cycle, "clip": clip, "trim": trim, "pairtrim": pairtrim, "posttrim": posttrim, "filter": filter_, "screen": screen}
+def adapter_content(B):
+    a, n, L, S = B.a, B.a.pairs, B.a.bases, 96
+    cases = {"p%d_%d" % (k, pct): (k, pct) for pct in (0, 10, 100) for k in (6, 16)}
+    B.once_in([None, "off"] + sorted(cases))
+    builtin = [probe for _, probe in hb.ADAPTER_BUILTIN]
+    more = ["".join("ACGT"[(i >> (2 * j)) & 3] for j in range(12)) for i in range(3000, 3010)]  # ten probes no read is planted with
+    search = B.lib.qd_adapters_device  # (context, the batch's four pointers, pairs, codes, stream)
+    search.restype, search.argtypes = C.c_int, [C.c_void_p] * 5 + [C.c_uint32] + [C.c_void_p] * 2
+    count, g = B.entry("qstats"), generator(7)
+    codes = torch.randint(0, S, (n,), generator=g, device="cuda") * 2 + (torch.rand(n, generator=g, device="cuda") < 0.1)  # a tenth fail
+    codes = codes.to(torch.int16).contiguous()
+
+    def measure(case):
+        k, pct = cases[case]
+        tally = []
+        b = Batch(n, L, plants=(adapters(ADAPTERS[0], pct / 100.0, tally),) * 2)  # both reads the universal adapter: the probe's 12 bases
+        kinds = {"off": None, "adapters": lambda e: e.adapters_set(builtin + more[:k - 6]), "qstats": lambda e: e.qstats_enable(True)}
+        engines = contexts({x: kinds[x] for x in (("off",) if a.once == "off" else ("adapters",) if a.once else kinds)}, S)
+
+        def run_search(eng):  # "off": what process_batch does with the stage off -- the same call, which launches nothing
+            rc = search(eng._h, b.t1.data_ptr(), b.r1.data_ptr(), b.t2.data_ptr(), b.r2.data_ptr(), n, codes.data_ptr(), B.st.cuda_stream)
+            assert rc == 0, rc
+        run = {x: ((lambda x=x: B.launch(count, engines[x], b, codes.data_ptr(), None)) if x == "qstats" else (lambda x=x: run_search(engines[x])))
+               for x in engines}
+        if a.once:
+            out = B.once(run["off" if a.once == "off" else "adapters"], {"once": a.once, "pairs": n, "bases": L})
+            close(engines)
+            return out
+        ms = B.timed(run)
+        launches = a.steps + a.warmup
+        t = engines["adapters"].adapters_read()
+        # the table against what the generator planted: every read once, the planted probes at least (a random read holds a given
+        # 12-mer about once in 120 000 reads), the unused slots empty, and the two parts of the table agree
+        assert t["dest"][:, :, 0].sum(axis=0).tolist() == [launches * n] * 2
+        found = [int(t["hist"][r, 0].sum()) for r in range(2)]
+        assert all(launches * tally[r] <= found[r] <= launches * (tally[r] + n // 20000) for r in range(2)), (found, tally)
+        assert (t["hist"].sum(axis=2) == t["dest"].sum(axis=0)[:, 1:]).all() and not t["hist"][:, k:16].any()
+        assert (t["hist"][:, 16].sum(axis=1) >= t["hist"][:, 0].sum(axis=1)).all()
+        floor = B.floor_ms(2)  # the two sequence lines
+        out = {"case": case, "probes": k, "adapter_percent": pct, "samples": S, "reads_with_universal": [f // launches for f in found],
+               "planted": tally, "byte_floor_ms": floor, "qstats_byte_floor_ms": B.floor_ms(4),
+               "adapters_over_qstats": median(ms["adapters"]) / median(ms["qstats"]), "adapters_over_floor": median(ms["adapters"]) / floor,
+               **by_name(ms)}
+        close(engines)
+        return out
+
+    if a.once:
+        return measure("p6_10" if a.once == "off" else a.once)
+    out = B.head("adapters_bench", steps=a.steps)
+    for case in cases:
+        out[case] = measure(case)
+    return out
+
+
+STAGES = {"adapters": adapter_content, "dup": dup, "qstats": qstats, "cycle": cycle, "clip": clip, "trim": trim, "pairtrim": pairtrim, "posttrim": posttrim, "filter": filter_, "screen": screen}
 
 
 def main():
