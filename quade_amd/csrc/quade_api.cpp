@@ -2880,6 +2880,29 @@ static int inflater_run(qd_inflater* f, const uint8_t* comp, int64_t comp_len, u
     if (out_len) INFCHK(f, hipMemcpyAsync(text, f->d_out, (size_t)out_len, hipMemcpyDeviceToHost, f->stream));
     INFCHK(f, hipEventRecord(f->done, f->stream));
     INFCHK(f, wait_event_napping(f->done));
+    if (f->form != 1) {
+        // The second form's match list holds QD_INFLATE_MATCHES_PER_BLOCK matches; a block with more (GNU gzip -1 makes 16 000 of 64 KiB
+        // of fastq) comes back as QD_INFLATE_OVERRUN, like one whose codes stand for more text than its ISIZE.  The one-wave form has no
+        // such list and tells the two apart: a launch over just those blocks.
+        std::vector<qd_inflate_block> redo;
+        std::vector<size_t> redo_at;
+        for (size_t i = 0; i < blk.size(); ++i)
+            if (f->h_st[i] == QD_INFLATE_OVERRUN) {
+                redo.push_back(blk[i]);
+                redo_at.push_back(i);
+            }
+        if (!redo.empty()) {
+            memcpy(f->h_blk, redo.data(), redo.size() * sizeof(qd_inflate_block));
+            INFCHK(f, hipMemcpyAsync(f->d_blk, f->h_blk, redo.size() * sizeof(qd_inflate_block), hipMemcpyHostToDevice, f->stream));
+            INFCHK(f, qd_launch_inflate(f->d_comp, f->d_blk, (uint32_t)redo.size(), f->d_out, f->d_st, f->stream));
+            std::vector<int32_t> rst(redo.size());
+            INFCHK(f, hipMemcpyAsync(rst.data(), f->d_st, redo.size() * 4, hipMemcpyDeviceToHost, f->stream));
+            for (const qd_inflate_block& b : redo)
+                if (b.out_len) INFCHK(f, hipMemcpyAsync(text + b.out_off, f->d_out + b.out_off, b.out_len, hipMemcpyDeviceToHost, f->stream));
+            INFCHK(f, hipStreamSynchronize(f->stream));
+            for (size_t k = 0; k < redo.size(); ++k) f->h_st[redo_at[k]] = rst[k];
+        }
+    }
     // 3. every block: decoder status, then the CRC32 of its text
     for (size_t i = 0; i < blk.size(); ++i) {
         if (f->h_st[i] != 0 || qd_io_crc32(text + blk[i].out_off, blk[i].out_len) != f->crc[i]) {

@@ -1148,7 +1148,10 @@ hipError_t qd_gz::decode(qd_gz_step* steps, int n, hipStream_t st, int slots_per
         std::vector<uint64_t>& v = starts[(size_t)i];
         for (size_t k = 0; k < v.size(); ++k) {
             const uint64_t stop = k + 1 < v.size() ? v[k + 1] : ~0ull;
-            const uint32_t cap = cap_for(steps[i], v[k], stop);
+            // (The second try gives a step's first unit room up to the end of its input: its stop may be a false candidate INSIDE a
+            //  block many times longer than the span in front of it, and then there is no block boundary to fall back to -- the step
+            //  failed at eight slots a byte of that span as it did at four, and a legal stream was given up.)
+            const uint32_t cap = cap_for(steps[i], v[k], k == 0 && per_byte >= 8 ? ~0ull : stop);
             if (tok_total + cap >= 0xFFFF0000ull) {  // a launch's slots are indexed with 32 bits: what does not fit waits for the next step
                 v.resize(k);
                 steps[i].starved = 1;
@@ -1251,6 +1254,14 @@ hipError_t qd_gz::decode(qd_gz_step* steps, int n, hipStream_t st, int slots_per
             //  no progress there and gives the stream up)
             stop_here = true;
         }
+        // (where the chain stopped inside a unit -- the block boundaries it passed count: the candidates it ran through on the way
+        //  there were no block starts either)
+        for (size_t q = 0; q < nu0 && !s.failed; ++q)
+            if (unit_of[q].first == i && !dropped[q] && G.units_[q].bit_start > s.bit_start && G.units_[q].bit_start < at &&
+                (G.acc_[(size_t)i].stretch.empty() || q > G.acc_[(size_t)i].stretch.back())) {
+                dropped[q] = 1;
+                ++G.st_.chain_retries;
+            }
         s.bit_next = at;
         if (debug)
             fprintf(stderr, "[qd_gz]   step %d: start %llu -> next %llu, text %llu, member_end %d, failed %d, %zu stretches accepted\n", i, (unsigned long long)s.bit_start,

@@ -58,9 +58,10 @@ def _table(lengths):
 _FIXED = None
 
 
-def read_deflate(data, bit=0, text=None):
+def read_deflate(data, bit=0, text=None, max_blocks=None):
     """the blocks of the DEFLATE stream that starts at bit `bit` of data, up to and with its final block: (text, blocks, bit
-    behind the final block).  text: a bytearray that is continued (history of a preset dictionary), a new one by default."""
+    behind the final block).  text: a bytearray that is continued (history of a preset dictionary), a new one by default.
+    max_blocks: stop behind that many blocks, final or not (what stands at a position where no stream begins)."""
     global _FIXED
     out = bytearray() if text is None else text
     blocks = []
@@ -90,7 +91,7 @@ def read_deflate(data, bit=0, text=None):
         return v
 
     final = 0
-    while not final:
+    while not final and (max_blocks is None or len(blocks) < max_blocks):
         bit_start = at()
         final = take(1)
         btype = take(2)
