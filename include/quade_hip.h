@@ -424,6 +424,55 @@ int qd_pairtrim_get(const qd_ctx* ctx, qd_pairtrim_params* out);
 int qd_pairtrim_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
 int qd_pairtrim_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
 
+/* ---- overlap base correction of read pairs (opt-in; no reference counterpart: Quade 0.3.2 never looks at R1 and R2 of a pair
+ * together) ---------------------------------------------------------------------------------------------------------------------
+ * What fastp does under --correction: at a disagreeing position of an accepted overlap the instrument read the same base twice,
+ * and the confident call, with its quality, is written over the doubtful one.  The first stage that edits the text itself.
+ *
+ * The rule (tests/paircorrect_model.py and quade_amd/csrc/quade_paircorrect.h state exactly this).  The stage runs directly behind the
+ * overlap trimming stage and in front of post-trimming, over every pair for which that stage found an insert length I* (I* >= M and
+ * I* < M alike), whatever its destination, the write flags and later filtering.  It uses the record tables the overlap stage
+ * RECEIVED: sequences s1, s2 and quality lines q1, q2 of lengths L1, L2, starting at the tables' seq / qual (a 5' clip is respected).
+ *   definitions : u(b) = b & 0xDF; valid(b) iff u(b) is one of A C G T; comp maps A<->T and C<->G; the phred of a quality byte c is
+ *                 (int)c - 33, so a byte below 33 is negative and therefore "bad" (as in quade_pairtrim.h)
+ *   positions   : i with max(0, I* - L2) <= i < min(L1, I*), with partner j = I* - 1 - i; every such i, j lies inside what the overlap
+ *                 stage keeps of both reads (<= Lp <= Lout)
+ *   mismatch    : a position mismatches iff not (valid(s1[i]) and u(s2[j]) == comp(u(s1[i]))): the overlap stage's definition exactly
+ *   at a mismatching position, with G = good_quality and B = bad_quality (B < G, so at most one of the first two cases holds):
+ *     1. if valid(s1[i]) and phred(q1[i]) >= G and phred(q2[j]) <= B: s2[j] = comp(u(s1[i])) and q2[j] = q1[i] -- R2 is corrected
+ *     2. else if valid(s2[j]) and phred(q2[j]) >= G and phred(q1[i]) <= B: s1[i] = comp(u(s2[j])) and q1[i] = q2[j] -- R1 is corrected
+ *     3. else nothing is written: the position is unresolved
+ *   The written base is upper case.  The doubtful byte may be anything (N, lower case, any other byte); the trusted one must be a letter.
+ *   properties  : nothing else in the text changes; no length changes and no pair is dropped; names, index reads and the :IDX[:MOL]
+ *                 tag never change; a position's outcome depends on its own four bytes only; applying the rule twice equals applying it
+ *                 once, because a corrected position matches afterwards
+ * Everything behind the stage sees the corrected reads: post-trimming, the read filter, the k-mer screen, the quality, cycle and
+ * duplication counters and the output files.  The adapter content still counts the raw reads, and the overlap trimming table is as
+ * before.  With the stage on, qd_pipe_run hands every pair's I* from the overlap kernel to this one (64 bits a pair: exact for every
+ * L1 + L2 the record tables can express) and launches it once per batch on its compute stream, no host sync; with overlap trimming
+ * off it fails with QD_ERR_STATE.  The device table, 10 uint64, whatever the write flags say:
+ *   [0] R1 corrected_reads   [1] R1 corrected_bases   [2] R2 corrected_reads   [3] R2 corrected_bases   [4] pairs
+ *   [5] overlapped_pairs (I* != 0)   [6] overlap_bases (sum of ov(I*))   [7] mismatches   [8] unresolved
+ *   [9] corrected_pairs (pairs with at least one write);   [7] == [1] + [3] + [8] by construction
+ * Off, nothing is allocated or launched.
+ *
+ * qd_paircorrect_set: NULL turns the stage off and frees the table; otherwise the values are checked (good_quality 1..93,
+ * bad_quality 0..good_quality - 1: QD_ERR_INVALID, the state as before) and a zeroed table allocated.  Waits for the context's
+ * outstanding work.  Independent of plan, barcodes and, at set time, of qd_pairtrim_set.
+ * qd_paircorrect_get: the parameters in force (all zero and QD_OK when off).
+ * qd_paircorrect_read: waits for the context's work, writes n_values = 10 values (QD_ERR_INVALID on another size, QD_ERR_STATE when
+ * off).
+ * qd_paircorrect_add: another context's table joins this one's, as qd_trim_add does.  qd_reset_counts zeroes the table. */
+#define QD_PAIRCORRECT_VALUES 10
+typedef struct qd_paircorrect_params {
+    int32_t good_quality;
+    int32_t bad_quality;
+} qd_paircorrect_params;
+int qd_paircorrect_set(qd_ctx* ctx, const qd_paircorrect_params* params);
+int qd_paircorrect_get(const qd_ctx* ctx, qd_paircorrect_params* out);
+int qd_paircorrect_read(qd_ctx* ctx, uint64_t* out, int64_t n_values);
+int qd_paircorrect_add(qd_ctx* ctx, const uint64_t* values, int64_t n_values);
+
 /* ---- post-trimming of the insert reads: trailing N, a poly-X tail and a crop to max_length (opt-in; no reference counterpart:
  * Quade 0.3.2 writes the insert reads as they came) -----------------------------------------------------------------------------
  * One stage behind the clip, 3' trimming and overlap trimming stages above and in front of the read filter below, where fastp runs
@@ -1147,6 +1196,15 @@ int qd_dev_trim(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t*
  * when the stage is off.  Returns when the launch has finished. */
 int qd_dev_pairtrim(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                     const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2);
+/* the overlap base correction (qd_paircorrect_set above; no reference counterpart) over host buffers, as qd_dev_pairtrim: pairs
+ * [0, n_pairs) of two texts with their record tables are uploaded (the texts 3 bytes off alignment) and run through the kernel
+ * qd_pipe_run launches; out_text1 / out_text2 (len1 / len2 bytes) receive the whole texts as the stage leaves them, and the context's
+ * table grows.  inserts != NULL: n_pairs insert lengths I (0 = none) used as given; every record's sequence and quality range is
+ * checked against len1 / len2, and inserts[k] <= L1 + L2, before anything is launched: QD_ERR_INVALID.  inserts == NULL: the
+ * overlap trimming kernel runs first with the context's parameters and supplies them, as in qd_pipe_run (QD_ERR_STATE when that stage
+ * is off; its table grows too).  QD_ERR_STATE when the stage is off.  Returns when the launches have finished. */
+int qd_dev_paircorrect(qd_ctx* ctx, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+                       const uint32_t* recs2, int64_t n_pairs, const uint64_t* inserts, uint8_t* out_text1, uint8_t* out_text2);
 /* the post-trimming stage (qd_posttrim_set above; no reference counterpart) over host buffers, as qd_dev_trim: reads [0, n_pairs)
  * of two texts with their record tables are uploaded (the texts 3 bytes off alignment) and run through the kernel qd_pipe_run
  * launches; out_recs1 / out_recs2 receive the tables with every seq_len replaced by the length the read keeps, and the context's

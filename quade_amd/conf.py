@@ -7,7 +7,7 @@ file written by `-i` is the reference's template byte for byte (src/Conf_file.py
 package data, quade_amd/data/Quade_conf_file.txt).  An optional [gpu] section that reference conf
 files simply do not have is read when present (defaults apply otherwise; see GPU_SECTION_HELP), and so are the optional
 mismatch budgets of the [index] section (MISMATCH_HELP), the unknown-barcode report (UNKNOWN_HELP), the index-hopping report (HOPPING_HELP) and the quality report
-(QUALITY_HELP), the per-cycle report (CYCLE_HELP), the adapter content report (ADAPTER_HELP) and the duplication report (DUPLICATION_HELP) of the [output] section, an optional [trim] section (CLIP_HELP, TRIM_HELP, PAIR_HELP, POSTTRIM_HELP), an optional [filter] section
+(QUALITY_HELP), the per-cycle report (CYCLE_HELP), the adapter content report (ADAPTER_HELP) and the duplication report (DUPLICATION_HELP) of the [output] section, an optional [trim] section (CLIP_HELP, TRIM_HELP, PAIR_HELP, CORRECT_HELP, POSTTRIM_HELP), an optional [filter] section
 (FILTER_HELP) and an optional [screen] section (SCREEN_HELP).
 """
 from __future__ import annotations
@@ -250,6 +250,30 @@ PAIR_OVERLAP = "Authorized values for pair_min_overlap : 8 to 1000"
 PAIR_MISMATCHES = "Authorized values for pair_max_mismatches : 0 to 64"
 PAIR_MISMATCH_PCT = "Authorized values for pair_max_mismatch_pct : 0 to 50"
 
+CORRECT_HELP = """\
+Optional [trim] options (not in Quade 0.3.2, whose parser ignores them; absent = as before): overlap base correction of the read
+pairs on the GPU, what fastp does under --correction.  pair_overlap (above) accepts an overlap with a few disagreeing positions; at
+each of them the instrument read the same base twice, and where one call is confident and the other doubtful the confident base,
+with its quality, is written over the doubtful one.  Runs directly behind pair_overlap, on the reads as that stage received them,
+for every pair with an insert length I (shorter than the reads or not), and in front of the post-trimming.
+  pair_correct : False               True: at a position i of R1 with partner j = I - 1 - i of R2 that is no pair of complementary
+                                     letters of ACGT (either case): if R1's byte is a letter with quality >= pair_correct_good_quality
+                                     and R2's quality is <= pair_correct_bad_quality, R2 gets the complement (upper case) and R1's
+                                     quality; else the same with the reads exchanged; else the position stays unresolved
+  pair_correct_good_quality : 30     1 to 93
+  pair_correct_bad_quality : 14      0 to pair_correct_good_quality - 1
+No length changes and no pair is dropped; the post-trimming, [filter], [screen], quality_report, cycle_report, duplication_report
+and the output files see the corrected reads, adapter_report the raw ones, and Quade_pair_trim_report.csv is as without the option.
+Quade_pair_correct_report.csv is then written next to the report: reads and bases corrected per read, overlap bases, mismatches,
+corrected, unresolved, and the mismatch rate per 100 000 overlap bases before and after.  pair_correct needs pair_overlap : True
+and, as that does, the device pipeline
+"""
+
+CORRECT_NEEDS = "pair_correct needs the device pipeline (device_pipeline, device_inflate, device_deflate : True and gzip_level 1 or -1)"
+CORRECT_NEEDS_OVERLAP = "pair_correct needs pair_overlap : True"
+CORRECT_GOOD = "Authorized values for pair_correct_good_quality : 1 to 93"
+CORRECT_BAD = "Authorized values for pair_correct_bad_quality : 0 to pair_correct_good_quality - 1"
+
 POSTTRIM_HELP = """\
 Optional [trim] options (not in Quade 0.3.2, whose parser ignores them; absent = as before): trailing-N, poly-X tail and
 max_length trimming of the insert reads on the GPU, behind the clipping, the 3' trimming and pair_overlap above and in front of
@@ -455,6 +479,10 @@ class QuadeConf(object):
         self.pair_min_overlap = trim("pair_min_overlap", 30)
         self.pair_max_mismatches = trim("pair_max_mismatches", 5)
         self.pair_max_mismatch_pct = trim("pair_max_mismatch_pct", 20)
+        # ... and the overlap base correction behind it (CORRECT_HELP)
+        self.pair_correct = trim("pair_correct", False, lambda v: v.strip().lower() in ("true", "1", "yes", "on"))
+        self.pair_correct_good_quality = trim("pair_correct_good_quality", 30)
+        self.pair_correct_bad_quality = trim("pair_correct_bad_quality", 14)
         # ... and what is trimmed behind all of that (POSTTRIM_HELP): a max_length of 0 = no crop
         self.tail_n = trim("tail_n", False, lambda v: v.strip().lower() in ("true", "1", "yes", "on"))
         self.poly_x = trim("poly_x", False, lambda v: v.strip().lower() in ("true", "1", "yes", "on"))
@@ -582,6 +610,10 @@ class QuadeConf(object):
         assert 0 <= self.pair_max_mismatches <= 64, PAIR_MISMATCHES
         assert 0 <= self.pair_max_mismatch_pct <= 50, PAIR_MISMATCH_PCT
         assert not self.pair_trim or self.can_pipe, PAIR_NEEDS
+        assert 1 <= self.pair_correct_good_quality <= 93, CORRECT_GOOD
+        assert 0 <= self.pair_correct_bad_quality < self.pair_correct_good_quality, CORRECT_BAD
+        assert not self.pair_correction or self.can_pipe, CORRECT_NEEDS
+        assert not self.pair_correction or self.pair_trim, CORRECT_NEEDS_OVERLAP
         assert 6 <= self.poly_x_min_length <= 100, POSTTRIM_POLY_X
         assert all(0 <= m <= 65535 for m in self.max_length), POSTTRIM_MAX_LENGTH
         assert all(self.min_length <= m for m in self.max_length if m), POSTTRIM_FLOOR
@@ -679,6 +711,15 @@ class QuadeConf(object):
         """what Engine.pairtrim_set takes"""
         return dict(min_overlap=self.pair_min_overlap, max_mismatches=self.pair_max_mismatches,
                     max_mismatch_pct=self.pair_max_mismatch_pct, min_length=self.min_length)
+
+    @property
+    def pair_correction(self):
+        """overlap base correction of the read pairs is on (CORRECT_HELP)"""
+        return bool(self.pair_correct)
+
+    def pair_correct_params(self):
+        """what Engine.paircorrect_set takes"""
+        return dict(good_quality=self.pair_correct_good_quality, bad_quality=self.pair_correct_bad_quality)
 
     @property
     def posttrim(self):

@@ -30,6 +30,7 @@
 #include "quade_clip.h"
 #include "quade_trim.h"
 #include "quade_pairtrim.h"
+#include "quade_paircorrect.h"
 #include "quade_posttrim.h"
 #include "quade_filter.h"
 #include "quade_screen.h"
@@ -99,7 +100,7 @@ struct StageTable {
 };
 
 // the read stages, in the pipeline's order
-enum StageId { ST_ADAPTERS, ST_CLIP, ST_TRIM, ST_PAIRTRIM, ST_POSTTRIM, ST_FILTER, ST_SCREEN, ST_QSTATS, ST_CSTATS, ST_DUP, ST_COUNT };
+enum StageId { ST_ADAPTERS, ST_CLIP, ST_TRIM, ST_PAIRTRIM, ST_PAIRCORRECT, ST_POSTTRIM, ST_FILTER, ST_SCREEN, ST_QSTATS, ST_CSTATS, ST_DUP, ST_COUNT };
 
 // a stage's parameters while it is off: all zero, but for the filter's, whose rules are off at -1 (and qualified_quality is 15)
 constexpr qd_filter_params FILTER_OFF{-1, -1, -1, 15, -1, -1};
@@ -182,7 +183,7 @@ struct qd_ctx {
     KeyTally uk;
 
     // The read stages' tables, by StageId: what each is called, whether it has a row per destination, and, while the stage is on,
-    // its counters.  adapters uint64[34850 + (2 * S + 1) * 36], clip uint64[2][12], trim [2][8], pairtrim [1040], posttrim [2][16], filter [(2 * S + 1)][8], screen
+    // its counters.  adapters uint64[34850 + (2 * S + 1) * 36], clip uint64[2][12], trim [2][8], pairtrim [1040], paircorrect [10], posttrim [2][16], filter [(2 * S + 1)][8], screen
     // [(2 * S + 1)][8], qstats [(2 * S + 1)][2][6], cstats [QD_CS_VALUES], dup [(2 * S + 1)][5].  Everything that switches stages off,
     // zeroes, reads or adds to a table goes through this array; a new stage adds its row here.
     StageTable stage[ST_COUNT] = {
@@ -190,6 +191,7 @@ struct qd_ctx {
         {"clip counters", "clip", "clipping is not on", "n_values must be 24", false},
         {"trim counters", "trim", "trimming is not on", "n_values must be 16", false},
         {"overlap trimming table", "overlap trimming", "overlap trimming is not on", "n_values must be 1040", false},
+        {"overlap correction counters", "overlap correction", "overlap base correction is not on", "n_values must be 10", false},
         {"post-trim counters", "post-trim", "post-trimming is not on", "n_values must be 32", false},
         {"filter table", "filter", "the read filter is not on", "n_values must be (2*S+1)*8", true},
         {"screen counters", "screen", "the k-mer screen is not on", "n_values must be (2*S+1)*8", true},
@@ -206,6 +208,8 @@ struct qd_ctx {
     qd_trim_dev trim_dev{};
     qd_pairtrim_params pairtrim{};  // paired-end overlap trimming with insert sizes
     qd_pairtrim_dev pairtrim_dev{};
+    qd_paircorrect_params paircorrect{};  // overlap base correction behind it
+    qd_paircorrect_dev paircorrect_dev{};
     qd_posttrim_params posttrim{};  // trailing-N, poly-X and max_length trimming behind the three stages above
     qd_posttrim_dev posttrim_dev{};
     qd_filter_params filter = FILTER_OFF;  // read filtering
@@ -576,6 +580,7 @@ void stage_off(qd_ctx* c, int id) {
         case ST_CLIP: c->clip = {}; c->clip_dev = {}; break;
         case ST_TRIM: c->trim = {}; c->trim_dev = {}; break;
         case ST_PAIRTRIM: c->pairtrim = {}; c->pairtrim_dev = {}; break;
+        case ST_PAIRCORRECT: c->paircorrect = {}; c->paircorrect_dev = {}; break;
         case ST_POSTTRIM: c->posttrim = {}; c->posttrim_dev = {}; break;
         case ST_FILTER: c->filter = FILTER_OFF; c->filter_dev = filter_dev_of(FILTER_OFF); break;
         case ST_SCREEN:
@@ -645,7 +650,9 @@ void fill_pair_args(ARGS& a, const uint8_t* text1, const qd_rec* recs1, const ui
 //     return up.close(qd_<stage>_device(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), ..., QD_STREAM_CONTEXT));
 class PairUpload {
 public:
-    enum { CODES = 1, OUT_RECS = 2, REASONS = 4, HITS = 8 };  // what the stage needs besides the texts and record tables
+    // what the stage needs besides the texts and record tables.  SCRATCH_RECS: the out tables on the device only (nothing comes
+    // back); INSERTS: a uint64 per pair on the device; TEXT_BACK: close() copies the two texts to texts_back()'s buffers
+    enum { CODES = 1, OUT_RECS = 2, REASONS = 4, HITS = 8, SCRATCH_RECS = 16, INSERTS = 32, TEXT_BACK = 64 };
 
     explicit PairUpload(qd_ctx* ctx) : c(ctx) {}
 
@@ -680,7 +687,7 @@ public:
         for (int r = 0; r < 2; ++r) {
             HIPCHK(c, uk_malloc(&d_text[r].p, (size_t)len[r] + 32));
             HIPCHK(c, uk_malloc(&d_recs[r].p, rec_bytes));
-            if (want & OUT_RECS) HIPCHK(c, uk_malloc(&d_out[r].p, rec_bytes));
+            if (want & (OUT_RECS | SCRATCH_RECS)) HIPCHK(c, uk_malloc(&d_out[r].p, rec_bytes));
             if (len[r]) HIPCHK(c, hipMemcpyAsync(static_cast<uint8_t*>(d_text[r].p) + 3, text[r], (size_t)len[r], hipMemcpyHostToDevice, c->stream));
             HIPCHK(c, hipMemcpyAsync(d_recs[r].p, recs[r], rec_bytes, hipMemcpyHostToDevice, c->stream));
         }
@@ -694,6 +701,11 @@ public:
         }
         if (want & REASONS) HIPCHK(c, uk_malloc(&d_reason.p, (size_t)n_pairs));
         if (want & HITS) HIPCHK(c, uk_malloc(&d_hits.p, (size_t)n_pairs * 8));
+        if (want & INSERTS) HIPCHK(c, uk_malloc(&d_inserts.p, (size_t)n_pairs * 8));
+        if (want & TEXT_BACK) {
+            text_len[0] = (size_t)len1;
+            text_len[1] = (size_t)len2;
+        }
         pairs = n_pairs;
         h_out[0] = out_recs1;
         h_out[1] = out_recs2;
@@ -711,12 +723,20 @@ public:
     qd_rec* out(int r) const { return static_cast<qd_rec*>(d_out[r].p); }
     uint8_t* reason() const { return static_cast<uint8_t*>(d_reason.p); }
     uint32_t* hits() const { return static_cast<uint32_t*>(d_hits.p); }  // uint32[n][2]
+    uint64_t* inserts() const { return static_cast<uint64_t*>(d_inserts.p); }
+    uint8_t* mutable_text(int r) const { return static_cast<uint8_t*>(d_text[r].p) + 3; }  // for the stage that writes into the text
+    void texts_back(uint8_t* out1, uint8_t* out2) {
+        h_text[0] = out1;
+        h_text[1] = out2;
+    }
 
     // behind the stage, which returned rc: what it wrote goes to the host when it succeeded, and the stream is waited for
     int close(int rc) {
         if (rc == QD_OK) {
             for (int r = 0; r < 2; ++r)
-                if (d_out[r].p) HIPCHK(c, hipMemcpyAsync(h_out[r], d_out[r].p, (size_t)pairs * sizeof(qd_rec), hipMemcpyDeviceToHost, c->stream));
+                if (d_out[r].p && h_out[r]) HIPCHK(c, hipMemcpyAsync(h_out[r], d_out[r].p, (size_t)pairs * sizeof(qd_rec), hipMemcpyDeviceToHost, c->stream));
+            for (int r = 0; r < 2; ++r)
+                if (h_text[r] && text_len[r]) HIPCHK(c, hipMemcpyAsync(h_text[r], mutable_text(r), text_len[r], hipMemcpyDeviceToHost, c->stream));
             if (d_reason.p) HIPCHK(c, hipMemcpyAsync(h_reason, d_reason.p, (size_t)pairs, hipMemcpyDeviceToHost, c->stream));
             if (d_hits.p) HIPCHK(c, hipMemcpyAsync(h_hits, d_hits.p, (size_t)pairs * 8, hipMemcpyDeviceToHost, c->stream));
         }
@@ -733,8 +753,10 @@ private:
     };
     qd_ctx* c;
     int64_t pairs = 0;
-    Dev d_text[2], d_recs[2], d_codes, d_drop, d_out[2], d_reason, d_hits;
+    Dev d_text[2], d_recs[2], d_codes, d_drop, d_out[2], d_reason, d_hits, d_inserts;
     uint32_t* h_out[2] = {nullptr, nullptr};
+    uint8_t* h_text[2] = {nullptr, nullptr};
+    size_t text_len[2] = {0, 0};
     uint8_t* h_reason = nullptr;
     uint32_t* h_hits = nullptr;
 };
@@ -1780,21 +1802,103 @@ int qd_pairtrim_read(qd_ctx* c, uint64_t* out, int64_t n_values) { return c ? ta
 
 int qd_pairtrim_add(qd_ctx* c, const uint64_t* values, int64_t n_values) { return c ? table_add(c, c->stage[ST_PAIRTRIM], values, n_values) : QD_ERR_INVALID; }
 
-int qd_pairtrim_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
-                       qd_rec* out1, qd_rec* out2, void* stream) {
+int qd_pairtrim_device_inserts(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
+                               qd_rec* out1, qd_rec* out2, uint64_t* inserts, void* stream) {
     return stage_launch(c, ST_PAIRTRIM, true, n, stream, [&](u64* table, hipStream_t st) {
         qd_pairtrim_args a{};
         fill_pair_args(a, text1, recs1, text2, recs2);
         a.out[0] = out1;
         a.out[1] = out2;
         a.table = table;
+        a.insert = inserts;
         return qd_pairtrim_launch(c->pairtrim_dev, a, n, st);
     });
+}
+
+int qd_pairtrim_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2, uint32_t n,
+                       qd_rec* out1, qd_rec* out2, void* stream) {
+    return qd_pairtrim_device_inserts(c, text1, recs1, text2, recs2, n, out1, out2, nullptr, stream);
 }
 
 int qd_dev_pairtrim(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
                     const uint32_t* recs2, int64_t n_pairs, uint32_t* out_recs1, uint32_t* out_recs2) {
     return dev_rewrite(c, ST_PAIRTRIM, qd_pairtrim_device, text1, len1, recs1, text2, len2, recs2, n_pairs, out_recs1, out_recs2);
+}
+
+static_assert(QD_PAIRCORRECT_VALUES == QD_PC_VALUES, "the public table size is the kernel's");
+
+int qd_paircorrect_set(qd_ctx* c, const qd_paircorrect_params* params) {
+    if (!c) return QD_ERR_INVALID;
+    qd_paircorrect_params P{};
+    qd_paircorrect_dev D{};
+    if (params) {  // checked as the configuration file's values are, before anything changes
+        P = *params;
+        if (P.good_quality < 1 || P.good_quality > 93) return fail(c, QD_ERR_INVALID, "pair_correct good_quality: 1 to 93");
+        if (P.bad_quality < 0 || P.bad_quality >= P.good_quality) return fail(c, QD_ERR_INVALID, "pair_correct bad_quality: 0 to good_quality - 1");
+        D.good_byte = 33u + (uint32_t)P.good_quality;
+        D.bad_byte = 33u + (uint32_t)P.bad_quality;
+    }
+    const int rc = stage_install(c, ST_PAIRCORRECT, params, QD_PC_VALUES);
+    if (rc != QD_OK || !params) return rc;
+    c->paircorrect = P;
+    c->paircorrect_dev = D;
+    return QD_OK;
+}
+
+int qd_paircorrect_get(const qd_ctx* c, qd_paircorrect_params* out) {
+    if (!c || !out) return QD_ERR_INVALID;
+    *out = c->paircorrect;
+    return QD_OK;
+}
+
+int qd_paircorrect_active(const qd_ctx* c) { return c && c->stage[ST_PAIRCORRECT].d ? 1 : 0; }
+
+int qd_paircorrect_read(qd_ctx* c, uint64_t* out, int64_t n_values) { return c ? table_read(c, c->stage[ST_PAIRCORRECT], out, n_values) : QD_ERR_INVALID; }
+
+int qd_paircorrect_add(qd_ctx* c, const uint64_t* values, int64_t n_values) { return c ? table_add(c, c->stage[ST_PAIRCORRECT], values, n_values) : QD_ERR_INVALID; }
+
+int qd_paircorrect_device(qd_ctx* c, uint8_t* text1, const qd_rec* recs1, uint8_t* text2, const qd_rec* recs2, const uint64_t* inserts,
+                          uint32_t n, void* stream) {
+    if (c && !inserts && n) return fail(c, QD_ERR_INVALID, "overlap correction: no insert lengths");
+    return stage_launch(c, ST_PAIRCORRECT, true, n, stream, [&](u64* table, hipStream_t st) {
+        qd_paircorrect_args a{};
+        a.text[0] = text1;
+        a.text[1] = text2;
+        a.recs[0] = recs1;
+        a.recs[1] = recs2;
+        a.insert = inserts;
+        a.table = table;
+        return qd_paircorrect_launch(c->paircorrect_dev, a, n, st);
+    });
+}
+
+int qd_dev_paircorrect(qd_ctx* c, const uint8_t* text1, int64_t len1, const uint32_t* recs1, const uint8_t* text2, int64_t len2,
+                       const uint32_t* recs2, int64_t n_pairs, const uint64_t* inserts, uint8_t* out_text1, uint8_t* out_text2) {
+    if (!c) return QD_ERR_INVALID;
+    if (!c->stage[ST_PAIRCORRECT].d) return fail(c, QD_ERR_STATE, c->stage[ST_PAIRCORRECT].off_text);
+    if (!inserts && !c->stage[ST_PAIRTRIM].d) return fail(c, QD_ERR_STATE, c->stage[ST_PAIRTRIM].off_text);
+    if ((len1 > 0 && (!text1 || !out_text1)) || (len2 > 0 && (!text2 || !out_text2))) return fail(c, QD_ERR_INVALID, "null argument");
+    if (inserts && recs1 && recs2 && n_pairs > 0 && n_pairs <= 0x7FFFFFFF)  // (open() below refuses the other cases)
+        for (int64_t j = 0; j < n_pairs; ++j)
+            if (inserts[j] > (uint64_t)recs1[6 * j + 4] + recs2[6 * j + 4]) return fail(c, QD_ERR_INVALID, "an insert length is above L1 + L2");
+    PairUpload up(c);
+    const int want = PairUpload::INSERTS | PairUpload::TEXT_BACK | (inserts ? 0 : PairUpload::SCRATCH_RECS);
+    int rc = up.open(text1, len1, recs1, text2, len2, recs2, n_pairs, want, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (rc != QD_OK) return rc;
+    if (up.empty()) {  // no pairs: the texts as they came
+        if (len1 > 0) std::memcpy(out_text1, text1, (size_t)len1);
+        if (len2 > 0) std::memcpy(out_text2, text2, (size_t)len2);
+        return QD_OK;
+    }
+    up.texts_back(out_text1, out_text2);
+    if (inserts) {
+        HIPCHK(c, hipMemcpyAsync(up.inserts(), inserts, (size_t)up.n() * 8, hipMemcpyHostToDevice, c->stream));
+    } else {  // the hand-over: the overlap kernel with the context's parameters supplies them (its table grows too)
+        rc = qd_pairtrim_device_inserts(c, up.text(0), up.recs(0), up.text(1), up.recs(1), up.n(), up.out(0), up.out(1), up.inserts(), QD_STREAM_CONTEXT);
+    }
+    if (rc == QD_OK)
+        rc = qd_paircorrect_device(c, up.mutable_text(0), up.recs(0), up.mutable_text(1), up.recs(1), up.inserts(), up.n(), QD_STREAM_CONTEXT);
+    return up.close(rc);
 }
 
 static_assert(QD_POSTTRIM_VALUES == QD_POST_TABLE, "the public table size is the kernel's");
@@ -2266,7 +2370,7 @@ int qd_add_counts(qd_ctx* c, const uint64_t* counts, int32_t n_values) {
 
 int qd_reset_counts(qd_ctx* c) {
     if (!c) return QD_ERR_INVALID;
-    if (!c->have_table) {  // no barcodes, no pair counters; the stages that need none (clip, trim, pairtrim, posttrim, cstats) may be on
+    if (!c->have_table) {  // no barcodes, no pair counters; the stages that need none (clip, trim, pairtrim, paircorrect, posttrim, cstats) may be on
         if (!stages_on(c, false)) return QD_OK;
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, wait_all(c));

@@ -50,11 +50,15 @@ struct qd_pairtrim_dev {
 
 // Pairs [0, n): out[r][j] = recs[r][j] with seq_len = the length the read keeps; adds to table (uint64[1040]).
 // Device pointers, returns after the launch.  n < 2^31.
+// insert: nullptr (every caller value-initialises the struct), or n values: lane 0 of the pair's row stores its I*, 0 = none, for the
+// overlap base correction behind this stage (quade_paircorrect.h).  64 bits wide: exact for every L1 + L2 the record tables can
+// express (two 32-bit lengths).  Nothing else the kernel computes or writes depends on it.
 struct qd_pairtrim_args {
     const uint8_t* text[2];
     const qd_rec* recs[2];
     qd_rec* out[2];
     uint64_t* table;
+    uint64_t* insert;
 };
 hipError_t qd_pairtrim_launch(const qd_pairtrim_dev& P, const qd_pairtrim_args& a, uint32_t n, hipStream_t st);
 
@@ -63,3 +67,6 @@ hipError_t qd_pairtrim_launch(const qd_pairtrim_dev& P, const qd_pairtrim_args& 
 extern "C" int qd_pairtrim_active(const qd_ctx* ctx);
 extern "C" int qd_pairtrim_device(qd_ctx* ctx, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2,
                                   uint32_t n, qd_rec* out1, qd_rec* out2, void* stream);
+// the same launch, which also stores every pair's I* (0 = none) in inserts[0 .. n) when inserts is not nullptr
+extern "C" int qd_pairtrim_device_inserts(qd_ctx* ctx, const uint8_t* text1, const qd_rec* recs1, const uint8_t* text2, const qd_rec* recs2,
+                                          uint32_t n, qd_rec* out1, qd_rec* out2, uint64_t* inserts, void* stream);

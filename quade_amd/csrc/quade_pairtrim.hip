@@ -187,6 +187,7 @@ __global__ __launch_bounds__(PT_BLOCK) void pairtrim(qd_pairtrim_dev P, qd_pairt
                 a.out[sub][j] = o;
             }
             if (sub == 0 && I) atomicAdd(&hist[I < QD_PT_BINS - 1 ? (uint32_t)I : QD_PT_BINS - 1], 1u);
+            if (sub == 0 && a.insert) a.insert[j] = I;  // the hand-over to the overlap base correction: 0 = none
             uint32_t add = 0;  // this lane's counter of the pair
             auto put = [&](uint32_t i, uint32_t x) {
                 if (sub == i) add = x;

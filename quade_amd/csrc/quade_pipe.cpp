@@ -54,6 +54,7 @@
 #include "quade_clip.h"
 #include "quade_trim.h"
 #include "quade_pairtrim.h"
+#include "quade_paircorrect.h"
 #include "quade_posttrim.h"
 #include "quade_filter.h"
 #include "quade_screen.h"
@@ -698,6 +699,7 @@ struct qd_pipe {
     DevBuf rows_seq[2], rows_qual[2], rows_len[2], codes, mol, short_idx, dest, len1, len2, hist, tmp, perm, sdest, g1, g2, scan_tiles, first, g1_first,
         g2_first;
     DevBuf recs_out[4][2];  // the insert reads' record tables as clip, trim, pairtrim and posttrim leave them (a stage's are never allocated when it is off)
+    DevBuf inserts;  // a pair's insert length I* from the overlap stage to the overlap base correction (uint64 per pair; never allocated when the correction is off)
     DevBuf drop;  // the read filter's reason byte per pair, 0x80 for a pair the k-mer screen drops (qd_filter_set, qd_screen_set with action drop; never allocated when both are off)
     PinBuf h_first;
     // tables and scratch of the format / CRC / coder launches: read by kernels on the compute stream only, so one set serves every batch
@@ -1678,8 +1680,8 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
     // The insert reads' tables: the opt-in stages below write copies of their own, which everything behind them reads sequence and
     // quality through.  The scan's tables stay as they are: the carry and the next batch use them
     const qd_rec* ins[2] = {p->win[0].recs.as<qd_rec>(), p->win[1].recs.as<qd_rec>()};
-    const uint8_t* const text1 = p->win[0].buf[p->win[0].cur].p;
-    const uint8_t* const text2 = p->win[1].buf[p->win[1].cur].p;
+    uint8_t* const text1 = p->win[0].buf[p->win[0].cur].p;  // (mutable for the one stage that writes into the text: the correction below)
+    uint8_t* const text2 = p->win[1].buf[p->win[1].cur].p;
     {  // opt-in adapter content (qd_adapters_set): the one stage that counts the reads as the scan left them, by the final codes
         const int rc = qd_adapters_device(p->ctx, text1, ins[0], text2, ins[1], n, p->codes.as<uint16_t>(), p->cs);
         if (rc != QD_OK) return pfail(p, rc, std::string("adapter content: ") + qd_last_error(p->ctx));
@@ -1696,12 +1698,28 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
                       {qd_trim_active, qd_trim_device, "trim: "},
                       {qd_pairtrim_active, qd_pairtrim_device, "overlap trim: "},
                       {qd_posttrim_active, qd_posttrim_device, "post-trim: "}};
+    // Opt-in overlap base correction (qd_paircorrect_set) directly behind the overlap trimming: that kernel stores every pair's I*,
+    // and the correction writes bases and qualities of pairs [0, n) into the windows' text, in place, through the tables the
+    // overlap stage received.  In place is safe here: the kernel touches the sequence and quality lines of records [0, n) only, so
+    // the carry (records >= n, copied later on this stream) never sees a changed byte; everything that reads these lines again --
+    // the stages below and the formatter -- is queued behind it on this stream; the next batch's text is inflated behind the carry
+    // in the window's OTHER buffer, on whatever stream; the index reads have windows of their own; and the text has been verified
+    // (block CRCs, a gzip member's running CRC and its 32 KiB of history) when the scan that made these tables ran.
+    const bool correct = qd_paircorrect_active(p->ctx) != 0;  // (qd_pipe_run has made sure that overlap trimming is on as well)
     for (int s = 0; s < 4; ++s) {
         if (!rewriting[s].active(p->ctx)) continue;
         DevBuf* out = p->recs_out[s];
         for (int k = 0; k < 2; ++k) PCHK(p, out[k].need((size_t)n * sizeof(qd_rec) + 64, 0, p->cs));
-        const int rc = rewriting[s].device(p->ctx, text1, ins[0], text2, ins[1], n, out[0].as<qd_rec>(), out[1].as<qd_rec>(), p->cs);
-        if (rc != QD_OK) return pfail(p, rc, std::string(rewriting[s].label) + qd_last_error(p->ctx));
+        if (correct && rewriting[s].device == qd_pairtrim_device) {
+            PCHK(p, p->inserts.need((size_t)n * 8 + 64, 0, p->cs));
+            int rc = qd_pairtrim_device_inserts(p->ctx, text1, ins[0], text2, ins[1], n, out[0].as<qd_rec>(), out[1].as<qd_rec>(), p->inserts.as<uint64_t>(), p->cs);
+            if (rc != QD_OK) return pfail(p, rc, std::string(rewriting[s].label) + qd_last_error(p->ctx));
+            rc = qd_paircorrect_device(p->ctx, text1, ins[0], text2, ins[1], p->inserts.as<uint64_t>(), n, p->cs);
+            if (rc != QD_OK) return pfail(p, rc, std::string("overlap correction: ") + qd_last_error(p->ctx));
+        } else {
+            const int rc = rewriting[s].device(p->ctx, text1, ins[0], text2, ins[1], n, out[0].as<qd_rec>(), out[1].as<qd_rec>(), p->cs);
+            if (rc != QD_OK) return pfail(p, rc, std::string(rewriting[s].label) + qd_last_error(p->ctx));
+        }
         for (int k = 0; k < 2; ++k) ins[k] = out[k].as<qd_rec>();
     }
     // opt-in read filtering (qd_filter_set) of what the trimming left: a reason byte per pair; a pair with one is counted by nothing
@@ -2435,6 +2453,8 @@ int qd_pipe_set_option(qd_pipe* p, const char* name, int64_t value) {
 int qd_pipe_run(qd_pipe* p, const qd_pipe_chunk* chunks, int32_t n_chunks, qd_pipe_stats* stats) {
     if (!p || n_chunks < 0 || (n_chunks && !chunks)) return pfail(p, QD_ERR_INVALID, "bad arguments");
     p->err.clear();
+    if (qd_paircorrect_active(p->ctx) && !qd_pairtrim_active(p->ctx))  // before anything is read: the correction has no search of its own
+        return pfail(p, QD_ERR_STATE, "overlap base correction is on and overlap trimming is off: the correction takes its insert lengths from that stage");
     PCHK(p, hipSetDevice(p->device));
     const auto run_t0 = std::chrono::steady_clock::now();
     g_alloc_seconds = 0;
@@ -2558,7 +2578,7 @@ int qd_pipe_destroy(qd_pipe* p) {
     p->gz = nullptr;
     for (DevBuf* b : {&p->d_res, &p->rows_seq[0], &p->rows_seq[1], &p->rows_qual[0], &p->rows_qual[1], &p->rows_len[0], &p->rows_len[1], &p->codes, &p->mol,
                       &p->short_idx, &p->dest, &p->len1, &p->len2, &p->hist, &p->tmp, &p->perm, &p->sdest, &p->g1, &p->g2, &p->scan_tiles, &p->first, &p->g1_first,
-                      &p->g2_first, &p->subs, &p->first_sub, &p->ranges, &p->crc, &p->tokens, &p->sub_out, &p->sub_bytes, &p->base1, &p->base2, &p->drop})
+                      &p->g2_first, &p->subs, &p->first_sub, &p->ranges, &p->crc, &p->tokens, &p->sub_out, &p->sub_bytes, &p->base1, &p->base2, &p->drop, &p->inserts})
         b->release();
     for (auto& stage : p->recs_out)
         for (DevBuf& b : stage) b.release();

@@ -17,7 +17,7 @@ from .stages import (ADAPTER_BINS, ADAPTER_BUILTIN, ADAPTER_COLUMNS, ADAPTER_DES
                      ADAPTER_PROBES, ADAPTERS, READ_STAGE, READ_STAGES, adapters_flat, adapters_values, adapters_views,
                      CLIP_COUNTERS, CSTATS_COUNTERS, CSTATS_CYCLES, CSTATS_GC_BINS, CSTATS_GR_VALUES, CSTATS_GROUPS,  # noqa: F401
                      CSTATS_LEN_BINS, CSTATS_MEANQ_BINS, CSTATS_SECTIONS, CSTATS_VALUES, FILTER_COUNTERS, FILTER_KEYS, FILTER_REASONS,
-                     PAIRTRIM_BINS, PAIRTRIM_COUNTERS, PAIRTRIM_PAIR_COUNTERS, PAIRTRIM_VALUES, POSTTRIM, POSTTRIM_COUNTERS,
+                     PAIRCORRECT, PAIRCORRECT_COUNTERS, PAIRCORRECT_VALUES, PAIRTRIM_BINS, PAIRTRIM_COUNTERS, PAIRTRIM_PAIR_COUNTERS, PAIRTRIM_VALUES, POSTTRIM, POSTTRIM_COUNTERS,
                      PIPE_STAGE, PIPE_STAGES, QSTATS_COUNTERS, RUN_STAGE, RUN_STAGES, SCREEN, SCREEN_ACTIONS, SCREEN_COUNTERS, STAGE,
                      STAGES, TRIM_COUNTERS, cstats_flat, cstats_views, pack_table, split_pairtrim, unpack_table)
 
@@ -70,6 +70,10 @@ class qd_trim_params(C.Structure):
 
 class qd_pairtrim_params(C.Structure):
     _fields_ = [("min_overlap", C.c_int32), ("max_mismatches", C.c_int32), ("max_mismatch_pct", C.c_int32), ("min_length", C.c_int32)]
+
+
+class qd_paircorrect_params(C.Structure):
+    _fields_ = [("good_quality", C.c_int32), ("bad_quality", C.c_int32)]
 
 
 class qd_posttrim_params(C.Structure):
@@ -166,6 +170,10 @@ SYMBOLS = [
     ("qd_pairtrim_get", C.c_int, [_P, C.POINTER(qd_pairtrim_params)]),
     ("qd_pairtrim_read", C.c_int, [_P, _P, C.c_int64]),
     ("qd_pairtrim_add", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_paircorrect_set", C.c_int, [_P, C.POINTER(qd_paircorrect_params)]),
+    ("qd_paircorrect_get", C.c_int, [_P, C.POINTER(qd_paircorrect_params)]),
+    ("qd_paircorrect_read", C.c_int, [_P, _P, C.c_int64]),
+    ("qd_paircorrect_add", C.c_int, [_P, _P, C.c_int64]),
     ("qd_posttrim_set", C.c_int, [_P, C.POINTER(qd_posttrim_params)]),
     ("qd_posttrim_get", C.c_int, [_P, C.POINTER(qd_posttrim_params)]),
     ("qd_posttrim_read", C.c_int, [_P, _P, C.c_int64]),
@@ -275,6 +283,7 @@ SYMBOLS = [
     ("qd_dev_clip", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_trim", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_pairtrim", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
+    ("qd_dev_paircorrect", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P]),
     ("qd_dev_posttrim", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_filter", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("qd_dev_screen", C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P]),
@@ -890,6 +899,45 @@ class Engine(object):
         """The overlap trimming stage over host buffers (qd_dev_pairtrim): texts as bytes or uint8 arrays, recs uint32[n, 6] in
         dev_fastq_scan's layout; -> the two tables with the lengths the reads keep; adds to the context's table."""
         return self._dev_recs(self.lib.qd_dev_pairtrim, text1, recs1, text2, recs2)
+
+    def paircorrect_set(self, good_quality=30, bad_quality=14, on=True):
+        """Overlap base correction of the read pairs in the device pipeline, directly behind pairtrim_set's stage
+        (qd_paircorrect_set; conf.CORRECT_HELP has the rule).  on=False turns it off and frees the table; a value out of range is
+        QD_ERR_INVALID and changes nothing."""
+        if not on:
+            self._chk(self.lib.qd_paircorrect_set(self._h, None))
+            return
+        P = qd_paircorrect_params(int(good_quality), int(bad_quality))
+        self._chk(self.lib.qd_paircorrect_set(self._h, C.byref(P)))
+
+    def paircorrect_get(self):
+        """The parameters in force, as paircorrect_set's keywords (the stage off: all zero)."""
+        P = qd_paircorrect_params()
+        self._chk(self.lib.qd_paircorrect_get(self._h, C.byref(P)))
+        return dict(good_quality=P.good_quality, bad_quality=P.bad_quality)
+
+    def paircorrect_read(self):
+        """numpy uint64[10]: PAIRCORRECT_COUNTERS"""
+        return self._table_read(self.lib.qd_paircorrect_read, PAIRCORRECT_VALUES)
+
+    def paircorrect_add(self, table):
+        """Another context's table (paircorrect_read's layout) joins this context's (qd_paircorrect_add)."""
+        self._table_add(self.lib.qd_paircorrect_add, table)
+
+    def dev_paircorrect(self, text1, recs1, text2, recs2, inserts=None):
+        """The overlap base correction over host buffers (qd_dev_paircorrect): texts as bytes or uint8 arrays, recs uint32[n, 6] in
+        dev_fastq_scan's layout; inserts: a pair's insert length I each (0 = none), used as given, or None: the overlap trimming
+        kernel runs first with the context's parameters and supplies them; -> the two texts as the stage leaves them (uint8
+        arrays); adds to the context's table."""
+        t, r, _, _, n = self._pair_inputs(text1, recs1, text2, recs2)
+        if inserts is not None:
+            inserts = np.ascontiguousarray(inserts, dtype=np.uint64)
+            if inserts.shape != (n,):
+                raise ValueError("inserts must have one value per pair")
+        out = [np.zeros_like(x) for x in t]
+        self._chk(self.lib.qd_dev_paircorrect(self._h, _ptr(t[0]), t[0].size, _ptr(r[0]), _ptr(t[1]), t[1].size, _ptr(r[1]), n,
+                                              None if inserts is None else _ptr(inserts), _ptr(out[0]), _ptr(out[1])))
+        return out[0], out[1]
 
     def posttrim_set(self, tail_n=0, poly_x_min_length=0, max_length_r1=0, max_length_r2=0, min_length=0):
         """Trailing-N, poly-X and max_length trimming of the insert reads in the device pipeline, behind pairtrim_set's stage and in

@@ -194,6 +194,8 @@ class Quade(object):
                 for stage in hb.READ_STAGES:  # what the pipeline does to the insert reads while it holds their text, in its order
                     if stage.on(cf):
                         stage.enable(eng, cf)
+                if hb.PAIRCORRECT.on(cf):  # the overlap base correction behind pairtrim: a stage outside that table
+                    hb.PAIRCORRECT.enable(eng, cf)
                 if not self.use_pipe:
                     eng.slots_create(cf.slots, cf.batch_pairs)
                 group.append(eng)
@@ -224,6 +226,8 @@ class Quade(object):
         with _timed("duplication gather + merge"):  # (nor is the duplication tally a stage of the table: it merges by key too)
             dup = self._collect_dup() if cf.duplication_report else None
         tables = [(stage, self._collect(stage)) for stage in hb.READ_STAGES if stage.on(cf)]
+        if hb.PAIRCORRECT.on(cf):  # summed over contexts and ranks and reported as the stages of the table are
+            tables.append((hb.PAIRCORRECT, self._collect(hb.PAIRCORRECT)))
         for eng in self.engines:
             eng.close()
         self.engines = []

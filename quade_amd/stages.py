@@ -1,7 +1,7 @@
 # -*- coding: utf-8 -*-
 """
 The read stages of the device pipeline, described once: the columns of their counter tables (include/quade_hip.h, qd_qstats_*,
-qd_cstats_*, qd_clip_*, qd_trim_*, qd_pairtrim_*, qd_posttrim_*, qd_filter_*, qd_screen_*, qd_adapters_*), the bytes a table has when the ranks
+qd_cstats_*, qd_clip_*, qd_trim_*, qd_pairtrim_*, qd_paircorrect_*, qd_posttrim_*, qd_filter_*, qd_screen_*, qd_adapters_*), the bytes a table has when the ranks
 exchange it, and READ_STAGES, the table Quade.__call__ walks to switch the stages on, to collect their tables and to write their reports.  hip_backend and the
 report modules take the columns from here; nothing here touches libquade_hip.so.
 """
@@ -36,6 +36,12 @@ def split_pairtrim(table):
     t = [int(x) for x in np.asarray(table).reshape(PAIRTRIM_VALUES)]
     k = len(PAIRTRIM_COUNTERS)
     return [t[:k], t[k:2 * k]], t[2 * k:2 * k + 3], t[2 * k + 3:]
+
+
+# qd_paircorrect_*'s table: the overlap base correction behind the overlap trimming
+PAIRCORRECT_COUNTERS = ("r1_corrected_reads", "r1_corrected_bases", "r2_corrected_reads", "r2_corrected_bases", "pairs", "overlapped_pairs",
+                        "overlap_bases", "mismatches", "unresolved", "corrected_pairs")
+PAIRCORRECT_VALUES = len(PAIRCORRECT_COUNTERS)  # 10
 
 
 # qd_filter_*: the reasons (the reason byte of a dropped pair is the index + 1), the table's columns and the parameters
@@ -204,6 +210,14 @@ ADAPTERS = Stage("adapters", "adapters", "adapter_report", "adapter_params", (-1
                  adapters_flat, adapters_views, "adapter_report", ("samples", "params"))
 READ_STAGES = (ADAPTERS,) + PIPE_STAGES  # adapters, quality, cycle, clip, trim, pairtrim, posttrim, filter, screen
 READ_STAGE = {s.name: s for s in READ_STAGES}
+
+
+# READ_STAGES is pinned at those nine in turn, and so is where Quade.__call__ walks it.  The overlap base correction
+# (qd_paircorrect_*) runs directly behind pairtrim: a Stage outside the tuples, which Quade.__call__ switches on and collects
+# explicitly beside its two walks, the way it handles the duplication tally and the hopping matrix.  pack_table and unpack_table
+# take it as they take any Stage.
+PAIRCORRECT = Stage("paircorrect", "paircorrect", "pair_correction", "pair_correct_params", (PAIRCORRECT_VALUES,), None,
+                    "an overlap correction table", None, None, "pair_correct_report", ("params",))
 
 
 def _stage(stage):

@@ -3,7 +3,7 @@
 the CLI driver.  Host bound (gunzip, scan, format, gzip); printed as one JSON line.
 usage: python tools/e2e_bench.py [pairs] [gzip level] [chunks] [--single-member | --members] [--binned] [--ranks N]
 input files: BGZF (bgzip layout) by default, --members = 8 MB gzip members, --single-member = one gzip member
-env: E2E_PARALLEL_GUNZIP (1; 0 = ordinary gzip files on one thread each), E2E_GUNZIP_CHUNK, E2E_GUNZIP_IN_FLIGHT, E2E_DEVICE_INFLATE (0; 1 = BGZF inflate on the GPU), E2E_DEVICE_DEFLATE (0; 1 = Huffman-only members made on the GPU, level -1), E2E_WORKERS (chunk_workers), E2E_IO_THREADS, E2E_SAMPLES (96), E2E_BATCH (the driver's default), E2E_DEVICE_PIPELINE (1; 0 = batch pipeline over pinned slots), E2E_MISMATCHES ("m1,m2": [index] index1_mismatches / index2_mismatches; unset = exact matching), E2E_UNKNOWN (N: [output] top_unknown_barcodes; unset = no tally), E2E_HOPPING (1: [output] index_hopping_report : True; unset = no matrix), E2E_QUALITY (1: [output] quality_report : True; unset = no counters), E2E_CYCLE (1: [output] cycle_report : True; unset = no per-cycle counters), E2E_ADAPTERS (1: [output] adapter_report : True with the built-in probes; unset = no adapter content), E2E_TRIM (1: a [trim] section with quality_cutoff 20 and the two TruSeq adapters; unset = no trimming), E2E_PAIRTRIM (1: [trim] pair_overlap : True with its defaults; unset = no overlap trimming), E2E_CLIP (1: [trim] tail_clip_R1 / tail_clip_R2 : 1, window_size 4 with window_quality 20 and poly_g : True; unset = no clipping), E2E_POSTTRIM (1: [trim] tail_n and poly_x : True and max_length_R1 / max_length_R2 : 140; unset = no post-trimming), E2E_FILTER (1: a [filter] section with min_length 30, max_n 5, max_unqualified_pct 40, min_mean_quality 20 and min_complexity_pct 30; unset = no filter), E2E_SCREEN (1: a [screen] section with a seeded random 5 386-base reference written next to the conf, kmer 31 and action report; "drop": action drop; unset = no screen), E2E_DUP (1: [output] duplication_report : True at duplication_sample E2E_DUP_SAMPLE (16); the JSON line then has the wall time of the end-of-run gather and merge; unset = no tally), QUADE_PROFILE=1 (stage timers)"""
+env: E2E_PARALLEL_GUNZIP (1; 0 = ordinary gzip files on one thread each), E2E_GUNZIP_CHUNK, E2E_GUNZIP_IN_FLIGHT, E2E_DEVICE_INFLATE (0; 1 = BGZF inflate on the GPU), E2E_DEVICE_DEFLATE (0; 1 = Huffman-only members made on the GPU, level -1), E2E_WORKERS (chunk_workers), E2E_IO_THREADS, E2E_SAMPLES (96), E2E_BATCH (the driver's default), E2E_DEVICE_PIPELINE (1; 0 = batch pipeline over pinned slots), E2E_MISMATCHES ("m1,m2": [index] index1_mismatches / index2_mismatches; unset = exact matching), E2E_UNKNOWN (N: [output] top_unknown_barcodes; unset = no tally), E2E_HOPPING (1: [output] index_hopping_report : True; unset = no matrix), E2E_QUALITY (1: [output] quality_report : True; unset = no counters), E2E_CYCLE (1: [output] cycle_report : True; unset = no per-cycle counters), E2E_ADAPTERS (1: [output] adapter_report : True with the built-in probes; unset = no adapter content), E2E_TRIM (1: a [trim] section with quality_cutoff 20 and the two TruSeq adapters; unset = no trimming), E2E_PAIRTRIM (1: [trim] pair_overlap : True with its defaults; unset = no overlap trimming), E2E_PAIRCORRECT (1, with E2E_PAIRTRIM: [trim] pair_correct : True with its defaults; unset = no overlap base correction), E2E_CLIP (1: [trim] tail_clip_R1 / tail_clip_R2 : 1, window_size 4 with window_quality 20 and poly_g : True; unset = no clipping), E2E_POSTTRIM (1: [trim] tail_n and poly_x : True and max_length_R1 / max_length_R2 : 140; unset = no post-trimming), E2E_FILTER (1: a [filter] section with min_length 30, max_n 5, max_unqualified_pct 40, min_mean_quality 20 and min_complexity_pct 30; unset = no filter), E2E_SCREEN (1: a [screen] section with a seeded random 5 386-base reference written next to the conf, kmer 31 and action report; "drop": action drop; unset = no screen), E2E_DUP (1: [output] duplication_report : True at duplication_sample E2E_DUP_SAMPLE (16); the JSON line then has the wall time of the end-of-run gather and merge; unset = no tally), QUADE_PROFILE=1 (stage timers)"""
 import json
 import os
 import shutil
@@ -96,14 +96,18 @@ try:
     if pairtrim:  # paired-end overlap trimming: into the [trim] section, which is the file's last when E2E_TRIM made one
         with open(conf, "a") as fh:
             fh.write(("" if trim else "\n[trim]\n") + "pair_overlap : True\n")
+    paircorrect = os.environ.get("E2E_PAIRCORRECT", "0") not in ("", "0")
+    if paircorrect:  # overlap base correction behind it: into the same [trim] section (the conf is rejected without pair_overlap)
+        with open(conf, "a") as fh:
+            fh.write(("" if trim or pairtrim else "\n[trim]\n") + "pair_correct : True\n")
     clip = os.environ.get("E2E_CLIP", "0") not in ("", "0")
     if clip:  # end clipping, window and poly-G trimming: into the [trim] section, the file's last when one of the two above made it
         with open(conf, "a") as fh:
-            fh.write(("" if trim or pairtrim else "\n[trim]\n") + "tail_clip_R1 : 1\ntail_clip_R2 : 1\nwindow_size : 4\nwindow_quality : 20\npoly_g : True\n")
+            fh.write(("" if trim or pairtrim or paircorrect else "\n[trim]\n") + "tail_clip_R1 : 1\ntail_clip_R2 : 1\nwindow_size : 4\nwindow_quality : 20\npoly_g : True\n")
     posttrim = os.environ.get("E2E_POSTTRIM", "0") not in ("", "0")
     if posttrim:  # trailing-N, poly-X and max_length trimming: into the [trim] section, the file's last when one of the three above made it
         with open(conf, "a") as fh:
-            fh.write(("" if trim or pairtrim or clip else "\n[trim]\n") + "tail_n : True\npoly_x : True\nmax_length_R1 : 140\nmax_length_R2 : 140\n")
+            fh.write(("" if trim or pairtrim or paircorrect or clip else "\n[trim]\n") + "tail_n : True\npoly_x : True\nmax_length_R1 : 140\nmax_length_R2 : 140\n")
     filt = os.environ.get("E2E_FILTER", "0") not in ("", "0")
     if filt:  # read filtering: a [filter] section behind everything else
         with open(conf, "a") as fh:
@@ -168,7 +172,7 @@ try:
     from quade_amd.fastq_writer import host_cores, io_backend, io_threads
     print(json.dumps({"mode": "end-to-end fastq.gz -> fastq.gz", "chunks": n_chunks, "pairs": n * n_chunks, "seconds": dt,
                       "pairs_per_s": n * n_chunks / dt, "gzip_level": level, "counts": counts, "chunk_workers": workers,
-                      "ranks": ranks, "qualities": quals, "device_inflate": dev_inflate, "device_deflate": dev_deflate, "device_pipeline": dev_pipe and ranks == 1 and pipe_stats is not None, "pipeline": pipe_stats if ranks == 1 else None, "parallel_gunzip": os.environ.get("E2E_PARALLEL_GUNZIP", "1") != "0", "samples": n_samples, "batch_pairs": batch, "mismatches": mm, "top_unknown_barcodes": unk, "index_hopping_report": hopping, "quality_report": quality, "cycle_report": cycle, "adapter_report": adapters, "duplication_sample": dup or None, "duplication_merge_seconds": getattr(_q, "dup_merge_seconds", None) if ranks == 1 else None, "trim": trim, "pair_trim": pairtrim, "clip": clip, "posttrim": posttrim, "filter": filt, "screen": screen or None, "input": {0: "single gzip member", "bgzf": "BGZF"}.get(fmt, "8 MB gzip members"), "gzip_backend": io_backend(),
+                      "ranks": ranks, "qualities": quals, "device_inflate": dev_inflate, "device_deflate": dev_deflate, "device_pipeline": dev_pipe and ranks == 1 and pipe_stats is not None, "pipeline": pipe_stats if ranks == 1 else None, "parallel_gunzip": os.environ.get("E2E_PARALLEL_GUNZIP", "1") != "0", "samples": n_samples, "batch_pairs": batch, "mismatches": mm, "top_unknown_barcodes": unk, "index_hopping_report": hopping, "quality_report": quality, "cycle_report": cycle, "adapter_report": adapters, "duplication_sample": dup or None, "duplication_merge_seconds": getattr(_q, "dup_merge_seconds", None) if ranks == 1 else None, "trim": trim, "pair_trim": pairtrim, "pair_correct": paircorrect, "clip": clip, "posttrim": posttrim, "filter": filt, "screen": screen or None, "input": {0: "single gzip member", "bgzf": "BGZF"}.get(fmt, "8 MB gzip members"), "gzip_backend": io_backend(),
                       "io_threads": io_threads(), "host_cores": host_cores(), "host_logical_cpus": os.cpu_count(), "dataset_seconds": round(t_gen, 1),
                       "cpu_seconds": cpu_s, "cpu_user_sys": [round(cpu_user, 2), round(cpu_sys, 2)] if cpu_s else None, "cpu_seconds_per_M_pairs": cpu_s / (n * n_chunks / 1e6) if cpu_s else None,
                       "core_utilisation": cpu_s / (dt * host_cores()) if cpu_s else None}))

@@ -7,7 +7,7 @@ each is timed by HIP events.  "off" does what process_batch does with the stage 
 itself costs.  After the timed steps the stage's table is read back and checked against what the batch must have counted.  Prints
 one JSON line ("tool": "<stage>_bench"): per case the medians, the spread and the byte floor (the lines' bytes at 6.3 TB/s).
 
-usage: python tools/stage_bench.py --stage qstats|cycle|clip|trim|pairtrim|posttrim|filter|screen|dup|adapters [--pairs N] [--bases L] [--steps K] [--warmup W]
+usage: python tools/stage_bench.py --stage qstats|cycle|clip|trim|pairtrim|paircorrect|posttrim|filter|screen|dup|adapters [--pairs N] [--bases L] [--steps K] [--warmup W]
                                    [--once CASE] [--out FILE]
   --once CASE  set up, run ONE launch and exit (for `rocprofv3 --kernel-trace --stats -- python ...`); CASE by stage:
     qstats    hot | spread | off      routing: 96 samples with 90 % of the pairs to 8 destinations (per-workgroup partials in LDS) |
@@ -18,6 +18,9 @@ usage: python tools/stage_bench.py --stage qstats|cycle|clip|trim|pairtrim|postt
                                       yardstick is the 3' trimming kernel with a cutoff only
     trim      PCT                     PCT % of the reads carry their adapter from a random position on
     pairtrim  PCT | poly              PCT % of the pairs read from an insert of 30 .. --bases - 1 bases | poly-A against poly-T
+    paircorrect PCT | unresolved      PCT % of the pairs read from a short insert, about 1 % of the overlap positions a Q2 call in R2
+                                      against Q37 in R1 | every pair from a short insert and both calls at Q37 (nothing to write);
+                                      interleaved with the pairtrim kernel, with and without the hand-over of I*, over the same batch
     posttrim  CASE:PCT                clip_poly_g | polyx | crop | all, over a batch with PCT % of the reads ending in 30 A;
                                       clip_poly_g is the clip kernel with its poly-G rule alone over the same share of G tails
     filter    drop0 | drop10 | drop100 | spread | off   the share of pairs dropped (poly-G in R1), hot or spread routing;
@@ -438,6 +441,83 @@ def pairtrim(B):
     return out
 
 
+def paircorrect(B):
+    """The overlap base correction beside the overlap kernel that feeds it, over the same batch in the same step: pairtrim as every
+    run launches it, pairtrim storing every pair's I* (the hand-over), then the correction.  The texts are put back before every step
+    (untimed): a corrected batch holds nothing to write."""
+    a, n, L = B.a, B.a.pairs, B.a.bases
+    engines = contexts({"pairtrim": lambda e: e.pairtrim_set(), "on": lambda e: (e.pairtrim_set(), e.paircorrect_set())})
+    floor = B.floor_ms(2)
+    lib, st = B.lib, B.st.cuda_stream
+    pt = B.entry("pairtrim")
+    pti = lib.qd_pairtrim_device_inserts
+    pti.restype, pti.argtypes = C.c_int, [C.c_void_p] * 5 + [C.c_uint32] + [C.c_void_p] * 4
+    pc = lib.qd_paircorrect_device
+    pc.restype, pc.argtypes = C.c_int, [C.c_void_p] * 6 + [C.c_uint32, C.c_void_p]
+    letters = torch.tensor(list(b"ACGT"), dtype=torch.uint8, device="cuda")
+
+    def measure(case):
+        pct, good2 = (100, True) if case == "unresolved" else (case, False)
+        c1, c2 = insert_pairs(n, L, 1, pct)
+        g = generator(11)
+        # a wrong call in one position of R2 in a hundred (over the whole read: those outside an overlap change nothing here)
+        wrong = torch.rand((n, L), generator=g, device="cuda") < 0.01
+        c2e = torch.where(wrong, (c2 + torch.randint(1, 4, (n, L), generator=g, device="cuda")) % 4, c2)
+        q1 = torch.full((n, L), 33 + 37, dtype=torch.uint8, device="cuda")
+        q2 = q1 if good2 else torch.where(wrong, torch.full_like(q1, 33 + 2), q1)
+        b = Batch(n, L, 2, 3, plants=(lambda g_, n_, L_: (letters[c1], q1), lambda g_, n_, L_: (letters[c2e], q2)))
+        del c1, c2, c2e, wrong, q1, q2
+        keep1, keep2 = b.t1.clone(), b.t2.clone()
+        o1, o2 = b.outputs()
+        inserts = torch.zeros(n, dtype=torch.int64, device="cuda")
+        args = (b.t1.data_ptr(), b.r1.data_ptr(), b.t2.data_ptr(), b.r2.data_ptr())
+
+        def check(rc):
+            assert rc == 0, rc
+
+        run = {"pairtrim": lambda: check(pt(engines["pairtrim"]._h, *args, n, o1, o2, st)),
+               "pairtrim_inserts": lambda: check(pti(engines["on"]._h, *args, n, o1, o2, inserts.data_ptr(), st)),
+               "paircorrect": lambda: check(pc(engines["on"]._h, *args, inserts.data_ptr(), n, st))}
+        if a.once is not None:
+            run["pairtrim_inserts"]()
+            return B.once(run["paircorrect"], {"once": case, "pairs": n, "bases": L})
+        for eng in engines.values():
+            eng.reset_counts()
+        ev = {k: [] for k in run}
+        for step in range(a.warmup + a.steps):
+            b.t1.copy_(keep1)
+            b.t2.copy_(keep2)
+            for k, f in run.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(B.st)
+                f()
+                e1.record(B.st)
+                if step >= a.warmup:
+                    ev[k].append((e0, e1))
+        torch.cuda.synchronize()
+        ms = {k: sorted(e0.elapsed_time(e1) for e0, e1 in v) for k, v in ev.items()}
+        t = [int(x) for x in engines["on"].paircorrect_read()]
+        launches = a.steps + a.warmup
+        reads, pairs, _ = hb.split_pairtrim(engines["on"].pairtrim_read())
+        assert t[4] == launches * n == pairs[0] and t[5] == pairs[1] and t[7] == t[1] + t[3] + t[8] and b.kept_whole()
+        # R1 is never the doubtful read; Q37 against Q37 stays; a Q2 call is corrected (but for the rare pair accepted at another insert)
+        assert t[1] == 0 and (t[3] == 0 and t[8] > 0 if good2 else t[8] * 1000 <= t[7])
+        assert bool((b.t1 == keep1).all()) and (good2 or pct == 0 or not bool((b.t2 == keep2).all()))
+        return {"case": case, "byte_floor_ms": floor, **by_name(ms), "paircorrect_over_pairtrim": median(ms["paircorrect"]) / median(ms["pairtrim"]),
+                "paircorrect_over_floor": median(ms["paircorrect"]) / floor,
+                "hand_over_store_ms": median(ms["pairtrim_inserts"]) - median(ms["pairtrim"]),
+                "overlapped_pair_share": t[5] / t[4], "overlap_bases_per_pair": t[6] / t[4], "mismatches_per_launch": t[7] / launches,
+                "corrected_bases_per_launch": t[3] / launches, "unresolved_per_launch": t[8] / launches, "corrected_pairs_per_launch": t[9] / launches}
+
+    if a.once is not None:
+        out = measure(a.once if a.once == "unresolved" else int(a.once))
+    else:
+        out = B.head("paircorrect_bench", line_bytes=2 * n * L, steps=a.steps, params=engines["on"].paircorrect_get(),
+                     pair_params=engines["on"].pairtrim_get(), batches=[measure(case) for case in (0, 10, 100, "unresolved")])
+    close(engines)
+    return out
+
+
 def x_tails(share, base):
     """a `share` of the reads ends in G_TAIL times `base`; plain qualities"""
     def plant(g, n, L):
@@ -763,7 +843,7 @@ def adapter_content(B):
     return out
 
 
-STAGES = {"adapters": adapter_content, "dup": dup, "qstats": qstats, "cycle": cycle, "clip": clip, "trim": trim, "pairtrim": pairtrim, "posttrim": posttrim, "filter": filter_, "screen": screen}
+STAGES = {"adapters": adapter_content, "dup": dup, "qstats": qstats, "cycle": cycle, "clip": clip, "trim": trim, "pairtrim": pairtrim, "paircorrect": paircorrect, "posttrim": posttrim, "filter": filter_, "screen": screen}
 
 
 def main():
