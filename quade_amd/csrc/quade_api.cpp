@@ -35,49 +35,57 @@
 #include "quade_filter.h"
 #include "quade_screen.h"
 #include "quade_dup.h"
-#include "quade_pool.h"
+#include "quade_buf.h"
 
 typedef uint64_t u64;
 
 namespace {
+
+// who owns what: quade_buf.h, DESIGN.md 7.0
+template <class T>
+using DevArr = qbuf::Arr<T, qbuf::DriverDev>;  // long-lived tables
+template <class T>
+using TrimArr = qbuf::Arr<T, qbuf::DriverDevTrim>;  // what is allocated while a pipeline's pool may hold the device's memory
+template <class T>
+using PinArr = qbuf::Arr<T, qbuf::DriverPin>;
 
 thread_local std::string g_create_error;
 
 struct Slot {
     hipStream_t stream = nullptr;   // kernel + downloads of this slot
     hipEvent_t uploaded = nullptr;  // recorded on the context's upload stream behind this slot's H2D copies
-    uint8_t* h_base = nullptr;  // pinned
-    uint8_t* d_base = nullptr;
+    PinArr<uint8_t> h_base;
+    DevArr<uint8_t> d_base;
     qd_slot_buffers h{};        // host views
     qd_slot_buffers d{};        // device views (same struct, device pointers)
     // pinned + device: the two streams' lists merged (unique, ascending; 2 * short_cap indices), then the
     // listed reads' lengths per stream (2 * short_cap bytes each): all the fixup kernel needs of the len rows
-    uint32_t* h_short = nullptr;
-    uint32_t* d_short = nullptr;
+    PinArr<uint32_t> h_short;
+    DevArr<uint32_t> d_short;
     bool busy = false;
 };
 
 enum { K_FAST = 1, K_GENERIC = 2 };
 
 // Per stream one device buffer that holds `units` units of a batch (pairs, here) and grows on demand: the rescue's list of a batch's
-// undetermined pairs and the two tallies' batch scratch.  Defined beside uk_malloc.
+// undetermined pairs and the two tallies' batch scratch.
 struct StreamScratch {
     struct Buf {
         hipStream_t stream;
-        uint8_t* buf;
-        size_t units;  // bytes_for(units) bytes; 0 beside buf == nullptr
+        TrimArr<uint8_t> buf;
+        size_t units;  // bytes_for(units) bytes; 0 beside an empty buf
     };
     std::vector<Buf> bufs;
     Buf* find(hipStream_t st);
     Buf* need(qd_ctx* c, hipStream_t st, size_t units, size_t (*bytes_for)(size_t));  // nullptr: failed, qd_last_error has the text
-    void release();  // (the caller waited for the context's work)
+    void release() { bufs.clear(); }  // (the caller waited for the context's work)
 };
 
 // A tally of keys on the device (the unknown barcodes, the duplication report): the table (one allocation, quade_unknown.h), per
 // stream the scratch of a batch, and the event behind the last launch's count kernel that a launch on another stream waits for
-// before its claim kernel.  The tally_* functions beside uk_malloc work on it.
+// before its claim kernel.  The tally_* functions work on it.
 struct KeyTally {
-    void* mem = nullptr;  // nullptr = off
+    TrimArr<uint8_t> mem;  // empty = off
     int64_t slots = 0;
     UnknownTable t{};
     int tag_bits = 64;  // options "unknown_tag_bits" / "dup_tag_bits" (tests); outlives the table
@@ -95,7 +103,7 @@ struct StageTable {
     const char* off_text;   // the error text while the table is off
     const char* size_text;  // the error text for a caller's table of another size
     bool per_destination;   // a row per destination: a new plan and new barcodes switch it off
-    u64* d = nullptr;       // nullptr = off
+    TrimArr<u64> d;         // empty = off
     size_t n_values = 0;    // as allocated
 };
 
@@ -128,12 +136,10 @@ struct qd_ctx {
     std::vector<int32_t> bc_off;
 
     // device table
-    uint32_t* d_slots_fast = nullptr;
-    uint32_t* d_slots_gen = nullptr;
-    u64* d_bk16 = nullptr;
-    u64* d_bk32 = nullptr;
-    u64* d_bkv = nullptr;   // wide plans: per barcode its two slices as the kernel extracts them (confirmation compare)
-    uint8_t* d_blen = nullptr;
+    DevArr<uint32_t> d_slots_fast, d_slots_gen;
+    DevArr<u64> d_bk16, d_bk32;
+    DevArr<u64> d_bkv;      // wide plans: per barcode its two slices as the kernel extracts them (confirmation compare)
+    DevArr<uint8_t> d_blen;
     uint32_t mask_fast = 0, mask_gen = 0, seed_fast = 0, seed_gen = 0;
     bool fast_ok = false;
     bool wide = false;      // the fast table holds nibble-packed keys (16 < K <= 32)
@@ -152,10 +158,10 @@ struct qd_ctx {
     std::vector<std::pair<hipStream_t, hipEvent_t>> tracked;
 
     // counters
-    qd_row_t* d_partial = nullptr;  // [partial_rows][cnt_stride] 32-bit rows the kernels flush into
-    u64* d_acc = nullptr;      // [cnt_stride] 64-bit totals: rows folded so far + demux_fixup's signed moves
-    u64* d_counts = nullptr;   // [cnt_stride + 4]: 2S+1 counters, then TOTAL at [cnt_stride] (reduce scratch)
-    u64* d_total = nullptr;    // all-reduce result, same shape
+    DevArr<qd_row_t> d_partial;  // [partial_rows][cnt_stride] 32-bit rows the kernels flush into
+    DevArr<u64> d_acc;         // [cnt_stride] 64-bit totals: rows folded so far + demux_fixup's signed moves
+    DevArr<u64> d_counts;      // [cnt_stride + 4]: 2S+1 counters, then TOTAL at [cnt_stride] (reduce scratch)
+    DevArr<u64> d_total;       // all-reduce result, same shape
     uint32_t partial_rows = 0, cnt_stride = 0;
     uint64_t total_pairs = 0;
     uint64_t pairs_in_rows = 0;             // pairs launched since the rows were last folded (bounds every row counter)
@@ -174,8 +180,8 @@ struct qd_ctx {
     // stream the list of a batch's undetermined pairs ([0] = count, the list from [4]; grown on demand)
     int32_t mm_m1 = 0, mm_m2 = 0;
     MismatchParams mm{};
-    QdMmBucket* d_mm_htab = nullptr;
-    uint16_t* d_mm_cand = nullptr;
+    DevArr<QdMmBucket> d_mm_htab;
+    DevArr<uint16_t> d_mm_cand;
     StreamScratch mm_list;  // pairs + 4 uint32 entries
 
     // tally of the unknown barcodes (qd_unknown_enable); per stream the scratch of a batch: 2 * pairs + 4 uint32 entries ([0] = count
@@ -218,7 +224,7 @@ struct qd_ctx {
     qd_screen_params screen{};
     qd_screen_dev screen_dev{};
     int64_t screen_kmers = 0;
-    u64* d_screen_slots = nullptr;
+    TrimArr<u64> d_screen_slots;
     // duplication tally: besides the parameters the key tally; per stream its scratch is the batch list, qd_dup_list_bytes(pairs)
     // bytes (quade_dup.h)
     qd_dup_params dup{};
@@ -229,7 +235,7 @@ struct qd_ctx {
     // part lookup tables in one allocation (slots of part 1, slots of part 2, then their key words), and per stream a list of
     // a batch's undetermined pairs (pairs + 4 uint32 entries) for the launches that neither rescue nor tally
     StageTable hop{"index-hopping matrix", nullptr, "the index-hopping matrix is not enabled", "n_values must be (n1+1)*(n2+1)+1", true};
-    void* d_hop_parts = nullptr;
+    TrimArr<uint8_t> d_hop_parts;
     HopPart hop_part[2]{};
     int32_t hop_n1 = 0, hop_n2 = 0;
     StreamScratch hop_list;
@@ -337,36 +343,11 @@ std::vector<uint32_t> build_slots(const std::vector<int>& ids, const std::vector
 }
 
 void free_table(qd_ctx* c) {
-    if (c->d_slots_fast) (void)hipFree(c->d_slots_fast);
-    if (c->d_slots_gen) (void)hipFree(c->d_slots_gen);
-    if (c->d_bk16) (void)hipFree(c->d_bk16);
-    if (c->d_bk32) (void)hipFree(c->d_bk32);
-    if (c->d_bkv) (void)hipFree(c->d_bkv);
-    c->d_bkv = nullptr;
-    if (c->d_blen) (void)hipFree(c->d_blen);
-    if (c->d_partial) (void)hipFree(c->d_partial);
-    if (c->d_acc) (void)hipFree(c->d_acc);
-    c->d_acc = nullptr;
-    if (c->d_counts) (void)hipFree(c->d_counts);
-    if (c->d_total) (void)hipFree(c->d_total);
-    c->d_total = nullptr;
-    c->d_slots_fast = c->d_slots_gen = nullptr;
-    c->d_bk16 = c->d_bk32 = nullptr;
-    c->d_blen = nullptr;
-    c->d_partial = nullptr;
-    c->d_counts = nullptr;
+    for (auto* b : {&c->d_slots_fast, &c->d_slots_gen}) b->release();
+    for (auto* b : {&c->d_bk16, &c->d_bk32, &c->d_bkv, &c->d_acc, &c->d_counts, &c->d_total}) b->release();
+    c->d_blen.release();
+    c->d_partial.release();
     c->have_table = false;
-}
-
-// hipMalloc; out of memory: the pool's idle buffers go back to the driver once (it can hold tens of GB) and the call is repeated
-hipError_t uk_malloc(void** p, size_t bytes) {
-    hipError_t e = hipMalloc(p, bytes);
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        (void)qd_pool_trim();
-        e = hipMalloc(p, bytes);
-    }
-    return e;
 }
 
 StreamScratch::Buf* StreamScratch::find(hipStream_t st) {
@@ -379,28 +360,22 @@ StreamScratch::Buf* StreamScratch::find(hipStream_t st) {
 StreamScratch::Buf* StreamScratch::need(qd_ctx* c, hipStream_t st, size_t units, size_t (*bytes_for)(size_t)) {
     Buf* b = find(st);
     if (!b) {
-        bufs.push_back(Buf{st, nullptr, 0});
+        bufs.emplace_back();
         b = &bufs.back();
+        b->stream = st;
+        b->units = 0;
     }
     if (b->buf && b->units >= units) return b;
     hipError_t e = hipStreamSynchronize(st);  // the old buffer may still be read by this stream's previous batch
     if (e == hipSuccess) {
-        if (b->buf) (void)hipFree(b->buf);
-        b->buf = nullptr;
-        const size_t grown = std::max(units, b->units * 2);
+        const size_t grown = qbuf::twice(units, b->units);
         b->units = 0;  // should the allocation fail, the next batch allocates again
-        e = uk_malloc(reinterpret_cast<void**>(&b->buf), bytes_for(grown));
+        e = b->buf.alloc(bytes_for(grown));
         if (e == hipSuccess) b->units = grown;
-        else b->buf = nullptr;
     }
     if (e == hipSuccess) return b;
     fail(c, QD_ERR_HIP, std::string("stream scratch: ") + hipGetErrorString(e));
     return nullptr;
-}
-
-void StreamScratch::release() {
-    for (auto& b : bufs) (void)hipFree(b.buf);
-    bufs.clear();
 }
 
 bool tally_slots_ok(int64_t slots) {  // a power of two in 2^10 .. 2^28
@@ -409,8 +384,7 @@ bool tally_slots_ok(int64_t slots) {  // a power of two in 2^10 .. 2^28
 
 // the tally off and its memory freed (the caller waited for the context's work)
 void tally_close(KeyTally& T) {
-    if (T.mem) (void)hipFree(T.mem);
-    T.mem = nullptr;
+    T.mem.release();
     T.slots = 0;
     T.recorded = false;
     T.scratch.release();
@@ -420,8 +394,7 @@ void tally_close(KeyTally& T) {
 
 // a closed tally on: a zeroed table of `slots` entries and its event; `what` names the table in the error text
 int tally_open(qd_ctx* c, KeyTally& T, int64_t slots, const char* what) {
-    hipError_t e = uk_malloc(&T.mem, qd_uk_bytes(slots));
-    if (e != hipSuccess) T.mem = nullptr;
+    hipError_t e = T.mem.alloc(qd_uk_bytes(slots));
     if (e == hipSuccess) e = hipMemsetAsync(T.mem, 0, qd_uk_bytes(slots), c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&T.done, hipEventDisableTiming);
@@ -473,10 +446,10 @@ int64_t tally_gather(qd_ctx* c, const KeyTally& T, const char* what, int64_t cap
     if (D > cap) return -D;
     if (D == 0) return 0;
     // the occupied entries packed on the device (uk_gather works on the table alone): only they cross the link
-    uint8_t* d_out = nullptr;
+    TrimArr<uint8_t> d_out;
     const size_t kbytes = (size_t)D * QD_KEY_WORDS * 8, cbytes = (size_t)D * 8;
-    if ((e = uk_malloc(reinterpret_cast<void**>(&d_out), kbytes + cbytes + 16)) != hipSuccess) return bad(hipGetErrorString(e));
-    u64* d_keys = reinterpret_cast<u64*>(d_out);
+    if ((e = d_out.alloc(kbytes + cbytes + 16)) != hipSuccess) return bad(hipGetErrorString(e));
+    u64* d_keys = reinterpret_cast<u64*>(d_out.p);
     u64* d_counts = reinterpret_cast<u64*>(d_out + kbytes);
     uint32_t* d_n = reinterpret_cast<uint32_t*>(d_out + kbytes + cbytes);
     hk.resize((size_t)D * QD_KEY_WORDS);
@@ -486,7 +459,6 @@ int64_t tally_gather(qd_ctx* c, const KeyTally& T, const char* what, int64_t cap
     if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, cbytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(&got, d_n, 4, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_out);
     if (e != hipSuccess) return bad(hipGetErrorString(e));
     if ((int64_t)got != D) return bad("the table's entry count and its occupied entries differ");
     return D;
@@ -494,10 +466,8 @@ int64_t tally_gather(qd_ctx* c, const KeyTally& T, const char* what, int64_t cap
 
 // budgets back to 0 and the rescue's tables freed (the caller waited for the context's work)
 void free_mismatch(qd_ctx* c, bool scratch) {
-    if (c->d_mm_htab) (void)hipFree(c->d_mm_htab);
-    if (c->d_mm_cand) (void)hipFree(c->d_mm_cand);
-    c->d_mm_htab = nullptr;
-    c->d_mm_cand = nullptr;
+    c->d_mm_htab.release();
+    c->d_mm_cand.release();
     c->mm_m1 = c->mm_m2 = 0;
     if (scratch) c->mm_list.release();
 }
@@ -506,7 +476,7 @@ void free_mismatch(qd_ctx* c, bool scratch) {
 int launch_mismatch(qd_ctx* c, int64_t n, const qd_rows* rows, uint16_t* codes, hipStream_t st) {
     StreamScratch::Buf* sc = c->mm_list.need(c, st, (size_t)n, [](size_t pairs) { return (pairs + 4) * 4; });
     if (!sc) return QD_ERR_HIP;
-    uint32_t* list = reinterpret_cast<uint32_t*>(sc->buf);
+    uint32_t* list = sc->buf.as<uint32_t>();
     MismatchParams p = c->mm;
     for (int k = 0; k < c->lay.n_streams; ++k) {
         p.seq[k] = rows->seq[k];
@@ -528,9 +498,8 @@ int launch_mismatch(qd_ctx* c, int64_t n, const qd_rows* rows, uint16_t* codes, 
 
 // T on: n_values 64-bit counters on the device, zero
 int table_alloc(qd_ctx* c, StageTable& T, size_t n_values) {
-    hipError_t e = uk_malloc(reinterpret_cast<void**>(&T.d), n_values * 8);
+    hipError_t e = T.d.alloc(n_values * 8);
     if (e != hipSuccess) {
-        T.d = nullptr;
         return fail(c, QD_ERR_HIP, std::string(T.what) + ": " + hipGetErrorString(e));
     }
     T.n_values = n_values;
@@ -541,8 +510,7 @@ int table_alloc(qd_ctx* c, StageTable& T, size_t n_values) {
 
 // (the caller waited for the context's work)
 void table_free(StageTable& T) {
-    if (T.d) (void)hipFree(T.d);
-    T.d = nullptr;
+    T.d.release();
     T.n_values = 0;
 }
 
@@ -585,8 +553,7 @@ void stage_off(qd_ctx* c, int id) {
         case ST_FILTER: c->filter = FILTER_OFF; c->filter_dev = filter_dev_of(FILTER_OFF); break;
         case ST_SCREEN:
             c->screen = {}; c->screen_dev = {};
-            if (c->d_screen_slots) (void)hipFree(c->d_screen_slots);
-            c->d_screen_slots = nullptr;
+            c->d_screen_slots.release();
             c->screen_kmers = 0;
             break;
         case ST_DUP:
@@ -685,23 +652,23 @@ public:
         // the texts start 3 bytes into their buffers: the kernels' aligned words must not depend on an aligned window (and reach up to
         // 15 bytes beyond a line: 32 bytes of slack)
         for (int r = 0; r < 2; ++r) {
-            HIPCHK(c, uk_malloc(&d_text[r].p, (size_t)len[r] + 32));
-            HIPCHK(c, uk_malloc(&d_recs[r].p, rec_bytes));
-            if (want & (OUT_RECS | SCRATCH_RECS)) HIPCHK(c, uk_malloc(&d_out[r].p, rec_bytes));
-            if (len[r]) HIPCHK(c, hipMemcpyAsync(static_cast<uint8_t*>(d_text[r].p) + 3, text[r], (size_t)len[r], hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, d_text[r].alloc((size_t)len[r] + 32));
+            HIPCHK(c, d_recs[r].alloc(rec_bytes));
+            if (want & (OUT_RECS | SCRATCH_RECS)) HIPCHK(c, d_out[r].alloc(rec_bytes));
+            if (len[r]) HIPCHK(c, hipMemcpyAsync(d_text[r].p + 3, text[r], (size_t)len[r], hipMemcpyHostToDevice, c->stream));
             HIPCHK(c, hipMemcpyAsync(d_recs[r].p, recs[r], rec_bytes, hipMemcpyHostToDevice, c->stream));
         }
         if (want & CODES) {
-            HIPCHK(c, uk_malloc(&d_codes.p, (size_t)n_pairs * 2));
+            HIPCHK(c, d_codes.alloc((size_t)n_pairs * 2));
             HIPCHK(c, hipMemcpyAsync(d_codes.p, codes, (size_t)n_pairs * 2, hipMemcpyHostToDevice, c->stream));
         }
         if (drop) {
-            HIPCHK(c, uk_malloc(&d_drop.p, (size_t)n_pairs));
+            HIPCHK(c, d_drop.alloc((size_t)n_pairs));
             HIPCHK(c, hipMemcpyAsync(d_drop.p, drop, (size_t)n_pairs, hipMemcpyHostToDevice, c->stream));
         }
-        if (want & REASONS) HIPCHK(c, uk_malloc(&d_reason.p, (size_t)n_pairs));
-        if (want & HITS) HIPCHK(c, uk_malloc(&d_hits.p, (size_t)n_pairs * 8));
-        if (want & INSERTS) HIPCHK(c, uk_malloc(&d_inserts.p, (size_t)n_pairs * 8));
+        if (want & REASONS) HIPCHK(c, d_reason.alloc((size_t)n_pairs));
+        if (want & HITS) HIPCHK(c, d_hits.alloc((size_t)n_pairs * 8));
+        if (want & INSERTS) HIPCHK(c, d_inserts.alloc((size_t)n_pairs * 8));
         if (want & TEXT_BACK) {
             text_len[0] = (size_t)len1;
             text_len[1] = (size_t)len2;
@@ -716,15 +683,15 @@ public:
     bool empty() const { return pairs == 0; }  // open() found no pairs: nothing was uploaded, there is nothing to launch
 
     uint32_t n() const { return (uint32_t)pairs; }
-    const uint8_t* text(int r) const { return static_cast<const uint8_t*>(d_text[r].p) + 3; }
-    const qd_rec* recs(int r) const { return static_cast<const qd_rec*>(d_recs[r].p); }
-    const uint16_t* codes() const { return static_cast<const uint16_t*>(d_codes.p); }
-    const uint8_t* drop() const { return static_cast<const uint8_t*>(d_drop.p); }  // nullptr when none was given
-    qd_rec* out(int r) const { return static_cast<qd_rec*>(d_out[r].p); }
-    uint8_t* reason() const { return static_cast<uint8_t*>(d_reason.p); }
-    uint32_t* hits() const { return static_cast<uint32_t*>(d_hits.p); }  // uint32[n][2]
-    uint64_t* inserts() const { return static_cast<uint64_t*>(d_inserts.p); }
-    uint8_t* mutable_text(int r) const { return static_cast<uint8_t*>(d_text[r].p) + 3; }  // for the stage that writes into the text
+    const uint8_t* text(int r) const { return d_text[r].p + 3; }
+    const qd_rec* recs(int r) const { return d_recs[r].as<const qd_rec>(); }
+    const uint16_t* codes() const { return d_codes.as<const uint16_t>(); }
+    const uint8_t* drop() const { return d_drop.as<const uint8_t>(); }  // nullptr when none was given
+    qd_rec* out(int r) const { return d_out[r].as<qd_rec>(); }
+    uint8_t* reason() const { return d_reason.as<uint8_t>(); }
+    uint32_t* hits() const { return d_hits.as<uint32_t>(); }  // uint32[n][2]
+    uint64_t* inserts() const { return d_inserts.as<uint64_t>(); }
+    uint8_t* mutable_text(int r) const { return d_text[r].p + 3; }  // for the stage that writes into the text
     void texts_back(uint8_t* out1, uint8_t* out2) {
         h_text[0] = out1;
         h_text[1] = out2;
@@ -745,15 +712,9 @@ public:
     }
 
 private:
-    struct Dev {
-        void* p = nullptr;
-        ~Dev() {
-            if (p) (void)hipFree(p);
-        }
-    };
     qd_ctx* c;
     int64_t pairs = 0;
-    Dev d_text[2], d_recs[2], d_codes, d_drop, d_out[2], d_reason, d_hits, d_inserts;
+    TrimArr<uint8_t> d_text[2], d_recs[2], d_codes, d_drop, d_out[2], d_reason, d_hits, d_inserts;
     uint32_t* h_out[2] = {nullptr, nullptr};
     uint8_t* h_text[2] = {nullptr, nullptr};
     size_t text_len[2] = {0, 0};
@@ -784,10 +745,10 @@ void free_unknown(qd_ctx* c) {
 int launch_unknown(qd_ctx* c, int64_t n, const qd_rows* rows, const uint16_t* codes, hipStream_t st, bool rescued) {
     StreamScratch::Buf* sc = c->uk.scratch.need(c, st, (size_t)n, [](size_t pairs) { return (2 * pairs + 4) * 4; });
     if (!sc) return QD_ERR_HIP;
-    uint32_t* const buf = reinterpret_cast<uint32_t*>(sc->buf);
+    uint32_t* const buf = sc->buf.as<uint32_t>();
     uint32_t* list = buf;
     if (rescued) {
-        if (const StreamScratch::Buf* m = c->mm_list.find(st)) list = reinterpret_cast<uint32_t*>(m->buf);
+        if (const StreamScratch::Buf* m = c->mm_list.find(st)) list = m->buf.as<uint32_t>();
     } else {
         hipError_t e = qd_launch_compact(codes, n, list, st);
         if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("unknown tally list: ") + hipGetErrorString(e));
@@ -853,8 +814,7 @@ size_t hop_values(const qd_ctx* c) { return (size_t)(c->hop_n1 + 1) * (size_t)(c
 // the matrix off and its memory freed (the caller waited for the context's work)
 void free_hop(qd_ctx* c) {
     table_free(c->hop);
-    if (c->d_hop_parts) (void)hipFree(c->d_hop_parts);
-    c->d_hop_parts = nullptr;
+    c->d_hop_parts.release();
     c->hop_n1 = c->hop_n2 = 0;
     c->hop_list.release();
 }
@@ -863,11 +823,11 @@ void free_hop(qd_ctx* c) {
 // (`rescued`), else the tally's (`tallied`: launch_unknown has listed the batch on this stream), else a compaction of its own
 int launch_hop(qd_ctx* c, int64_t n, const qd_rows* rows, const uint16_t* codes, hipStream_t st, bool rescued, bool tallied) {
     const StreamScratch::Buf* have = rescued ? c->mm_list.find(st) : (tallied ? c->uk.scratch.find(st) : nullptr);
-    const uint32_t* list = have ? reinterpret_cast<const uint32_t*>(have->buf) : nullptr;
+    const uint32_t* list = have ? have->buf.as<const uint32_t>() : nullptr;
     if (!list) {
         StreamScratch::Buf* sc = c->hop_list.need(c, st, (size_t)n, [](size_t pairs) { return (pairs + 4) * 4; });
         if (!sc) return QD_ERR_HIP;
-        uint32_t* own = reinterpret_cast<uint32_t*>(sc->buf);
+        uint32_t* own = sc->buf.as<uint32_t>();
         hipError_t e = qd_launch_compact(codes, n, own, st);
         if (e != hipSuccess) return fail(c, QD_ERR_HIP, std::string("index-hopping list: ") + hipGetErrorString(e));
         list = own;
@@ -971,12 +931,12 @@ int rebuild(qd_ctx* c) {
                                     : build_slots(ids_fast, k32, blen, c->mask_fast, c->seed_fast, nullptr, 0, slot_factor);
     std::vector<uint32_t> sg = build_slots(ids_gen, k32, blen, c->mask_gen, c->seed_gen);
 
-    HIPCHK(c, hipMalloc(&c->d_slots_fast, sf.size() * 4));
-    HIPCHK(c, hipMalloc(&c->d_slots_gen, sg.size() * 4));
-    HIPCHK(c, hipMalloc(&c->d_bk16, k16.size() * 8));
-    HIPCHK(c, hipMalloc(&c->d_bk32, k32.size() * 8));
-    HIPCHK(c, hipMalloc(&c->d_blen, blen.size()));
-    HIPCHK(c, hipMalloc(&c->d_bkv, kv.size() * 8));
+    HIPCHK(c, c->d_slots_fast.alloc(sf.size() * 4));
+    HIPCHK(c, c->d_slots_gen.alloc(sg.size() * 4));
+    HIPCHK(c, c->d_bk16.alloc(k16.size() * 8));
+    HIPCHK(c, c->d_bk32.alloc(k32.size() * 8));
+    HIPCHK(c, c->d_blen.alloc(blen.size()));
+    HIPCHK(c, c->d_bkv.alloc(kv.size() * 8));
     HIPCHK(c, hipMemcpy(c->d_bkv, kv.data(), kv.size() * 8, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->d_slots_fast, sf.data(), sf.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->d_slots_gen, sg.data(), sg.size() * 4, hipMemcpyHostToDevice));
@@ -1027,10 +987,10 @@ int rebuild(qd_ctx* c) {
     c->cnt_stride = (uint32_t)((2 * S + 1 + 3) & ~3);
     // one counter row per workgroup (modulo), capped at 64 MiB of rows for very large tables
     c->partial_rows = (uint32_t)std::max<size_t>(8, std::min<size_t>((size_t)c->cu * 8, ((size_t)64 << 20) / ((size_t)c->cnt_stride * sizeof(qd_row_t))));
-    HIPCHK(c, hipMalloc(&c->d_partial, (size_t)c->partial_rows * c->cnt_stride * sizeof(qd_row_t)));
-    HIPCHK(c, hipMalloc(&c->d_acc, (size_t)c->cnt_stride * 8));
-    HIPCHK(c, hipMalloc(&c->d_counts, ((size_t)c->cnt_stride + 4) * 8));
-    HIPCHK(c, hipMalloc(&c->d_total, ((size_t)c->cnt_stride + 4) * 8));
+    HIPCHK(c, c->d_partial.alloc((size_t)c->partial_rows * c->cnt_stride * sizeof(qd_row_t)));
+    HIPCHK(c, c->d_acc.alloc((size_t)c->cnt_stride * 8));
+    HIPCHK(c, c->d_counts.alloc(((size_t)c->cnt_stride + 4) * 8));
+    HIPCHK(c, c->d_total.alloc(((size_t)c->cnt_stride + 4) * 8));
     HIPCHK(c, hipMemset(c->d_partial, 0, (size_t)c->partial_rows * c->cnt_stride * sizeof(qd_row_t)));
     HIPCHK(c, hipMemset(c->d_acc, 0, (size_t)c->cnt_stride * 8));
     c->total_pairs = 0;
@@ -1259,11 +1219,8 @@ int qd_destroy(qd_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)wait_all(c);
     qd_slots_destroy(c);
-    free_table(c);
-    free_mismatch(c, true);
-    free_unknown(c);
-    free_hop(c);
-    stages_off(c, false);
+    tally_close(c->uk);  // (their events; every table and scratch buffer goes back with `delete c`, the device being current)
+    tally_close(c->dup_keys);
     for (auto& t : c->tracked) (void)hipEventDestroy(t.second);
     c->tracked.clear();
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1376,8 +1333,8 @@ int qd_set_mismatches(qd_ctx* c, int32_t m1, int32_t m2) {
     p.thr = (uint32_t)(P.min_qual + 33);
     p.n_samples = (uint32_t)c->S;
     p.hist_entries = 2 * c->S <= 16000 ? (uint32_t)(2 * c->S) : 0;  // <= 64 KB of LDS, else global 64-bit adds per pair
-    HIPCHK(c, hipMalloc(&c->d_mm_htab, htab.size() * sizeof(QdMmBucket)));
-    HIPCHK(c, hipMalloc(&c->d_mm_cand, cand.size() * sizeof(uint16_t)));
+    HIPCHK(c, c->d_mm_htab.alloc(htab.size() * sizeof(QdMmBucket)));
+    HIPCHK(c, c->d_mm_cand.alloc(cand.size() * sizeof(uint16_t)));
     HIPCHK(c, hipMemcpy(c->d_mm_htab, htab.data(), htab.size() * sizeof(QdMmBucket), hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->d_mm_cand, cand.data(), cand.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     c->mm_m1 = m1;
@@ -1456,12 +1413,11 @@ int qd_hop_enable(qd_ctx* c, int32_t on) {
     }
     const size_t sb[2] = {slots[0].size() * sizeof(HopSlot), slots[1].size() * sizeof(HopSlot)};
     const size_t kb[2] = {key[0].size() * 8, key[1].size() * 8};
-    hipError_t e = uk_malloc(&c->d_hop_parts, sb[0] + sb[1] + kb[0] + kb[1]);
+    hipError_t e = c->d_hop_parts.alloc(sb[0] + sb[1] + kb[0] + kb[1]);
     if (e != hipSuccess) {
-        c->d_hop_parts = nullptr;
         return fail(c, QD_ERR_HIP, std::string("index-hopping part tables: ") + hipGetErrorString(e));
     }
-    uint8_t* base = static_cast<uint8_t*>(c->d_hop_parts);
+    uint8_t* base = c->d_hop_parts;
     const size_t so[2] = {0, sb[0]}, ko[2] = {sb[0] + sb[1], sb[0] + sb[1] + kb[0]};
     for (int h = 0; h < 2 && e == hipSuccess; ++h) {
         c->hop_part[h].slots = reinterpret_cast<const HopSlot*>(base + so[h]);
@@ -2069,9 +2025,8 @@ int qd_screen_set(qd_ctx* c, const qd_screen_params* params, const uint64_t* kme
     }
     const int rc = stage_install(c, ST_SCREEN, on, qd_screen_values((uint32_t)c->S));
     if (rc != QD_OK || !on) return rc;
-    hipError_t e = uk_malloc(reinterpret_cast<void**>(&c->d_screen_slots), slots.size() * 8);
+    hipError_t e = c->d_screen_slots.alloc(slots.size() * 8);
     if (e != hipSuccess) {
-        c->d_screen_slots = nullptr;
         stage_off(c, ST_SCREEN);
         return fail(c, QD_ERR_HIP, std::string("screen hash table: ") + hipGetErrorString(e));
     }
@@ -2203,7 +2158,7 @@ int qd_dup_device(qd_ctx* c, const uint8_t* text1, const qd_rec* recs1, const ui
         a.codes = codes;
         a.drop = drop;
         a.table = table;
-        a.list_n = reinterpret_cast<uint32_t*>(sc->buf);
+        a.list_n = sc->buf.as<uint32_t>();
         a.list = reinterpret_cast<uint64_t*>(sc->buf + QD_DUP_LIST_HEAD);
         a.where = reinterpret_cast<uint32_t*>(sc->buf + QD_DUP_LIST_HEAD + sc->units * QD_DUP_KEY_WORDS * 8);
         a.t = tally_view(c->dup_keys);
@@ -2429,12 +2384,12 @@ int qd_slots_create(qd_ctx* c, int32_t n_slots, int64_t max_pairs) {
     for (auto& s : c->slots) {
         HIPCHK(c, hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
         HIPCHK(c, hipEventCreateWithFlags(&s.uploaded, hipEventDisableTiming));
-        HIPCHK(c, hipHostMalloc((void**)&s.h_base, bytes, hipHostMallocDefault));
-        HIPCHK(c, hipMalloc((void**)&s.d_base, bytes));
+        HIPCHK(c, s.h_base.alloc(bytes));
+        HIPCHK(c, s.d_base.alloc(bytes));
         carve(s.h, s.h_base, c->lay, max_pairs);
         carve(s.d, s.d_base, c->lay, max_pairs);
-        HIPCHK(c, hipHostMalloc((void**)&s.h_short, (size_t)s.h.short_cap * 12, hipHostMallocDefault));
-        HIPCHK(c, hipMalloc((void**)&s.d_short, (size_t)s.h.short_cap * 12));
+        HIPCHK(c, s.h_short.alloc((size_t)s.h.short_cap * 12));
+        HIPCHK(c, s.d_short.alloc((size_t)s.h.short_cap * 12));
     }
     return QD_OK;
 }
@@ -2449,12 +2404,8 @@ int qd_slots_destroy(qd_ctx* c) {
             (void)hipStreamDestroy(s.stream);
         }
         if (s.uploaded) (void)hipEventDestroy(s.uploaded);
-        if (s.h_base) (void)hipHostFree(s.h_base);
-        if (s.d_base) (void)hipFree(s.d_base);
-        if (s.h_short) (void)hipHostFree(s.h_short);
-        if (s.d_short) (void)hipFree(s.d_short);
     }
-    c->slots.clear();
+    c->slots.clear();  // (their buffers go back here)
     if (c->up_stream) {
         (void)hipStreamSynchronize(c->up_stream);
         (void)hipStreamDestroy(c->up_stream);
@@ -2722,25 +2673,21 @@ int qd_comm_destroy(qd_comm* cm) {
 // ---- BGZF inflate on the device (include/quade_hip.h; kernel: quade_inflate.hip) ------------------------------
 uint32_t qd_io_crc32(const uint8_t* p, size_t n);  // quade_io.cpp: libdeflate's when loaded, else zlib's
 
-struct qd_inflater {
+struct __attribute__((visibility("hidden"))) qd_inflater {  // (hidden: its destructor is no symbol of the library)
     int device = -1;
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;  // blocking-sync event: the calling thread sleeps while the device works
     std::string err;
     // grow-only staging: pinned host + device, for the compressed run, its text, the block table and the states
-    uint8_t *h_comp = nullptr, *d_comp = nullptr, *h_out = nullptr, *d_out = nullptr;
-    size_t cap_comp = 0, cap_out = 0;
-    qd_inflate_block *h_blk = nullptr, *d_blk = nullptr;
-    int32_t *h_st = nullptr, *d_st = nullptr;
-    size_t cap_blk = 0, cap_st = 0;
+    qbuf::Pair<uint8_t> comp, out;
+    qbuf::Pair<qd_inflate_block> blk;
+    qbuf::Pair<int32_t> st;
     std::vector<uint32_t> crc;
     // which kernel: 2 (the default) = 512 lanes per block, 1 = one wave per block (QUADE_INFLATE_FORM / qd_inflater_set_form); the second form's match lists
     int form = 3;
-    unsigned long long* d_matches = nullptr;
-    size_t cap_matches = 0;  // blocks the scratch holds
+    DevArr<unsigned long long> d_matches;  // QD_INFLATE_MATCHES_PER_BLOCK per block
     // the third form (3: one lane decodes a block's symbols once, a workgroup resolves its tokens -- quade_inflate3.hip): its scratch
-    void* d_scratch3 = nullptr;
-    size_t cap_scratch3 = 0;  // bytes
+    DevArr<uint8_t> d_scratch3;
 };
 
 namespace {
@@ -2754,67 +2701,39 @@ int inf_fail(qd_inflater* f, int code, const std::string& msg) {
         if (e_ != hipSuccess) return inf_fail((f), QD_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+// the stand-alone coders' staging pairs grow to n + n/4 + 4096 elements
 template <class T>
-hipError_t grow_pair(T*& h, T*& d, size_t& cap, size_t need) {
-    if (need <= cap) return hipSuccess;
-    if (h) (void)hipHostFree(h);
-    if (d) (void)hipFree(d);
-    h = nullptr;
-    d = nullptr;
-    cap = 0;
-    const size_t n = need + need / 4 + 4096;
-    hipError_t e = hipHostMalloc((void**)&h, n * sizeof(T), hipHostMallocDefault);
-    if (e != hipSuccess) return e;
-    e = hipMalloc((void**)&d, n * sizeof(T));
-    if (e != hipSuccess) return e;
-    cap = n;
-    return hipSuccess;
+hipError_t need_pair(qbuf::Pair<T>& b, size_t n) {
+    return b.need(n, qbuf::quarter(n, 4096));
 }
 thread_local std::string g_inflater_error;
 
-// Waits for an event without holding a core: hipEventSynchronize spins on this runtime even for events made with
-// hipEventBlockingSync (measured: the reader's device lanes burnt 0.95 core-seconds per M pairs waiting for their kernels,
-// profiles/r03_e2e_16m_level1_stages_device_inflate.txt).  A few immediate polls (short kernels), then naps of 100 us.
+// quade_buf.h's wait with naps of 100 us
 hipError_t wait_event_napping(hipEvent_t ev) {
     static const int nap_us = [] {
         const char* e = getenv("QUADE_NAP_US");  // measurement knob
         const int v = e && *e ? atoi(e) : 100;
         return v < 10 ? 10 : (v > 5000 ? 5000 : v);
     }();
-    for (int i = 0; i < 64; ++i) {
-        const hipError_t e = hipEventQuery(ev);
-        if (e != hipErrorNotReady) return e;
-    }
-    for (;;) {
-        const hipError_t e = hipEventQuery(ev);
-        if (e != hipErrorNotReady) return e;
-        usleep(nap_us);
-    }
+    return qbuf::wait_event_napping(ev, (unsigned)nap_us);
 }
-// The first n blocks of f->d_blk (states to f->d_st) through the speculative spans (form 2) when that form is allowed and the longest
+// The first n blocks of f->blk.d (states to f->st.d) through the speculative spans (form 2) when that form is allowed and the longest
 // payload leaves its workgroup room in 160 KB of LDS -- beyond ~52 KB, stored blocks, it does not -- else a wave per block (form 1).
 int inflate_spans_or_wave(qd_inflater* f, uint32_t n, uint32_t longest, bool spans_allowed) {
     if (!spans_allowed || qd_inflate2_lds(longest) > 160 * 1024) {
-        INFCHK(f, qd_launch_inflate(f->d_comp, f->d_blk, n, f->d_out, f->d_st, f->stream));
+        INFCHK(f, qd_launch_inflate(f->comp.d, f->blk.d, n, f->out.d, f->st.d, f->stream));
         return QD_OK;
     }
-    if (n > f->cap_matches) {
-        if (f->d_matches) (void)hipFree(f->d_matches);
-        f->d_matches = nullptr;
-        f->cap_matches = 0;
-        const size_t nb = (size_t)n + n / 4 + 16;
-        INFCHK(f, hipMalloc((void**)&f->d_matches, nb * (size_t)QD_INFLATE_MATCHES_PER_BLOCK * 8));
-        f->cap_matches = nb;
-    }
+    const size_t per_block = (size_t)QD_INFLATE_MATCHES_PER_BLOCK * 8;
+    INFCHK(f, f->d_matches.need(n * per_block, qbuf::quarter(n, 16) * per_block));
     static const bool debug_rounds = getenv("QUADE_INFLATE_DEBUG") != nullptr;  // measurement: rounds per block on stderr
-    uint32_t* d_rounds = nullptr;
-    if (debug_rounds) INFCHK(f, hipMalloc((void**)&d_rounds, (size_t)n * 32));
-    INFCHK(f, qd_launch_inflate2(f->d_comp, f->d_blk, n, f->d_out, f->d_st, f->d_matches, QD_INFLATE_MATCHES_PER_BLOCK, longest,
+    DevArr<uint32_t> d_rounds;
+    if (debug_rounds) INFCHK(f, d_rounds.alloc((size_t)n * 32));
+    INFCHK(f, qd_launch_inflate2(f->comp.d, f->blk.d, n, f->out.d, f->st.d, f->d_matches, QD_INFLATE_MATCHES_PER_BLOCK, longest,
                                  f->stream, d_rounds));
     if (debug_rounds) {
         std::vector<uint32_t> r((size_t)n * 8);
         INFCHK(f, hipMemcpy(r.data(), d_rounds, (size_t)n * 32, hipMemcpyDeviceToHost));
-        (void)hipFree(d_rounds);
         uint64_t sum = 0, db = 0, tk[8] = {0};
         uint32_t mx = 0, over8 = 0;
         for (size_t q = 0; q < n; ++q) {
@@ -2866,16 +2785,6 @@ int qd_inflater_destroy(qd_inflater* f) {
         (void)hipStreamDestroy(f->stream);
     }
     if (f->done) (void)hipEventDestroy(f->done);
-    if (f->h_comp) (void)hipHostFree(f->h_comp);
-    if (f->d_comp) (void)hipFree(f->d_comp);
-    if (f->h_out) (void)hipHostFree(f->h_out);
-    if (f->d_out) (void)hipFree(f->d_out);
-    if (f->h_blk) (void)hipHostFree(f->h_blk);
-    if (f->d_blk) (void)hipFree(f->d_blk);
-    if (f->h_st) (void)hipHostFree(f->h_st);
-    if (f->d_st) (void)hipFree(f->d_st);
-    if (f->d_matches) (void)hipFree(f->d_matches);
-    if (f->d_scratch3) (void)hipFree(f->d_scratch3);
     delete f;
     return QD_OK;
 }
@@ -2927,34 +2836,28 @@ static int inflater_run(qd_inflater* f, const uint8_t* comp, int64_t comp_len, u
     if (blk.empty()) return QD_OK;
     // 2. stage, inflate one block per lane, fetch
     INFCHK(f, hipSetDevice(f->device));
-    INFCHK(f, grow_pair(f->h_comp, f->d_comp, f->cap_comp, (size_t)comp_len));
-    INFCHK(f, grow_pair(f->h_out, f->d_out, f->cap_out, (size_t)out_len + 16));
-    uint8_t* const text = out_pinned ? out : f->h_out;  // where the D2H copy lands
-    INFCHK(f, grow_pair(f->h_blk, f->d_blk, f->cap_blk, blk.size()));
-    INFCHK(f, grow_pair(f->h_st, f->d_st, f->cap_st, blk.size()));
-    memcpy(f->h_comp, comp, (size_t)comp_len);
-    memcpy(f->h_blk, blk.data(), blk.size() * sizeof(qd_inflate_block));
-    INFCHK(f, hipMemcpyAsync(f->d_comp, f->h_comp, (size_t)comp_len, hipMemcpyHostToDevice, f->stream));
-    INFCHK(f, hipMemcpyAsync(f->d_blk, f->h_blk, blk.size() * sizeof(qd_inflate_block), hipMemcpyHostToDevice, f->stream));
+    INFCHK(f, need_pair(f->comp, (size_t)comp_len));
+    INFCHK(f, need_pair(f->out, (size_t)out_len + 16));
+    uint8_t* const text = out_pinned ? out : f->out.h;  // where the D2H copy lands
+    INFCHK(f, need_pair(f->blk, blk.size()));
+    INFCHK(f, need_pair(f->st, blk.size()));
+    memcpy(f->comp.h, comp, (size_t)comp_len);
+    memcpy(f->blk.h, blk.data(), blk.size() * sizeof(qd_inflate_block));
+    INFCHK(f, hipMemcpyAsync(f->comp.d, f->comp.h, (size_t)comp_len, hipMemcpyHostToDevice, f->stream));
+    INFCHK(f, hipMemcpyAsync(f->blk.d, f->blk.h, blk.size() * sizeof(qd_inflate_block), hipMemcpyHostToDevice, f->stream));
     uint32_t longest = 0;
     for (const qd_inflate_block& bk : blk) longest = std::max(longest, bk.in_len);
     bool form3_ran = false;
     if (f->form == 3) {
         const size_t need = qd_inflate3_scratch_bytes((uint32_t)blk.size());
-        if (need > f->cap_scratch3) {
-            if (f->d_scratch3) (void)hipFree(f->d_scratch3);
-            f->d_scratch3 = nullptr;
-            f->cap_scratch3 = 0;
-            INFCHK(f, hipMalloc(&f->d_scratch3, need + need / 4));
-            f->cap_scratch3 = need + need / 4;
-        }
-        INFCHK(f, qd_launch_inflate3(f->d_comp, (size_t)comp_len, f->d_blk, (uint32_t)blk.size(), f->d_out, f->d_st, f->d_scratch3, f->stream));
+        INFCHK(f, f->d_scratch3.need(need, qbuf::quarter(need, 0)));
+        INFCHK(f, qd_launch_inflate3(f->comp.d, (size_t)comp_len, f->blk.d, (uint32_t)blk.size(), f->out.d, f->st.d, f->d_scratch3, f->stream));
         form3_ran = true;
     } else {
         const int rc = inflate_spans_or_wave(f, (uint32_t)blk.size(), longest, f->form == 2);
         if (rc != QD_OK) return rc;
     }
-    INFCHK(f, hipMemcpyAsync(f->h_st, f->d_st, blk.size() * 4, hipMemcpyDeviceToHost, f->stream));
+    INFCHK(f, hipMemcpyAsync(f->st.h, f->st.d, blk.size() * 4, hipMemcpyDeviceToHost, f->stream));
     if (form3_ran) {
         // blocks whose Huffman codes hold more long symbols than a lane's table takes (byte soup, not fastq) go through the second
         // form -- or the first, when their payload leaves no room for it: a second launch over just those blocks
@@ -2964,24 +2867,24 @@ static int inflater_run(qd_inflater* f, const uint8_t* comp, int64_t comp_len, u
         std::vector<size_t> redo_at;
         uint32_t redo_longest = 0;
         for (size_t i = 0; i < blk.size(); ++i)
-            if (f->h_st[i] == QD_INFLATE_TABLE_SPACE) {
+            if (f->st.h[i] == QD_INFLATE_TABLE_SPACE) {
                 redo.push_back(blk[i]);
                 redo_at.push_back(i);
                 redo_longest = std::max(redo_longest, blk[i].in_len);
             }
         if (!redo.empty()) {
             // (the first launch is done with the block table and has handed its states over: the redo's go through the same buffers)
-            memcpy(f->h_blk, redo.data(), redo.size() * sizeof(qd_inflate_block));
-            INFCHK(f, hipMemcpyAsync(f->d_blk, f->h_blk, redo.size() * sizeof(qd_inflate_block), hipMemcpyHostToDevice, f->stream));
+            memcpy(f->blk.h, redo.data(), redo.size() * sizeof(qd_inflate_block));
+            INFCHK(f, hipMemcpyAsync(f->blk.d, f->blk.h, redo.size() * sizeof(qd_inflate_block), hipMemcpyHostToDevice, f->stream));
             const int rc = inflate_spans_or_wave(f, (uint32_t)redo.size(), redo_longest, true);
             if (rc != QD_OK) return rc;
             std::vector<int32_t> rst(redo.size());
-            INFCHK(f, hipMemcpyAsync(rst.data(), f->d_st, redo.size() * 4, hipMemcpyDeviceToHost, f->stream));
+            INFCHK(f, hipMemcpyAsync(rst.data(), f->st.d, redo.size() * 4, hipMemcpyDeviceToHost, f->stream));
             INFCHK(f, hipStreamSynchronize(f->stream));
-            for (size_t k = 0; k < redo.size(); ++k) f->h_st[redo_at[k]] = rst[k];
+            for (size_t k = 0; k < redo.size(); ++k) f->st.h[redo_at[k]] = rst[k];
         }
     }
-    if (out_len) INFCHK(f, hipMemcpyAsync(text, f->d_out, (size_t)out_len, hipMemcpyDeviceToHost, f->stream));
+    if (out_len) INFCHK(f, hipMemcpyAsync(text, f->out.d, (size_t)out_len, hipMemcpyDeviceToHost, f->stream));
     INFCHK(f, hipEventRecord(f->done, f->stream));
     INFCHK(f, wait_event_napping(f->done));
     if (f->form != 1) {
@@ -2991,64 +2894,61 @@ static int inflater_run(qd_inflater* f, const uint8_t* comp, int64_t comp_len, u
         std::vector<qd_inflate_block> redo;
         std::vector<size_t> redo_at;
         for (size_t i = 0; i < blk.size(); ++i)
-            if (f->h_st[i] == QD_INFLATE_OVERRUN) {
+            if (f->st.h[i] == QD_INFLATE_OVERRUN) {
                 redo.push_back(blk[i]);
                 redo_at.push_back(i);
             }
         if (!redo.empty()) {
-            memcpy(f->h_blk, redo.data(), redo.size() * sizeof(qd_inflate_block));
-            INFCHK(f, hipMemcpyAsync(f->d_blk, f->h_blk, redo.size() * sizeof(qd_inflate_block), hipMemcpyHostToDevice, f->stream));
-            INFCHK(f, qd_launch_inflate(f->d_comp, f->d_blk, (uint32_t)redo.size(), f->d_out, f->d_st, f->stream));
+            memcpy(f->blk.h, redo.data(), redo.size() * sizeof(qd_inflate_block));
+            INFCHK(f, hipMemcpyAsync(f->blk.d, f->blk.h, redo.size() * sizeof(qd_inflate_block), hipMemcpyHostToDevice, f->stream));
+            INFCHK(f, qd_launch_inflate(f->comp.d, f->blk.d, (uint32_t)redo.size(), f->out.d, f->st.d, f->stream));
             std::vector<int32_t> rst(redo.size());
-            INFCHK(f, hipMemcpyAsync(rst.data(), f->d_st, redo.size() * 4, hipMemcpyDeviceToHost, f->stream));
+            INFCHK(f, hipMemcpyAsync(rst.data(), f->st.d, redo.size() * 4, hipMemcpyDeviceToHost, f->stream));
             for (const qd_inflate_block& b : redo)
-                if (b.out_len) INFCHK(f, hipMemcpyAsync(text + b.out_off, f->d_out + b.out_off, b.out_len, hipMemcpyDeviceToHost, f->stream));
+                if (b.out_len) INFCHK(f, hipMemcpyAsync(text + b.out_off, f->out.d + b.out_off, b.out_len, hipMemcpyDeviceToHost, f->stream));
             INFCHK(f, hipStreamSynchronize(f->stream));
-            for (size_t k = 0; k < redo.size(); ++k) f->h_st[redo_at[k]] = rst[k];
+            for (size_t k = 0; k < redo.size(); ++k) f->st.h[redo_at[k]] = rst[k];
         }
     }
     // 3. every block: decoder status, then the CRC32 of its text
     for (size_t i = 0; i < blk.size(); ++i) {
-        if (f->h_st[i] != 0 || qd_io_crc32(text + blk[i].out_off, blk[i].out_len) != f->crc[i]) {
+        if (f->st.h[i] != 0 || qd_io_crc32(text + blk[i].out_off, blk[i].out_len) != f->crc[i]) {
             if (bad_block) *bad_block = (int32_t)i;
             char m[128];
-            if (f->h_st[i])
-                snprintf(m, sizeof m, "BGZF block %zu: did not inflate (decoder status %d)", i, (int)f->h_st[i]);
+            if (f->st.h[i])
+                snprintf(m, sizeof m, "BGZF block %zu: did not inflate (decoder status %d)", i, (int)f->st.h[i]);
             else
                 snprintf(m, sizeof m, "BGZF block %zu: CRC32 mismatch", i);
             return inf_fail(f, QD_ERR_FORMAT, m);
         }
     }
-    if (!out_pinned) memcpy(out, f->h_out, (size_t)out_len);
+    if (!out_pinned) memcpy(out, f->out.h, (size_t)out_len);
     return QD_OK;
 }
 
 }  // extern "C"
 
 // ---- Huffman-only gzip members on the device (include/quade_hip.h; kernel: quade_deflate.hip) -------------------------
-struct qd_deflater {
+struct __attribute__((visibility("hidden"))) qd_deflater {
     int device = -1;
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
     std::string err;
     // grow-only staging: pinned host + device, for the text, the members, the piece table and the member lengths
-    uint8_t *h_text = nullptr, *d_text = nullptr, *h_out = nullptr, *d_out = nullptr;
-    size_t cap_text = 0, cap_out = 0;
-    qd_deflate_piece *h_pc = nullptr, *d_pc = nullptr;
-    uint32_t *h_len = nullptr, *d_len = nullptr;
-    size_t cap_pc = 0, cap_len = 0;
+    PinArr<uint8_t> h_text;  // (only for pageable callers, and then as large as d_text)
+    DevArr<uint8_t> d_text;
+    qbuf::Pair<uint8_t> out;
+    qbuf::Pair<qd_deflate_piece> pc;
+    qbuf::Pair<uint32_t> len;
     // level 1 (LZ77 + dynamic Huffman, quade_deflate.hip): sub-block table, piece -> first sub-block, device scratch
     int level = -1;
-    qd_lz_sub *h_sub = nullptr, *d_sub = nullptr;
-    uint32_t *h_first = nullptr, *d_first = nullptr;
-    size_t cap_sub = 0, cap_first = 0;
-    uint32_t *d_tokens = nullptr, *d_sub_bytes = nullptr;
-    uint8_t* d_sub_out = nullptr;
-    size_t cap_scratch = 0;  // sub-blocks the scratch arrays hold
+    qbuf::Pair<qd_lz_sub> sub;
+    qbuf::Pair<uint32_t> first;
+    DevArr<uint32_t> d_tokens, d_sub_bytes;  // these and the next two hold the same number of sub-blocks
+    DevArr<uint8_t> d_sub_out;
     // crc32 == NULL at level 1: the sub-blocks' CRC-32s out of the coder, their lengths for the combine
-    uint32_t* d_sub_crc = nullptr;
-    qd_crc_range *h_rg = nullptr, *d_rg = nullptr;
-    size_t cap_rg = 0;
+    DevArr<uint32_t> d_sub_crc;
+    qbuf::Pair<qd_crc_range> rg;
 };
 
 namespace {
@@ -3107,24 +3007,6 @@ int qd_deflater_destroy(qd_deflater* f) {
         (void)hipStreamDestroy(f->stream);
     }
     if (f->done) (void)hipEventDestroy(f->done);
-    if (f->h_text) (void)hipHostFree(f->h_text);
-    if (f->d_text) (void)hipFree(f->d_text);
-    if (f->h_out) (void)hipHostFree(f->h_out);
-    if (f->d_out) (void)hipFree(f->d_out);
-    if (f->h_pc) (void)hipHostFree(f->h_pc);
-    if (f->d_pc) (void)hipFree(f->d_pc);
-    if (f->h_len) (void)hipHostFree(f->h_len);
-    if (f->d_len) (void)hipFree(f->d_len);
-    if (f->h_sub) (void)hipHostFree(f->h_sub);
-    if (f->d_sub) (void)hipFree(f->d_sub);
-    if (f->h_first) (void)hipHostFree(f->h_first);
-    if (f->d_first) (void)hipFree(f->d_first);
-    if (f->d_tokens) (void)hipFree(f->d_tokens);
-    if (f->d_sub_bytes) (void)hipFree(f->d_sub_bytes);
-    if (f->d_sub_out) (void)hipFree(f->d_sub_out);
-    if (f->d_sub_crc) (void)hipFree(f->d_sub_crc);
-    if (f->h_rg) (void)hipHostFree(f->h_rg);
-    if (f->d_rg) (void)hipFree(f->d_rg);
     delete f;
     return QD_OK;
 }
@@ -3147,22 +3029,16 @@ int qd_deflater_run(qd_deflater* f, int32_t n_pieces, const uint8_t* const* text
         total += ((size_t)text_len[i] + 15) & ~(size_t)15;
     }
     DEFCHK(f, hipSetDevice(f->device));
-    DEFCHK(f, grow_pair(f->h_pc, f->d_pc, f->cap_pc, (size_t)n_pieces));
-    DEFCHK(f, grow_pair(f->h_len, f->d_len, f->cap_len, (size_t)n_pieces));
-    DEFCHK(f, grow_pair(f->h_out, f->d_out, f->cap_out, (size_t)n_pieces * (size_t)out_stride));
-    if (total + 16 > f->cap_text) {  // device text always; the pinned staging copy only for pageable callers
-        if (f->h_text) (void)hipHostFree(f->h_text);
-        if (f->d_text) (void)hipFree(f->d_text);
-        f->h_text = f->d_text = nullptr;
-        f->cap_text = 0;
-        const size_t n = total + total / 4 + 4096;
-        DEFCHK(f, hipMalloc((void**)&f->d_text, n));
-        f->cap_text = n;
-    }
-    if (!text_pinned && !f->h_text) DEFCHK(f, hipHostMalloc((void**)&f->h_text, f->cap_text, hipHostMallocDefault));
+    DEFCHK(f, need_pair(f->pc, (size_t)n_pieces));
+    DEFCHK(f, need_pair(f->len, (size_t)n_pieces));
+    DEFCHK(f, need_pair(f->out, (size_t)n_pieces * (size_t)out_stride));
+    // device text always; the pinned staging copy only for pageable callers, and as large as the device text
+    if (total + 16 > f->d_text.cap) f->h_text.release();
+    DEFCHK(f, f->d_text.need(total + 16, qbuf::quarter(total, 4096)));
+    if (!text_pinned && !f->h_text) DEFCHK(f, f->h_text.alloc(f->d_text.cap));
     size_t at = 0;
     for (int i = 0; i < n_pieces; ++i) {
-        f->h_pc[i] = qd_deflate_piece{(uint64_t)at, (uint32_t)text_len[i], crc32 ? crc32[i] : 0u};
+        f->pc.h[i] = qd_deflate_piece{(uint64_t)at, (uint32_t)text_len[i], crc32 ? crc32[i] : 0u};
         if (text_len[i]) {
             const uint8_t* src = text[i];
             if (!text_pinned) {
@@ -3173,68 +3049,58 @@ int qd_deflater_run(qd_deflater* f, int32_t n_pieces, const uint8_t* const* text
         }
         at += ((size_t)text_len[i] + 15) & ~(size_t)15;
     }
-    DEFCHK(f, hipMemcpyAsync(f->d_pc, f->h_pc, (size_t)n_pieces * sizeof(qd_deflate_piece), hipMemcpyHostToDevice, f->stream));
+    DEFCHK(f, hipMemcpyAsync(f->pc.d, f->pc.h, (size_t)n_pieces * sizeof(qd_deflate_piece), hipMemcpyHostToDevice, f->stream));
     if (f->level == 1) {  // LZ77 + dynamic Huffman: one workgroup per 64 KiB sub-block, then the members are strung together
         size_t n_subs = 0;
         for (int i = 0; i < n_pieces; ++i) n_subs += ((size_t)text_len[i] + QD_LZ_SUB - 1) / QD_LZ_SUB;
         const int64_t sub_stride = qd_huffman_member_bound(QD_LZ_SUB);
-        DEFCHK(f, grow_pair(f->h_sub, f->d_sub, f->cap_sub, n_subs + 1));
-        DEFCHK(f, grow_pair(f->h_first, f->d_first, f->cap_first, (size_t)n_pieces + 1));
-        if (n_subs > f->cap_scratch) {
-            if (f->d_tokens) (void)hipFree(f->d_tokens);
-            if (f->d_sub_bytes) (void)hipFree(f->d_sub_bytes);
-            if (f->d_sub_out) (void)hipFree(f->d_sub_out);
-            if (f->d_sub_crc) (void)hipFree(f->d_sub_crc);
-            f->d_tokens = f->d_sub_bytes = f->d_sub_crc = nullptr;
-            f->d_sub_out = nullptr;
-            f->cap_scratch = 0;
-            const size_t n = n_subs + n_subs / 4 + 16;
-            DEFCHK(f, hipMalloc((void**)&f->d_tokens, n * (size_t)QD_LZ_SUB * 4));
-            DEFCHK(f, hipMalloc((void**)&f->d_sub_bytes, n * 4));
-            DEFCHK(f, hipMalloc((void**)&f->d_sub_out, n * (size_t)sub_stride));
-            DEFCHK(f, hipMalloc((void**)&f->d_sub_crc, n * 4));
-            f->cap_scratch = n;
-        }
+        DEFCHK(f, need_pair(f->sub, n_subs + 1));
+        DEFCHK(f, need_pair(f->first, (size_t)n_pieces + 1));
+        const size_t grown = qbuf::quarter(n_subs, 16);  // sub-blocks the four scratch arrays hold behind a growth
+        DEFCHK(f, f->d_tokens.need(n_subs * (size_t)QD_LZ_SUB * 4, grown * (size_t)QD_LZ_SUB * 4));
+        DEFCHK(f, f->d_sub_bytes.need(n_subs * 4, grown * 4));
+        DEFCHK(f, f->d_sub_out.need(n_subs * (size_t)sub_stride, grown * (size_t)sub_stride));
+        DEFCHK(f, f->d_sub_crc.need(n_subs * 4, grown * 4));
         size_t js = 0, off = 0;
         for (int i = 0; i < n_pieces; ++i) {
-            f->h_first[i] = (uint32_t)js;
+            f->first.h[i] = (uint32_t)js;
             for (int64_t a = 0; a < text_len[i]; a += QD_LZ_SUB)
-                f->h_sub[js++] = qd_lz_sub{(uint64_t)(off + (size_t)a), (uint32_t)std::min<int64_t>(QD_LZ_SUB, text_len[i] - a), (uint32_t)i};
+                f->sub.h[js++] = qd_lz_sub{(uint64_t)(off + (size_t)a), (uint32_t)std::min<int64_t>(QD_LZ_SUB, text_len[i] - a), (uint32_t)i};
             off += ((size_t)text_len[i] + 15) & ~(size_t)15;
         }
-        f->h_first[n_pieces] = (uint32_t)js;
-        if (js) DEFCHK(f, hipMemcpyAsync(f->d_sub, f->h_sub, js * sizeof(qd_lz_sub), hipMemcpyHostToDevice, f->stream));
-        DEFCHK(f, hipMemcpyAsync(f->d_first, f->h_first, ((size_t)n_pieces + 1) * 4, hipMemcpyHostToDevice, f->stream));
+        f->first.h[n_pieces] = (uint32_t)js;
+        if (js) DEFCHK(f, hipMemcpyAsync(f->sub.d, f->sub.h, js * sizeof(qd_lz_sub), hipMemcpyHostToDevice, f->stream));
+        DEFCHK(f, hipMemcpyAsync(f->first.d, f->first.h, ((size_t)n_pieces + 1) * 4, hipMemcpyHostToDevice, f->stream));
         if (crc32) {
-            DEFCHK(f, qd_launch_lz(f->d_text, f->d_pc, (uint32_t)n_pieces, f->d_sub, f->d_first, (uint32_t)js, f->d_tokens, f->d_sub_out, sub_stride,
-                                   f->d_sub_bytes, f->d_out, out_stride, f->d_len, f->stream));
+            DEFCHK(f, qd_launch_lz(f->d_text, f->pc.d, (uint32_t)n_pieces, f->sub.d, f->first.d, (uint32_t)js, f->d_tokens, f->d_sub_out, sub_stride,
+                                   f->d_sub_bytes, f->out.d, out_stride, f->len.d, f->stream));
         } else {  // as the pipeline (quade_pipe.cpp): the sub-blocks' CRC-32s out of the coder, combined per piece into the piece table
             static_assert(sizeof(qd_deflate_piece) == 16 && offsetof(qd_deflate_piece, crc32) == 12, "the combined CRCs land in the piece table");
-            DEFCHK(f, grow_pair(f->h_rg, f->d_rg, f->cap_rg, js + 1));
-            for (size_t k = 0; k < js; ++k) f->h_rg[k] = qd_crc_range{f->h_sub[k].text_off, f->h_sub[k].text_len, 0};
-            if (js) DEFCHK(f, hipMemcpyAsync(f->d_rg, f->h_rg, js * sizeof(qd_crc_range), hipMemcpyHostToDevice, f->stream));
-            DEFCHK(f, qd_launch_lz_subblocks(f->d_text, f->d_sub, (uint32_t)js, f->d_tokens, f->d_sub_out, sub_stride, f->d_sub_bytes, f->d_sub_crc, f->stream));
-            DEFCHK(f, qd_text_crc32_combine(f->d_rg, f->d_sub_crc, f->d_first, (uint32_t)n_pieces, reinterpret_cast<uint32_t*>(f->d_pc) + 3, 4, f->stream));
-            DEFCHK(f, qd_launch_lz_members(f->d_pc, (uint32_t)n_pieces, f->d_sub, f->d_first, (uint32_t)js, f->d_sub_out, sub_stride, f->d_sub_bytes,
-                                           f->d_out, out_stride, f->d_len, f->stream));
+            DEFCHK(f, need_pair(f->rg, js + 1));
+            for (size_t k = 0; k < js; ++k) f->rg.h[k] = qd_crc_range{f->sub.h[k].text_off, f->sub.h[k].text_len, 0};
+            if (js) DEFCHK(f, hipMemcpyAsync(f->rg.d, f->rg.h, js * sizeof(qd_crc_range), hipMemcpyHostToDevice, f->stream));
+            DEFCHK(f, qd_launch_lz_subblocks(f->d_text, f->sub.d, (uint32_t)js, f->d_tokens, f->d_sub_out, sub_stride, f->d_sub_bytes, f->d_sub_crc, f->stream));
+            DEFCHK(f, qd_text_crc32_combine(f->rg.d, f->d_sub_crc, f->first.d, (uint32_t)n_pieces, f->pc.d.as<uint32_t>() + 3, 4, f->stream));
+            DEFCHK(f, qd_launch_lz_members(f->pc.d, (uint32_t)n_pieces, f->sub.d, f->first.d, (uint32_t)js, f->d_sub_out, sub_stride, f->d_sub_bytes,
+                                           f->out.d, out_stride, f->len.d, f->stream));
         }
     } else {
-        DEFCHK(f, qd_launch_huffman(f->d_text, f->d_pc, (uint32_t)n_pieces, f->d_out, out_stride, f->d_len, f->stream));
+        DEFCHK(f, qd_launch_huffman(f->d_text, f->pc.d, (uint32_t)n_pieces, f->out.d, out_stride, f->len.d, f->stream));
     }
-    DEFCHK(f, hipMemcpyAsync(f->h_len, f->d_len, (size_t)n_pieces * 4, hipMemcpyDeviceToHost, f->stream));
+    DEFCHK(f, hipMemcpyAsync(f->len.h, f->len.d, (size_t)n_pieces * 4, hipMemcpyDeviceToHost, f->stream));
     DEFCHK(f, hipEventRecord(f->done, f->stream));
     DEFCHK(f, wait_event_napping(f->done));
     for (int i = 0; i < n_pieces; ++i) {  // the used bytes of every member
-        if (f->h_len[i] > (uint64_t)out_stride) return def_fail(f, QD_ERR_HIP, "member longer than its slot");
-        if (f->h_len[i])
-            DEFCHK(f, hipMemcpyAsync(f->h_out + (size_t)i * (size_t)out_stride, f->d_out + (size_t)i * (size_t)out_stride, f->h_len[i],
+        if (f->len.h[i] > (uint64_t)out_stride) return def_fail(f, QD_ERR_HIP, "member longer than its slot");
+        if (f->len.h[i])
+            DEFCHK(f, hipMemcpyAsync(f->out.h + (size_t)i * (size_t)out_stride, f->out.d + (size_t)i * (size_t)out_stride, f->len.h[i],
                                      hipMemcpyDeviceToHost, f->stream));
     }
     DEFCHK(f, hipEventRecord(f->done, f->stream));
     DEFCHK(f, wait_event_napping(f->done));
     for (int i = 0; i < n_pieces; ++i) {
-        member_len[i] = f->h_len[i];  // 0: this member did not fit out_stride (the caller makes it itself)
-        if (f->h_len[i]) memcpy(out + (size_t)i * (size_t)out_stride, f->h_out + (size_t)i * (size_t)out_stride, f->h_len[i]);
+        member_len[i] = f->len.h[i];  // 0: this member did not fit out_stride (the caller makes it itself)
+        if (f->len.h[i]) memcpy(out + (size_t)i * (size_t)out_stride, f->out.h + (size_t)i * (size_t)out_stride, f->len.h[i]);
     }
     return QD_OK;
 }
@@ -3248,7 +3114,7 @@ extern "C" int qd_dev_gunzip(int device_id, const uint8_t* gz, int64_t gz_len, u
     *out_len = 0;
     if (hipSetDevice(device_id) != hipSuccess) return QD_ERR_NO_DEVICE;
     hipStream_t st = nullptr;
-    uint8_t *d_gz = nullptr, *d_out = nullptr, *d_win = nullptr;
+    DevArr<uint8_t> d_gz, d_out, d_win;  // (freed on return: done() has drained the stream by then)
     int rc = QD_OK;
     qd_gz G;
     if (stretch_bytes > 0) G.stretch_bytes = (uint64_t)stretch_bytes;
@@ -3256,9 +3122,6 @@ extern "C" int qd_dev_gunzip(int device_id, const uint8_t* gz, int64_t gz_len, u
     int64_t members = 0, steps_run = 0;
     auto done = [&](int code) {
         if (st) (void)hipStreamSynchronize(st);
-        if (d_gz) (void)hipFree(d_gz);
-        if (d_out) (void)hipFree(d_out);
-        if (d_win) (void)hipFree(d_win);
         if (st) (void)hipStreamDestroy(st);
         if (stats) {
             const qd_gz_stats s = G.stats();
@@ -3274,8 +3137,8 @@ extern "C" int qd_dev_gunzip(int device_id, const uint8_t* gz, int64_t gz_len, u
         return code;
     };
     if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return done(QD_ERR_HIP);
-    if (hipMalloc((void**)&d_gz, (size_t)gz_len + 4096) != hipSuccess || hipMalloc((void**)&d_out, (size_t)std::max<int64_t>(out_cap, 1) + 4096) != hipSuccess ||
-        hipMalloc((void**)&d_win, 32768) != hipSuccess)
+    if (d_gz.alloc((size_t)gz_len + 4096) != hipSuccess || d_out.alloc((size_t)std::max<int64_t>(out_cap, 1) + 4096) != hipSuccess ||
+        d_win.alloc(32768) != hipSuccess)
         return done(QD_ERR_HIP);
     if (hipMemset(d_gz + gz_len, 0, 4096) != hipSuccess || (gz_len && hipMemcpy(d_gz, gz, (size_t)gz_len, hipMemcpyHostToDevice) != hipSuccess) ||
         hipMemset(d_win, 0, 32768) != hipSuccess)

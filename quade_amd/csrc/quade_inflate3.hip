@@ -947,44 +947,17 @@ hipError_t qd_launch_inflate3(const uint8_t* comp, size_t comp_bytes, const qd_i
 #include <algorithm>
 #include <vector>
 
+#include "quade_buf.h"
 #include "quade_text.h"
 
 namespace {
-struct GBuf {  // grow-only device allocation
-    uint8_t* p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) qd_pool_put(p, cap);  // (drains the device first)
-        p = nullptr;
-        cap = 0;
-        const size_t want = n + n / 4 + 65536;
-        return qd_pool_get(want, (void**)&p, &cap);  // (quade_pool.h: from what an earlier pipeline of this process released)
-    }
-    ~GBuf() {
-        if (p) qd_pool_put(p, cap);
-    }
-    template <class T>
-    T* as() const { return reinterpret_cast<T*>(p); }
+// grow-only, owned (quade_buf.h): the device side from the pool -- what an earlier pipeline of this process released -- and the
+// page-locked side from the driver
+struct GzDev : qbuf::Buf<qbuf::PoolDev> {
+    hipError_t need(size_t n) { return Buf::need(n, qbuf::quarter(n, 65536)); }
 };
-struct HBuf {  // grow-only page-locked host allocation
-    uint8_t* p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = n + n / 4 + 4096;
-        const hipError_t e = hipHostMalloc((void**)&p, want, hipHostMallocDefault);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    ~HBuf() {
-        if (p) (void)hipHostFree(p);
-    }
-    template <class T>
-    T* as() const { return reinterpret_cast<T*>(p); }
+struct GzPin : qbuf::Buf<qbuf::DriverPin> {
+    hipError_t need(size_t n) { return Buf::need(n, qbuf::quarter(n, 4096)); }
 };
 #define GZCHK(call)                     \
     do {                                \
@@ -1002,9 +975,9 @@ class qd_gz_impl {
     };
     std::vector<qd3::Unit> units_;
     std::vector<Acc> acc_;
-    GBuf d_stretch, d_found, d_units, d_res, d_tokens, d_lens, d_use, d_gzunits, d_chains, d_tiles, d_sym, d_wout, d_winin, d_ustat, d_cstat, d_outptr, d_uoff, d_floor,
+    GzDev d_stretch, d_found, d_units, d_res, d_tokens, d_lens, d_use, d_gzunits, d_chains, d_tiles, d_sym, d_wout, d_winin, d_ustat, d_cstat, d_outptr, d_uoff, d_floor,
         d_ranges, d_crc;
-    HBuf h_found, h_res, h_back, h_up;
+    GzPin h_found, h_res, h_back, h_up;
     std::vector<GzUnit> gzunits_;
     std::vector<uint32_t> unit_step_;  // R-unit -> step
     std::vector<qd_crc_range> ranges_;

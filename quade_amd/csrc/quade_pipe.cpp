@@ -45,7 +45,7 @@
 #include "quade_inflate.h"
 #include "quade_inflate3.h"
 #include "quade_io_internal.h"
-#include "quade_pool.h"
+#include "quade_buf.h"
 #include "quade_qstats.h"
 #include "quade_cstats.h"
 #include "quade_adapters.h"
@@ -74,17 +74,7 @@ constexpr size_t WINDOW_MAX = (size_t)1 << 30;   // text per stream and batch (o
 constexpr size_t GROUP_SEGMENTS = 8;             // uploads gathered per inflate launch
 constexpr size_t READ_PART = 4u << 20;           // an upload buffer is filled by parallel reads of this much
 
-hipError_t wait_event_napping(hipEvent_t ev) {  // hipEventSynchronize spins on this runtime: poll, then nap
-    for (int i = 0; i < 64; ++i) {
-        const hipError_t e = hipEventQuery(ev);
-        if (e != hipErrorNotReady) return e;
-    }
-    for (;;) {
-        const hipError_t e = hipEventQuery(ev);
-        if (e != hipErrorNotReady) return e;
-        usleep(50);
-    }
-}
+hipError_t wait_event_napping(hipEvent_t ev) { return qbuf::wait_event_napping(ev, 50); }
 
 struct Tick {  // adds the wall time of its scope to a counter
     double& acc;
@@ -94,55 +84,18 @@ struct Tick {  // adds the wall time of its scope to a counter
 };
 thread_local double g_alloc_seconds = 0;  // (device allocations are made by the driving thread)
 
-struct DevBuf {  // grow-only device allocation
-    uint8_t* p = nullptr;
-    size_t cap = 0;
+// The pipeline's device and page-locked buffers (quade_buf.h; who owns what: DESIGN.md 7.0): grow-only, from the pool -- what an
+// earlier pipeline of this process released.  A device growth asks for n + n/4 + 64 KiB and counts on the alloc_s clock.
+struct PipeDev : qbuf::Buf<qbuf::PoolDev> {
     // keep: the first `keep` bytes survive the growth (copied on `st`, which is then drained)
     hipError_t need(size_t n, size_t keep = 0, hipStream_t st = nullptr) {
         if (n <= cap) return hipSuccess;
         Tick tick(g_alloc_seconds);
-        const size_t want = n + n / 4 + (1u << 16);
-        uint8_t* q = nullptr;
-        size_t got = want;
-        hipError_t e = qd_pool_get(want, (void**)&q, &got);  // (quade_pool.h: from what an earlier pipeline of this process released)
-        if (e != hipSuccess) return e;
-        // nothing queued anywhere may still use the old allocation (the inflate launches run on a stream of their own)
-        if (p) (void)hipDeviceSynchronize();
-        if (p && keep) {
-            e = hipMemcpyAsync(q, p, keep, hipMemcpyDeviceToDevice, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return e;
-        }
-        if (p) qd_pool_put(p, cap);
-        p = q;
-        cap = got;
-        return hipSuccess;
+        return Buf::need(n, qbuf::quarter(n, 1u << 16), keep, st);
     }
-    void release() {
-        if (p) qd_pool_put(p, cap);
-        p = nullptr;
-        cap = 0;
-    }
-    template <class T>
-    T* as() const { return reinterpret_cast<T*>(p); }
 };
-
-struct PinBuf {  // grow-only page-locked host allocation (quade_pool.h: from what an earlier pipeline of this process released)
-    uint8_t* p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) qd_pool_put_pinned(p, cap);
-        p = nullptr;
-        cap = 0;
-        const size_t want = n + n / 4 + 4096;
-        return qd_pool_get_pinned(want, (void**)&p, &cap);
-    }
-    void release() {
-        if (p) qd_pool_put_pinned(p, cap);
-        p = nullptr;
-        cap = 0;
-    }
+struct PipePin : qbuf::Buf<qbuf::PoolPin> {
+    hipError_t need(size_t n) { return Buf::need(n, qbuf::quarter(n, 4096)); }
 };
 
 // Small tables on their way to the device: page-locked chunks that are reused once the copy that read them has run.
@@ -151,7 +104,6 @@ class StagePool {
     ~StagePool() {
         for (Chunk& c : chunks_) {
             if (c.ev) (void)hipEventDestroy(c.ev);
-            if (c.p) (void)hipHostFree(c.p);
         }
     }
     // copies n bytes of src to dst (device) on st through a page-locked chunk
@@ -159,22 +111,21 @@ class StagePool {
         if (!n) return hipSuccess;
         Chunk* c = nullptr;
         for (Chunk& k : chunks_)
-            if (k.cap >= n && (!k.used || hipEventQuery(k.ev) == hipSuccess)) {
+            if (k.buf.cap >= n && (!k.used || hipEventQuery(k.ev) == hipSuccess)) {
                 c = &k;
                 break;
             }
         if (!c) {
             Chunk k;
-            k.cap = std::max<size_t>(n + n / 2, 256u << 10);
-            hipError_t e = hipHostMalloc((void**)&k.p, k.cap, hipHostMallocDefault);
+            hipError_t e = k.buf.alloc(std::max<size_t>(n + n / 2, 256u << 10));
             if (e != hipSuccess) return e;
             e = hipEventCreateWithFlags(&k.ev, hipEventDisableTiming);
             if (e != hipSuccess) return e;
-            chunks_.push_back(k);
+            chunks_.push_back(std::move(k));
             c = &chunks_.back();
         }
-        memcpy(c->p, src, n);
-        hipError_t e = hipMemcpyAsync(dst, c->p, n, hipMemcpyHostToDevice, st);
+        memcpy(c->buf.p, src, n);
+        hipError_t e = hipMemcpyAsync(dst, c->buf.p, n, hipMemcpyHostToDevice, st);
         if (e != hipSuccess) return e;
         c->used = true;
         return hipEventRecord(c->ev, st);
@@ -182,8 +133,7 @@ class StagePool {
 
   private:
     struct Chunk {
-        uint8_t* p = nullptr;
-        size_t cap = 0;
+        qbuf::Buf<qbuf::DriverPin> buf;
         hipEvent_t ev = nullptr;
         bool used = false;
     };
@@ -215,7 +165,7 @@ class Feeder {
         hipError_t e = hipSetDevice(device_);
         if (e != hipSuccess) return e;
         if ((e = hipStreamCreateWithFlags(&up_, hipStreamNonBlocking)) != hipSuccess) return e;
-        if ((e = qd_pool_get((size_t)RING_SLOTS * SEG_BYTES + 4096, (void**)&ring_, &ring_cap_)) != hipSuccess) return e;  // (the third inflater's lanes read up to 512 bytes ahead of a payload)
+        if ((e = ring_.alloc((size_t)RING_SLOTS * SEG_BYTES + 4096)) != hipSuccess) return e;  // (the third inflater's lanes read up to 512 bytes ahead of a payload)
         for (int i = 0; i < RING_SLOTS; ++i) {
             if ((e = hipEventCreateWithFlags(&ready_[i], hipEventDisableTiming)) != hipSuccess) return e;
             if ((e = hipEventCreateWithFlags(&consumed_[i], hipEventDisableTiming)) != hipSuccess) return e;
@@ -240,12 +190,8 @@ class Feeder {
             if (consumed_[i]) (void)hipEventDestroy(consumed_[i]);
             ready_[i] = consumed_[i] = nullptr;
         }
-        for (int i = 0; i < PIN_SLOTS; ++i) {
-            if (pin_[i]) qd_pool_put_pinned(pin_[i], pin_cap_[i]);
-            pin_[i] = nullptr;
-        }
-        if (ring_) qd_pool_put(ring_, ring_cap_);
-        ring_ = nullptr;
+        for (auto& b : pin_) b.release();
+        ring_.release();
     }
     // the next segment of the stream (blocks); SEG_END closes a chunk
     Segment pop() {
@@ -255,7 +201,7 @@ class Feeder {
         q_.pop_front();
         return s;
     }
-    const uint8_t* ring() const { return ring_; }
+    const uint8_t* ring() const { return ring_.p; }
     hipEvent_t ready(int slot) const { return ready_[slot]; }
     // the driver has queued the last reader of `slot` on st
     hipError_t consumed(int slot, hipStream_t st) {
@@ -296,11 +242,11 @@ class Feeder {
     uint8_t* take_pin() {
         const int j = pin_next_;
         pin_next_ = (pin_next_ + 1) % PIN_SLOTS;
-        if (!pin_[j] && qd_pool_get_pinned(SEG_BYTES + 65536, (void**)&pin_[j], &pin_cap_[j]) != hipSuccess) return nullptr;
+        if (!pin_[j].p && pin_[j].alloc(SEG_BYTES + 65536) != hipSuccess) return nullptr;
         if (pin_slot_[j] >= 0 && wait_event_napping(ready_[pin_slot_[j]]) != hipSuccess) return nullptr;
         pin_slot_[j] = -1;
         pin_cur_ = j;
-        return pin_[j];
+        return pin_[j].p;
     }
     // a free ring slot (-1: stopping)
     int take_slot() {
@@ -323,7 +269,7 @@ class Feeder {
             if (!stopping()) fail(seg.chunk, "upload failed: waiting for a ring slot");
             return false;
         }
-        hipError_t e = hipMemcpyAsync(ring_ + (size_t)s * SEG_BYTES, pin, n, hipMemcpyHostToDevice, up_);
+        hipError_t e = hipMemcpyAsync(ring_.p + (size_t)s * SEG_BYTES, pin, n, hipMemcpyHostToDevice, up_);
         if (e == hipSuccess) e = hipEventRecord(ready_[s], up_);
         if (e != hipSuccess) {
             fail(seg.chunk, std::string("upload failed: ") + hipGetErrorString(e));
@@ -555,12 +501,10 @@ class Feeder {
     std::vector<FileSpec> files_;
     bool device_gunzip_ = false;
     hipStream_t up_ = nullptr;
-    uint8_t* ring_ = nullptr;
-    size_t ring_cap_ = 0;
+    qbuf::Buf<qbuf::PoolDev> ring_;
     hipEvent_t ready_[RING_SLOTS] = {nullptr}, consumed_[RING_SLOTS] = {nullptr};
     int state_[RING_SLOTS] = {0};  // 0 free, 1 with the driver, 2 its last reader is queued (consumed_ tells when it has run)
-    uint8_t* pin_[PIN_SLOTS] = {nullptr};
-    size_t pin_cap_[PIN_SLOTS] = {0};
+    qbuf::Buf<qbuf::PoolPin> pin_[PIN_SLOTS];
     int pin_slot_[PIN_SLOTS] = {-1, -1, -1};  // the ring slot whose upload read this buffer last
     int pin_next_ = 0, pin_cur_ = 0, slot_next_ = 0;
     std::mutex m_;
@@ -591,8 +535,8 @@ struct BatchOut {
 };
 
 struct OutSet {  // per-batch output resources, two of them: the collector drains one while the device fills the other
-    DevBuf text, pieces, members, member_len, member_off, packed;
-    PinBuf h_len;
+    PipeDev text, pieces, members, member_len, member_off, packed;
+    PipePin h_len;
     hipEvent_t done = nullptr;
     bool busy = false;
 };
@@ -607,6 +551,11 @@ struct qd_pipe_stats_impl {
     int64_t gzip_steps = 0, gzip_units = 0, gzip_members = 0, gzip_fallbacks = 0;
 };
 
+// Every buffer in here is an owner (PipeDev, PipePin, the staging chunks) and goes back to the pool in ~qd_pipe, that is in
+// qd_pipe_destroy's `delete p`, in reverse order of declaration.  No buffer depends on another, so the order among them carries
+// nothing; what a release does depend on -- a pooled device buffer's drains the device and asks which device is current -- is
+// qd_pipe_destroy's business before the delete: threads joined, device current, streams drained.  The two std::thread members stand
+// behind the buffers their threads use, so they are gone (joined long before) when the first buffer is.
 struct qd_pipe {
     qd_ctx* ctx = nullptr;
     int device = 0;
@@ -644,19 +593,19 @@ struct qd_pipe {
     int64_t gz_units0 = 0;
     std::vector<qd_inflate3_job> q3_jobs;   // (out: the offset inside the window's text until the launch -- the buffer may still grow)
     std::vector<Queued3> q3_parts;
-    DevBuf jobs3, status3, scratch3;
+    PipeDev jobs3, status3, scratch3;
     StagePool stage;
     qd_pipe_stats_impl st;
 
     struct Window {
-        DevBuf buf[2];
+        PipeDev buf[2];
         int cur = 0;
         uint32_t len = 0;       // bytes of text in buf[cur]
         bool eof = false;       // the feeder has delivered the stream's last byte
         bool dirty = true;      // text arrived since the last scan
         double avg = 0;         // bytes per record, learned
         uint32_t carry_kept = 0;
-        DevBuf tile_counts, tile_base, lines, rec_tile, recs;
+        PipeDev tile_counts, tile_base, lines, rec_tile, recs;
         uint32_t line_cap = 0;
         std::vector<Segment> pending;                                  // BGZF uploads waiting for their inflate launch
         uint32_t pending_text = 0;
@@ -676,12 +625,12 @@ struct qd_pipe {
         // comp[ccur]; the next block header (or, walk.need_header: the next member's header) is known exactly
         struct Gz {
             bool active = false;
-            DevBuf comp[2];
+            PipeDev comp[2];
             int ccur = 0;
             uint64_t comp_off = 0, comp_len = 0;
             bool file_done = false;   // the feeder has delivered the file's last byte
             gzf::MemberWalk walk;     // where the stream stands: member, next block header, the member's text and CRC so far
-            DevBuf carried;           // the 32 KiB of text in front of the next block header
+            PipeDev carried;           // the 32 KiB of text in front of the next block header
             uint32_t carried_valid = 0;
             double ratio = 3.5;       // text per compressed byte, learned
             int fd = -1;
@@ -693,19 +642,19 @@ struct qd_pipe {
         } gz;
     } win[4];
     int n_streams = 4;  // R1, R2, I1 [, I2]
-    DevBuf d_res;       // qd_scan_result[4] + pack's short counter
-    PinBuf h_res;
+    PipeDev d_res;       // qd_scan_result[4] + pack's short counter
+    PipePin h_res;
     // index rows, codes, routing scratch (sized for batch_pairs)
-    DevBuf rows_seq[2], rows_qual[2], rows_len[2], codes, mol, short_idx, dest, len1, len2, hist, tmp, perm, sdest, g1, g2, scan_tiles, first, g1_first,
+    PipeDev rows_seq[2], rows_qual[2], rows_len[2], codes, mol, short_idx, dest, len1, len2, hist, tmp, perm, sdest, g1, g2, scan_tiles, first, g1_first,
         g2_first;
-    DevBuf recs_out[4][2];  // the insert reads' record tables as clip, trim, pairtrim and posttrim leave them (a stage's are never allocated when it is off)
-    DevBuf inserts;  // a pair's insert length I* from the overlap stage to the overlap base correction (uint64 per pair; never allocated when the correction is off)
-    DevBuf drop;  // the read filter's reason byte per pair, 0x80 for a pair the k-mer screen drops (qd_filter_set, qd_screen_set with action drop; never allocated when both are off)
-    PinBuf h_first;
+    PipeDev recs_out[4][2];  // the insert reads' record tables as clip, trim, pairtrim and posttrim leave them (a stage's are never allocated when it is off)
+    PipeDev inserts;  // a pair's insert length I* from the overlap stage to the overlap base correction (uint64 per pair; never allocated when the correction is off)
+    PipeDev drop;  // the read filter's reason byte per pair, 0x80 for a pair the k-mer screen drops (qd_filter_set, qd_screen_set with action drop; never allocated when both are off)
+    PipePin h_first;
     // tables and scratch of the format / CRC / coder launches: read by kernels on the compute stream only, so one set serves every batch
-    DevBuf subs, first_sub, ranges, crc, tokens, sub_out, sub_bytes, base1, base2;
+    PipeDev subs, first_sub, ranges, crc, tokens, sub_out, sub_bytes, base1, base2;
     OutSet out[2];
-    PinBuf slab[3];                                // the collector's download ring
+    PipePin slab[3];                                // the collector's download ring
     hipEvent_t slab_ev[3] = {nullptr, nullptr, nullptr};
     size_t window_max = WINDOW_MAX;                // text a window may hold (the index pass of a shared chunk raises it for its one window)
     bool reserved = false;                         // the buffers have been sized for batch_pairs (after the first scan)
@@ -1510,7 +1459,7 @@ int reserve_output(qd_pipe* p, uint32_t n_dest, double out_text) {
     const size_t n_pieces = T / piece_bytes + 2 * (size_t)n_dest + 2, n_subs = T / QD_LZ_SUB + n_pieces;
     const size_t out_stride = (size_t)qd_huffman_member_bound(piece_bytes), sub_stride = (size_t)qd_huffman_member_bound(QD_LZ_SUB);
     hipError_t e = hipSuccess;
-    auto need = [&](DevBuf& b, size_t n) {  // (first allocations: nothing to keep, no stream involved)
+    auto need = [&](PipeDev& b, size_t n) {  // (first allocations: nothing to keep, no stream involved)
         if (e == hipSuccess) e = b.need(n);
     };
     for (OutSet& o : p->out) {
@@ -1603,7 +1552,7 @@ int reserve_buffers(qd_pipe* p, uint32_t B, uint32_t n_dest) {
     PCHK(p, p->short_idx.need((n / 2 + 64) * 4, 0, p->cs));
     const size_t H = 256 * ((n + 1023) / 1024);
     PCHK(p, p->hist.need((H + H / 4096 + 8) * 4, 0, p->cs));
-    for (DevBuf* b : {&p->len1, &p->len2, &p->tmp, &p->perm, &p->g1, &p->g2}) PCHK(p, b->need((n + 1) * 4 + 64, 0, p->cs));
+    for (PipeDev* b : {&p->len1, &p->len2, &p->tmp, &p->perm, &p->g1, &p->g2}) PCHK(p, b->need((n + 1) * 4 + 64, 0, p->cs));
     PCHK(p, p->dest.need(n * 2 + 64, 0, p->cs));
     PCHK(p, p->sdest.need(n * 2 + 64, 0, p->cs));
     PCHK(p, p->scan_tiles.need((n / 4096 + 4) * 4, 0, p->cs));
@@ -1708,7 +1657,7 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
     const bool correct = qd_paircorrect_active(p->ctx) != 0;  // (qd_pipe_run has made sure that overlap trimming is on as well)
     for (int s = 0; s < 4; ++s) {
         if (!rewriting[s].active(p->ctx)) continue;
-        DevBuf* out = p->recs_out[s];
+        PipeDev* out = p->recs_out[s];
         for (int k = 0; k < 2; ++k) PCHK(p, out[k].need((size_t)n * sizeof(qd_rec) + 64, 0, p->cs));
         if (correct && rewriting[s].device == qd_pairtrim_device) {
             PCHK(p, p->inserts.need((size_t)n * 8 + 64, 0, p->cs));
@@ -2360,7 +2309,7 @@ int index_stream(qd_pipe* p, const char* path, int32_t world, int32_t rank, int3
             gstart[(size_t)k] = b - b_from < (int64_t)text_at.size() ? text_at[(size_t)(b - b_from)] : (uint32_t)text_total;
         }
         if (g_hi == G && at_eof) gstart[(size_t)ng] = (uint32_t)text_total + 1;  // (the unterminated last line of the file ends "at" text_total)
-        DevBuf d_g, d_out;
+        PipeDev d_g, d_out;
         PCHK(p, d_g.need(((size_t)ng + 1) * 4, 0, p->cs));
         PCHK(p, d_out.need((size_t)ng * sizeof(qd_grain_index), 0, p->cs));
         PCHK(p, p->stage.upload(d_g.p, gstart.data(), ((size_t)ng + 1) * 4, p->cs));
@@ -2567,39 +2516,20 @@ int qd_pipe_destroy(qd_pipe* p) {
     if (p->is) (void)hipStreamSynchronize(p->is);
     for (qd_pipe::Window& w : p->win) {
         if (w.inflated) (void)hipEventDestroy(w.inflated);
-        for (DevBuf* b : {&w.buf[0], &w.buf[1], &w.tile_counts, &w.tile_base, &w.lines, &w.rec_tile, &w.recs}) b->release();
-    }
-    for (DevBuf* b : {&p->jobs3, &p->status3, &p->scratch3}) b->release();
-    for (qd_pipe::Window& w : p->win) {
         gz_close(w);
-        for (DevBuf* b : {&w.gz.comp[0], &w.gz.comp[1], &w.gz.carried}) b->release();
     }
     delete p->gz;
-    p->gz = nullptr;
-    for (DevBuf* b : {&p->d_res, &p->rows_seq[0], &p->rows_seq[1], &p->rows_qual[0], &p->rows_qual[1], &p->rows_len[0], &p->rows_len[1], &p->codes, &p->mol,
-                      &p->short_idx, &p->dest, &p->len1, &p->len2, &p->hist, &p->tmp, &p->perm, &p->sdest, &p->g1, &p->g2, &p->scan_tiles, &p->first, &p->g1_first,
-                      &p->g2_first, &p->subs, &p->first_sub, &p->ranges, &p->crc, &p->tokens, &p->sub_out, &p->sub_bytes, &p->base1, &p->base2, &p->drop, &p->inserts})
-        b->release();
-    for (auto& stage : p->recs_out)
-        for (DevBuf& b : stage) b.release();
-    for (OutSet& o : p->out) {
-        for (DevBuf* b : {&o.text, &o.pieces, &o.members, &o.member_len, &o.member_off, &o.packed}) b->release();
-        o.h_len.release();
+    for (OutSet& o : p->out)
         if (o.done) (void)hipEventDestroy(o.done);
-    }
-    p->h_res.release();
-    p->h_first.release();
-    for (int k = 0; k < 3; ++k) {
-        p->slab[k].release();
-        if (p->slab_ev[k]) (void)hipEventDestroy(p->slab_ev[k]);
-    }
+    for (hipEvent_t ev : p->slab_ev)
+        if (ev) (void)hipEventDestroy(ev);
     if (p->sync_ev) (void)hipEventDestroy(p->sync_ev);
     if (p->is) (void)hipStreamDestroy(p->is);
     for (hipStream_t st : p->placeholder)
         if (st) (void)hipStreamDestroy(st);
     if (p->cs) (void)hipStreamDestroy(p->cs);
     if (p->ds) (void)hipStreamDestroy(p->ds);
-    delete p;
+    delete p;  // (the buffers go back here: see qd_pipe)
     return QD_OK;
 }
 

@@ -7,7 +7,7 @@
 // default 64; 0: no pool) and qd_pool_trim() gives all of it back to the driver.
 // Nothing here is on a kernel's path; the reference has no counterpart (its buffers are Python objects).
 #pragma once
-#include <hip/hip_runtime.h>
+#include <hip/hip_runtime_api.h>
 #include <stddef.h>
 
 // an allocation of at least `want` bytes: *cap says how large it is

@@ -7,17 +7,12 @@
 #include <vector>
 
 #include "../../include/quade_hip.h"
+#include "quade_buf.h"
 #include "quade_text.h"
 
 namespace {
-struct Dev {  // a scratch allocation freed at scope exit
-    void* p = nullptr;
-    ~Dev() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
-    template <class T>
-    T* as() { return static_cast<T*>(p); }
+struct Scratch : qbuf::Buf<qbuf::DriverDev> {  // a scratch allocation freed at scope exit; never empty: a kernel gets a real address for n == 0 too
+    hipError_t alloc(size_t n) { return Buf::alloc(n ? n : 16); }
 };
 #define TCHK(call)                            \
     do {                                      \
@@ -33,7 +28,7 @@ int64_t qd_dev_fastq_scan(int device_id, const uint8_t* text, int64_t text_len, 
     TCHK(hipSetDevice(device_id));
     const uint32_t len = (uint32_t)text_len, n_tiles = len / QD_TEXT_TILE + 1;
     line_cap &= ~(int64_t)3;
-    Dev d_text, tc, tb, lines, rt, recs, res;
+    Scratch d_text, tc, tb, lines, rt, recs, res;
     TCHK(d_text.alloc((size_t)len + 2 * QD_TEXT_TILE));
     TCHK(tc.alloc((size_t)(n_tiles + 2) * 4));
     TCHK(tb.alloc((size_t)(n_tiles + 2) * 4));
@@ -67,7 +62,7 @@ int qd_dev_crc32(int device_id, const uint8_t* data, int64_t n, int64_t range_by
     std::vector<qd_crc_range> ranges;
     for (int64_t a = 0; a < n; a += range_bytes) ranges.push_back(qd_crc_range{(uint64_t)a + 3, (uint32_t)std::min<int64_t>(range_bytes, n - a), 0});
     const uint32_t first[2] = {0, (uint32_t)ranges.size()};
-    Dev d, dr, dc, df, out;
+    Scratch d, dr, dc, df, out;
     TCHK(d.alloc((size_t)n + 16));
     TCHK(dr.alloc(ranges.size() * sizeof(qd_crc_range)));
     TCHK(dc.alloc(ranges.size() * 4));
@@ -87,7 +82,7 @@ int qd_dev_sort_by_dest(int device_id, const uint16_t* dest, int64_t n, int32_t 
     if (!dest || n < 1 || n > 0x7FFFFFFF || n_dest < 1 || n_dest > 65536 || !perm_out) return QD_ERR_INVALID;
     TCHK(hipSetDevice(device_id));
     const size_t H = 256 * (((size_t)n + 1023) / 1024);
-    Dev d, hist, tmp, perm, dl, tiles, g;
+    Scratch d, hist, tmp, perm, dl, tiles, g;
     TCHK(d.alloc((size_t)n * 2));
     TCHK(hist.alloc((H + H / 4096 + 8) * 4));
     TCHK(tmp.alloc((size_t)n * 4));
@@ -129,7 +124,7 @@ int qd_dev_pack_rows(int device_id, const qd_layout* layout, const uint8_t* cons
         }
     }
     TCHK(hipSetDevice(device_id));
-    Dev d_text[2], d_recs[2], d_seq[2], d_qual[2], d_len[2], d_short, d_n;
+    Scratch d_text[2], d_recs[2], d_seq[2], d_qual[2], d_len[2], d_short, d_n;
     qd_pack_args pa{};
     for (int k = 0; k < L.n_streams; ++k) {
         TCHK(d_text[k].alloc((size_t)text_len[k] + 64));
@@ -194,7 +189,7 @@ int qd_dev_route_format(int device_id, const qd_plan* plan, int32_t n_samples, i
     TCHK(hipSetDevice(device_id));
     const uint32_t N = (uint32_t)n, S = (uint32_t)n_samples, nd = 2 * S + 1;
     const size_t H = 256 * (((size_t)n + 1023) / 1024);
-    Dev d_text[4], d_recs[4], d_codes, d_drop, d_dest, d_len1, d_len2, hist, tmp, d_perm, d_sdest, d_g1, d_g2, tiles, d_first, d_g1f, d_g2f, d_b1,
+    Scratch d_text[4], d_recs[4], d_codes, d_drop, d_dest, d_len1, d_len2, hist, tmp, d_perm, d_sdest, d_g1, d_g2, tiles, d_first, d_g1f, d_g2f, d_b1,
         d_b2, d_out;
     const uint8_t* t[4] = {nullptr, nullptr, nullptr, nullptr};
     for (int s = 0; s < ns; ++s) {  // byte o of a text lies at device address o + shift (mod 16)
@@ -212,10 +207,10 @@ int qd_dev_route_format(int device_id, const qd_plan* plan, int32_t n_samples, i
     }
     TCHK(d_dest.alloc((size_t)n * 2));
     TCHK(d_sdest.alloc((size_t)n * 2));
-    for (Dev* b : {&d_len1, &d_len2, &tmp, &d_perm, &d_g1, &d_g2}) TCHK(b->alloc(((size_t)n + 1) * 4));
+    for (Scratch* b : {&d_len1, &d_len2, &tmp, &d_perm, &d_g1, &d_g2}) TCHK(b->alloc(((size_t)n + 1) * 4));
     TCHK(hist.alloc((H + H / 4096 + 8) * 4));
     TCHK(tiles.alloc(((size_t)n / 4096 + 4) * 4));
-    for (Dev* b : {&d_first, &d_g1f, &d_g2f}) {
+    for (Scratch* b : {&d_first, &d_g1f, &d_g2f}) {
         TCHK(b->alloc((size_t)nd * 4));
         TCHK(hipMemset(b->p, 0xFF, (size_t)nd * 4));  // an entry of g1_first / g2_first that no kernel writes stays 0xFFFFFFFF
     }
@@ -296,7 +291,7 @@ int qd_dev_pack_members(int device_id, const uint8_t* slots, int64_t stride, con
     }
     if (total > (uint64_t)packed_cap) return QD_ERR_INVALID;
     TCHK(hipSetDevice(device_id));
-    Dev d_slots, d_len, d_off, d_packed;
+    Scratch d_slots, d_len, d_off, d_packed;
     TCHK(d_slots.alloc((size_t)(n * stride)));
     TCHK(d_len.alloc((size_t)n * 4));
     TCHK(d_off.alloc(((size_t)n + 1) * 8));
