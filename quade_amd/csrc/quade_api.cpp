@@ -15,6 +15,7 @@
 
 #include "../../include/quade_hip.h"
 #include "quade_common.h"
+#include "batch_sizes.h"
 #include "gz_framing.h"
 #include "quade_kernels.h"
 #include "quade_inflate.h"
@@ -2683,7 +2684,7 @@ struct __attribute__((visibility("hidden"))) qd_inflater {  // (hidden: its dest
     qbuf::Pair<qd_inflate_block> blk;
     qbuf::Pair<int32_t> st;
     std::vector<uint32_t> crc;
-    // which kernel: 2 (the default) = 512 lanes per block, 1 = one wave per block (QUADE_INFLATE_FORM / qd_inflater_set_form); the second form's match lists
+    // which kernel: 3 (the default, below), 2 = 512 lanes per block, 1 = one wave per block (QUADE_INFLATE_FORM / qd_inflater_set_form); the second form's match lists
     int form = 3;
     DevArr<unsigned long long> d_matches;  // QD_INFLATE_MATCHES_PER_BLOCK per block
     // the third form (3: one lane decodes a block's symbols once, a workgroup resolves its tokens -- quade_inflate3.hip): its scratch
@@ -2976,9 +2977,7 @@ int def_fail(qd_deflater* f, int code, const std::string& msg) {
 extern "C" {
 
 int64_t qd_huffman_member_bound(int64_t text_len) {
-    // a code for 257 symbols never needs more than 9 bits per byte on average (the fixed 9-bit code is a candidate); the
-    // 15-bit limit's repair and the header (149 bytes), end-of-block code and trailer ride in the slack
-    return text_len < 0 ? -1 : ((text_len * 9 + 7) / 8 + text_len / 64 + 1024 + 3) & ~(int64_t)3;
+    return bsz::huffman_member_bound(text_len);  // (the formula and its reasons: batch_sizes.h)
 }
 
 int qd_deflater_create(int device_id, qd_deflater** out) {
@@ -3052,7 +3051,7 @@ int qd_deflater_run(qd_deflater* f, int32_t n_pieces, const uint8_t* const* text
     DEFCHK(f, hipMemcpyAsync(f->pc.d, f->pc.h, (size_t)n_pieces * sizeof(qd_deflate_piece), hipMemcpyHostToDevice, f->stream));
     if (f->level == 1) {  // LZ77 + dynamic Huffman: one workgroup per 64 KiB sub-block, then the members are strung together
         size_t n_subs = 0;
-        for (int i = 0; i < n_pieces; ++i) n_subs += ((size_t)text_len[i] + QD_LZ_SUB - 1) / QD_LZ_SUB;
+        for (int i = 0; i < n_pieces; ++i) n_subs += outplan::subs_of((uint64_t)text_len[i]);
         const int64_t sub_stride = qd_huffman_member_bound(QD_LZ_SUB);
         DEFCHK(f, need_pair(f->sub, n_subs + 1));
         DEFCHK(f, need_pair(f->first, (size_t)n_pieces + 1));
@@ -3061,12 +3060,14 @@ int qd_deflater_run(qd_deflater* f, int32_t n_pieces, const uint8_t* const* text
         DEFCHK(f, f->d_sub_bytes.need(n_subs * 4, grown * 4));
         DEFCHK(f, f->d_sub_out.need(n_subs * (size_t)sub_stride, grown * (size_t)sub_stride));
         DEFCHK(f, f->d_sub_crc.need(n_subs * 4, grown * 4));
-        size_t js = 0, off = 0;
-        for (int i = 0; i < n_pieces; ++i) {
+        if (!crc32) DEFCHK(f, need_pair(f->rg, n_subs + 1));  // (the sub-blocks' CRC-32s out of the coder: their ranges for the combine)
+        size_t js = 0;
+        for (int i = 0; i < n_pieces; ++i) {  // the pieces' sub-blocks, cut as the pipeline cuts them (out_plan.h)
             f->first.h[i] = (uint32_t)js;
-            for (int64_t a = 0; a < text_len[i]; a += QD_LZ_SUB)
-                f->sub.h[js++] = qd_lz_sub{(uint64_t)(off + (size_t)a), (uint32_t)std::min<int64_t>(QD_LZ_SUB, text_len[i] - a), (uint32_t)i};
-            off += ((size_t)text_len[i] + 15) & ~(size_t)15;
+            outplan::cut_piece(f->pc.h[i].text_off, f->pc.h[i].text_len, (uint32_t)i, [&](const qd_lz_sub& s, const qd_crc_range& r) {
+                if (!crc32) f->rg.h[js] = r;
+                f->sub.h[js++] = s;
+            });
         }
         f->first.h[n_pieces] = (uint32_t)js;
         if (js) DEFCHK(f, hipMemcpyAsync(f->sub.d, f->sub.h, js * sizeof(qd_lz_sub), hipMemcpyHostToDevice, f->stream));
@@ -3076,8 +3077,6 @@ int qd_deflater_run(qd_deflater* f, int32_t n_pieces, const uint8_t* const* text
                                    f->d_sub_bytes, f->out.d, out_stride, f->len.d, f->stream));
         } else {  // as the pipeline (quade_pipe.cpp): the sub-blocks' CRC-32s out of the coder, combined per piece into the piece table
             static_assert(sizeof(qd_deflate_piece) == 16 && offsetof(qd_deflate_piece, crc32) == 12, "the combined CRCs land in the piece table");
-            DEFCHK(f, need_pair(f->rg, js + 1));
-            for (size_t k = 0; k < js; ++k) f->rg.h[k] = qd_crc_range{f->sub.h[k].text_off, f->sub.h[k].text_len, 0};
             if (js) DEFCHK(f, hipMemcpyAsync(f->rg.d, f->rg.h, js * sizeof(qd_crc_range), hipMemcpyHostToDevice, f->stream));
             DEFCHK(f, qd_launch_lz_subblocks(f->d_text, f->sub.d, (uint32_t)js, f->d_tokens, f->d_sub_out, sub_stride, f->d_sub_bytes, f->d_sub_crc, f->stream));
             DEFCHK(f, qd_text_crc32_combine(f->rg.d, f->d_sub_crc, f->first.d, (uint32_t)n_pieces, f->pc.d.as<uint32_t>() + 3, 4, f->stream));

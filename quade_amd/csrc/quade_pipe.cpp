@@ -40,7 +40,9 @@
 #include <vector>
 
 #include "../../include/quade_hip.h"
+#include "batch_sizes.h"
 #include "gz_framing.h"
+#include "out_plan.h"
 #include "quade_deflate.h"
 #include "quade_inflate.h"
 #include "quade_inflate3.h"
@@ -69,7 +71,6 @@ constexpr size_t SEG_BYTES = 16u << 20;  // bytes per upload (compressed blocks 
 constexpr size_t SEG_TEXT_MAX = 128u << 20;  // text one BGZF upload inflates to at most (a buffer of blocks that hold more goes out in several)
 constexpr int RING_SLOTS = 64;           // device ring per stream: how far a feeder runs ahead of the kernels (a 2 M-pair batch of 2 x 150 bp takes ~24 uploads)
 constexpr int PIN_SLOTS = 3;             // page-locked upload buffers per stream
-constexpr uint32_t PIECE_BYTES = 1u << 20;       // text per gzip member at most (piece_bytes_for)
 constexpr size_t WINDOW_MAX = (size_t)1 << 30;   // text per stream and batch (offsets are 32 bit)
 constexpr size_t GROUP_SEGMENTS = 8;             // uploads gathered per inflate launch
 constexpr size_t READ_PART = 4u << 20;           // an upload buffer is filled by parallel reads of this much
@@ -516,12 +517,7 @@ class Feeder {
 };
 
 // ---- what a batch hands to the collector -------------------------------------------------------------------------------------
-struct FileRun {  // the members of one output file made by one batch: pieces [first, first + n)
-    uint32_t code;
-    int k;
-    uint32_t first, n;
-    uint64_t text_bytes;
-};
+using outplan::FileRun;  // the members of one output file made by one batch (out_plan.h)
 struct BatchOut {
     int set = -1;  // resource set; -1: no members, just a message
     qd_sink* sink = nullptr;
@@ -913,9 +909,8 @@ int join_inflate(qd_pipe* p, Window& w) {
 
 // room for `extra` more bytes of text in the window (the line kernels read whole tiles: padding behind the text)
 int window_room(qd_pipe* p, Window& w, size_t extra) {
-    const size_t need = (size_t)w.len + extra + 2 * QD_TEXT_TILE;
     if ((size_t)w.len + extra > p->window_max) return pfail(p, QD_ERR_UNSUPPORTED, w.path + ": more text in one window than its 32-bit offsets reach (lower batch_pairs)");
-    PCHK(p, w.buf[w.cur].need(need, w.len, p->cs));
+    PCHK(p, w.buf[w.cur].need((size_t)w.len + extra + 2 * QD_TEXT_TILE, w.len, p->cs));
     return QD_OK;
 }
 
@@ -1344,11 +1339,21 @@ int drain_chunk(qd_pipe* p, Feeder& f, Window& w, int chunk) {
     return QD_OK;
 }
 
+static_assert(bsz::TEXT_TILE == QD_TEXT_TILE && bsz::REC_BYTES == sizeof(qd_rec), "batch_sizes.h states quade_text.h's tile and record");
+
+// the tables of a window's scan, for text_bytes of text and line_cap lines
+int need_scan_tables(qd_pipe* p, Window& w, size_t text_bytes, size_t line_cap) {
+    const bsz::ScanSizes z = bsz::scan_sizes(text_bytes, line_cap);
+    PCHK(p, w.tile_counts.need(z.tiles, 0, p->cs));
+    PCHK(p, w.tile_base.need(z.tiles, 0, p->cs));
+    PCHK(p, w.lines.need(z.lines, 0, p->cs));
+    PCHK(p, w.rec_tile.need(z.rec_tile, 0, p->cs));
+    PCHK(p, w.recs.need(z.recs, 0, p->cs));
+    return QD_OK;
+}
+
 int scan_window(qd_pipe* p, Window& w, int stream_index, qd_scan_job* job = nullptr) {
     if (join_inflate(p, w) != QD_OK) return QD_ERR_HIP;
-    const uint32_t n_tiles = w.len / QD_TEXT_TILE + 1;
-    PCHK(p, w.tile_counts.need((size_t)(n_tiles + 2) * 4, 0, p->cs));
-    PCHK(p, w.tile_base.need((size_t)(n_tiles + 2) * 4, 0, p->cs));
     if (w.line_cap == 0 || (w.avg > 0 && (double)w.len / w.avg * 4.4 + 4096 > (double)w.line_cap)) {
         // lines expected: 4 per record of the learned size (first scan: one line per 16 bytes); a scan that finds more says so
         const double guess = w.avg > 0 ? (double)w.len / w.avg * 4.4 : (double)w.len / 16.0;
@@ -1356,9 +1361,8 @@ int scan_window(qd_pipe* p, Window& w, int stream_index, qd_scan_job* job = null
         w.line_cap = (w.line_cap + 3) & ~3u;
     }
     {
-        PCHK(p, w.lines.need((size_t)w.line_cap * 4 + 64, 0, p->cs));
-        PCHK(p, w.rec_tile.need(((size_t)w.line_cap / 4 / 1024 + 4) * 4, 0, p->cs));
-        PCHK(p, w.recs.need(((size_t)w.line_cap / 4 + 1) * sizeof(qd_rec), 0, p->cs));
+        const int rc = need_scan_tables(p, w, w.len, w.line_cap);
+        if (rc != QD_OK) return rc;
         qd_scan_scratch sc;
         sc.tile_counts = w.tile_counts.as<uint32_t>();
         sc.tile_base = w.tile_base.as<uint32_t>();
@@ -1437,47 +1441,79 @@ int host_inflate_window(qd_pipe* p, Window& w) {
     return rc;
 }
 
-// Text per gzip member: 1 MiB -- less when so many destinations take members in one batch that their slots (every member gets one of
-// the longest member's bound) would not fit member_slots_bytes: thousands of samples make thousands of small members per batch.
-uint32_t piece_bytes_for(const qd_pipe* p, uint64_t text_bytes, uint64_t n_dest) {
-    uint32_t pb = PIECE_BYTES;
-    while (pb > QD_LZ_SUB && (text_bytes / pb + 2 * n_dest + 2) * (uint64_t)qd_huffman_member_bound(pb) > (uint64_t)p->member_slots_bytes) pb >>= 1;
-    return pb;
+// ---- the batch's buffers: how large is batch_sizes.h's business; the reservation and the per-batch path both ask through these ---------
+uint32_t piece_bytes_for(const qd_pipe* p, uint64_t text_bytes, uint64_t n_dest) { return bsz::piece_bytes_for(p->member_slots_bytes, text_bytes, n_dest); }
+
+// The opt-in stages that rewrite the insert reads' tables, each on what the one before left: end clipping, window and poly-G trimming
+// (qd_clip_set; copies with seq, qual and seq_len of their own, so that a 5' clip reaches every stage behind it through the tables
+// alone), 3' trimming (qd_trim_set), paired-end overlap trimming of R1 and R2 together (qd_pairtrim_set), then trailing N, a poly-X
+// tail and the max_length crop (qd_posttrim_set)
+const struct {
+    int (*active)(const qd_ctx*);
+    int (*device)(qd_ctx*, const uint8_t*, const qd_rec*, const uint8_t*, const qd_rec*, uint32_t, qd_rec*, qd_rec*, void*);
+    const char* label;
+} rewriting[4] = {{qd_clip_active, qd_clip_device, "clip: "},
+                  {qd_trim_active, qd_trim_device, "trim: "},
+                  {qd_pairtrim_active, qd_pairtrim_device, "overlap trim: "},
+                  {qd_posttrim_active, qd_posttrim_device, "post-trim: "}};
+
+// which stages' tables a batch needs (a stage's are never allocated when it is off)
+bsz::StagesOn stages_on(const qd_ctx* ctx) {
+    bsz::StagesOn on;
+    for (int s = 0; s < 4; ++s) on.recs_out[s] = rewriting[s].active(ctx) != 0;
+    on.inserts = qd_paircorrect_active(ctx) != 0 && qd_pairtrim_active(ctx) != 0;
+    on.drop = qd_filter_active(ctx) != 0 || qd_screen_active(ctx) == 2;
+    return on;
 }
 
-// The coder's scratch of candidates / tokens is 4 bytes per byte of text: a batch's sub-blocks go through it a quarter at a time (a
-// launch of some thousand workgroups still fills the device several times over), which keeps 2.5 GB of a 2 M-pair batch's 3.3 unallocated.
-uint32_t lz_slice_subs(uint32_t n_subs) { return std::max<uint32_t>(2048, (n_subs + 3) / 4); }
+// every buffer that is a function of the pair count, for n pairs to n_dest destinations
+int need_pair_buffers(qd_pipe* p, size_t n, size_t n_dest, hipStream_t st) {
+    const bsz::PairSizes z = bsz::pair_sizes(p->lay, n, n_dest, stages_on(p->ctx));
+    const struct {
+        PipeDev& b;
+        size_t bytes;  // (0: not needed -- a buffer that is never asked for more is never allocated)
+    } all[] = {{p->rows_seq[0], z.rows_seq[0]},   {p->rows_seq[1], z.rows_seq[1]},   {p->rows_qual[0], z.rows_qual[0]}, {p->rows_qual[1], z.rows_qual[1]},
+               {p->rows_len[0], z.rows_len[0]},   {p->rows_len[1], z.rows_len[1]},   {p->codes, z.halves},              {p->mol, z.mol},
+               {p->short_idx, z.short_idx},       {p->hist, z.hist},                 {p->len1, z.words},                {p->len2, z.words},
+               {p->tmp, z.words},                 {p->perm, z.words},                {p->g1, z.words},                  {p->g2, z.words},
+               {p->dest, z.halves},               {p->sdest, z.halves},              {p->scan_tiles, z.scan_tiles},     {p->first, z.dest_words},
+               {p->g1_first, z.dest_words},       {p->g2_first, z.dest_words},       {p->base1, z.dest_longs},          {p->base2, z.dest_longs},
+               {p->recs_out[0][0], z.recs_out[0]}, {p->recs_out[0][1], z.recs_out[0]}, {p->recs_out[1][0], z.recs_out[1]}, {p->recs_out[1][1], z.recs_out[1]},
+               {p->recs_out[2][0], z.recs_out[2]}, {p->recs_out[2][1], z.recs_out[2]}, {p->recs_out[3][0], z.recs_out[3]}, {p->recs_out[3][1], z.recs_out[3]},
+               {p->inserts, z.inserts},           {p->drop, z.drop}};
+    for (const auto& x : all) PCHK(p, x.b.need(x.bytes, 0, st));
+    PCHK(p, p->h_first.need(z.h_first));
+    return QD_OK;
+}
 
-// The output side's buffers (two thirds of the bytes: text, member slots, packed members, the coder's scratch): allocated by a thread of
-// their own while the driver fills and scans the first batch's windows -- a device allocation costs ~10 ms per GB, 0.1-0.25 s for a
-// pipeline's 12 GB, and the first batch's inflate launches need none of these.  Joined before the first batch is processed.
-int reserve_output(qd_pipe* p, uint32_t n_dest, double out_text) {
-    if (hipSetDevice(p->device) != hipSuccess) return QD_ERR_HIP;
-    const size_t T = (size_t)out_text + (size_t)n_dest * 64;
-    const uint32_t piece_bytes = piece_bytes_for(p, T, n_dest);
-    const size_t n_pieces = T / piece_bytes + 2 * (size_t)n_dest + 2, n_subs = T / QD_LZ_SUB + n_pieces;
-    const size_t out_stride = (size_t)qd_huffman_member_bound(piece_bytes), sub_stride = (size_t)qd_huffman_member_bound(QD_LZ_SUB);
-    hipError_t e = hipSuccess;
-    auto need = [&](PipeDev& b, size_t n) {  // (first allocations: nothing to keep, no stream involved)
-        if (e == hipSuccess) e = b.need(n);
-    };
-    for (OutSet& o : p->out) {
-        need(o.text, T + 64);
-        need(o.pieces, n_pieces * sizeof(qd_deflate_piece));
-        need(o.members, n_pieces * out_stride);
-        need(o.member_len, n_pieces * 4);
-        need(o.member_off, (n_pieces + 1) * 8);
-        need(o.packed, n_pieces * out_stride);
+// One output set's buffers and the tables of the format / CRC / coder launches (lz: and the level-1 coder's scratch).  No word of the
+// pipeline's state is touched but the buffers: the reservation calls this on a thread of its own, without a stream
+hipError_t need_out_buffers(qd_pipe* p, OutSet& o, const bsz::OutSizes& z, bool lz, hipStream_t st) {
+    const struct {
+        PipeDev& b;
+        size_t bytes;
+    } all[] = {{o.text, z.text},          {o.pieces, z.pieces}, {o.members, z.members}, {o.member_len, z.member_len},      {o.member_off, z.member_off},
+               {o.packed, z.packed},      {p->subs, z.subs},    {p->ranges, z.ranges},  {p->crc, z.crc},                   {p->first_sub, z.first_sub},
+               {p->tokens, lz ? z.tokens : 0}, {p->sub_out, lz ? z.sub_out : 0}, {p->sub_bytes, lz ? z.sub_bytes : 0}};
+    for (const auto& x : all) {
+        const hipError_t e = x.b.need(x.bytes, 0, st);
+        if (e != hipSuccess) return e;
     }
-    need(p->subs, (n_subs + 1) * sizeof(qd_lz_sub));
-    need(p->ranges, (n_subs + 1) * sizeof(qd_crc_range));
-    need(p->crc, (n_subs + 1) * 4);
-    need(p->first_sub, (n_pieces + 1) * 4);
-    need(p->tokens, (size_t)lz_slice_subs((uint32_t)std::min<size_t>(n_subs, 0xFFFFFFFFu)) * QD_LZ_SUB * 4);
-    need(p->sub_out, n_subs * sub_stride);
-    need(p->sub_bytes, n_subs * 4);
-    return e == hipSuccess ? QD_OK : QD_ERR_HIP;
+    return hipSuccess;
+}
+
+// The output side's buffers (two thirds of the bytes: text, member slots, packed members, the coder's scratch) for T bytes of text at
+// the bounds of what the plan can make of them: allocated by a thread of their own while the driver fills and scans the first
+// batch's windows -- a device allocation costs ~10 ms per GB, 0.1-0.25 s for a pipeline's 12 GB, and the first batch's inflate
+// launches need none of these.  Joined before the first batch is processed.
+int reserve_output(qd_pipe* p, uint32_t n_dest, size_t T) {
+    if (hipSetDevice(p->device) != hipSuccess) return QD_ERR_HIP;
+    const uint32_t piece_bytes = piece_bytes_for(p, T, n_dest);
+    const size_t n_pieces = bsz::max_pieces(T, piece_bytes, n_dest);
+    const bsz::OutSizes z = bsz::out_sizes(T, n_pieces, bsz::max_subs(T, n_pieces), piece_bytes);
+    for (OutSet& o : p->out)  // (first allocations: nothing to keep, no stream involved)
+        if (need_out_buffers(p, o, z, true, nullptr) != hipSuccess) return QD_ERR_HIP;
+    return QD_OK;
 }
 
 int join_reserve(qd_pipe* p) {
@@ -1492,36 +1528,31 @@ int join_reserve(qd_pipe* p) {
 // Every buffer at the size a full batch needs, in one go, once the first scan has told what a record of every stream weighs:
 // growing them one by one as the first batches arrive drains the compute stream each time (a quarter of a 16 M-pair run).
 int reserve_buffers(qd_pipe* p, uint32_t B, uint32_t n_dest) {
-    const qd_layout& L = p->lay;
-    double out_text = 0;
-    for (int s = 0; s < 2; ++s) out_text += (double)B * (p->win[s].avg > 0 ? p->win[s].avg : 400.0) * 1.06;
+    auto record = [p](int s) { return bsz::record_bytes(p->win[s].avg, s < 2 ? bsz::RECORD_INSERT : bsz::RECORD_INDEX); };
+    const size_t T = (size_t)((double)B * record(0) * 1.06 + (double)B * record(1) * 1.06) + (size_t)n_dest * 64;  // a batch's output text
     if (join_reserve(p) != QD_OK) return QD_ERR_HIP;
     p->reserve_rc = QD_OK;
     try {
-        p->reserve_thread = std::thread([p, n_dest, out_text] { p->reserve_rc = reserve_output(p, n_dest, out_text); });
+        p->reserve_thread = std::thread([p, n_dest, T] { p->reserve_rc = reserve_output(p, n_dest, T); });
     } catch (const std::system_error&) {  // (no thread to be had: on this one)
-        p->reserve_rc = reserve_output(p, n_dest, out_text);
+        p->reserve_rc = reserve_output(p, n_dest, T);
         if (p->reserve_rc != QD_OK) return pfail(p, QD_ERR_HIP, "device allocation of the output buffers failed");
     }
+    size_t blocks3 = 0;  // a batch's blocks of all streams go down together: ~a block per 64 KiB of text (+ the uploads a top-up overshoots by)
     for (int s = 0; s < p->n_streams; ++s) {
         Window& w = p->win[s];
-        const double avg = w.avg > 0 ? w.avg : (s < 2 ? 400.0 : 64.0);
-        const size_t text = std::min<size_t>((size_t)((double)B * avg * 1.08) + (96u << 20), WINDOW_MAX + (64u << 20));
+        const size_t text = std::min<size_t>((size_t)((double)B * record(s) * 1.08) + (96u << 20), WINDOW_MAX + (64u << 20));
         for (int k = 0; k < 2; ++k) PCHK(p, w.buf[k].need(text + 2 * QD_TEXT_TILE, k == w.cur ? w.len : 0, p->cs));
-        const size_t lines = (size_t)((double)text / avg * 4.4 * 1.25) + 65536;
-        PCHK(p, w.tile_counts.need((text / QD_TEXT_TILE + 3) * 4, 0, p->cs));
-        PCHK(p, w.tile_base.need((text / QD_TEXT_TILE + 3) * 4, 0, p->cs));
-        PCHK(p, w.lines.need(lines * 4 + 64, 0, p->cs));
-        PCHK(p, w.rec_tile.need((lines / 4 / 1024 + 4) * 4, 0, p->cs));
-        PCHK(p, w.recs.need((lines / 4 + 1) * sizeof(qd_rec), 0, p->cs));
+        const int rc = need_scan_tables(p, w, text, (size_t)((double)text / record(s) * 4.4 * 1.25) + 65536);
+        if (rc != QD_OK) return rc;
+        blocks3 += (size_t)((double)B * record(s) * 1.08 / 60000.0) + 64 + 3 * (SEG_BYTES * 5 / 60000);
     }
     {  // ordinary gzip streams: the gzip kernels' buffers for a batch's steps, and the streams' compressed bytes
         uint64_t comp = 0, text = 0;
         for (int s = 0; s < p->n_streams; ++s) {
             Window& w = p->win[s];
             if (!w.gz.active) continue;
-            const double avg = w.avg > 0 ? w.avg : (s < 2 ? 400.0 : 64.0);
-            const uint64_t t = (uint64_t)((double)B * avg * 1.15) + (64u << 20), c = (uint64_t)((double)t / std::max(1.5, w.gz.ratio)) + 2 * SEG_BYTES;
+            const uint64_t t = (uint64_t)((double)B * record(s) * 1.15) + (64u << 20), c = (uint64_t)((double)t / std::max(1.5, w.gz.ratio)) + 2 * SEG_BYTES;
             comp += c;
             text += t;
             for (int k = 0; k < 2; ++k) PCHK(p, w.gz.comp[k].need((size_t)c + SEG_BYTES, k == w.gz.ccur ? (size_t)w.gz.comp_len : 0, p->cs));
@@ -1531,32 +1562,10 @@ int reserve_buffers(qd_pipe* p, uint32_t B, uint32_t n_dest) {
             PCHK(p, p->gz->reserve(comp, text));
         }
     }
-    {  // a batch's blocks of all streams go down together: ~a block per 64 KiB of text
-        size_t blocks3 = 0;
-        for (int s = 0; s < p->n_streams; ++s) {
-            const double avg = p->win[s].avg > 0 ? p->win[s].avg : (s < 2 ? 400.0 : 64.0);
-            blocks3 += (size_t)((double)B * avg * 1.08 / 60000.0) + 64 + 3 * (SEG_BYTES * 5 / 60000);  // (+ the uploads a top-up overshoots by)
-        }
-        PCHK(p, p->jobs3.need(blocks3 * sizeof(qd_inflate3_job), 0, p->cs));
-        PCHK(p, p->status3.need(blocks3 * 4, 0, p->cs));
-        PCHK(p, p->scratch3.need(qd_inflate3_scratch_bytes((uint32_t)std::min<size_t>(blocks3, LAUNCH_BLOCKS3)), 0, p->cs));
-    }
-    const size_t n = B;
-    for (int k = 0; k < L.n_streams; ++k) {
-        PCHK(p, p->rows_seq[k].need(n * L.seq_stride[k] + 64, 0, p->cs));
-        PCHK(p, p->rows_qual[k].need(n * L.qual_stride[k] + 64, 0, p->cs));
-        PCHK(p, p->rows_len[k].need(n + 64, 0, p->cs));
-    }
-    PCHK(p, p->codes.need(n * 2 + 64, 0, p->cs));
-    if (L.mol_width) PCHK(p, p->mol.need(n * L.mol_width + 64, 0, p->cs));
-    PCHK(p, p->short_idx.need((n / 2 + 64) * 4, 0, p->cs));
-    const size_t H = 256 * ((n + 1023) / 1024);
-    PCHK(p, p->hist.need((H + H / 4096 + 8) * 4, 0, p->cs));
-    for (PipeDev* b : {&p->len1, &p->len2, &p->tmp, &p->perm, &p->g1, &p->g2}) PCHK(p, b->need((n + 1) * 4 + 64, 0, p->cs));
-    PCHK(p, p->dest.need(n * 2 + 64, 0, p->cs));
-    PCHK(p, p->sdest.need(n * 2 + 64, 0, p->cs));
-    PCHK(p, p->scan_tiles.need((n / 4096 + 4) * 4, 0, p->cs));
-    return QD_OK;
+    PCHK(p, p->jobs3.need(blocks3 * sizeof(qd_inflate3_job), 0, p->cs));
+    PCHK(p, p->status3.need(blocks3 * 4, 0, p->cs));
+    PCHK(p, p->scratch3.need(qd_inflate3_scratch_bytes((uint32_t)std::min<size_t>(blocks3, LAUNCH_BLOCKS3)), 0, p->cs));
+    return need_pair_buffers(p, B, n_dest, p->cs);
 }
 
 // an output set the collector is done with
@@ -1569,45 +1578,42 @@ int take_out_set(qd_pipe* p, int b) {
     return b;
 }
 
-// pairs [0, n) of the four windows: rows -> codes -> sorted by destination -> formatted -> coded; members to the collector
-int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
-    if (join_reserve(p) != QD_OK) return QD_ERR_HIP;
+// ---- one batch, step by step ---------------------------------------------------------------------------------------------------------
+struct Batch {  // what the steps of a batch hand on to the ones behind them
+    uint32_t n, nd;          // pairs [0, n) of the four windows; destinations = 2 * samples + 1
+    qd_sink* sink;
+    qdio::SinkInfo si;
+    Window* iw[2];           // the index reads' windows
+    uint8_t *text1, *text2;  // the insert reads' text (mutable for the one stage that writes into it: the overlap correction)
+    const qd_rec* ins[2];    // the insert reads' tables: the scan's, then as the last rewriting stage left them
+    const uint8_t* drop;     // the filter's / the screen's byte per pair, or none
+    qd_route_args ra;
+};
+
+// 1. index rows, 2. codes (src/Sample.py:56-91); the counters move in the context
+int pack_and_demux(qd_pipe* p, Batch& b) {
     const qd_layout& L = p->lay;
-    const qdio::SinkInfo si = qdio::sink_info(sink);
-    const uint32_t S = si.n_samples, nd = 2 * S + 1;
-    const int ni = L.n_streams;
-    Window* iw[2] = {&p->win[2], &p->win[3]};
-    // 1. index rows
-    for (int k = 0; k < ni; ++k) {
-        PCHK(p, p->rows_seq[k].need((size_t)n * L.seq_stride[k] + 64, 0, p->cs));
-        PCHK(p, p->rows_qual[k].need((size_t)n * L.qual_stride[k] + 64, 0, p->cs));
-        PCHK(p, p->rows_len[k].need((size_t)n + 64, 0, p->cs));
-    }
-    PCHK(p, p->codes.need((size_t)n * 2 + 64, 0, p->cs));
-    if (L.mol_width) PCHK(p, p->mol.need((size_t)n * L.mol_width + 64, 0, p->cs));
-    const uint32_t short_cap = n / 2 + 64;
-    PCHK(p, p->short_idx.need((size_t)short_cap * 4, 0, p->cs));
+    const uint32_t n = b.n;
     uint32_t* d_nshort = reinterpret_cast<uint32_t*>(p->d_res.p + 4 * sizeof(qd_scan_result));
     PCHK(p, hipMemsetAsync(d_nshort, 0, 4, p->cs));
     qd_pack_args pa{};
-    for (int k = 0; k < ni; ++k) {
-        pa.text[k] = iw[k]->buf[iw[k]->cur].p;
-        pa.recs[k] = iw[k]->recs.as<qd_rec>();
+    for (int k = 0; k < p->lay.n_streams; ++k) {
+        pa.text[k] = b.iw[k]->buf[b.iw[k]->cur].p;
+        pa.recs[k] = b.iw[k]->recs.as<qd_rec>();
         pa.seq[k] = p->rows_seq[k].p;
         pa.qual[k] = p->rows_qual[k].p;
         pa.len[k] = p->rows_len[k].p;
     }
     pa.short_idx = p->short_idx.as<uint32_t>();
     pa.n_short = d_nshort;
-    pa.short_cap = short_cap;
+    pa.short_cap = bsz::short_cap(n);
     PCHK(p, qd_text_pack_rows(L, n, pa, p->cs));
-    // 2. codes (src/Sample.py:56-91); the counters move in the context
     qd_rows rows{};
     bool ragged = false;
-    for (int k = 0; k < ni; ++k) {
+    for (int k = 0; k < p->lay.n_streams; ++k) {
         rows.seq[k] = p->rows_seq[k].p;
         rows.qual[k] = p->rows_qual[k].p;
-        ragged = ragged || iw[k]->res.n_short > 0;  // (short reads somewhere in the window: maybe among these pairs)
+        ragged = ragged || b.iw[k]->res.n_short > 0;  // (short reads somewhere in the window: maybe among these pairs)
     }
     uint8_t* d_mol = L.mol_width ? p->mol.p : nullptr;
     if (ragged) {
@@ -1617,7 +1623,7 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
         if (rc != QD_OK) return rc;
         ragged = *h_nshort > 0;
         if (ragged) {
-            for (int k = 0; k < ni; ++k) rows.len[k] = p->rows_len[k].p;
+            for (int k = 0; k < p->lay.n_streams; ++k) rows.len[k] = p->rows_len[k].p;
             rc = qd_demux_device_ragged(p->ctx, n, &rows, p->codes.as<uint16_t>(), d_mol, *h_nshort, p->short_idx.as<uint32_t>(), p->cs);
             if (rc != QD_OK) return pfail(p, rc, std::string("demux: ") + qd_last_error(p->ctx));
         }
@@ -1626,27 +1632,23 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
         const int rc = qd_demux_device(p->ctx, n, &rows, p->codes.as<uint16_t>(), d_mol, p->cs);
         if (rc != QD_OK) return pfail(p, rc, std::string("demux: ") + qd_last_error(p->ctx));
     }
-    // The insert reads' tables: the opt-in stages below write copies of their own, which everything behind them reads sequence and
-    // quality through.  The scan's tables stay as they are: the carry and the next batch use them
-    const qd_rec* ins[2] = {p->win[0].recs.as<qd_rec>(), p->win[1].recs.as<qd_rec>()};
-    uint8_t* const text1 = p->win[0].buf[p->win[0].cur].p;  // (mutable for the one stage that writes into the text: the correction below)
-    uint8_t* const text2 = p->win[1].buf[p->win[1].cur].p;
+    return QD_OK;
+}
+
+// The opt-in stages over the insert reads: leaves the final tables in b.ins and the drop bytes (or none) in b.drop.
+// The stages that rewrite the tables write copies of their own, which everything behind them reads sequence and quality through.
+// The scan's tables stay as they are: the carry and the next batch use them
+int read_stages(qd_pipe* p, Batch& b) {
+    const uint32_t n = b.n;
+    uint8_t* const text1 = b.text1;
+    uint8_t* const text2 = b.text2;
+    const qd_rec*(&ins)[2] = b.ins;
+    const uint8_t*& drop = b.drop;
     {  // opt-in adapter content (qd_adapters_set): the one stage that counts the reads as the scan left them, by the final codes
         const int rc = qd_adapters_device(p->ctx, text1, ins[0], text2, ins[1], n, p->codes.as<uint16_t>(), p->cs);
         if (rc != QD_OK) return pfail(p, rc, std::string("adapter content: ") + qd_last_error(p->ctx));
     }
-    // The opt-in stages that rewrite the tables, each on what the one before left: end clipping, window and poly-G trimming
-    // (qd_clip_set; copies with seq, qual and seq_len of their own, so that a 5' clip reaches every stage behind it through the tables
-    // alone), 3' trimming (qd_trim_set), paired-end overlap trimming of R1 and R2 together (qd_pairtrim_set), then trailing N, a poly-X
-    // tail and the max_length crop (qd_posttrim_set)
-    static const struct {
-        int (*active)(const qd_ctx*);
-        int (*device)(qd_ctx*, const uint8_t*, const qd_rec*, const uint8_t*, const qd_rec*, uint32_t, qd_rec*, qd_rec*, void*);
-        const char* label;
-    } rewriting[4] = {{qd_clip_active, qd_clip_device, "clip: "},
-                      {qd_trim_active, qd_trim_device, "trim: "},
-                      {qd_pairtrim_active, qd_pairtrim_device, "overlap trim: "},
-                      {qd_posttrim_active, qd_posttrim_device, "post-trim: "}};
+    // The stages that rewrite the tables (`rewriting`, above), each on what the one before left.
     // Opt-in overlap base correction (qd_paircorrect_set) directly behind the overlap trimming: that kernel stores every pair's I*,
     // and the correction writes bases and qualities of pairs [0, n) into the windows' text, in place, through the tables the
     // overlap stage received.  In place is safe here: the kernel touches the sequence and quality lines of records [0, n) only, so
@@ -1658,9 +1660,7 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
     for (int s = 0; s < 4; ++s) {
         if (!rewriting[s].active(p->ctx)) continue;
         PipeDev* out = p->recs_out[s];
-        for (int k = 0; k < 2; ++k) PCHK(p, out[k].need((size_t)n * sizeof(qd_rec) + 64, 0, p->cs));
         if (correct && rewriting[s].device == qd_pairtrim_device) {
-            PCHK(p, p->inserts.need((size_t)n * 8 + 64, 0, p->cs));
             int rc = qd_pairtrim_device_inserts(p->ctx, text1, ins[0], text2, ins[1], n, out[0].as<qd_rec>(), out[1].as<qd_rec>(), p->inserts.as<uint64_t>(), p->cs);
             if (rc != QD_OK) return pfail(p, rc, std::string(rewriting[s].label) + qd_last_error(p->ctx));
             rc = qd_paircorrect_device(p->ctx, text1, ins[0], text2, ins[1], p->inserts.as<uint64_t>(), n, p->cs);
@@ -1673,9 +1673,7 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
     }
     // opt-in read filtering (qd_filter_set) of what the trimming left: a reason byte per pair; a pair with one is counted by nothing
     // behind this point, gets output lengths 0 and is not formatted -- the way a destination whose write flag is off leaves no text
-    const uint8_t* drop = nullptr;
     if (qd_filter_active(p->ctx)) {
-        PCHK(p, p->drop.need((size_t)n + 64, 0, p->cs));
         const int rc = qd_filter_device(p->ctx, text1, ins[0], text2, ins[1], n, p->codes.as<uint16_t>(), p->drop.p, p->cs);
         if (rc != QD_OK) return pfail(p, rc, std::string("filter: ") + qd_last_error(p->ctx));
         drop = p->drop.p;
@@ -1684,11 +1682,7 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
     // action drop writes QD_SC_DROPPED over the 0 of a matched pair, in the filter's buffer or, the filter off, in a buffer of its
     // own that the kernel fills whole -- everything behind tests the byte for non-zero
     if (const int screen = qd_screen_active(p->ctx)) {
-        uint8_t* flag = nullptr;
-        if (screen == 2) {
-            PCHK(p, p->drop.need((size_t)n + 64, 0, p->cs));
-            flag = p->drop.p;
-        }
+        uint8_t* flag = screen == 2 ? p->drop.p : nullptr;
         const int rc = qd_screen_device(p->ctx, text1, ins[0], text2, ins[1], n, p->codes.as<uint16_t>(), drop, nullptr, flag, p->cs);
         if (rc != QD_OK) return pfail(p, rc, std::string("screen: ") + qd_last_error(p->ctx));
         if (flag) drop = flag;
@@ -1706,49 +1700,41 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
         const int rc = qd_dup_device(p->ctx, text1, ins[0], text2, ins[1], n, p->codes.as<uint16_t>(), drop, p->cs);
         if (rc != QD_OK) return pfail(p, rc, std::string("duplication tally: ") + qd_last_error(p->ctx));
     }
-    // 3. destinations, output lengths, stable sort by destination, output offsets
-    PCHK(p, p->dest.need((size_t)n * 2 + 64, 0, p->cs));
-    PCHK(p, p->len1.need((size_t)n * 4 + 64, 0, p->cs));
-    PCHK(p, p->len2.need((size_t)n * 4 + 64, 0, p->cs));
-    const size_t H = 256 * (((size_t)n + 1023) / 1024);
-    PCHK(p, p->hist.need((H + H / 4096 + 8) * 4, 0, p->cs));
-    PCHK(p, p->tmp.need((size_t)n * 4 + 64, 0, p->cs));
-    PCHK(p, p->perm.need((size_t)n * 4 + 64, 0, p->cs));
-    PCHK(p, p->sdest.need((size_t)n * 2 + 64, 0, p->cs));
-    PCHK(p, p->g1.need(((size_t)n + 1) * 4 + 64, 0, p->cs));
-    PCHK(p, p->g2.need(((size_t)n + 1) * 4 + 64, 0, p->cs));
-    PCHK(p, p->scan_tiles.need(((size_t)n / 4096 + 4) * 4, 0, p->cs));
-    PCHK(p, p->first.need((size_t)nd * 4, 0, p->cs));
-    PCHK(p, p->g1_first.need((size_t)nd * 4, 0, p->cs));
-    PCHK(p, p->g2_first.need((size_t)nd * 4, 0, p->cs));
-    qd_route_args ra{};
+    return QD_OK;
+}
+
+// 3. destinations, output lengths, stable sort by destination, output offsets; what the next batch keeps of every window
+int route_and_sort(qd_pipe* p, Batch& b) {
+    const uint32_t n = b.n, nd = b.nd;
+    qd_route_args& ra = b.ra;
     ra.codes = p->codes.as<uint16_t>();
-    ra.drop = drop;
-    ra.r1 = ins[0];
-    ra.r2 = ins[1];
-    for (int k = 0; k < ni; ++k) ra.idx[k] = iw[k]->recs.as<qd_rec>();
+    ra.drop = b.drop;
+    ra.r1 = b.ins[0];
+    ra.r2 = b.ins[1];
+    for (int k = 0; k < p->lay.n_streams; ++k) ra.idx[k] = b.iw[k]->recs.as<qd_rec>();
     ra.dest = p->dest.as<uint16_t>();
     ra.len1 = p->len1.as<uint32_t>();
     ra.len2 = p->len2.as<uint32_t>();
-    PCHK(p, qd_text_dest_lens(p->plan, S, si.write_pass, si.write_fail, si.write_undet, n, ra, p->cs));
+    PCHK(p, qd_text_dest_lens(p->plan, b.si.n_samples, b.si.write_pass, b.si.write_fail, b.si.write_undet, n, ra, p->cs));
     PCHK(p, qd_text_sort_by_dest(ra.dest, n, nd, p->hist.as<uint32_t>(), p->tmp.as<uint32_t>(), p->perm.as<uint32_t>(), p->cs));
     PCHK(p, qd_text_scan_gathered(ra.len1, p->perm.as<uint32_t>(), n, p->scan_tiles.as<uint32_t>(), p->g1.as<uint32_t>(), ra.dest, p->sdest.as<uint16_t>(), p->cs));
     PCHK(p, qd_text_scan_gathered(ra.len2, p->perm.as<uint32_t>(), n, p->scan_tiles.as<uint32_t>(), p->g2.as<uint32_t>(), nullptr, nullptr, p->cs));
     PCHK(p, qd_text_dest_bounds(p->sdest.as<uint16_t>(), p->g1.as<uint32_t>(), p->g2.as<uint32_t>(), n, nd, p->first.as<uint32_t>(), p->g1_first.as<uint32_t>(),
                                 p->g2_first.as<uint32_t>(), p->cs));
-    // what the next batch keeps of every window
-    {
-        const qd_rec* recs[4] = {nullptr, nullptr, nullptr, nullptr};
-        qd_scan_result* res[4] = {nullptr, nullptr, nullptr, nullptr};
-        for (int s = 0; s < p->n_streams; ++s) {
-            recs[s] = p->win[s].recs.as<qd_rec>();
-            res[s] = p->d_res.as<qd_scan_result>() + s;
-        }
-        const uint32_t taken[4] = {n, n, n, n};
-        PCHK(p, qd_text_carry_info(recs, res, p->n_streams, taken, p->cs));
+    const qd_rec* recs[4] = {nullptr, nullptr, nullptr, nullptr};
+    qd_scan_result* res[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int s = 0; s < p->n_streams; ++s) {
+        recs[s] = p->win[s].recs.as<qd_rec>();
+        res[s] = p->d_res.as<qd_scan_result>() + s;
     }
-    // 4. read back: per-destination bounds, totals, carry starts
-    PCHK(p, p->h_first.need((size_t)nd * 12 + 16));
+    const uint32_t taken[4] = {n, n, n, n};
+    PCHK(p, qd_text_carry_info(recs, res, p->n_streams, taken, p->cs));
+    return QD_OK;
+}
+
+// 4. read back: per-destination bounds, totals, carry starts
+int read_back(qd_pipe* p, const Batch& b) {
+    const uint32_t n = b.n, nd = b.nd;
     uint32_t* h_first = reinterpret_cast<uint32_t*>(p->h_first.p);
     uint32_t* h_g1f = h_first + nd;
     uint32_t* h_g2f = h_g1f + nd;
@@ -1759,98 +1745,50 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
     PCHK(p, hipMemcpyAsync(h_tot, p->g1.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, p->cs));
     PCHK(p, hipMemcpyAsync(h_tot + 1, p->g2.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, p->cs));
     PCHK(p, hipMemcpyAsync(p->h_res.p, p->d_res.p, (size_t)p->n_streams * sizeof(qd_scan_result), hipMemcpyDeviceToHost, p->cs));
-    int rc = sync_compute(p);
+    const int rc = sync_compute(p);
     if (rc != QD_OK) return rc;
     for (int s = 0; s < p->n_streams; ++s) p->win[s].res.carry_start = reinterpret_cast<qd_scan_result*>(p->h_res.p)[s].carry_start;
-    // 5. layout of the output text: every destination's R1 region, then every R2 region, 16-byte aligned (qd_text_out_layout,
-    //    quade_text.h); pieces of 1 MiB
-    std::vector<int64_t> base1(nd, 0), base2(nd, 0);
-    const uint32_t piece_bytes = piece_bytes_for(p, (uint64_t)h_tot[0] + h_tot[1], nd);
-    BatchOut bo;
-    bo.sink = sink;
-    bo.level = si.level;
-    std::vector<qd_lz_sub> subs;
-    std::vector<uint32_t> first_sub;
-    std::vector<qd_crc_range> ranges;
-    std::vector<qd_out_region> regions;
-    const uint64_t at = qd_text_out_layout(nd, h_first, h_g1f, h_g2f, h_tot[0], h_tot[1], base1.data(), base2.data(), &regions);
-    for (const qd_out_region& rg : regions) {
-        FileRun fr;
-        fr.code = rg.dest == 2 * S ? QD_CODE_UNDETERMINED : rg.dest;
-        fr.k = rg.k;
-        fr.first = (uint32_t)bo.pieces.size();
-        fr.text_bytes = rg.bytes;
-        for (uint64_t a = 0; a < rg.bytes; a += piece_bytes) {
-            const uint32_t plen = (uint32_t)std::min<uint64_t>(piece_bytes, rg.bytes - a);
-            first_sub.push_back((uint32_t)subs.size());
-            for (uint32_t q = 0; q < plen; q += QD_LZ_SUB) {
-                const uint32_t slen = std::min<uint32_t>(QD_LZ_SUB, plen - q);
-                subs.push_back(qd_lz_sub{rg.at + a + q, slen, (uint32_t)bo.pieces.size()});
-                ranges.push_back(qd_crc_range{rg.at + a + q, slen, 0});
-            }
-            bo.pieces.push_back(qd_deflate_piece{rg.at + a, plen, 0});
-        }
-        fr.n = (uint32_t)bo.pieces.size() - fr.first;
-        bo.files.push_back(fr);
-    }
-    first_sub.push_back((uint32_t)subs.size());
-    const uint32_t n_pieces = (uint32_t)bo.pieces.size(), n_subs = (uint32_t)subs.size();
-    p->st.pairs += n;
-    ++p->st.batches;
-    p->st.text_out_bytes += (int64_t)h_tot[0] + h_tot[1];
-    p->st.pieces += n_pieces;
-    if (!n_pieces) return QD_OK;  // every destination's write flag is off, or the read filter dropped every pair
-    // 6. format, CRC-32, code, pack
+    return QD_OK;
+}
+
+// 6. format, CRC-32, code, pack: the plan's tables go up, the members to the collector
+int format_and_code(qd_pipe* p, const Batch& b, outplan::Plan&& plan, uint64_t text_bytes, uint32_t piece_bytes, const std::vector<int64_t>& base1,
+                    const std::vector<int64_t>& base2, int64_t batch_index) {
+    const uint32_t n_pieces = (uint32_t)plan.pieces.size(), n_subs = (uint32_t)plan.subs.size(), nd = b.nd;
     const int set = take_out_set(p, (int)(batch_index & 1));
     OutSet& o = p->out[set];
-    bo.set = set;
-    bo.n_pieces = n_pieces;
-    const int64_t out_stride = qd_huffman_member_bound(piece_bytes);
-    const int64_t sub_stride = qd_huffman_member_bound(QD_LZ_SUB);
-    PCHK(p, o.text.need((size_t)at + 64, 0, p->cs));
-    PCHK(p, p->base1.need((size_t)nd * 8, 0, p->cs));
-    PCHK(p, p->base2.need((size_t)nd * 8, 0, p->cs));
-    PCHK(p, o.pieces.need((size_t)n_pieces * sizeof(qd_deflate_piece), 0, p->cs));
-    PCHK(p, p->subs.need((size_t)(n_subs + 1) * sizeof(qd_lz_sub), 0, p->cs));
-    PCHK(p, p->first_sub.need((size_t)(n_pieces + 1) * 4, 0, p->cs));
-    PCHK(p, p->ranges.need((size_t)(n_subs + 1) * sizeof(qd_crc_range), 0, p->cs));
-    PCHK(p, p->crc.need((size_t)(n_subs + 1) * 4, 0, p->cs));
-    PCHK(p, o.members.need((size_t)n_pieces * (size_t)out_stride, 0, p->cs));
-    PCHK(p, o.member_len.need((size_t)n_pieces * 4, 0, p->cs));
-    PCHK(p, o.member_off.need((size_t)(n_pieces + 1) * 8, 0, p->cs));
-    PCHK(p, o.packed.need((size_t)n_pieces * (size_t)out_stride, 0, p->cs));
+    const bsz::OutSizes z = bsz::out_sizes((size_t)text_bytes, n_pieces, n_subs, piece_bytes);
+    PCHK(p, need_out_buffers(p, o, z, b.si.level == 1, p->cs));
     PCHK(p, p->stage.upload(p->base1.p, base1.data(), (size_t)nd * 8, p->cs));
     PCHK(p, p->stage.upload(p->base2.p, base2.data(), (size_t)nd * 8, p->cs));
-    PCHK(p, p->stage.upload(o.pieces.p, bo.pieces.data(), (size_t)n_pieces * sizeof(qd_deflate_piece), p->cs));
-    PCHK(p, p->stage.upload(p->subs.p, subs.data(), (size_t)n_subs * sizeof(qd_lz_sub), p->cs));
-    PCHK(p, p->stage.upload(p->first_sub.p, first_sub.data(), (size_t)(n_pieces + 1) * 4, p->cs));
-    PCHK(p, p->stage.upload(p->ranges.p, ranges.data(), (size_t)n_subs * sizeof(qd_crc_range), p->cs));
+    PCHK(p, p->stage.upload(o.pieces.p, plan.pieces.data(), (size_t)n_pieces * sizeof(qd_deflate_piece), p->cs));
+    PCHK(p, p->stage.upload(p->subs.p, plan.subs.data(), (size_t)n_subs * sizeof(qd_lz_sub), p->cs));
+    PCHK(p, p->stage.upload(p->first_sub.p, plan.first_sub.data(), (size_t)(n_pieces + 1) * 4, p->cs));
+    PCHK(p, p->stage.upload(p->ranges.p, plan.ranges.data(), (size_t)n_subs * sizeof(qd_crc_range), p->cs));
     qd_format_args fa{};
     fa.perm = p->perm.as<uint32_t>();
-    fa.drop = drop;
+    fa.drop = b.drop;
     fa.sdest = p->sdest.as<uint16_t>();
     fa.g1 = p->g1.as<uint32_t>();
     fa.g2 = p->g2.as<uint32_t>();
     fa.base1 = p->base1.as<int64_t>();
     fa.base2 = p->base2.as<int64_t>();
-    fa.text1 = text1;
-    fa.text2 = text2;
-    fa.r1 = ra.r1;
-    fa.r2 = ra.r2;
-    for (int k = 0; k < ni; ++k) {
-        fa.itext[k] = iw[k]->buf[iw[k]->cur].p;
-        fa.idx[k] = ra.idx[k];
+    fa.text1 = b.text1;
+    fa.text2 = b.text2;
+    fa.r1 = b.ra.r1;
+    fa.r2 = b.ra.r2;
+    for (int k = 0; k < p->lay.n_streams; ++k) {
+        fa.itext[k] = b.iw[k]->buf[b.iw[k]->cur].p;
+        fa.idx[k] = b.ra.idx[k];
     }
     fa.out1 = o.text.p;
     fa.out2 = o.text.p;
-    PCHK(p, qd_text_format(p->plan, S, si.write_pass, si.write_fail, si.write_undet, n, fa, p->cs));
+    PCHK(p, qd_text_format(p->plan, b.si.n_samples, b.si.write_pass, b.si.write_fail, b.si.write_undet, b.n, fa, p->cs));
     static_assert(sizeof(qd_deflate_piece) == 16 && offsetof(qd_deflate_piece, crc32) == 12, "the combined CRCs land in the piece table");
     uint32_t* piece_crc = reinterpret_cast<uint32_t*>(o.pieces.p) + 3;
-    if (si.level == 1) {
-        const uint32_t slice = lz_slice_subs(n_subs);
-        PCHK(p, p->tokens.need((size_t)slice * QD_LZ_SUB * 4, 0, p->cs));
-        PCHK(p, p->sub_out.need((size_t)n_subs * (size_t)sub_stride, 0, p->cs));
-        PCHK(p, p->sub_bytes.need((size_t)n_subs * 4, 0, p->cs));
+    const int64_t out_stride = z.out_stride, sub_stride = z.sub_stride;
+    if (b.si.level == 1) {
+        const uint32_t slice = (uint32_t)bsz::lz_slice_subs(n_subs);
         // the sub-blocks' CRC-32s come out of the coder (taken while a sub-block's text is staged), the pieces' are combined from them
         for (uint32_t at = 0; at < n_subs; at += slice)
             PCHK(p, qd_launch_lz_subblocks(o.text.p, p->subs.as<qd_lz_sub>() + at, std::min(slice, n_subs - at), p->tokens.as<uint32_t>(), p->sub_out.p + (size_t)at * sub_stride,
@@ -1864,10 +1802,52 @@ int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
         PCHK(p, qd_launch_huffman(o.text.p, o.pieces.as<qd_deflate_piece>(), n_pieces, o.members.p, out_stride, o.member_len.as<uint32_t>(), p->cs));
     }
     PCHK(p, qd_text_pack_members(o.members.p, out_stride, o.member_len.as<uint32_t>(), n_pieces, o.member_off.as<uint64_t>(), o.packed.p, p->cs));
+    BatchOut bo;
+    bo.sink = b.sink;
+    bo.level = b.si.level;
+    bo.set = set;
+    bo.n_pieces = n_pieces;
+    bo.files = std::move(plan.files);
+    bo.pieces = std::move(plan.pieces);
     PCHK(p, hipEventCreateWithFlags(&bo.done, hipEventDisableTiming));
     PCHK(p, hipEventRecord(bo.done, p->cs));
     to_collector(p, std::move(bo));
     return QD_OK;
+}
+
+// pairs [0, n) of the four windows: rows -> codes -> sorted by destination -> formatted -> coded; members to the collector
+int process_batch(qd_pipe* p, uint32_t n, qd_sink* sink, int64_t batch_index) {
+    if (join_reserve(p) != QD_OK) return QD_ERR_HIP;
+    Batch b{};
+    b.n = n;
+    b.sink = sink;
+    b.si = qdio::sink_info(sink);
+    b.nd = 2 * b.si.n_samples + 1;
+    for (int k = 0; k < 2; ++k) b.iw[k] = &p->win[2 + k];
+    b.text1 = p->win[0].buf[p->win[0].cur].p;
+    b.text2 = p->win[1].buf[p->win[1].cur].p;
+    for (int k = 0; k < 2; ++k) b.ins[k] = p->win[k].recs.as<qd_rec>();
+    int rc = need_pair_buffers(p, n, b.nd, p->cs);  // (what the reservation gave serves every batch no larger than it was made for)
+    if (rc == QD_OK) rc = pack_and_demux(p, b);
+    if (rc == QD_OK) rc = read_stages(p, b);
+    if (rc == QD_OK) rc = route_and_sort(p, b);
+    if (rc == QD_OK) rc = read_back(p, b);
+    if (rc != QD_OK) return rc;
+    // 5. layout of the output text: every destination's R1 region, then every R2 region, 16-byte aligned; members of piece_bytes
+    //    at most, their sub-blocks and CRC ranges (out_plan.h)
+    std::vector<int64_t> base1(b.nd, 0), base2(b.nd, 0);
+    std::vector<qd_out_region> regions;
+    const uint32_t* h = reinterpret_cast<const uint32_t*>(p->h_first.p);  // first, g1_first, g2_first, then G1[n], G2[n] (read_back)
+    const uint32_t* tot = h + 3 * b.nd;
+    const uint64_t text_bytes = qd_text_out_layout(b.nd, h, h + b.nd, h + 2 * b.nd, tot[0], tot[1], base1.data(), base2.data(), &regions);
+    const uint32_t piece_bytes = piece_bytes_for(p, (uint64_t)tot[0] + tot[1], b.nd);
+    outplan::Plan plan = outplan::plan_output(regions, piece_bytes, b.si.n_samples);
+    p->st.pairs += n;
+    ++p->st.batches;
+    p->st.text_out_bytes += (int64_t)tot[0] + tot[1];
+    p->st.pieces += (int64_t)plan.pieces.size();
+    if (plan.pieces.empty()) return QD_OK;  // every destination's write flag is off, or the read filter dropped every pair
+    return format_and_code(p, b, std::move(plan), text_bytes, piece_bytes, base1, base2, batch_index);
 }
 
 // a D2D move of a window's text from `from` on to the front of its other buffer
@@ -1982,15 +1962,14 @@ int run_chunk(qd_pipe* p, std::vector<std::unique_ptr<Feeder>>& feeders, int chu
                 }
             }
             p->reserved = true;
-            const uint32_t most = (uint32_t)std::min<double>((double)B, (double)p->max_r1_bytes * (p->r1_compressed ? 8.0 : 1.0) / avg[0] + 1024.0);
-            const int rc = reserve_buffers(p, most, 2 * qdio::sink_info(sink).n_samples + 1);
+            const int rc = reserve_buffers(p, bsz::most_pairs(B, p->max_r1_bytes, p->r1_compressed, avg[0]), 2 * qdio::sink_info(sink).n_samples + 1);
             if (rc != QD_OK) return rc;
         }
     }
     std::vector<size_t> want(ns, 1);  // first round: one upload, to learn the stream's bytes per record ...
     if (p->reserved)                  // ... unless the chunks before (or a look at the files' heads) have told (a small first top-up is an inflate launch of its own)
         for (int s = 0; s < ns; ++s)
-            if (p->win[s].avg > 0) want[s] = std::min<size_t>((size_t)((double)B * p->win[s].avg * 1.03) + 4096, WINDOW_MAX * 3 / 4);
+            if (p->win[s].avg > 0) want[s] = bsz::want_text(0, B, p->win[s].avg, p->window_max);
     static const bool trace = getenv("QUADE_PIPE_TRACE") != nullptr;  // (debugging: one line per turn of the loop)
     for (uint64_t turn = 0;; ++turn) {
         if (trace && (turn < 60 || turn % 1000000 == 0)) {
@@ -2084,10 +2063,7 @@ int run_chunk(qd_pipe* p, std::vector<std::unique_ptr<Feeder>>& feeders, int chu
         }
         if (!p->reserved) {  // every stream's record size is known now
             p->reserved = true;
-            // (not for more pairs than the run's largest seq_R1 file can hold: gzip at its best makes 1 byte of 8)
-            const double avg1 = p->win[0].avg > 0 ? p->win[0].avg : 400.0;
-            const uint32_t most = (uint32_t)std::min<double>((double)B, (double)p->max_r1_bytes * (p->r1_compressed ? 8.0 : 1.0) / avg1 + 1024.0);
-            const int rc = reserve_buffers(p, most, 2 * qdio::sink_info(sink).n_samples + 1);
+            const int rc = reserve_buffers(p, bsz::most_pairs(B, p->max_r1_bytes, p->r1_compressed, p->win[0].avg), 2 * qdio::sink_info(sink).n_samples + 1);
             if (rc != QD_OK) return rc;
             for (int s = 0; s < ns; ++s) p->win[s].dirty = true;  // (the scans' tables moved: once more, over these first small windows)
             continue;
@@ -2117,8 +2093,7 @@ int run_chunk(qd_pipe* p, std::vector<std::unique_ptr<Feeder>>& feeders, int chu
                     if (skip_kept[s] && w.eof && drop[s] == w.res.n_kept) skip_kept[s] = 0;  // (the stream ends before this rank's part: nothing to do)
                     rc = carry_window(p, w, reinterpret_cast<qd_scan_result*>(p->h_res.p)[s].carry_start);
                     if (rc != QD_OK) return rc;
-                    const double per = w.avg > 0 ? w.avg : 256.0;
-                    want[s] = std::min<size_t>((size_t)w.len + (size_t)((double)(skip_kept[s] + B) * per * 1.03) + 4096, p->window_max * 3 / 4);
+                    want[s] = bsz::want_text(w.len, skip_kept[s] + B, bsz::record_bytes(w.avg, bsz::RECORD_TOP_UP), p->window_max);
                 }
                 continue;
             }
@@ -2128,13 +2103,11 @@ int run_chunk(qd_pipe* p, std::vector<std::unique_ptr<Feeder>>& feeders, int chu
         for (int s = 0; s < ns; ++s) {
             Window& w = p->win[s];
             if (w.res.n_kept >= B || w.eof) continue;
-            if (w.res.n_kept > 0 && (size_t)w.len > WINDOW_MAX / 2) continue;  // a full window: a smaller batch rather than more text
+            if (w.res.n_kept > 0 && (size_t)w.len > p->window_max / 2) continue;  // a full window: a smaller batch rather than more text
             // (... and a batch that is most of B rather than another round: a top-up is an inflate launch of its own, which takes as
             //  long for a few hundred blocks as for ten thousand -- a lane decodes its block's symbols one after the other)
             if ((uint64_t)w.res.n_kept * 10 >= (uint64_t)B * 8) continue;
-            const double per = w.avg > 0 ? w.avg : 256.0;
-            const size_t more = (size_t)((double)(B - w.res.n_kept) * per * 1.03) + 4096;
-            want[s] = std::min<size_t>(std::max<size_t>((size_t)w.len + more, (size_t)w.len + 1), WINDOW_MAX * 3 / 4);
+            want[s] = bsz::want_text(w.len, B - w.res.n_kept, bsz::record_bytes(w.avg, bsz::RECORD_TOP_UP), p->window_max);
             if (want[s] <= (size_t)w.len) want[s] = (size_t)w.len + 1;
             short_of = true;
         }
@@ -2160,9 +2133,7 @@ int run_chunk(qd_pipe* p, std::vector<std::unique_ptr<Feeder>>& feeders, int chu
             const int rc = carry_window(p, w, w.res.carry_start);
             if (rc != QD_OK) return rc;
             w.carry_kept = w.res.n_kept - n;
-            const uint32_t left = w.len;
-            const double per = w.avg > 0 ? w.avg : 256.0;
-            want[s] = std::min<size_t>((size_t)left + (size_t)((double)(B > w.carry_kept ? B - w.carry_kept : 0) * per * 1.03) + 4096, WINDOW_MAX * 3 / 4);
+            want[s] = bsz::want_text(w.len, B > w.carry_kept ? B - w.carry_kept : 0, bsz::record_bytes(w.avg, bsz::RECORD_TOP_UP), p->window_max);
         }
     }
     // the streams the chunk did not exhaust: their feeders stop reading this chunk, what they had read is dropped

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/quade_hip.h"
+#include "out_plan.h"  // qd_out_region, qd_text_out_layout, qd_crc_range: the host's plan of a batch's output
 
 // one kept record of a text window: offsets into the window's text
 struct qd_rec {
@@ -130,40 +131,6 @@ hipError_t qd_text_scan_gathered(const uint32_t* in, const uint32_t* perm, uint3
 hipError_t qd_text_dest_bounds(const uint16_t* sdest, const uint32_t* g1, const uint32_t* g2, uint32_t n, uint32_t n_dest,
                                uint32_t* first, uint32_t* g1_first, uint32_t* g2_first, hipStream_t st);
 
-// Where every destination's text lies in a batch's output buffer (host; the pipeline and qd_dev_route_format share it): the R1
-// regions of destinations 0 .. n_dest-1 in ascending order, then their R2 regions, each non-empty region starting on a multiple of
-// 16.  first / g1_first / g2_first: qd_text_dest_bounds' tables read back, tot1 / tot2 = G1[n] / G2[n].  A destination without
-// pairs starts where the next one does, so its region is empty.  base1[d] / base2[d] = where d's region starts minus G at d's
-// first position (qd_text_format adds G back); the non-empty regions are appended to `regions` in buffer order.  Returns the
-// bytes of the buffer the regions take, rounded up to 16.
-struct qd_out_region {
-    uint32_t dest;
-    int k;  // 0: R1, 1: R2
-    uint64_t at, bytes;
-};
-inline uint64_t qd_text_out_layout(uint32_t n_dest, const uint32_t* first, const uint32_t* g1_first, const uint32_t* g2_first, uint32_t tot1,
-                                   uint32_t tot2, int64_t* base1, int64_t* base2, std::vector<qd_out_region>* regions) {
-    std::vector<uint32_t> g1s(n_dest + 1), g2s(n_dest + 1);
-    g1s[n_dest] = tot1;
-    g2s[n_dest] = tot2;
-    for (int64_t d = (int64_t)n_dest - 1; d >= 0; --d) {
-        const bool none = first[d] == 0xFFFFFFFFu;
-        g1s[d] = none ? g1s[d + 1] : g1_first[d];
-        g2s[d] = none ? g2s[d + 1] : g2_first[d];
-    }
-    uint64_t at = 0;
-    for (int k = 0; k < 2; ++k)
-        for (uint32_t d = 0; d < n_dest; ++d) {
-            const std::vector<uint32_t>& gs = k ? g2s : g1s;
-            const uint64_t bytes = gs[d + 1] - gs[d];
-            (k ? base2 : base1)[d] = (int64_t)at - (int64_t)gs[d];
-            if (!bytes) continue;
-            regions->push_back(qd_out_region{d, k, at, bytes});
-            at = (at + bytes + 15) & ~(uint64_t)15;
-        }
-    return at;
-}
-
 // The records themselves: pair perm[k]'s two records to out1 + base1[sdest[k]] + g1[k] and out2 + base2[sdest[k]] + g2[k]
 // (a destination's base is what the host made of its first position: where its text starts minus g at that position).
 // drop: as qd_route_args', whose lengths left the pair no room -- nothing is written for it.
@@ -188,11 +155,6 @@ hipError_t qd_text_format(const qd_plan& P, uint32_t n_samples, int write_pass, 
                           const qd_format_args& a, hipStream_t st);
 
 // CRC-32 (the gzip / zlib polynomial) of n ranges of text, each at most 64 KiB: crc[i] of text[off[i] .. off[i] + len[i])
-struct qd_crc_range {
-    uint64_t off;
-    uint32_t len;
-    uint32_t pad;
-};
 hipError_t qd_text_crc32(const uint8_t* text, const qd_crc_range* ranges, uint32_t n, uint32_t* crc, hipStream_t st);
 // crc of piece i = the CRCs of its ranges first[i] .. first[i + 1] combined, written to piece_crc[i * stride_words] (the
 // pipeline points this at qd_deflate_piece::crc32)
